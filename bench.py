@@ -12,6 +12,10 @@ stereo match), inputs resident in HBM.
 Contract: `python bench.py --gpus N --steps K --warmup W` prints ONE JSON line on rank 0.
 N > 1 is launched by torch.distributed.run (one rank per GPU); stereo frames are independent
 units, so ranks shard batches with no data-path collective ("scaling": "weak").
+A plain run sets up, warms up, times exactly K steps and prints the headline fields (`value`,
+`ms_per_step`, ...); `--full` adds everything else the line has carried (per-stage and roofline
+blocks, the CPU baseline and its parity check, the informational legs).  `--dump-outputs DIR`
+writes what the last timed step returned for a fixed, seeded sample of its frames as DIR/*.npy.
 """
 import argparse
 import json
@@ -192,6 +196,53 @@ def cpu_baseline(cfg, base_imgs, fe, grav, poses, budget_s=12.0):
                       f"host has {os.cpu_count()} logical cores",
             "parity_checked_frames": checked, "parity_mismatches": mismatches,
             "parity_scope": "keypoints, descriptors, back-projections (u64), match rows incl. hp_W"}
+
+
+DUMP_MAX_FRAMES = 64  # --dump-outputs: at most this many frames of the step, drawn with a fixed seed
+DUMP_BUDGET_BYTES = 48 << 20  # ... and fewer where their outputs would exceed this
+
+
+def dump_sample(n_frames, bytes_per_frame):
+    """The frames --dump-outputs writes: a fixed, seeded sample of the step's frames, sorted."""
+    n = max(1, min(n_frames, DUMP_MAX_FRAMES, DUMP_BUDGET_BYTES // max(1, bytes_per_frame)))
+    return np.sort(np.random.default_rng(0).choice(n_frames, size=n, replace=False))
+
+
+def dump_outputs(path, capi, fes, d_match, B, Bl, C, K):
+    """--dump-outputs: what the last timed step returned to its caller for a sample of its frames (dump_sample):
+    per image the keypoints (x, y, size, angle, response, octave, class_id), the descriptors (one value per byte),
+    the back-projected rays and their validity; per frame with C > 1 the stereo match rows of camera 0 against
+    camera 1 (k1, dist, initialisable, hp_W).  Rows past an image's keypoint count are zero.  fes: the lanes'
+    contexts, Bl frames each; d_match: [B, K] match rows on the device."""
+    per_image = K * (7 * 8 + capi.DESC_BYTES * 4 + 3 * 8 + 4) + 8
+    frames = dump_sample(B, C * per_image + (K * 7 * 8 if C > 1 else 0))
+    n = len(frames) * C
+    out = {"sample_frames": frames.astype(np.float64),
+           "keypoint_counts": np.zeros(n),
+           "keypoints": np.zeros((n, K, 7)),
+           "descriptors": np.zeros((n, K, capi.DESC_BYTES), np.float32),
+           "rays": np.zeros((n, K, 3)),
+           "ray_valid": np.zeros((n, K), np.float32)}
+    for a, f in enumerate(frames):
+        for c in range(C):
+            k, d, bp, bv = fes[f // Bl].download(C * (f % Bl) + c)
+            r, m = C * a + c, len(k)
+            out["keypoint_counts"][r] = m
+            out["keypoints"][r, :m] = np.stack([k[name].astype(np.float64) for name in k.dtype.names], axis=1)
+            out["descriptors"][r, :m] = d
+            out["rays"][r, :m] = bp
+            out["ray_valid"][r, :m] = bv
+    if C > 1:
+        import torch
+        idx = torch.as_tensor(frames, device=d_match.device)
+        rows = d_match[idx].cpu().numpy().view(capi.STEREO_MATCH_DTYPE).reshape(len(frames), K)
+        live = np.arange(K)[None, :] < out["keypoint_counts"][::C, None]
+        for name in ("k1", "dist", "initialisable"):
+            out["match_" + name] = np.where(live, rows[name], 0).astype(np.float64)
+        out["match_hp_W"] = np.where(live[:, :, None], rows["hp_W"], 0.0)
+    os.makedirs(path, exist_ok=True)
+    for name, arr in out.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
 
 
 def self_launch(args):
@@ -390,6 +441,13 @@ def run_map_workload(args, torch, capi, synth, dev):
         step()
     st.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:  # the best landmark and its Hamming distance per keypoint, for a sample of the frames
+        frames = dump_sample(B, K * 2 * 8)
+        idx = torch.as_tensor(frames, device=dev)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "sample_frames.npy"), frames.astype(np.float64))
+        np.save(os.path.join(args.dump_outputs, "best_landmark.npy"), d_lm[idx].cpu().numpy().astype(np.float64))
+        np.save(os.path.join(args.dump_outputs, "best_distance.npy"), d_bd[idx].cpu().numpy().astype(np.float64))
     ms, cnt = fe.profile_read()["map"]
     launch_ms = ms / cnt
     lm = d_lm.cpu().numpy()
@@ -746,7 +804,7 @@ def main():
                     help="independent contexts/streams the batch is split over on each GPU.  With 3-4 lanes the "
                          "latency-bound kernels of one lane hide behind the VALU-bound score kernel of another "
                          "(+9-11 %% at the same frames per step), but the score kernel then shares the GPU while it "
-                         "is being timed; the default run reports that configuration as the `four_lanes` leg")
+                         "is being timed; a --full run reports that configuration as the `four_lanes` leg")
     ap.add_argument("--stagger", type=int, default=1,
                     help="with --lanes > 1: serialise the score kernels of the lanes (okvfe_set_heavy_kernel_chaining "
                          "mode 1) so that the lanes run out of phase")
@@ -763,7 +821,7 @@ def main():
     ap.add_argument("--feed", choices=("device", "host"), default="device",
                     help="device = images resident in HBM (the metric); host = every step copies its "
                          "images from pinned host memory (okvfe_detect_describe_batch_host, copy "
-                         "overlapped with the previous step's kernels).  The device-fed run also "
+                         "overlapped with the previous step's kernels).  A device-fed --full run also "
                          "reports a short host-fed measurement as `host_fed`")
     ap.add_argument("--content", choices=("corners", "checker"), default="corners")
     ap.add_argument("--box-widen", type=float, default=1.0,
@@ -772,10 +830,19 @@ def main():
                          "cpu_baseline leg gets the same pattern")
     ap.add_argument("--pipelined-lanes", type=int, default=4,
                     help="lanes of the `pipelined_lanes` leg (okvfe_set_internal_lanes(-K) on the one context of `value`)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the host-fed / dense-content legs")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: per-stage and roofline blocks, the CPU baseline with "
+                         "its parity check, the capacity check, the informational legs (host-fed, dense / real content, "
+                         "four / pipelined lanes, batch sweep, B = 1 latency) and `long_region`.  Without it a run sets "
+                         "up, warms up, times --steps steps and prints the headline line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller (a fixed, "
+                         "seeded sample of its frames) as DIR/<name>.npy in float32 / float64")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline leg")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the host-fed / dense-content legs")
     ap.add_argument("--exact-steps", action="store_true",
-                    help="skip the informational `long_region` leg (the timed region is always exactly --steps)")
+                    help="with --full: skip the informational `long_region` leg (the timed region is always exactly "
+                         "--steps)")
     args = ap.parse_args()
     steps_flag = args.steps is not None
     if args.steps is None:
@@ -822,6 +889,8 @@ def main():
         args.batch = {"euroc": 3072, "tumvi": 1024, "hilti": 960, "mono640": 3072, "tumvi512": 1536, "d455": 1536,
                       "d435i": 1536}[args.workload]
     if args.workload == "hilti" and args.split == "cameras":
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs: not available with --split cameras")
         res = run_hilti_split_cameras(args, torch, dist, capi, synth, world, rank, dev)
         if res is not None:
             print(json.dumps(res), flush=True)
@@ -937,10 +1006,13 @@ def main():
     while time.perf_counter() - t_ramp < 0.3:
         step(args.feed)
         torch.cuda.synchronize()
+    # the ramp's step count depends on the clock: the variant sequence starts afresh after it, so that the
+    # last timed step -- the one --dump-outputs writes -- has the same host parameters in every run
+    state["step"] = 0
     for _ in range(args.warmup):
         step(args.feed)
     torch.cuda.synchronize()
-    if os.environ.get("OKVFE_PMC_CALIB"):
+    if args.full and os.environ.get("OKVFE_PMC_CALIB"):
         # counter calibration for the --pmc passes (tools/collect_profiles.sh): a device-to-device
         # copy of known size in the same process, so FETCH_SIZE / WRITE_SIZE units can be checked
         cal_src = torch.zeros(256 << 20, dtype=torch.uint8, device=dev)
@@ -948,16 +1020,52 @@ def main():
         for _ in range(3):
             torch.bitwise_not(cal_src, out=cal_dst)  # a kernel name of its own in the csv
         torch.cuda.synchronize()
-    # timed region: only the dominant kernel (score+NMS) carries HIP events, on its launch stream;
+    # timed region (--full): only the dominant kernel (score+NMS) carries HIP events, on its launch stream;
     # the full per-stage breakdown is taken in a short extra pass after the timed region
-    for lane in lanes:
-        lane[0].profile_enable(True, stages=("harris",))
+    if args.full:
+        for lane in lanes:
+            lane[0].profile_enable(True, stages=("harris",))
     # the timed region is EXACTLY args.steps steps (the contract).  A region shorter than
-    # MIN_TIMED_S cannot resolve a 2 % change, so a second, longer region is timed as well and
+    # MIN_TIMED_S cannot resolve a 2 % change, so with --full a second, longer region is timed as well and
     # reported beside it as `long_region` -- `value` always comes from the requested steps.
     elapsed, last_v = timed(args.steps, args.feed)
     elapsed_local = state["elapsed_local"]
     steps_timed = args.steps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, capi, [lane[0] for lane in lanes], d_match, B, Bl, C, cfg.max_kpts)
+    unit = {1: "frames/s", 2: "stereo-frames/s"}.get(C, "multiframes/s")
+    metric, text = WORKLOAD_TEXT[args.workload]
+    if args.workload == "hilti":
+        text += ", forward pair matched (frame-sharded variant; --split cameras runs the 9-pair rig)"
+    headline = {
+        "metric": metric,
+        "value": world * B * steps_timed / elapsed,
+        "unit": unit,
+        "n_gpus": world,
+        "steps": steps_timed,
+        "warmup": args.warmup,
+        "ms_per_step": 1e3 * elapsed / steps_timed,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u8/int32 (detect, describe, Hamming) + f64 (match gate)",
+        "data": "synthetic",
+        "config": {"workload": text,
+                   "stereo_frames_per_step_per_gpu": B, "lanes_per_gpu": S,
+                   "score_kernels_serialised_across_lanes": bool(S > 1 and args.stagger),
+                   "stereo_frames_per_launch": Bl, "distinct_frames": n_content,
+                   "content": args.content, "feed": args.feed,
+                   "host_parameter_variants": N_VARIANTS,
+                   "cameras_per_multiframe": C,
+                   "parallelism": f"frames sharded over {world} GPU(s), no collective"},
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline), flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     long_region = None
     if elapsed < MIN_TIMED_S and not args.exact_steps and steps_flag:
         reps = int(math.ceil(MIN_TIMED_S / max(elapsed, 1e-6)))
@@ -1282,34 +1390,11 @@ def main():
         P = cfg.w * cfg.h
         stage_ms = {k: (v[0] / v[1] if v[1] else None) for k, v in prof_all.items()}
         harris_ms = prof["harris"][0] / prof["harris"][1]
-        metric, text = WORKLOAD_TEXT[args.workload]
-        if args.workload == "hilti":
-            text += ", forward pair matched (frame-sharded variant; --split cameras runs the 9-pair rig)"
-        unit = {1: "frames/s", 2: "stereo-frames/s"}.get(C, "multiframes/s")
-        result = {
-            "metric": metric,
-            "value": world * B * steps_timed / elapsed,
-            "unit": unit,
-            "n_gpus": world,
-            "ranks_seen": ranks_seen,
-            "per_rank_value": per_rank,
-            "steps": steps_timed,
-            "warmup": args.warmup,
-            "ms_per_step": 1e3 * elapsed / steps_timed,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u8/int32 (detect, describe, Hamming) + f64 (match gate)",
-            "data": "synthetic",
-            "config": {"workload": text,
-                       "stereo_frames_per_step_per_gpu": B, "lanes_per_gpu": S,
-                       "score_kernels_serialised_across_lanes": bool(S > 1 and args.stagger),
-                       "stereo_frames_per_launch": Bl, "distinct_frames": n_content,
-                       "content": args.content, "feed": args.feed,
-                       "host_parameter_variants": N_VARIANTS,
-                       "mean_keypoints_per_image": kp_total / max(1, min(n_img, C * distinct)),
-                       "cameras_per_multiframe": C,
-                       "parallelism": f"frames sharded over {world} GPU(s), no collective"},
+        result = dict(headline)
+        result["ranks_seen"] = ranks_seen
+        result["per_rank_value"] = per_rank
+        result["config"]["mean_keypoints_per_image"] = kp_total / max(1, min(n_img, C * distinct))
+        result.update({
             "roofline": roofline_block(P, n_lane_img, harris_ms, {
                 "isolated_launch_ms": iso[0] / iso[1],
                 "with_score_map": {
@@ -1351,7 +1436,7 @@ def main():
             "stage_ms_per_launch": stage_ms,
             "stage_ms_note": "all-stage event pass of 3 steps after the timed region; avg_launch_ms of "
                              "the roofline comes from the timed region itself",
-        }
+        })
         valu_issue_blocks(result["rooflines_other"], stage_ms, n_lane_img, args.workload, args.content)
         result.update(extras)
         if long_region is not None:

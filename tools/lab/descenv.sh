@@ -4,9 +4,7 @@
 for wl in ${WLS:-euroc mono640}; do
 for a in "$@"; do
   envs=""; [ "$a" != "-" ] && envs=$(echo "$a" | tr ',' ' ')
-  env $envs python bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-extras --workload $wl > gpurun_out/ab_tmp.json 2>gpurun_out/ab_tmp.err
-  python - "$a" $wl <<'PY'
-import json,sys; r=json.load(open("gpurun_out/ab_tmp.json")); s=r["stage_ms_per_launch"]; print(sys.argv[2], sys.argv[1], "ms/step %.3f describe %.3f fps %.0f"%(r["ms_per_step"], s["describe"], r["value"]))
-PY
+  env $envs python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-extras --workload $wl 2>/dev/null | grep '^{"metric"' | python -c "
+import json,sys; r=json.loads(sys.stdin.read()); s=r['stage_ms_per_launch']; print('$wl', '$a', 'ms/step %.3f describe %.3f fps %.0f'%(r['ms_per_step'], s['describe'], r['value']))"
 done
 done

@@ -76,7 +76,7 @@ out = {
     "kernel": name,
     "workload": f"{w}x{h} u8 x {n_img} images per launch (bench.py --lanes 1)",
     "command": "rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE --output-format csv -- "
-               "python bench.py --steps 3 --warmup 3 --no-cpu-baseline --lanes 1 "
+               "python bench.py --full --steps 3 --warmup 3 --no-cpu-baseline --lanes 1 "
                "(two separate passes, tools/collect_profiles.sh)",
     "FETCH_SIZE_KiB": fetch, "WRITE_SIZE_KiB": write,
     "calibration": {"kernel": "at::native bitwise_not, 262144 KiB read + 262144 KiB written",
