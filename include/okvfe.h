@@ -49,7 +49,7 @@
 extern "C" {
 #endif
 
-#define OKVFE_ABI_VERSION 7
+#define OKVFE_ABI_VERSION 8
 #define OKVFE_STREAM_LEGACY_DEFAULT ((void*)(uintptr_t)1) /* = hipStreamLegacy */
 #define OKVFE_DESC_BYTES 48 /* okvis_frontend/include/DBoW2/FBrisk.hpp:35 */
 
@@ -78,7 +78,17 @@ typedef struct okvfe_keypoint {
 typedef enum okvfe_distortion {
   OKVFE_DIST_NONE = 0,
   OKVFE_DIST_RADTAN = 1,     /* okvis::cameras::RadialTangentialDistortion */
-  OKVFE_DIST_EQUIDISTANT = 2 /* okvis::cameras::EquidistantDistortion */
+  OKVFE_DIST_EQUIDISTANT = 2, /* okvis::cameras::EquidistantDistortion */
+  OKVFE_DIST_RADTAN8 = 3      /* okvis::cameras::RadialTangentialDistortion8 (OpenCV "rational"
+                               * model, k1 k2 p1 p2 k3 k4 k5 k6); ABI 8, okvfe_camera_ext only.
+                               * distort: rad = (1 + rho (k1 + rho (k2 + k3 rho))) /
+                               * (1 + rho (k4 + rho (k5 + k6 rho))), rho = |u|^2; it FAILS for
+                               * rho > 9 (projection status Invalid, awareness-map Jacobian 0).
+                               * undistort: 5 Gauss-Newton steps, success at chi2 < 1e-4 (the
+                               * 4-coefficient model: 1e-6).  Defined deviation: the reference
+                               * ignores a failing distort inside its Gauss-Newton loop and reads
+                               * an uninitialised point; here such a step ends the iteration and
+                               * the back-projection is invalid. */
 } okvfe_distortion;
 
 /* okvis::cameras::PinholeCamera<DISTORTION_T> intrinsics
@@ -88,7 +98,15 @@ typedef struct okvfe_camera {
   double fu, fv, cu, cv;
   int32_t distortion; /* okvfe_distortion */
   double d[4];        /* k1 k2 p1 p2 | k1 k2 k3 k4 */
-} okvfe_camera;
+} okvfe_camera;         /* 80 bytes; distortion 0..2 */
+
+/* ABI 8: every distortion type, OKVFE_DIST_RADTAN8 included.  For RADTAN8 base.d = k1 k2 p1 p2
+ * and d_ext = k3 k4 k5 k6 -- the order of PinholeCamera<RadialTangentialDistortion8>::
+ * getIntrinsics() after fu fv cu cv; for types 0..2 d_ext is ignored.  112 bytes. */
+typedef struct okvfe_camera_ext {
+  okvfe_camera base;
+  double d_ext[4];
+} okvfe_camera_ext;
 
 /* T_WC as rotation (row-major) and translation: p_W = C p_C + r. */
 typedef struct okvfe_pose {
@@ -173,9 +191,15 @@ okvfe_status okvfe_set_camera_maps(okvfe_ctx* ctx, int32_t cam, const float* ray
  * (= PinholeCamera::initialiseCameraAwarenessMaps, PinholeCamera.hpp:180-208)
  * and uploads them; also stores the intrinsics for back-projection. */
 okvfe_status okvfe_set_camera(okvfe_ctx* ctx, int32_t cam, const okvfe_camera* camera);
+/* ABI 8: the same for every distortion type (OKVFE_DIST_RADTAN8 included).  The plain okvfe_camera
+ * entry points forward here with d_ext zeroed and reject OKVFE_DIST_RADTAN8 with
+ * OKVFE_ERR_INVALID_ARGUMENT (its last four coefficients do not fit okvfe_camera). */
+okvfe_status okvfe_set_camera_ext(okvfe_ctx* ctx, int32_t cam, const okvfe_camera_ext* camera);
 /* Host helper: fills caller buffers with the awareness maps of a camera. */
 okvfe_status okvfe_build_awareness_maps(const okvfe_camera* camera, float* rays_hw3,
                                         float* jacobians_hw6);
+okvfe_status okvfe_build_awareness_maps_ext(const okvfe_camera_ext* camera, float* rays_hw3,
+                                            float* jacobians_hw6);
 
 /* Host helper: field-of-view overlap of `camera` as seen by `other`
  * (= NCameraSystem::computeOverlaps, okvis_cv/src/NCameraSystem.cpp:48-119; decides which
@@ -184,6 +208,9 @@ okvfe_status okvfe_build_awareness_maps(const okvfe_camera* camera, float* rays_
 okvfe_status okvfe_camera_overlap(const okvfe_camera* camera, const okvfe_camera* other,
                                   const double R_other_cam[9], uint8_t* mask_hw,
                                   int32_t* has_overlap);
+okvfe_status okvfe_camera_overlap_ext(const okvfe_camera_ext* camera, const okvfe_camera_ext* other,
+                                      const double R_other_cam[9], uint8_t* mask_hw,
+                                      int32_t* has_overlap);
 
 /* ---- detect + describe, host buffers (cv::Feature2D-shaped) -------------- */
 /* One image: detect(), compute() and Frame::computeBackProjections in one
@@ -434,6 +461,14 @@ okvfe_status okvfe_match_motion_stereo(okvfe_ctx* ctx, const okvfe_camera* camer
                                        const uint8_t* valid1, const uint8_t* matched1, int32_t n1,
                                        const okvfe_pose* T_WC0, const okvfe_pose* T_WC1,
                                        okvfe_motion_match* matches /* n0 */);
+okvfe_status okvfe_match_motion_stereo_ext(okvfe_ctx* ctx, const okvfe_camera_ext* camera,
+                                           const uint8_t* desc0, const okvfe_keypoint* kp0,
+                                           const double* backproj0, const uint8_t* valid0,
+                                           const uint8_t* skip0, int32_t n0, const uint8_t* desc1,
+                                           const okvfe_keypoint* kp1, const double* backproj1,
+                                           const uint8_t* valid1, const uint8_t* matched1, int32_t n1,
+                                           const okvfe_pose* T_WC0, const okvfe_pose* T_WC1,
+                                           okvfe_motion_match* matches /* n0 */);
 
 /* = Frontend::matchToMapByThread for the 3-D landmarks (Frontend.cpp:1552-1589), all keypoints
  * in one call.  Landmarks in the caller's order (ascending LandmarkId in the reference);

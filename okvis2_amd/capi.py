@@ -17,7 +17,8 @@ LIB_PATH = os.environ.get("OKVFE_LIB") or os.path.join(_HERE, "libokvfe.so")  # 
 OK = 0
 ERR_INVALID_ARGUMENT, ERR_NO_DEVICE, ERR_OUT_OF_MEMORY, ERR_UNSUPPORTED, ERR_CAPACITY, ERR_DEVICE, \
     ERR_NOT_READY = 1, 2, 3, 4, 5, 6, 7
-ABI_VERSION = 7
+ABI_VERSION = 8
+DIST_NONE, DIST_RADTAN, DIST_EQUIDISTANT, DIST_RADTAN8 = 0, 1, 2, 3
 SCORE_HARRIS, SCORE_AGAST_9_16, SCORE_BRISK_SCALESPACE = 0, 1, 2
 DESC_BYTES = 48
 
@@ -44,6 +45,11 @@ class Camera(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("fu", C.c_double), ("fv", C.c_double),
                 ("cu", C.c_double), ("cv", C.c_double), ("distortion", C.c_int32),
                 ("d", C.c_double * 4)]
+
+
+class CameraExt(C.Structure):
+    """okvfe_camera_ext (ABI 8): base.d = k1 k2 p1 p2, d_ext = k3 k4 k5 k6 of DIST_RADTAN8."""
+    _fields_ = [("base", Camera), ("d_ext", C.c_double * 4)]
 
 
 class Pose(C.Structure):
@@ -101,6 +107,8 @@ EXPORTS = [
     "okvfe_comm_world", "okvfe_comm_rank", "okvfe_comm_last_error", "okvfe_gather_blocks",
     "okvfe_device_alloc", "okvfe_device_free", "okvfe_stream_create", "okvfe_stream_destroy",
     "okvfe_stream_synchronize", "okvfe_copy_to_device", "okvfe_copy_to_host", "okvfe_device_fill",
+    "okvfe_set_camera_ext", "okvfe_build_awareness_maps_ext", "okvfe_camera_overlap_ext",
+    "okvfe_match_motion_stereo_ext",
 ]
 
 STAGES = ["harris", "nms", "sort", "select", "map", "describe", "compact", "match"]
@@ -235,13 +243,30 @@ def _s(stream):
     return C.c_void_p(int(stream)) if int(stream) else None
 
 
-def make_camera(cam) -> Camera:
+def make_camera(cam):
+    """okvfe_camera of a synth.Camera-like object; a CameraExt for DIST_RADTAN8 (8 coefficients),
+    which the callers route to the _ext entry points."""
     c = Camera()
     c.width, c.height, c.fu, c.fv, c.cu, c.cv = cam.w, cam.h, cam.fu, cam.fv, cam.cu, cam.cv
     c.distortion = cam.dist_type
     for i in range(4):
         c.d[i] = cam.d[i]
-    return c
+    if cam.dist_type != DIST_RADTAN8:
+        return c
+    e = CameraExt()
+    e.base = c
+    for i in range(4):
+        e.d_ext[i] = cam.d[4 + i]
+    return e
+
+
+def _camera_fn(name, *cams):
+    """The entry point `name` or, when a camera is DIST_RADTAN8, its _ext form; and the structs."""
+    structs = [make_camera(c) for c in cams]
+    if not any(isinstance(s, CameraExt) for s in structs):
+        return getattr(lib(), name), structs
+    ext = [s if isinstance(s, CameraExt) else CameraExt(base=s) for s in structs]
+    return getattr(lib(), name + "_ext"), ext
 
 
 def make_pose(Cm, r) -> Pose:
@@ -290,10 +315,10 @@ def scale_index(size) -> int:
 
 
 def build_awareness_maps(cam):
-    c = make_camera(cam)
+    fn, (c,) = _camera_fn("okvfe_build_awareness_maps", cam)
     rays = np.zeros((cam.h, cam.w, 3), dtype=np.float32)
     jac = np.zeros((cam.h, cam.w, 6), dtype=np.float32)
-    st = lib().okvfe_build_awareness_maps(C.byref(c), _p(rays), _p(jac))
+    st = fn(C.byref(c), _p(rays), _p(jac))
     if st != OK:
         raise OkvfeError(st, lib().okvfe_last_error(None).decode())
     return rays, jac
@@ -339,11 +364,11 @@ def fbrisk_mean(descriptors) -> np.ndarray:
 
 
 def camera_overlap(cam, other, R_other_cam, want_mask=False):
-    c, o = make_camera(cam), make_camera(other)
+    fn, (c, o) = _camera_fn("okvfe_camera_overlap", cam, other)
     R = (C.c_double * 9)(*[float(v) for v in np.asarray(R_other_cam).reshape(-1)])
     mask = np.zeros((cam.h, cam.w), dtype=np.uint8) if want_mask else None
     has = C.c_int32()
-    st = lib().okvfe_camera_overlap(C.byref(c), C.byref(o), R, _p(mask), C.byref(has))
+    st = fn(C.byref(c), C.byref(o), R, _p(mask), C.byref(has))
     if st != OK:
         raise OkvfeError(st, lib().okvfe_last_error(None).decode())
     return (bool(has.value), mask) if want_mask else bool(has.value)
@@ -391,8 +416,8 @@ class Frontend:
 
     # -- setup ----------------------------------------------------------------------------
     def set_camera(self, slot, cam):
-        c = make_camera(cam)
-        self._check(lib().okvfe_set_camera(self._h, int(slot), C.byref(c)))
+        fn, (c,) = _camera_fn("okvfe_set_camera", cam)
+        self._check(fn(self._h, int(slot), C.byref(c)))
 
     def set_camera_maps(self, slot, rays, jac, fu):
         rays = np.ascontiguousarray(rays, dtype=np.float32)
@@ -556,9 +581,9 @@ class Frontend:
         out = np.zeros(max(n0, 1), dtype=MOTION_MATCH_DTYPE)
         arrs = [None if a is None else np.ascontiguousarray(a)
                 for a in (desc0, kp0, bp0, bpv0, skip0, desc1, kp1, bp1, bpv1, matched1)]
-        c = make_camera(cam)
+        fn, (c,) = _camera_fn("okvfe_match_motion_stereo", cam)
         P0, P1 = make_pose(*T0), make_pose(*T1)
-        self._check(lib().okvfe_match_motion_stereo(
+        self._check(fn(
             self._h, C.byref(c), _p(arrs[0]), _p(arrs[1]), _p(arrs[2]), _p(arrs[3]), _p(arrs[4]), n0,
             _p(arrs[5]), _p(arrs[6]), _p(arrs[7]), _p(arrs[8]), _p(arrs[9]), n1, C.byref(P0),
             C.byref(P1), _p(out)))

@@ -1,7 +1,8 @@
 // camera_dev.h -- device-side pinhole camera model (FP64), shared by k_describe.hip and k_match.hip.
 // Restates okvis::cameras::PinholeCamera<D>::backProject / project and the distortion models
 // (okvis_cv/include/okvis/cameras/implementation/PinholeCamera.hpp:241-283,574-593,
-//  RadialTangentialDistortion.hpp:90-135,214-252, EquidistantDistortion.hpp:87-171,319-351).
+//  RadialTangentialDistortion.hpp:90-135,214-252, EquidistantDistortion.hpp:87-171,319-351,
+//  RadialTangentialDistortion8.hpp:108-222,326-364 via radtan8_distortion.h).
 // Component-wise, sums left to right, no FMA (-ffp-contract=off).
 //
 // Attribution: the distortion formulas in distort() below (radial-tangential value + Jacobian, and
@@ -18,15 +19,23 @@
 #include "atan_fixed.h"
 #include "equidistant_jacobian.h"
 #include "okvfe_internal.h"
+#include "radtan8_distortion.h"
 
 namespace okvfe {
 namespace cam {
 
-__device__ inline void distort(const DeviceCamera& c, double u0, double u1, double out[2], double J[4]) {
+// kRT8: the form that also knows OKVFE_DIST_RADTAN8 (radtan8_distortion.h).  The host launches it only
+// when a camera slot of the call holds such a camera, so the kernels of the other three models keep
+// their code (and registers) exactly.  distort returns false where the model fails (RADTAN8, rho > 9).
+template <bool kRT8 = false>
+__device__ inline bool distort(const DeviceCamera& c, double u0, double u1, double out[2], double J[4]) {
+  if constexpr (kRT8) {
+    if (c.distortion == OKVFE_DIST_RADTAN8) return radtan8_distort(u0, u1, c.d, out, J);
+  }
   if (c.distortion == OKVFE_DIST_NONE) {
     out[0] = u0; out[1] = u1;
     J[0] = 1.0; J[1] = 0.0; J[2] = 0.0; J[3] = 1.0;
-    return;
+    return true;
   }
   if (c.distortion == OKVFE_DIST_RADTAN) {
     const double k1 = c.d[0], k2 = c.d[1], p1 = c.d[2], p2 = c.d[3];
@@ -41,7 +50,7 @@ __device__ inline void distort(const DeviceCamera& c, double u0, double u1, doub
     J[2] = k1 * 2.0 * u0 * u1 + k2 * 4 * rho_u * u0 * u1 + p1 * 2.0 * u0 + 2.0 * p2 * u1;
     J[1] = J[2];
     J[3] = 1 + rad_dist_u + k1 * 2.0 * my_u + k2 * rho_u * 4 * my_u + 6 * p1 * u1 + 2.0 * p2 * u0;
-    return;
+    return true;
   }
   // equidistant; atan_fixed: the same operation sequence as on the host (atan_fixed.h)
   const double k1 = c.d[0], k2 = c.d[1], k3 = c.d[2], k4 = c.d[3];
@@ -60,8 +69,13 @@ __device__ inline void distort(const DeviceCamera& c, double u0, double u1, doub
   } else {
     J[0] = 1.0; J[1] = 0.0; J[2] = 0.0; J[3] = 1.0;
   }
+  return true;
 }
 
+// Gauss-Newton undistortion: 5 steps for the radial-tangential models, 20 for equidistant; success at
+// chi2 < 1e-6 (RADTAN8: 1e-4), early stop at 1e-15.  A RADTAN8 step whose distort fails ends the
+// iteration with the back-projection invalid (okvfe.h, OKVFE_DIST_RADTAN8).
+template <bool kRT8 = false>
 __device__ inline bool backproject(const DeviceCamera& c, double px, double py, double dir[3]) {
   const double pd0 = (px - c.cu) * c.one_over_fu;
   const double pd1 = (py - c.cv) * c.one_over_fv;
@@ -70,10 +84,15 @@ __device__ inline bool backproject(const DeviceCamera& c, double px, double py, 
   if (c.distortion == OKVFE_DIST_NONE) {
     success = true;
   } else {
-    const int n = c.distortion == OKVFE_DIST_RADTAN ? 5 : 20;
+    const bool rt8 = kRT8 && c.distortion == OKVFE_DIST_RADTAN8;
+    const int n = c.distortion == OKVFE_DIST_RADTAN || rt8 ? 5 : 20;
+    const double chi2_ok = rt8 ? 1e-4 : 1e-6;
     for (int i = 0; i < n; ++i) {
       double xt[2], E[4];
-      distort(c, x0, x1, xt, E);
+      if (!distort<kRT8>(c, x0, x1, xt, E)) {
+        success = false;
+        break;
+      }
       const double e0 = pd0 - xt[0], e1 = pd1 - xt[1];
       const double a = E[0] * E[0] + E[2] * E[2];
       const double b = E[0] * E[1] + E[2] * E[3];
@@ -91,7 +110,7 @@ __device__ inline bool backproject(const DeviceCamera& c, double px, double py, 
       x0 += du0;
       x1 += du1;
       const double chi2 = e0 * e0 + e1 * e1;
-      if (chi2 < 1e-6) success = true;
+      if (chi2 < chi2_ok) success = true;
       if (chi2 < 1e-15) {
         success = true;
         break;
@@ -107,11 +126,12 @@ __device__ inline bool backproject(const DeviceCamera& c, double px, double py, 
 
 // PinholeCamera::project without Jacobian; status 0 = Successful, 1 = OutsideImage, 3 = Behind,
 // 4 = Invalid (PinholeCamera.hpp:241-283, CameraBase.hpp:97-106)
+template <bool kRT8 = false>
 __device__ inline int project(const DeviceCamera& c, int w, int h, const double p[3], double pt[2]) {
   if (fabs(p[2]) < 1.0e-12) return 4;
   const double rz = 1.0 / p[2];
   double dist[2], J[4];
-  distort(c, p[0] * rz, p[1] * rz, dist, J);
+  if (!distort<kRT8>(c, p[0] * rz, p[1] * rz, dist, J)) return 4;
   pt[0] = c.fu * dist[0] + c.cu;
   pt[1] = c.fv * dist[1] + c.cv;
   if (pt[0] < 0.0 || pt[1] < 0.0) return 1;

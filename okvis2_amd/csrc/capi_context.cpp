@@ -167,14 +167,23 @@ void ring_destroy(okvfe_ctx::ParamRing* r) {
   if (r->d) (void)hipFree(r->d);
 }
 
-DeviceCamera to_device_camera(const okvfe_camera& c) {
+DeviceCamera to_device_camera(const okvfe_camera_ext& ce) {
+  const okvfe_camera& c = ce.base;
   DeviceCamera d{};
   d.fu = c.fu; d.fv = c.fv; d.cu = c.cu; d.cv = c.cv;
   d.one_over_fu = 1.0 / c.fu;
   d.one_over_fv = 1.0 / c.fv;
   for (int i = 0; i < 4; ++i) d.d[i] = c.d[i];
+  if (c.distortion == OKVFE_DIST_RADTAN8)
+    for (int i = 0; i < 4; ++i) d.d[4 + i] = ce.d_ext[i];
   d.distortion = c.distortion;
   return d;
+}
+
+okvfe_camera_ext widen_camera(const okvfe_camera& c) {
+  okvfe_camera_ext e{};
+  e.base = c;
+  return e;
 }
 
 PairParams to_pair_params(const okvfe_stereo_pair& p) {
@@ -343,20 +352,41 @@ uint32_t okvfe_popcnt_xor(const uint8_t* a, const uint8_t* b, int32_t n128) {
   return c;
 }
 
-okvfe_status okvfe_build_awareness_maps(const okvfe_camera* camera, float* rays_hw3,
-                                        float* jacobians_hw6) {
-  if (!camera || !rays_hw3 || !jacobians_hw6 || camera->width <= 0 || camera->height <= 0)
+static bool known_distortion(int32_t t) { return t >= OKVFE_DIST_NONE && t <= OKVFE_DIST_RADTAN8; }
+
+okvfe_status okvfe_build_awareness_maps_ext(const okvfe_camera_ext* camera, float* rays_hw3,
+                                            float* jacobians_hw6) {
+  if (!camera || !rays_hw3 || !jacobians_hw6 || camera->base.width <= 0 || camera->base.height <= 0 ||
+      !known_distortion(camera->base.distortion))
     return fail(nullptr, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_build_awareness_maps: bad argument");
   build_awareness_maps(*camera, rays_hw3, jacobians_hw6);
   return OKVFE_OK;
 }
 
-okvfe_status okvfe_camera_overlap(const okvfe_camera* camera, const okvfe_camera* other,
-                                  const double R_other_cam[9], uint8_t* mask_hw, int32_t* has_overlap) {
-  if (!camera || !other || !R_other_cam || !has_overlap || camera->width <= 0 || camera->height <= 0)
+// the plain okvfe_camera entry points: types 0..2 only (RADTAN8's k3..k6 do not fit), d_ext = 0
+okvfe_status okvfe_build_awareness_maps(const okvfe_camera* camera, float* rays_hw3,
+                                        float* jacobians_hw6) {
+  if (!camera || camera->distortion == OKVFE_DIST_RADTAN8)
+    return fail(nullptr, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_build_awareness_maps: bad argument");
+  const okvfe_camera_ext e = widen_camera(*camera);
+  return okvfe_build_awareness_maps_ext(&e, rays_hw3, jacobians_hw6);
+}
+
+okvfe_status okvfe_camera_overlap_ext(const okvfe_camera_ext* camera, const okvfe_camera_ext* other,
+                                      const double R_other_cam[9], uint8_t* mask_hw, int32_t* has_overlap) {
+  if (!camera || !other || !R_other_cam || !has_overlap || camera->base.width <= 0 || camera->base.height <= 0 ||
+      !known_distortion(camera->base.distortion) || !known_distortion(other->base.distortion))
     return fail(nullptr, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_camera_overlap: bad argument");
   *has_overlap = camera_overlap(*camera, *other, R_other_cam, mask_hw) ? 1 : 0;
   return OKVFE_OK;
+}
+
+okvfe_status okvfe_camera_overlap(const okvfe_camera* camera, const okvfe_camera* other,
+                                  const double R_other_cam[9], uint8_t* mask_hw, int32_t* has_overlap) {
+  if (!camera || !other || camera->distortion == OKVFE_DIST_RADTAN8 || other->distortion == OKVFE_DIST_RADTAN8)
+    return fail(nullptr, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_camera_overlap: bad argument");
+  const okvfe_camera_ext a = widen_camera(*camera), b = widen_camera(*other);
+  return okvfe_camera_overlap_ext(&a, &b, R_other_cam, mask_hw, has_overlap);
 }
 
 }  // extern "C"
@@ -688,17 +718,28 @@ okvfe_status okvfe_set_camera_maps(okvfe_ctx* ctx, int32_t cam, const float* ray
 
 okvfe_status okvfe_set_camera(okvfe_ctx* ctx, int32_t cam, const okvfe_camera* camera) {
   if (!ctx) return OKVFE_ERR_INVALID_ARGUMENT;
+  if (!camera || camera->distortion == OKVFE_DIST_RADTAN8) {
+    ctx->ahead.valid = false;
+    return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_set_camera: bad argument (cam=%d)", cam);
+  }
+  const okvfe_camera_ext e = widen_camera(*camera);
+  return okvfe_set_camera_ext(ctx, cam, &e);
+}
+
+okvfe_status okvfe_set_camera_ext(okvfe_ctx* ctx, int32_t cam, const okvfe_camera_ext* camera_ext) {
+  if (!ctx) return OKVFE_ERR_INVALID_ARGUMENT;
   ctx->ahead.valid = false;
+  const okvfe_camera* camera = camera_ext ? &camera_ext->base : nullptr;
   if (!camera || cam < 0 || cam >= ctx->cfg.num_cameras || camera->width != ctx->w ||
       camera->height != ctx->h || !(camera->fu > 0.0) || !(camera->fv > 0.0) ||
-      camera->distortion < 0 || camera->distortion > 2)
+      !known_distortion(camera->distortion))
     return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_set_camera: bad argument (cam=%d)", cam);
   const size_t P = (size_t)ctx->w * ctx->h;
   std::vector<float> rays(P * 3), jac(P * 6);
-  build_awareness_maps(*camera, rays.data(), jac.data());
+  build_awareness_maps(*camera_ext, rays.data(), jac.data());
   okvfe_status st = okvfe_set_camera_maps(ctx, cam, rays.data(), jac.data(), (float)camera->fu);
   if (st != OKVFE_OK) return st;
-  ctx->h_cams[cam] = to_device_camera(*camera);
+  ctx->h_cams[cam] = to_device_camera(*camera_ext);
   ctx->cam_has_intrinsics[cam] = true;
   HIP_TRY(ctx, hipMemcpy(ctx->d_cams + cam, &ctx->h_cams[cam], sizeof(DeviceCamera), hipMemcpyHostToDevice));
   return OKVFE_OK;

@@ -55,6 +55,7 @@ static okvfe_status upload_image_params(okvfe_ctx* ctx, int n_images, const int3
   ctx->aware_fast = true;
   ctx->all_aware = n_images > 0;
   ctx->none_aware = true;
+  ctx->rt8_call = false;
   for (int i = 0; i < n_images; ++i) {
     ImageParams& p = prm[i];
     p.cam = cam_ids ? cam_ids[i] : -1;
@@ -80,6 +81,7 @@ static okvfe_status upload_image_params(okvfe_ctx* ctx, int n_images, const int3
       p.fu = 1.0f;
     }
     if (p.cam >= 0 && !ctx->cam_has_intrinsics[p.cam]) p.cam = aware ? p.cam : -1;
+    if (p.cam >= 0 && ctx->h_cams[p.cam].distortion == OKVFE_DIST_RADTAN8) ctx->rt8_call = true;
   }
   // intrinsics are needed for back-projection; a slot with maps only (set_camera_maps) keeps its
   // cam id for the maps and gets invalid back-projections (DeviceCamera zeroed -> fu = 0)
@@ -579,7 +581,7 @@ okvfe_status describe_stage(okvfe_ctx* ctx, const uint8_t* images_dev, int n_ima
     StageTimer t(ctx, OKVFE_STAGE_COMPACT, s);
     launch_compact(n_images, ctx->d_cams, ctx->d_prm, ctx->d_kps_tmp, ctx->d_desc_tmp, ctx->d_valid_tmp,
                    ctx->d_det_count, ctx->kp_cap, ctx->d_kps, ctx->d_desc, ctx->d_bp, ctx->d_bpv,
-                   ctx->d_count, s);
+                   ctx->d_count, s, ctx->rt8_call);
   }
   HIP_TRY(ctx, hipGetLastError());
   ctx->last_stream = s;
@@ -681,6 +683,7 @@ void bind_lane(okvfe_ctx* v, okvfe_ctx* p, int first, int n) {
   v->d_prm = p->d_prm + f;
   v->d_cams = p->d_cams; v->d_rays_ptrs = p->d_rays_ptrs; v->d_jac_ptrs = p->d_jac_ptrs;
   v->wide_patches = p->wide_patches; v->all_aware = p->all_aware; v->aware_fast = p->aware_fast;
+  v->rt8_call = p->rt8_call;
   v->aware_extra_box = p->aware_extra_box; v->box_class_call = p->box_class_call;
   v->none_aware = p->none_aware; v->rot_fast_call = p->rot_fast_call;
   v->fuse_setup = p->fuse_setup;
@@ -1183,7 +1186,7 @@ okvfe_status okvfe_compute(okvfe_ctx* ctx, const uint8_t* image, size_t stride, 
                   ctx->all_aware, pattern_box_class(ctx->host_pattern), aware_box_for_call(ctx, ctx->d_img_stage),
                   ctx->none_aware && pattern_rot_ok(ctx->host_pattern));
   launch_compact(1, ctx->d_cams, ctx->d_prm, ctx->d_kps_tmp, ctx->d_desc_tmp, ctx->d_valid_tmp, ctx->d_det_count,
-                 ctx->kp_cap, ctx->d_kps, ctx->d_desc, ctx->d_bp, ctx->d_bpv, ctx->d_count, s);
+                 ctx->kp_cap, ctx->d_kps, ctx->d_desc, ctx->d_bp, ctx->d_bpv, ctx->d_count, s, ctx->rt8_call);
   HIP_TRY(ctx, hipGetLastError());
   ctx->last_n_images = 1;
   ctx->last_stream = s;

@@ -118,7 +118,8 @@ okvfe_status okvfe_match_to_map_landmarks(okvfe_ctx* ctx, int32_t cam, const okv
   launch_prepare_landmarks(D(o_hp), D(o_q), I(o_ob), nl, I(o_op), D(o_obp),
                            reinterpret_cast<const okvfe_pose*>(base + o_poses), *T_WC1, ctx->d_cams + cam, ctx->w,
                            ctx->h, reprojection_threshold, exclusive ? 1 : 0, std::cos(10.0 / focal), std::cos(0.6),
-                           I(o_st), I(o_nd), I(o_rows), D(o_proj), D(o_e), D(o_r), s);
+                           I(o_st), I(o_nd), I(o_rows), D(o_proj), D(o_e), D(o_r), s,
+                           dc.distortion == OKVFE_DIST_RADTAN8);
   launch_compact_landmarks(I(o_st), I(o_nd), I(o_rows), D(o_proj), base + o_od, nl, 1, I(o_idx), D(o_p3), I(o_b3),
                            base + o_pool3, I(o_n3), s);
   HIP_TRY(ctx, hipGetLastError());

@@ -180,7 +180,22 @@ okvfe_status okvfe_match_motion_stereo(okvfe_ctx* ctx, const okvfe_camera* camer
                                        const uint8_t* matched1, int32_t n1, const okvfe_pose* T_WC0,
                                        const okvfe_pose* T_WC1, okvfe_motion_match* matches) {
   if (!ctx) return OKVFE_ERR_INVALID_ARGUMENT;
-  if (!camera || n0 < 0 || n1 < 0 || !T_WC0 || !T_WC1 ||
+  if (!camera || camera->distortion == OKVFE_DIST_RADTAN8)  // (its k3..k6 need okvfe_camera_ext)
+    return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_match_motion_stereo: bad argument");
+  const okvfe_camera_ext e = widen_camera(*camera);
+  return okvfe_match_motion_stereo_ext(ctx, &e, desc0, kp0, backproj0, valid0, skip0, n0, desc1, kp1, backproj1,
+                                       valid1, matched1, n1, T_WC0, T_WC1, matches);
+}
+
+okvfe_status okvfe_match_motion_stereo_ext(okvfe_ctx* ctx, const okvfe_camera_ext* camera_ext, const uint8_t* desc0,
+                                           const okvfe_keypoint* kp0, const double* backproj0, const uint8_t* valid0,
+                                           const uint8_t* skip0, int32_t n0, const uint8_t* desc1,
+                                           const okvfe_keypoint* kp1, const double* backproj1, const uint8_t* valid1,
+                                           const uint8_t* matched1, int32_t n1, const okvfe_pose* T_WC0,
+                                           const okvfe_pose* T_WC1, okvfe_motion_match* matches) {
+  if (!ctx) return OKVFE_ERR_INVALID_ARGUMENT;
+  const okvfe_camera* camera = camera_ext ? &camera_ext->base : nullptr;
+  if (!camera || camera->distortion < OKVFE_DIST_NONE || camera->distortion > OKVFE_DIST_RADTAN8 || n0 < 0 || n1 < 0 || !T_WC0 || !T_WC1 ||
       (n0 > 0 && (!desc0 || !kp0 || !backproj0 || !valid0 || !matches)) ||
       (n1 > 0 && (!desc1 || !kp1 || !backproj1 || !valid1)))
     return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_match_motion_stereo: bad argument");
@@ -212,7 +227,7 @@ okvfe_status okvfe_match_motion_stereo(okvfe_ctx* ctx, const okvfe_camera* camer
   sp.T_WC0 = *T_WC0; sp.T_WC1 = *T_WC1;
   sp.f0 = sp.f1 = 0.5 * (camera->fu + camera->fv);  // sigma = size0 / f0 * 0.125 (Frontend.cpp:1834)
   PairParams pp = to_pair_params(sp);
-  const DeviceCamera dc = to_device_camera(*camera);
+  const DeviceCamera dc = to_device_camera(*camera_ext);
   auto put = [&](size_t o, const void* src, size_t bytes) {
     if (bytes) std::memcpy(hb + o, src, bytes);
   };
@@ -246,7 +261,7 @@ okvfe_status okvfe_match_motion_stereo(okvfe_ctx* ctx, const okvfe_camera* camer
                       reinterpret_cast<double*>(base + o_b0), base + o_v0, skip0 ? base + o_s0 : nullptr, n0,
                       base + o_d1, reinterpret_cast<okvfe_keypoint*>(base + o_k1),
                       reinterpret_cast<double*>(base + o_b1), base + o_v1, matched1 ? base + o_m1 : nullptr, n1,
-                      ctx->cfg.match_threshold, out_dev, s);
+                      ctx->cfg.match_threshold, out_dev, s, dc.distortion == OKVFE_DIST_RADTAN8);
   HIP_TRY(ctx, hipGetLastError());
   if (!ctx->h_pinned_dev)
     HIP_TRY(ctx, hipMemcpyAsync(hb + o_out, base + o_out, (size_t)n0 * sizeof(okvfe_motion_match), hipMemcpyDeviceToHost, s));
@@ -414,7 +429,8 @@ okvfe_status okvfe_match_motion_stereo_blocks_device(okvfe_ctx* ctx, int32_t cam
   }
   launch_match_motion_blocks(pp, ctx->d_cams + cam, ctx->w, ctx->h, offs,
                              static_cast<const uint8_t*>(block0_dev), static_cast<const uint8_t*>(block1_dev),
-                             skip0_dev, matched1_dev, ctx->kp_cap, ctx->cfg.match_threshold, matches_dev, s);
+                             skip0_dev, matched1_dev, ctx->kp_cap, ctx->cfg.match_threshold, matches_dev, s,
+                             dc.distortion == OKVFE_DIST_RADTAN8);
   HIP_TRY(ctx, hipGetLastError());
   ctx->last_stream = s;
   return ring_release(ctx, &ctx->cls_ring, cls_slot, s);

@@ -7,7 +7,8 @@
 //                            per-pixel unit ray (CV_32FC3) and 2x3 image Jacobian (CV_32FC6).
 //   host_backproject       = PinholeCamera<D>::backProject (PinholeCamera.hpp:574-593) with the
 //                            Gauss-Newton undistortion of RadialTangentialDistortion.hpp:214-252 /
-//                            EquidistantDistortion.hpp:319-351.
+//                            EquidistantDistortion.hpp:319-351 / RadialTangentialDistortion8.hpp:326-364
+//                            (the 8-coefficient model itself: radtan8_distortion.h).
 // FP64, explicit evaluation order, compiled with -ffp-contract=off.
 //
 // Attribution: distort() keeps the reference's operation order (bit-exact FP64 depends on it) and
@@ -23,6 +24,7 @@
 #include "brisk2_pairs.h"
 #include "equidistant_jacobian.h"
 #include "okvfe_internal.h"
+#include "radtan8_distortion.h"
 
 namespace okvfe {
 
@@ -230,13 +232,24 @@ struct Mat2 {
   double a, b, c, d;  // [a b; c d]
 };
 
-void distort(const okvfe_camera& cam, Vec2 u, Vec2* out, Mat2* J) {
+// false: the model fails at this point (RADTAN8, rho > 9); out / J untouched
+bool distort(const okvfe_camera_ext& ce, Vec2 u, Vec2* out, Mat2* J) {
+  const okvfe_camera& cam = ce.base;
   if (cam.distortion == OKVFE_DIST_NONE) {
     *out = u;
     if (J) *J = {1.0, 0.0, 0.0, 1.0};
-    return;
+    return true;
   }
   const double u0 = u.x, u1 = u.y;
+  if (cam.distortion == OKVFE_DIST_RADTAN8) {
+    const double k[8] = {cam.d[0], cam.d[1], cam.d[2], cam.d[3], ce.d_ext[0], ce.d_ext[1], ce.d_ext[2], ce.d_ext[3]};
+    double o[2], j4[4];
+    if (!radtan8_distort(u0, u1, k, o, J ? j4 : nullptr)) return false;
+    out->x = o[0];
+    out->y = o[1];
+    if (J) *J = {j4[0], j4[1], j4[2], j4[3]};
+    return true;
+  }
   if (cam.distortion == OKVFE_DIST_RADTAN) {
     const double k1 = cam.d[0], k2 = cam.d[1], p1 = cam.d[2], p2 = cam.d[3];
     const double mx_u = u0 * u0;
@@ -252,7 +265,7 @@ void distort(const okvfe_camera& cam, Vec2 u, Vec2* out, Mat2* J) {
       J->b = J->c;
       J->d = 1 + rad_dist_u + k1 * 2.0 * my_u + k2 * rho_u * 4 * my_u + 6 * p1 * u1 + 2.0 * p2 * u0;
     }
-    return;
+    return true;
   }
   const double k1 = cam.d[0], k2 = cam.d[1], k3 = cam.d[2], k4 = cam.d[3];
   const double r = std::sqrt(u0 * u0 + u1 * u1);
@@ -265,7 +278,7 @@ void distort(const okvfe_camera& cam, Vec2 u, Vec2* out, Mat2* J) {
   const double scaling = (r > 1e-8) ? thetad / r : 1.0;
   out->x = scaling * u0;
   out->y = scaling * u1;
-  if (!J) return;
+  if (!J) return true;
   if (r > 1e-8) {
     // generated expression of the reference (EquidistantDistortion.hpp:128-171): equidistant_jacobian.h
     double j4[4];
@@ -277,20 +290,29 @@ void distort(const okvfe_camera& cam, Vec2 u, Vec2* out, Mat2* J) {
   } else {
     *J = {1.0, 0.0, 0.0, 1.0};
   }
+  return true;
 }
 
-bool undistort(const okvfe_camera& cam, Vec2 pd, Vec2* out) {
+// RADTAN8: 5 steps, success at chi2 < 1e-4; a step whose distort fails ends the iteration with the
+// result invalid (defined deviation, okvfe.h: the reference reads an uninitialised point there)
+bool undistort(const okvfe_camera_ext& ce, Vec2 pd, Vec2* out) {
+  const okvfe_camera& cam = ce.base;
   if (cam.distortion == OKVFE_DIST_NONE) {
     *out = pd;
     return true;
   }
-  const int iterations = cam.distortion == OKVFE_DIST_RADTAN ? 5 : 20;
+  const bool rt8 = cam.distortion == OKVFE_DIST_RADTAN8;
+  const int iterations = cam.distortion == OKVFE_DIST_RADTAN || rt8 ? 5 : 20;
+  const double chi2_ok = rt8 ? 1e-4 : 1e-6;
   Vec2 x_bar = pd;
   bool success = false;
   for (int it = 0; it < iterations; ++it) {
     Vec2 x_tmp;
     Mat2 E;
-    distort(cam, x_bar, &x_tmp, &E);
+    if (!distort(ce, x_bar, &x_tmp, &E)) {
+      success = false;
+      break;
+    }
     const double e0 = pd.x - x_tmp.x, e1 = pd.y - x_tmp.y;
     // E2 = E^T E ; du = (inv(E2) * E^T) * e
     const double a = E.a * E.a + E.c * E.c;
@@ -307,7 +329,7 @@ bool undistort(const okvfe_camera& cam, Vec2 pd, Vec2* out) {
     x_bar.x += b00 * e0 + b01 * e1;
     x_bar.y += b10 * e0 + b11 * e1;
     const double chi2 = e0 * e0 + e1 * e1;
-    if (chi2 < 1e-6) success = true;
+    if (chi2 < chi2_ok) success = true;
     if (chi2 < 1e-15) {
       success = true;
       break;
@@ -317,14 +339,15 @@ bool undistort(const okvfe_camera& cam, Vec2 pd, Vec2* out) {
   return success;
 }
 
-// status 0 = Successful (only that one matters here)
-int project_point(const okvfe_camera& cam, const double p[3], double* out_x, double* out_y, double J23[6]) {
+// status 0 = Successful (only that one matters here), 4 = Invalid (also: the distortion fails)
+int project_point(const okvfe_camera_ext& ce, const double p[3], double* out_x, double* out_y, double J23[6]) {
+  const okvfe_camera& cam = ce.base;
   if (std::fabs(p[2]) < 1.0e-12) return 4;
   const double rz = 1.0 / p[2];
   const double rz2 = rz * rz;
   Vec2 und{p[0] * rz, p[1] * rz}, dist;
   Mat2 D;
-  distort(cam, und, &dist, &D);
+  if (!distort(ce, und, &dist, &D)) return 4;
   J23[0] = cam.fu * D.a * rz;
   J23[1] = cam.fu * D.b * rz;
   J23[2] = -cam.fu * (p[0] * D.a + p[1] * D.b) * rz2;
@@ -342,10 +365,11 @@ int project_point(const okvfe_camera& cam, const double p[3], double* out_x, dou
 
 }  // namespace
 
-bool host_backproject(const okvfe_camera& cam, double px, double py, double dir[3]) {
+bool host_backproject(const okvfe_camera_ext& ce, double px, double py, double dir[3]) {
+  const okvfe_camera& cam = ce.base;
   const double one_over_fu = 1.0 / cam.fu, one_over_fv = 1.0 / cam.fv;
   Vec2 p2{(px - cam.cu) * one_over_fu, (py - cam.cv) * one_over_fv}, und;
-  const bool ok = undistort(cam, p2, &und);
+  const bool ok = undistort(ce, p2, &und);
   dir[0] = und.x;
   dir[1] = und.y;
   dir[2] = 1.0;
@@ -353,12 +377,13 @@ bool host_backproject(const okvfe_camera& cam, double px, double py, double dir[
 }
 
 // = NCameraSystem::computeOverlaps for one ordered camera pair (okvis_cv/src/NCameraSystem.cpp:48-119)
-bool camera_overlap(const okvfe_camera& cam, const okvfe_camera& other, const double R[9], uint8_t* mask) {
+bool camera_overlap(const okvfe_camera_ext& ce, const okvfe_camera_ext& other, const double R[9], uint8_t* mask) {
+  const okvfe_camera& cam = ce.base;
   bool any = false;
   for (int u = 0; u < cam.width; ++u) {
     for (int v = 0; v < cam.height; ++v) {
       double ray[3], ro[3], ver[3], J[6];
-      host_backproject(cam, static_cast<double>(u), static_cast<double>(v), ray);
+      host_backproject(ce, static_cast<double>(u), static_cast<double>(v), ray);
       for (int i = 0; i < 3; ++i) ro[i] = R[3 * i] * ray[0] + R[3 * i + 1] * ray[1] + R[3 * i + 2] * ray[2];
       bool hit = false;
       double px = 0.0, py = 0.0;
@@ -376,11 +401,12 @@ bool camera_overlap(const okvfe_camera& cam, const okvfe_camera& other, const do
   return any;
 }
 
-void build_awareness_maps(const okvfe_camera& cam, float* rays, float* jac) {
+void build_awareness_maps(const okvfe_camera_ext& ce, float* rays, float* jac) {
+  const okvfe_camera& cam = ce.base;
   for (int v = 0; v < cam.height; ++v) {
     for (int u = 0; u < cam.width; ++u) {
       double ray[3];
-      if (host_backproject(cam, static_cast<double>(u), static_cast<double>(v), ray)) {
+      if (host_backproject(ce, static_cast<double>(u), static_cast<double>(v), ray)) {
         const double n = std::sqrt(ray[0] * ray[0] + ray[1] * ray[1] + ray[2] * ray[2]);
         ray[0] /= n;
         ray[1] /= n;
@@ -392,7 +418,7 @@ void build_awareness_maps(const okvfe_camera& cam, float* rays, float* jac) {
       for (int i = 0; i < 3; ++i) rays[px * 3 + i] = static_cast<float>(ray[i]);
       double J[6];
       double qx, qy;
-      const bool ok = project_point(cam, ray, &qx, &qy, J) == 0;
+      const bool ok = project_point(ce, ray, &qx, &qy, J) == 0;
       // the reference leaves failed entries uninitialised; they are defined as zero here and
       // never read for a kept keypoint (a zero ray removes the keypoint)
       for (int i = 0; i < 6; ++i) jac[px * 6 + i] = ok ? static_cast<float>(J[i]) : 0.0f;

@@ -786,6 +786,8 @@ __global__ __launch_bounds__(64 * kDescWaves) __attribute__((amdgpu_waves_per_eu
 }
 
 // ---- compaction + back-projection -----------------------------------------------------------
+// kRT8: the back-projection also knows OKVFE_DIST_RADTAN8 (launched only for calls that use such a slot)
+template <bool kRT8>
 __global__ __launch_bounds__(256) void compact_kernel(
     const DeviceCamera* __restrict__ cams, const ImageParams* __restrict__ prm,
     const okvfe_keypoint* __restrict__ kps_tmp, const uint8_t* __restrict__ desc_tmp,
@@ -821,7 +823,7 @@ __global__ __launch_bounds__(256) void compact_kernel(
       d[2] = s[2];
       double dir[3] = {0.0, 0.0, 0.0};
       bool ok = false;
-      if (cam >= 0 && cams[cam].fu > 0.0) ok = cam::backproject(cams[cam], (double)kp.x, (double)kp.y, dir);
+      if (cam >= 0 && cams[cam].fu > 0.0) ok = cam::backproject<kRT8>(cams[cam], (double)kp.x, (double)kp.y, dir);
       bp[(off + pos) * 3 + 0] = dir[0];
       bp[(off + pos) * 3 + 1] = dir[1];
       bp[(off + pos) * 3 + 2] = dir[2];
@@ -913,10 +915,10 @@ void launch_compact(int n_images, const DeviceCamera* cams, const ImageParams* p
                     const okvfe_keypoint* kps_tmp, const uint8_t* desc_tmp,
                     const uint8_t* valid_tmp, const int32_t* kp_count_in, int kp_cap,
                     okvfe_keypoint* kps, uint8_t* desc, double* bp, uint8_t* bpv,
-                    int32_t* kp_count, hipStream_t stream) {
+                    int32_t* kp_count, hipStream_t stream, bool rt8) {
   if (n_images <= 0) return;
-  hipLaunchKernelGGL(compact_kernel, dim3(n_images), dim3(256), 0, stream, cams, prm, kps_tmp,
-                     desc_tmp, valid_tmp, kp_count_in, kp_cap, kps, desc, bp, bpv, kp_count);
+  hipLaunchKernelGGL(rt8 ? compact_kernel<true> : compact_kernel<false>, dim3(n_images), dim3(256), 0, stream, cams,
+                     prm, kps_tmp, desc_tmp, valid_tmp, kp_count_in, kp_cap, kps, desc, bp, bpv, kp_count);
 }
 
 }  // namespace okvfe

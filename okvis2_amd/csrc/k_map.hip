@@ -34,6 +34,7 @@ __device__ __forceinline__ void normalize3m(const double v[3], double out[3]) {
   out[2] = v[2] / n;
 }
 
+template <bool kRT8>  // camera_dev.h: the form that also knows OKVFE_DIST_RADTAN8
 __global__ __launch_bounds__(128) void prepare_landmarks_kernel(
     const double* __restrict__ hp_W, const double* __restrict__ quality,
     const int32_t* __restrict__ obs_begin, int n_landmarks, const int32_t* __restrict__ obs_pose,
@@ -71,7 +72,7 @@ __global__ __launch_bounds__(128) void prepare_landmarks_kernel(
   } else {
     head[0] = hp_C[0]; head[1] = hp_C[1]; head[2] = hp_C[2];
   }
-  const int st = cam::project(cam, w, h, head, kp);
+  const int st = cam::project<kRT8>(cam, w, h, head, kp);
   if (st == 4 || st == 3) return;  // Invalid, Behind
   const double maxU = (double)w + repr, maxV = (double)h + repr;
   if (kp[0] < -repr || kp[1] < -repr || kp[0] > maxU || kp[1] > maxV) return;
@@ -196,9 +197,9 @@ void launch_prepare_landmarks(const double* hp_W, const double* quality, const i
                               const okvfe_pose* poses, const okvfe_pose& T_WC1, const DeviceCamera* camera,
                               int w, int h, double repr, int exclusive, double cos10, double cos06,
                               int32_t* status, int32_t* n_desc, int32_t* obs_rows, double* projection,
-                              double* e_W, double* r_W, hipStream_t stream) {
+                              double* e_W, double* r_W, hipStream_t stream, bool rt8) {
   if (n_landmarks <= 0) return;
-  hipLaunchKernelGGL(prepare_landmarks_kernel, dim3((n_landmarks + 127) / 128), dim3(128), 0, stream, hp_W,
+  hipLaunchKernelGGL(rt8 ? prepare_landmarks_kernel<true> : prepare_landmarks_kernel<false>, dim3((n_landmarks + 127) / 128), dim3(128), 0, stream, hp_W,
                      quality, obs_begin, n_landmarks, obs_pose, obs_bp, poses, T_WC1, camera, w, h, repr,
                      exclusive, cos10, cos06, status, n_desc, obs_rows, projection, e_W, r_W);
 }

@@ -1154,6 +1154,7 @@ struct SegBestMotion {
 // Same scheme as match_stereo_rows (segments, LDS scan of the two best keys, converged FP64 gate):
 // the gate of the reference loop (Frontend.cpp:1843-1895) does not depend on the running best, so
 // its result is the gated candidate with the smallest (dist, k1).
+template <bool kRT8>  // camera_dev.h: the form that also knows OKVFE_DIST_RADTAN8
 __device__ void match_motion_rows(const PairParams& P, const DeviceCamera& camera, int w, int h,
                                   const MotionView& I0, const MotionView& I1, int threshold,
                                   okvfe_motion_match* __restrict__ out) {
@@ -1296,7 +1297,7 @@ __device__ void match_motion_rows(const PairParams& P, const DeviceCamera& camer
       head[0] = hp_C1[3] < 0 ? -hp_C1[0] : hp_C1[0];
       head[1] = hp_C1[3] < 0 ? -hp_C1[1] : hp_C1[1];
       head[2] = hp_C1[3] < 0 ? -hp_C1[2] : hp_C1[2];
-      const int status = cam::project(camera, w, h, head, pt1p);
+      const int status = cam::project<kRT8>(camera, w, h, head, pt1p);
       const double ex = (double)I1.kps[k1_max].x - pt1p[0], ey = (double)I1.kps[k1_max].y - pt1p[1];
       m.accepted = (status == 0 && sqrt(ex * ex + ey * ey) < 4.0) ? 1 : 0;
     }
@@ -1304,6 +1305,7 @@ __device__ void match_motion_rows(const PairParams& P, const DeviceCamera& camer
   }
 }
 
+template <bool kRT8>
 __global__ __launch_bounds__(64 * kStereoSegs) void match_motion_kernel(
     const PairParams* __restrict__ pair, const DeviceCamera* __restrict__ camera, int w, int h,
     const uint8_t* __restrict__ desc0, const okvfe_keypoint* __restrict__ kp0,
@@ -1314,7 +1316,7 @@ __global__ __launch_bounds__(64 * kStereoSegs) void match_motion_kernel(
     okvfe_motion_match* __restrict__ out) {
   const MotionView I0{desc0, kp0, bp0, bpv0, skip0, n0};
   const MotionView I1{desc1, kp1, bp1, bpv1, matched1, n1};
-  match_motion_rows(*pair, *camera, w, h, I0, I1, threshold, out);
+  match_motion_rows<kRT8>(*pair, *camera, w, h, I0, I1, threshold, out);
 }
 
 // ---- matchToMapByThread, 3-D landmarks (Frontend.cpp:1552-1589) ----------------------------------
@@ -1714,6 +1716,7 @@ __global__ __launch_bounds__(64 * kStereoSegs) void match_stereo_blocks_kernel(
 }
 
 // motion-stereo matcher on two gathered blocks (older frame, current frame) of one camera
+template <bool kRT8>
 __global__ __launch_bounds__(64 * kStereoSegs) void match_motion_blocks_kernel(
     const PairParams pair, const DeviceCamera* __restrict__ camera, int w, int h,
     BlockOffsets L, const uint8_t* __restrict__ b0, const uint8_t* __restrict__ b1,
@@ -1726,7 +1729,7 @@ __global__ __launch_bounds__(64 * kStereoSegs) void match_motion_blocks_kernel(
   I1.desc = b1 + L.o_desc; I1.kps = reinterpret_cast<const okvfe_keypoint*>(b1 + L.o_kps);
   I1.bp = reinterpret_cast<const double*>(b1 + L.o_bp); I1.bpv = b1 + L.o_bpv; I1.flag = matched1;
   I1.n = *reinterpret_cast<const int32_t*>(b1 + L.o_count);
-  match_motion_rows(pair, *camera, w, h, I0, I1, threshold, out);
+  match_motion_rows<kRT8>(pair, *camera, w, h, I0, I1, threshold, out);
 }
 
 
@@ -1772,9 +1775,9 @@ __global__ __launch_bounds__(256) void bow_query_l1_kernel(const int32_t* __rest
 void launch_match_motion_blocks(const PairParams& pair, const DeviceCamera* camera, int w, int h,
                                 const int offs[6], const uint8_t* block0, const uint8_t* block1,
                                 const uint8_t* skip0, const uint8_t* matched1, int kp_cap,
-                                int threshold, okvfe_motion_match* out, hipStream_t stream) {
+                                int threshold, okvfe_motion_match* out, hipStream_t stream, bool rt8) {
   const BlockOffsets L{offs[0], offs[1], offs[2], offs[3], offs[4], offs[5]};
-  hipLaunchKernelGGL(match_motion_blocks_kernel, dim3((kp_cap + 63) / 64), dim3(64, kStereoSegs), 0,
+  hipLaunchKernelGGL(rt8 ? match_motion_blocks_kernel<true> : match_motion_blocks_kernel<false>, dim3((kp_cap + 63) / 64), dim3(64, kStereoSegs), 0,
                      stream, pair, camera, w, h, L, block0, block1, skip0, matched1, threshold, out);
 }
 
@@ -1825,9 +1828,9 @@ void launch_match_motion(const PairParams* pair, const DeviceCamera* camera, int
                          const uint8_t* bpv0, const uint8_t* skip0, int n0, const uint8_t* desc1,
                          const okvfe_keypoint* kp1, const double* bp1, const uint8_t* bpv1,
                          const uint8_t* matched1, int n1, int threshold, okvfe_motion_match* out,
-                         hipStream_t stream) {
+                         hipStream_t stream, bool rt8) {
   if (n0 <= 0) return;
-  hipLaunchKernelGGL(match_motion_kernel, dim3((n0 + 63) / 64), dim3(64, kStereoSegs), 0, stream, pair, camera, w,
+  hipLaunchKernelGGL(rt8 ? match_motion_kernel<true> : match_motion_kernel<false>, dim3((n0 + 63) / 64), dim3(64, kStereoSegs), 0, stream, pair, camera, w,
                      h, desc0, kp0, bp0, bpv0, skip0, n0, desc1, kp1, bp1, bpv1, matched1, n1,
                      threshold, out);
 }

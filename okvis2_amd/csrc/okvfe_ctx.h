@@ -157,6 +157,7 @@ struct okvfe_ctx {
   int aware_extra_box = -1;       // of the running call (aware_box_for_call): >= 0 = describe_aware_kernel serves it
   bool wide_patches = false;      // of the images of the current batch
   bool all_aware = false;         // every image of the current batch is extracted camera-aware
+  bool rt8_call = false;          // an image of the current batch uses an OKVFE_DIST_RADTAN8 slot (compact_kernel<true>)
   bool counters_cleared = false;  // upload_image_params zeroed d_cand_count on the call's stream
   bool fuse_setup = false;        // the current call describes what it detects: setup rides in the selection kernel
   bool setup_done = false;        // ... and did
@@ -230,7 +231,8 @@ okvfe_status ring_upload(okvfe_ctx* ctx, okvfe_ctx::ParamRing* r, const void* sr
                          bool* zeroed = nullptr);
 okvfe_status ring_release(okvfe_ctx* ctx, okvfe_ctx::ParamRing* r, int slot, hipStream_t s);
 void ring_destroy(okvfe_ctx::ParamRing* r);
-DeviceCamera to_device_camera(const okvfe_camera& c);
+DeviceCamera to_device_camera(const okvfe_camera_ext& c);
+okvfe_camera_ext widen_camera(const okvfe_camera& c);  // d_ext = 0
 PairParams to_pair_params(const okvfe_stereo_pair& p);
 double layer_keypoint_size(int l);
 void fill_class_table(double* t, double f0, double f1, bool motion);

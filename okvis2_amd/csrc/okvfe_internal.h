@@ -104,10 +104,11 @@ constexpr int kStampCells = 697;
 constexpr int kStampTableOffset = 1024;
 constexpr int kLutFloats = kStampTableOffset + 2 * kStampSlots;
 void build_uniformity_lut(float lut[kLutFloats]);
-void build_awareness_maps(const okvfe_camera& cam, float* rays_hw3, float* jac_hw6);
-bool camera_overlap(const okvfe_camera& cam, const okvfe_camera& other, const double R_other_cam[9],
+// (the extended camera of ABI 8: every distortion type; okvfe_camera callers widen with d_ext = 0)
+void build_awareness_maps(const okvfe_camera_ext& cam, float* rays_hw3, float* jac_hw6);
+bool camera_overlap(const okvfe_camera_ext& cam, const okvfe_camera_ext& other, const double R_other_cam[9],
                     uint8_t* mask_hw);
-bool host_backproject(const okvfe_camera& cam, double px, double py, double dir[3]);
+bool host_backproject(const okvfe_camera_ext& cam, double px, double py, double dir[3]);
 
 struct Candidate {  // NMS maximum
   int32_t x, y, score;
@@ -122,7 +123,7 @@ constexpr int kFixListCap = 1024;
 struct DeviceCamera {  // intrinsics for on-device back-projection
   double fu, fv, cu, cv;
   double one_over_fu, one_over_fv;
-  double d[4];
+  double d[8];  // k1 k2 p1 p2 | k1 k2 k3 k4, then k3 k4 k5 k6 of OKVFE_DIST_RADTAN8 (zero otherwise)
   int32_t distortion;
   int32_t pad;
 };
@@ -327,7 +328,7 @@ void launch_compact(int n_images, const DeviceCamera* cams, const ImageParams* p
                     const okvfe_keypoint* kps_tmp, const uint8_t* desc_tmp,
                     const uint8_t* valid_tmp, const int32_t* kp_count_in, int kp_cap,
                     okvfe_keypoint* kps, uint8_t* desc, double* bp, uint8_t* bpv,
-                    int32_t* kp_count, hipStream_t stream);
+                    int32_t* kp_count, hipStream_t stream, bool rt8 = false);
 void launch_match_stereo(const PairParams* pairs, int n_pairs, const okvfe_keypoint* kps,
                          const uint8_t* desc, const double* bp, const uint8_t* bpv,
                          const int32_t* counts, int kp_cap, int threshold,
@@ -343,7 +344,7 @@ void launch_match_motion(const PairParams* pair, const DeviceCamera* camera, int
                          const uint8_t* bpv0, const uint8_t* skip0, int n0, const uint8_t* desc1,
                          const okvfe_keypoint* kp1, const double* bp1, const uint8_t* bpv1,
                          const uint8_t* matched1, int n1, int threshold, okvfe_motion_match* out,
-                         hipStream_t stream);
+                         hipStream_t stream, bool rt8 = false);
 void launch_match_to_map(const uint8_t* desc_k, const okvfe_keypoint* kps, const uint8_t* use, int n_k,
                          const double* projections, const int32_t* desc_begin, int n_lm,
                          const uint8_t* pool, double thr_sq, int threshold, int32_t* best_lm,
@@ -375,7 +376,7 @@ void launch_pack_blocks(const int offs[6], int first, int n, int kp_cap, const i
 void launch_match_motion_blocks(const PairParams& pair, const DeviceCamera* camera, int w, int h,
                                 const int offs[6], const uint8_t* block0, const uint8_t* block1,
                                 const uint8_t* skip0, const uint8_t* matched1, int kp_cap,
-                                int threshold, okvfe_motion_match* out, hipStream_t stream);
+                                int threshold, okvfe_motion_match* out, hipStream_t stream, bool rt8 = false);
 void launch_match_stereo_blocks(const PairParams& pair, const int offs[6], const uint8_t* blocks0,
                                 const uint8_t* blocks1, int n_frames, int kp_cap, int threshold,
                                 okvfe_stereo_match* out, hipStream_t stream);
@@ -391,7 +392,7 @@ void launch_prepare_landmarks(const double* hp_W, const double* quality, const i
                               const okvfe_pose* poses, const okvfe_pose& T_WC1, const DeviceCamera* camera,
                               int w, int h, double repr, int exclusive, double cos10, double cos06,
                               int32_t* status, int32_t* n_desc, int32_t* obs_rows, double* projection,
-                              double* e_W, double* r_W, hipStream_t stream);
+                              double* e_W, double* r_W, hipStream_t stream, bool rt8 = false);
 void launch_compact_landmarks(const int32_t* status, const int32_t* n_desc, const int32_t* obs_rows,
                               const double* projection, const uint8_t* obs_desc, int n_landmarks, int want,
                               int32_t* index_out, double* proj_out, int32_t* begin_out, uint8_t* pool_out,

@@ -91,6 +91,11 @@ class CrossCameraMatcher {
   CrossCameraMatcher(const std::vector<okvfe_camera>& cameras, const std::vector<okvfe_pose>& T_WC,
                      const FrontendParameters& p, int nFrames, const std::function<bool(int, int)>& overlap,
                      std::shared_ptr<Communicator> comm, int device)
+      : CrossCameraMatcher(extendCameras(cameras), T_WC, p, nFrames, overlap, std::move(comm), device) {}
+  // every distortion type, OKVFE_DIST_RADTAN8 included
+  CrossCameraMatcher(const std::vector<okvfe_camera_ext>& cameras, const std::vector<okvfe_pose>& T_WC,
+                     const FrontendParameters& p, int nFrames, const std::function<bool(int, int)>& overlap,
+                     std::shared_ptr<Communicator> comm, int device)
       : cameras_(cameras), poses_(T_WC), nFrames_(nFrames), comm_(std::move(comm)), device_(device) {
     world_ = comm_->world();
     rank_ = comm_->rank();
@@ -102,8 +107,8 @@ class CrossCameraMatcher {
       okvfe_config cfg{};
       cfg.abi_version = OKVFE_ABI_VERSION;
       cfg.device = device;
-      cfg.width = cameras[size_t(c)].width;
-      cfg.height = cameras[size_t(c)].height;
+      cfg.width = cameras[size_t(c)].base.width;
+      cfg.height = cameras[size_t(c)].base.height;
       cfg.max_batch = nFrames;
       cfg.num_cameras = 1;
       cfg.uniformity_radius = p.detection_threshold;
@@ -115,7 +120,7 @@ class CrossCameraMatcher {
       cfg.match_threshold = p.matching_threshold;
       cfg.box_scale = p.box_scale;
       auto ctx = std::make_shared<Context>(cfg);
-      ctx->check(okvfe_set_camera(ctx->get(), 0, &cameras[size_t(c)]));
+      ctx->check(okvfe_set_camera_ext(ctx->get(), 0, &cameras[size_t(c)]));
       local_[c] = ctx;
     }
     const Context& any = *local_.begin()->second;
@@ -167,8 +172,8 @@ class CrossCameraMatcher {
     Context& m = *local_.begin()->second;
     for (const auto& pr : mine_) {
       const int i = pr.first, j = pr.second;
-      const double fi = 0.5 * (cameras_[size_t(i)].fu + cameras_[size_t(i)].fv);
-      const double fj = 0.5 * (cameras_[size_t(j)].fu + cameras_[size_t(j)].fv);
+      const double fi = 0.5 * (cameras_[size_t(i)].base.fu + cameras_[size_t(i)].base.fv);
+      const double fj = 0.5 * (cameras_[size_t(j)].base.fu + cameras_[size_t(j)].base.fv);
       m.check(okvfe_match_stereo_blocks_batch_device(
           m.get(), blockOf(i), blockOf(j), nFrames_, &poses_[size_t(i)], &poses_[size_t(j)], fi, fj,
           static_cast<okvfe_stereo_match*>(dMatches_.at(pr)), stream_));
@@ -206,7 +211,7 @@ class CrossCameraMatcher {
            (size_t(cameraOwner(cam, world_)) * size_t(slots_) + size_t(cam / world_)) * size_t(nFrames_) * blockBytes_;
   }
 
-  std::vector<okvfe_camera> cameras_;
+  std::vector<okvfe_camera_ext> cameras_;
   std::vector<okvfe_pose> poses_;
   int nFrames_;
   std::shared_ptr<Communicator> comm_;

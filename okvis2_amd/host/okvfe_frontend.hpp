@@ -26,6 +26,19 @@
 
 namespace okvfe {
 
+// okvfe_camera (distortion types 0..2) as the extended camera of ABI 8 (d_ext = 0)
+inline okvfe_camera_ext extendCamera(const okvfe_camera& c) {
+  okvfe_camera_ext e{};
+  e.base = c;
+  return e;
+}
+inline std::vector<okvfe_camera_ext> extendCameras(const std::vector<okvfe_camera>& cameras) {
+  std::vector<okvfe_camera_ext> out;
+  out.reserve(cameras.size());
+  for (const okvfe_camera& c : cameras) out.push_back(extendCamera(c));
+  return out;
+}
+
 class Exception : public std::runtime_error {
  public:
   Exception(okvfe_status st, const std::string& what)
@@ -137,6 +150,12 @@ class HipBriskExtractor {
     aware_ = true;
     if (ctx_->nextExtraction().cam == cam_) ctx_->nextExtraction().aware = true;
   }
+  // every distortion type, OKVFE_DIST_RADTAN8 (PinholeCamera<RadialTangentialDistortion8>) included
+  void setCamera(const okvfe_camera_ext& camera) {
+    ctx_->check(okvfe_set_camera_ext(ctx_->get(), cam_, &camera));
+    aware_ = true;
+    if (ctx_->nextExtraction().cam == cam_) ctx_->nextExtraction().aware = true;
+  }
   void setExtractionDirection(const std::array<float, 3>& dir) {
     dir_ = dir;
     if (ctx_->nextExtraction().cam == cam_) ctx_->nextExtraction().dir = dir;
@@ -195,14 +214,16 @@ struct FrontendParameters {  // okvis_common/include/okvis/Parameters.hpp:123-13
 class HipFrontend {
  public:
   HipFrontend(const std::vector<okvfe_camera>& cameras, const FrontendParameters& p, int device = 0)
+      : HipFrontend(extendCameras(cameras), p, device) {}
+  HipFrontend(const std::vector<okvfe_camera_ext>& cameras, const FrontendParameters& p, int device = 0)
       : cameras_(cameras), mutexes_(cameras.size()), bp_scratch_(cameras.size()) {
     if (cameras.empty()) throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "no cameras");
     for (size_t i = 0; i < cameras.size(); ++i) {
       okvfe_config cfg{};
       cfg.abi_version = OKVFE_ABI_VERSION;
       cfg.device = device;
-      cfg.width = cameras[i].width;
-      cfg.height = cameras[i].height;
+      cfg.width = cameras[i].base.width;
+      cfg.height = cameras[i].base.height;
       cfg.max_batch = 1;
       cfg.num_cameras = 1;
       cfg.uniformity_radius = p.detection_threshold;
@@ -261,8 +282,8 @@ class HipFrontend {
                                               size_t im1, const FrameData& f1, const okvfe_pose& T_WC1) {
     std::lock_guard<std::mutex> lock(mutexes_[im0]);
     std::vector<okvfe_stereo_match> out(f0.keypoints.size());
-    const double fa = 0.5 * (cameras_[im0].fu + cameras_[im0].fv);
-    const double fb = 0.5 * (cameras_[im1].fu + cameras_[im1].fv);
+    const double fa = 0.5 * (cameras_[im0].base.fu + cameras_[im0].base.fv);
+    const double fb = 0.5 * (cameras_[im1].base.fu + cameras_[im1].base.fv);
     std::vector<double> b0(f0.backProjections.size() * 3 + 3), b1(f1.backProjections.size() * 3 + 3);
     for (size_t k = 0; k < f0.backProjections.size(); ++k)
       for (int i = 0; i < 3; ++i) b0[3 * k + size_t(i)] = f0.backProjections[k][size_t(i)];
@@ -290,7 +311,7 @@ class HipFrontend {
     std::lock_guard<std::mutex> lock(mutexes_[cameraIndex]);
     std::vector<okvfe_motion_match> out(f0.keypoints.size());
     const std::vector<double> b0 = flat(f0.backProjections), b1 = flat(f1.backProjections);
-    contexts_[cameraIndex]->check(okvfe_match_motion_stereo(
+    contexts_[cameraIndex]->check(okvfe_match_motion_stereo_ext(
         contexts_[cameraIndex]->get(), &cameras_[cameraIndex], f0.descriptors.data.data(), f0.keypoints.data(),
         b0.data(), f0.backProjectionsValid.data(), skip0.empty() ? nullptr : skip0.data(),
         int32_t(f0.keypoints.size()), f1.descriptors.data.data(), f1.keypoints.data(), b1.data(),
@@ -356,7 +377,7 @@ class HipFrontend {
     std::vector<double> hp(4 * n + 4);
     u.hpSet.assign(n, 0);
     const std::vector<double> bp = flat(frame.backProjections);
-    const double focal = 0.5 * (cameras_[cameraIndex].fu + cameras_[cameraIndex].fv);
+    const double focal = 0.5 * (cameras_[cameraIndex].base.fu + cameras_[cameraIndex].base.fv);
     // empty = "every keypoint" / "no keypoint carries a landmark yet", like the sibling wrappers
     if (!use.empty() && use.size() != n) throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "use: one entry per keypoint");
     if (!previousLandmark.empty() && previousLandmark.size() != n)
@@ -399,7 +420,7 @@ class HipFrontend {
       for (int i = 0; i < 3; ++i) b[3 * k + size_t(i)] = v[k][size_t(i)];
     return b;
   }
-  std::vector<okvfe_camera> cameras_;
+  std::vector<okvfe_camera_ext> cameras_;
   std::vector<std::mutex> mutexes_;
   std::vector<std::shared_ptr<Context>> contexts_;
   std::vector<HipBriskDetector> detectors_;

@@ -47,6 +47,10 @@ class HipViFrontend : public okvis::ViFrontendInterface {
   HipViFrontend(std::unique_ptr<okvis::ViFrontendInterface> rest, const std::vector<okvfe_camera>& cameras,
                 const FrontendParameters& p, int device = 0)
       : rest_(std::move(rest)), gpu_(cameras, p, device), last_(cameras.size()) {}
+  // every distortion type, OKVFE_DIST_RADTAN8 (PinholeCamera<RadialTangentialDistortion8>) included
+  HipViFrontend(std::unique_ptr<okvis::ViFrontendInterface> rest, const std::vector<okvfe_camera_ext>& cameras,
+                const FrontendParameters& p, int device = 0)
+      : rest_(std::move(rest)), gpu_(cameras, p, device), last_(cameras.size()) {}
 
   bool detectAndDescribe(size_t cameraIndex, std::shared_ptr<okvis::MultiFrame> frameOut,
                          const okvis::kinematics::Transformation& T_WC,

@@ -53,6 +53,7 @@ class HipExtractor : public cv::DescriptorExtractor {
   }
   // full intrinsics instead of caller-built maps: also enables the GPU's FP64 back-projection
   void setCamera(const okvfe_camera& camera) { impl_.setCamera(camera); }
+  void setCamera(const okvfe_camera_ext& camera) { impl_.setCamera(camera); }  // every distortion type
   void setExtractionDirection(const cv::Vec3f& d) { impl_.setExtractionDirection({d[0], d[1], d[2]}); }
   void compute(cv::InputArray image, std::vector<cv::KeyPoint>& keypoints, cv::OutputArray descriptors) override {
     std::vector<KeyPoint> k(keypoints.size());

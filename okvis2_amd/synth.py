@@ -78,8 +78,8 @@ class Camera:
     fv: float
     cu: float
     cv: float
-    dist_type: int  # 0 none, 1 radial-tangential, 2 equidistant
-    d: tuple
+    dist_type: int  # 0 none, 1 radial-tangential, 2 equidistant, 3 radial-tangential 8
+    d: tuple  # 4 coefficients; 8 for type 3 (k1 k2 p1 p2 k3 k4 k5 k6)
 
 
 @dataclasses.dataclass
@@ -104,6 +104,17 @@ def euroc_config() -> Config:
     c1 = Camera(752, 480, 457.587426604, 456.13442556, 379.99944652, 255.238185386, 1,
                 (-0.283683654496, 0.0745128430929, -0.000104738949098, -3.55590700274e-05))
     return Config("euroc", 752, 480, [c0, c1], 0.11, 38.0, 150, 60, 0, 700)
+
+
+def radtan8_config() -> Config:
+    """The reference's own 8-coefficient test camera (PinholeCamera::createTestObject with
+    RadialTangentialDistortion8::testObject: 752x480, fu fv cu cv = 350 360 378 238) and a slightly
+    perturbed copy as the second camera, with the EuRoC front-end parameters (the EuRoC shape)."""
+    c0 = Camera(752, 480, 350.0, 360.0, 378.0, 238.0, 3,
+                (0.6261, 0.001, -0.0002, 0.0001, 0.0001, 0.9541, 0.1151, -0.0075))
+    c1 = Camera(752, 480, 351.2, 358.9, 376.5, 239.4, 3,
+                (0.6180, 0.0012, -0.00015, 0.00012, 0.00011, 0.9478, 0.1163, -0.0071))
+    return Config("radtan8", 752, 480, [c0, c1], 0.11, 38.0, 150, 60, 0, 700)
 
 
 def mono640_config() -> Config:
