@@ -310,11 +310,20 @@ okvfe_status okvfe_set_keep_score_map(okvfe_ctx* ctx, int32_t keep);
  * the NEXT call's score kernel behind its own previous work instead of behind everybody's: the lanes drift out of phase
  * and stay there, which is what makes several contexts on several streams faster than one.  The price is the contract:
  * after such a call returns, work the CALLER queues on its stream is NOT ordered behind the results.  Any other entry
- * point of the context joins first (stream-taking ones make their stream wait, host-side readers synchronise), and
- * okvfe_lanes_join(ctx, stream) does it explicitly; the caller must join before it overwrites the input images or reads
- * okvfe_device_outputs / the match rows with kernels of its own.  Results are the unsplit call's, byte for byte. */
+ * point of the context that touches its buffers joins first (the host-array matchers, which do not, are listed in
+ * tests/test_capi_join_audit.py): a stream-taking one makes the stream it is given wait for the lanes, every time,
+ * until the host has waited for them; a host-side reader (okvfe_download_image_result, okvfe_check_capacity,
+ * okvfe_get_device_outputs, okvfe_profile_*) synchronises the lanes themselves, whatever streams were joined before.
+ * okvfe_lanes_join(ctx, stream) joins explicitly, and orders THAT stream only: a join on one stream says nothing about
+ * another.  The caller must join the stream it uses before it overwrites the input images or reads the match rows with
+ * kernels of its own.  A pipelined call that cuts its batch differently from the previous one waits for the old slices
+ * first.  okvfe_set_camera* and okvfe_set_pattern apply to LATER calls: they wait for the calls already queued (the
+ * lanes, the last stream used, the context's own) before they change anything.  Results are the unsplit call's, byte
+ * for byte. */
 okvfe_status okvfe_set_internal_lanes(okvfe_ctx* ctx, int32_t lanes);
-/* Makes `stream` (NULL: the context's own) wait for every pipelined lane of the context; no-op when none is pending. */
+/* Makes `stream` wait for every pipelined lane of the context (no-op when none was issued since the host last waited).
+ * NULL = the context's OWN stream, not the caller's current one: a caller that means torch.cuda.current_stream() or the
+ * legacy default stream passes it (OKVFE_STREAM_LEGACY_DEFAULT for the latter). */
 okvfe_status okvfe_lanes_join(okvfe_ctx* ctx, void* stream);
 
 /* Order of every 3-term FP64 sum in the matchers' gate chain (dot products, norms, C * v and C^T * v:

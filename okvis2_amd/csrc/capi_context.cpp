@@ -245,20 +245,23 @@ hipStream_t pick_stream_raw(okvfe_ctx* ctx, void* stream) {
 }
 hipStream_t pick_stream(okvfe_ctx* ctx, void* stream) {
   hipStream_t s = pick_stream_raw(ctx, stream);
-  if (ctx->lanes_pending && ctx->join_done) {  // pipelined lanes: whatever this call queues on s sees their results
+  // pipelined lanes: whatever this call queues on s sees their results.  The flag stays set: waiting orders s only, and
+  // the next stream (or the host) must wait as well
+  if (ctx->lanes_unsynced && ctx->join_done) {
     if (hipStreamWaitEvent(s, ctx->join_done, 0) != hipSuccess) {
       (void)hipGetLastError();
       (void)hipDeviceSynchronize();
     }
-    ctx->lanes_pending = false;
   }
+  ctx->lanes_open = false;
   return s;
 }
 okvfe_status lanes_join_host(okvfe_ctx* ctx) {
-  if (!ctx->lanes_pending) return OKVFE_OK;
+  if (!ctx->lanes_unsynced) return OKVFE_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
   if (ctx->join_stream) HIP_TRY(ctx, hipStreamSynchronize(ctx->join_stream));
-  ctx->lanes_pending = false;
+  ctx->lanes_unsynced = false;
+  ctx->lanes_open = false;
   return OKVFE_OK;
 }
 
@@ -693,6 +696,10 @@ okvfe_status okvfe_set_camera_maps(okvfe_ctx* ctx, int32_t cam, const float* ray
     HIP_TRY(ctx, hipMalloc(&p, P * 6 * sizeof(float)));
     ctx->cam_jac[cam] = static_cast<float*>(p);
   }
+  // a change applies to LATER calls: calls already queued (pipelined lanes, the last caller stream, the context's own)
+  // still read the old maps, as okvfe_set_pattern drains before it writes
+  { const okvfe_status js = lanes_join_host(ctx); if (js != OKVFE_OK) return js; }
+  if (ctx->last_stream) HIP_TRY(ctx, hipStreamSynchronize(ctx->last_stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   HIP_TRY(ctx, hipMemcpy(ctx->cam_rays[cam], rays_hw3, P * 3 * sizeof(float), hipMemcpyHostToDevice));
   HIP_TRY(ctx, hipMemcpy(ctx->cam_jac[cam], jacobians_hw6, P * 6 * sizeof(float), hipMemcpyHostToDevice));

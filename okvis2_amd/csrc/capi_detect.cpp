@@ -747,7 +747,8 @@ okvfe_status detect_describe_split(okvfe_ctx* ctx, const uint8_t* images_dev, in
     // and `join_done` is what a later consumer waits for (pick_stream / lanes_join_host)
     if ((st = ensure_join(ctx)) != OKVFE_OK) return st;
     for (int l = 0; l < used; ++l) HIP_TRY(ctx, hipStreamWaitEvent(ctx->join_stream, ctx->lane_done[l], 0));
-    ctx->lanes_pending = true;
+    ctx->lanes_unsynced = true;
+    ctx->lanes_open = true;
     ctx->lanes_used = used;
     ctx->lane_chunk = chunk;
   } else {
@@ -811,14 +812,17 @@ okvfe_status okvfe_detect_describe_batch_device(okvfe_ctx* ctx, const uint8_t* i
                 n_images, ctx->B);
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
   // pipelined lanes (okvfe_set_internal_lanes(-k)): no join onto the caller's stream, neither before nor after the call,
-  // as long as the slices stay what they were (a lane only ever follows ITS OWN previous work)
-  bool piped = false;
+  // as long as the slices stay what they were (a lane only ever follows ITS OWN previous work).  A call that re-slices
+  // the buffers first makes its stream wait for every lane (pick_stream): lane l of the new call would otherwise write
+  // ranges that lane l' of the old one may still be working on
+  bool piped = false, same_slices = false;
   if (ctx->lanes_pipelined) {
     const int k = lanes_for_call(ctx, n_images);
     const int chunk = (((n_images + k - 1) / k) + 7) & ~7;
-    piped = k > 1 && (!ctx->lanes_pending || ctx->lane_chunk == chunk);
+    piped = k > 1;
+    same_slices = piped && ctx->lane_chunk == chunk;
   }
-  hipStream_t s = piped ? pick_stream_raw(ctx, stream) : pick_stream(ctx, stream);
+  hipStream_t s = same_slices ? pick_stream_raw(ctx, stream) : pick_stream(ctx, stream);
   // (pipelined: the candidate counters are cleared by every lane on its own stream, not by the parameter upload on the
   // caller's -- a lane may still be reading last call's)
   okvfe_status st = upload_image_params(ctx, n_images, cam_ids, gravity_C, s, !piped);
@@ -1094,9 +1098,9 @@ okvfe_status okvfe_detect(okvfe_ctx* ctx, const uint8_t* image, size_t stride, o
   if (!image || !n_out) return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_detect: null argument");
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
   ctx->ahead.valid = false;
+  hipStream_t s = pick_stream(ctx, nullptr);  // (pipelined lanes may still write image slot 0)
   okvfe_status st = stage_image(ctx, image, stride);
   if (st != OKVFE_OK) return st;
-  hipStream_t s = ctx->stream;
   if ((st = detect_stage(ctx, ctx->d_img_stage, 1, s)) != OKVFE_OK) return st;
   if ((st = export_and_wait(ctx, 0, false, s)) != OKVFE_OK) return st;
   const int n = reinterpret_cast<const int32_t*>(ctx->h_result)[2];
@@ -1158,9 +1162,9 @@ okvfe_status okvfe_compute(okvfe_ctx* ctx, const uint8_t* image, size_t stride, 
     if (hit) return copy_results_out(ctx, keypoints, descriptors, backproj, backproj_valid, n_in, n_out);
     ctx->ahead.valid = false;
   }
+  hipStream_t s = pick_stream(ctx, nullptr);  // (pipelined lanes may still write image slot 0)
   okvfe_status st = stage_image(ctx, image, stride);
   if (st != OKVFE_OK) return st;
-  hipStream_t s = ctx->stream;
   const int32_t cam_id = cam;
   st = upload_image_params(ctx, 1, &cam_id, aware ? gravity_C : nullptr, s);
   if (st != OKVFE_OK) return st;

@@ -24,7 +24,7 @@ okvfe_status okvfe_match_stereo_batch_device(okvfe_ctx* ctx, const okvfe_stereo_
   // pipelined lanes (okvfe_set_internal_lanes(-k)): the pairs of a slice are matched on the slice's lane stream, behind
   // its detect + describe chain, when every pair lies inside one slice and the slices' pairs are contiguous runs
   std::vector<int> lane_first;
-  bool piped = ctx->lanes_pipelined && ctx->lanes_pending && ctx->n_layers == 1 && ctx->lane_chunk > 0 &&
+  bool piped = ctx->lanes_pipelined && ctx->lanes_open && ctx->n_layers == 1 && ctx->lane_chunk > 0 &&
                ctx->lanes_used > 1 && (int)ctx->lane_ctx.size() >= ctx->lanes_used && ctx->join_stream;
   if (piped) {
     lane_first.assign(ctx->lanes_used + 1, n_pairs);

@@ -98,7 +98,7 @@ struct okvfe_ctx {
   // okvis_multisensor_processing/src/ThreadedSlam.cpp:434-448, inside the call).  A lane is a VIEW: an okvfe_ctx
   // whose per-image pointers are this context's, offset to the slice (bind_lane, capi_detect.cpp); it owns a stream
   // and two events, nothing else.
-  int internal_lanes = 0;  // 0 = automatic (4 from 512 images per call), 1 = off
+  int internal_lanes = 0;  // 0 = the library's choice (not to cut: lanes_for_call), 1 = off, 2..8 = that many
   bool lane_view = false;
   okvfe_ctx* prof_owner = nullptr;  // lane view: stage timers record into the owning context
   hipEvent_t k1_wait = nullptr;     // lane view: its score kernel starts behind this event (the previous lane's k1_done)
@@ -116,7 +116,14 @@ struct okvfe_ctx {
   // contexts do.  The join happens when something needs the results: any other entry point of this context (the stream
   // it is given waits for `join_done`; host-side readers synchronise), or okvfe_lanes_join.
   bool lanes_pipelined = false;        // owner: internal_lanes was set negative
-  bool lanes_pending = false;          // owner: lane work has been issued that the caller's streams have not waited for
+  // owner: pipelined lane work has been issued and the HOST has not yet waited for it.  Only lanes_join_host clears it: a
+  // stream that waited for `join_done` orders that one stream, not the others, so every stream-taking entry point waits
+  // again (pick_stream) for as long as the flag is set
+  bool lanes_unsynced = false;
+  // owner: the last detect + describe ran on pipelined lanes and no call of this context has been ordered behind them
+  // since (pick_stream and lanes_join_host clear it): an okvfe_match_stereo_batch_device that follows may run on the
+  // lane streams, each slice's pairs behind that slice's chain
+  bool lanes_open = false;
   int lanes_used = 0;                  // owner: lanes of the pending call
   int lane_chunk = 0;                  // owner: images per lane of the pending call
   hipStream_t join_stream = nullptr;   // owner: waits for every lane, releases the parameter slots, records join_done
