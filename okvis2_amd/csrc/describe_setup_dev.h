@@ -85,11 +85,19 @@ __device__ __forceinline__ bool extra_sample_value(const uint8_t* __restrict__ i
   constexpr int NDW = (3 + MAXB2) / 4 + 1;
   const int b = x_left & 3;
   const uint8_t* p0 = im + (size_t)y_top * w + (x_left & ~3);
-  auto byte_at = [&](const uint32_t (&r)[NDW], int pos) -> int {  // byte `pos` of a row window
-    uint32_t v = r[0];
+  // byte `pos` of a row window, by a binary tree of selects on the bits of pos >> 2 (a chain of compares
+  // against j is folded back into an indexed read, which puts the whole window in scratch)
+  auto byte_at = [&](const uint32_t (&r)[NDW], int pos) -> int {
+    uint32_t v[NDW];
 #pragma unroll
-    for (int j = 1; j < NDW; ++j) v = (pos >> 2) == j ? r[j] : v;
-    return (int)((v >> (8 * (pos & 3))) & 0xFFu);
+    for (int j = 0; j < NDW; ++j) v[j] = r[j];
+#pragma unroll
+    for (int bit = 0; (1 << bit) < NDW; ++bit) {
+      const bool hi = ((pos >> (2 + bit)) & 1) != 0;
+#pragma unroll
+      for (int j = 0; j + (1 << bit) < NDW; j += 2 << bit) v[j] = hi ? v[j + (1 << bit)] : v[j];
+    }
+    return (int)((v[0] >> (8 * (pos & 3))) & 0xFFu);
   };
   uint32_t msk[NDW];  // bytes b + 1 .. b + bw - 1 of a row window
 #pragma unroll

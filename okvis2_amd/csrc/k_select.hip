@@ -22,6 +22,35 @@
 namespace okvfe {
 namespace {
 
+// ---- K4 of both lazy-occupancy kernels: sub-pixel refinement and emission of kept keypoint i (one lane each) ----
+__device__ __forceinline__ void refine_emit(const int32_t* __restrict__ scores, const ScoreLayout& layout, int w, int h,
+                                            int img, const uint8_t* __restrict__ images, const DescribeSetup& setup,
+                                            okvfe_keypoint* __restrict__ out, int i, size_t slot) {
+  okvfe_keypoint kp = out[i];  // pixel position and exact score, left there by the acceptance
+  const int u = (int)kp.x, v = (int)kp.y;
+  int32_t patch[9];
+  if (images) {  // map-free call: the nine scores from the pixels (block-uniform)
+    harris_scores_3x3(images + (size_t)img * w * h, w, h, u, v, patch);
+  } else {
+    const int32_t* sc = scores + (size_t)img * layout.pitch * h;
+#pragma unroll
+    for (int dy = -1; dy <= 1; ++dy)
+#pragma unroll
+      for (int dx = -1; dx <= 1; ++dx)
+        patch[(dy + 1) * 3 + (dx + 1)] = sc[score_index(layout, u + dx, v + dy)];
+  }
+  float ddx, ddy;
+  subpixel2d(patch, &ddx, &ddy);
+  kp.x = (float)u + ddx;
+  kp.y = (float)v + ddy;
+  kp.response = (float)kp.class_id;
+  kp.class_id = -1;
+  out[i] = kp;
+  // detection and description in one call: the extractor's per-keypoint preparation right here
+  // (describe_setup_dev.h) instead of a launch of its own
+  if (setup.pat) describe_setup_one(setup, w, h, img, slot, kp);
+}
+
 // ---- lazy-occupancy selection: no grid, one workgroup of 4 waves per image ----------------------
 // The occupancy grid of the reference is only ever READ at the cells of candidates: a candidate
 // passes when its level is not below the grid value at its own cell, and that value is
@@ -184,12 +213,23 @@ __global__ __launch_bounds__(kLazyThreads) __attribute__((amdgpu_waves_per_eu(OK
     int32_t scv0[SORTS ? kFuseFirst : 1];
     uint32_t pyx0[SORTS ? kFuseFirst : 1];
     if constexpr (SORTS) {
+      // (x and y are read as 16-bit values, not with the record: twenty whole 12-byte records in flight need 60
+      // registers, and four of them spilled to scratch)
+      typedef unsigned short ushort2_t __attribute__((ext_vector_type(2)));
 #pragma unroll
       for (int u = 0; u < kFuseFirst; ++u) {
         const int i = tid + u * kLazyThreads;
-        const Candidate c = i < n ? crec[i] : Candidate{0, 0, INT_MIN};
-        scv0[u] = c.score;
-        pyx0[u] = ((uint32_t)c.y << 16) | (uint32_t)c.x;
+        if (i < n) {
+          const unsigned short* c16 = reinterpret_cast<const unsigned short*>(crec + i);
+          ushort2_t yx;
+          yx.x = c16[0];
+          yx.y = c16[2];
+          pyx0[u] = __builtin_bit_cast(uint32_t, yx);
+          scv0[u] = crec[i].score;
+        } else {
+          pyx0[u] = 0u;
+          scv0[u] = INT_MIN;
+        }
       }
     }
     const float scaling = (float)(15.0 / (double)radius);
@@ -613,9 +653,9 @@ __global__ __launch_bounds__(kLazyThreads) __attribute__((amdgpu_waves_per_eu(OK
             }
           }
         }
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) mx = max(mx, __shfl_xor(mx, d));
-        if (lane == 0) atomicMax(&s_max, mx);
+        // (one LDS atomic per lane, not a shuffle tree: the compiler hoists a tree's lane addresses to the kernel
+        // start and keeps them in scratch for the key-range split below)
+        atomicMax(&s_max, mx);
       }
       __syncthreads();
 #ifdef OKVFE_LAB
@@ -716,15 +756,14 @@ __global__ __launch_bounds__(kLazyThreads) __attribute__((amdgpu_waves_per_eu(OK
 #endif
       const int nsched = s_nsched;
       uint64_t kcur[4] = {0ull, 0ull, 0ull, 0ull}, knxt[4] = {0ull, 0ull, 0ull, 0ull};
-      // this wave's quarter of keys[c0 .. c0 + m)
+      // this wave's quarter of keys[c0 .. c0 + m), m >= 1: lanes past the quarter read some other key of the chunk
+      // (clamped to its last one; the prefilter masks them), so the four requests go out without a branch each and
+      // nothing waits for them here
       auto load_chunk = [&](int c0, int m, uint64_t kr[4]) {
         const int q = (m + 3) >> 2;
-        const int lo = c0 + wave * q, hi = min(lo + q, c0 + m);
+        const int lo = c0 + wave * q;
 #pragma unroll
-        for (int t = 0; t < 4; ++t) {
-          const int i = lo + 64 * t + lane;
-          kr[t] = i < hi ? keys[i] : 0ull;
-        }
+        for (int t = 0; t < 4; ++t) kr[t] = keys[min(lo + 64 * t + lane, c0 + m - 1)];
       };
       int cpos = 0, j = 0, par = 0;
       bool have_next = false;
@@ -774,16 +813,8 @@ __global__ __launch_bounds__(kLazyThreads) __attribute__((amdgpu_waves_per_eu(OK
                 mxk = k > mxk ? k : mxk;
               }
             }
-#pragma unroll
-            for (int d = 32; d > 0; d >>= 1) {
-              const unsigned long long a1 = __shfl_xor(mn, d), a2 = __shfl_xor(mxk, d);
-              mn = a1 < mn ? a1 : mn;
-              mxk = a2 > mxk ? a2 : mxk;
-            }
-            if (lane == 0) {
-              atomicMin(&s_kmin, mn);
-              atomicMax(&s_kmax, mxk);
-            }
+            atomicMin(&s_kmin, mn);  // (per lane, like s_max above)
+            atomicMax(&s_kmax, mxk);
             __syncthreads();
             const unsigned long long kmin = s_kmin, range = s_kmax - kmin;
             int sh = range < 256ull ? 0 : (64 - __clzll((long long)range)) - 8;  // (range >> sh) < 256
@@ -881,12 +912,16 @@ __global__ __launch_bounds__(kLazyThreads) __attribute__((amdgpu_waves_per_eu(OK
             my_cnt += __popcll(m);
           }
         }
-        // the next chunk's keys: requested now, used after this chunk's ordered windows
-        if (!refining && j < nsched) {
-          const int m2 = (int)s_sched[j] - cpos;
-          if (m2 <= round_cap) {
+        // the next chunk's keys: requested now, used after this chunk's ordered windows (knxt is assigned on
+        // every round, so last round's value is dead here and does not occupy registers through the prefilter)
+        {
+          const int m2 = !refining && j < nsched ? (int)s_sched[j] - cpos : 0;
+          have_next = m2 > 0 && m2 <= round_cap;
+          if (have_next) {
             load_chunk(cpos, m2, knxt);
-            have_next = true;
+          } else {
+#pragma unroll
+            for (int t = 0; t < 4; ++t) knxt[t] = 0ull;
           }
         }
         int* racc = reinterpret_cast<int*>(part);  // rank accumulators of the survivor sort (the windows are not running)
@@ -971,31 +1006,8 @@ __global__ __launch_bounds__(kLazyThreads) __attribute__((amdgpu_waves_per_eu(OK
 #ifdef OKVFE_LAB
   t_blocks = __builtin_amdgcn_s_memrealtime();
 #endif
-  for (int i = tid; i < kept; i += kLazyThreads) {
-    okvfe_keypoint kp = out[i];
-    const int u = (int)kp.x, v = (int)kp.y;
-    int32_t patch[9];
-    if (images) {  // map-free call: the nine scores from the pixels (block-uniform)
-      harris_scores_3x3(images + (size_t)img * w * h, w, h, u, v, patch);
-    } else {
-      const int32_t* sc = scores + (size_t)img * layout.pitch * h;
-#pragma unroll
-      for (int dy = -1; dy <= 1; ++dy)
-#pragma unroll
-        for (int dx = -1; dx <= 1; ++dx)
-          patch[(dy + 1) * 3 + (dx + 1)] = sc[score_index(layout, u + dx, v + dy)];
-    }
-    float ddx, ddy;
-    subpixel2d(patch, &ddx, &ddy);
-    kp.x = (float)u + ddx;
-    kp.y = (float)v + ddy;
-    kp.response = (float)kp.class_id;
-    kp.class_id = -1;
-    out[i] = kp;
-    // detection and description in one call: the extractor's per-keypoint preparation right here
-    // (describe_setup_dev.h) instead of a launch of its own
-    if (setup.pat) describe_setup_one(setup, w, h, img, (size_t)img * kp_cap + i, kp);
-  }
+  for (int i = tid; i < kept; i += kLazyThreads)
+    refine_emit(scores, layout, w, h, img, images, setup, out, i, (size_t)img * kp_cap + i);
   if (tid == 0) kp_count[img] = kept;
 #ifdef OKVFE_LAB
   __syncthreads();
@@ -1285,31 +1297,8 @@ __global__ __launch_bounds__(kLazyThreads) __attribute__((amdgpu_waves_per_eu(6,
   }
   // ---- K4: sub-pixel refinement and keypoint emission (all four waves)
   __syncthreads();
-  for (int i = tid; i < kept; i += kLazyThreads) {
-    okvfe_keypoint kp = out[i];
-    const int u = (int)kp.x, v = (int)kp.y;
-    int32_t patch[9];
-    if (images) {  // map-free call: the nine scores from the pixels (block-uniform)
-      harris_scores_3x3(images + (size_t)img * w * h, w, h, u, v, patch);
-    } else {
-      const int32_t* sc = scores + (size_t)img * layout.pitch * h;
-#pragma unroll
-      for (int dy = -1; dy <= 1; ++dy)
-#pragma unroll
-        for (int dx = -1; dx <= 1; ++dx)
-          patch[(dy + 1) * 3 + (dx + 1)] = sc[score_index(layout, u + dx, v + dy)];
-    }
-    float ddx, ddy;
-    subpixel2d(patch, &ddx, &ddy);
-    kp.x = (float)u + ddx;
-    kp.y = (float)v + ddy;
-    kp.response = (float)kp.class_id;
-    kp.class_id = -1;
-    out[i] = kp;
-    // detection and description in one call: the extractor's per-keypoint preparation right here
-    // (describe_setup_dev.h) instead of a launch of its own
-    if (setup.pat) describe_setup_one(setup, w, h, img, (size_t)img * kp_cap + i, kp);
-  }
+  for (int i = tid; i < kept; i += kLazyThreads)
+    refine_emit(scores, layout, w, h, img, images, setup, out, i, (size_t)img * kp_cap + i);
   if (tid == 0) kp_count[img] = kept;
 }
 
