@@ -619,10 +619,6 @@ void okvfe_destroy(okvfe_ctx* ctx) {
   for (hipEvent_t ev : ctx->lane_done)
     if (ev) (void)hipEventDestroy(ev);
   if (ctx->lane_fork) (void)hipEventDestroy(ctx->lane_fork);
-  if (ctx->score_stream && !ctx->lane_view) {
-    (void)hipStreamSynchronize(ctx->score_stream);
-    (void)hipStreamDestroy(ctx->score_stream);
-  }
   for (hipEvent_t ev : ctx->layer_ev)
     if (ev) (void)hipEventDestroy(ev);
   if (ctx->layer_fork) (void)hipEventDestroy(ctx->layer_fork);

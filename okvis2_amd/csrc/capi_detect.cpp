@@ -149,11 +149,10 @@ extern "C" int32_t okvfe_pattern_kernel_class(const okvfe_ctx* ctx) { return ctx
 // Every image camera-aware on a camera whose patches fit the kernel's LDS classes, the fixed-scale pattern with boxes
 // inside the fixed-trip slots, dword-aligned images.
 static int aware_box_for_call(const okvfe_ctx* ctx, const uint8_t* images_dev) {
-  static const bool old_aware = lab_env("OKVFE_DESC_R5") != nullptr;  // A/B knob: the round-5 kernels
   const okvfe::Pattern& P = ctx->host_pattern;
   const int cls = pattern_box_class(P);
   const int extra = P.n_points > 64 ? P.n_points - 64 : 0;
-  if (old_aware || !ctx->all_aware || !ctx->aware_fast || cls > 1 || extra > okvfe::kAwareMaxExtra || ctx->d_scales ||
+  if (!ctx->all_aware || !ctx->aware_fast || cls > 1 || extra > okvfe::kAwareMaxExtra || ctx->d_scales ||
       ctx->n_layers != 1 || ctx->w % 4 != 0 || (reinterpret_cast<uintptr_t>(images_dev) & 3) != 0 || ctx->w >= 4096 ||
       ctx->h >= 4096)
     return -1;
@@ -234,17 +233,12 @@ void layer_select(okvfe_ctx* L, int n_images, hipStream_t s) {
   if (!L->lane_view) L->aware_extra_box = aware_box_for_call(L, L->live_images);  // (a view: its owner decided)
   const DescribeSetup setup{L->d_pattern, L->d_prm, L->d_rays_ptrs, L->d_jac_ptrs, L->d_kps_tmp, L->d_desc_tmp,
                             L->d_valid_tmp, L->d_scales, L->live_images,
-                            L->aware_extra_box > 0 && okvfe::aware_extras_in_setup() ? (L->aware_extra_box & 0xFF) : 0};
+                            L->aware_extra_box > 0 ? (L->aware_extra_box & 0xFF) : 0};
   const bool fuse = L->fuse_setup && L->n_layers == 1 && L->d_pattern && L->d_kps_tmp && L->d_prm;
   L->setup_done = launch_select(L->d_scores, L->live_layout, L->w, L->h, n_images, L->d_cand, L->cand_cap,
                                 L->d_cand_count, L->cfg.uniformity_radius, L->cfg.max_keypoints, L->d_lut, L->d_occ,
                                 L->occ_image_bytes, L->occ_rows, L->occ_cols, L->d_kps_det, L->kp_cap, L->d_det_count,
                                 L->d_sort_ws, s, fuse ? &setup : nullptr, L->map_free_live ? L->live_images : nullptr);
-}
-
-static bool scale_space_serial() {
-  static const bool serial = lab_env("OKVFE_SS_SERIAL") != nullptr;  // A/B knob: the layers one after the other on one stream
-  return serial;
 }
 
 // scale of layer l relative to layer m, reduced (oracle: the layer ratios of detect_scale_space)
@@ -273,7 +267,6 @@ static okvfe_status detect_layers_concurrent(okvfe_ctx* ctx, const uint8_t* imag
     HIP_TRY(ctx, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     ctx->layer_ev.push_back(ev);
   }
-  static const int own_mask = lab_env("OKVFE_SS_OWN") ? atoi(lab_env("OKVFE_SS_OWN")) : 0xFF;  // bisecting knob: layers on streams of their own
   auto ev_img = [&](int l) { return ctx->layer_ev[3 * l]; };
   auto ev_map = [&](int l) { return ctx->layer_ev[3 * l + 1]; };
   auto ev_done = [&](int l) { return ctx->layer_ev[3 * l + 2]; };
@@ -285,7 +278,7 @@ static okvfe_status detect_layers_concurrent(okvfe_ctx* ctx, const uint8_t* imag
   // ---- per layer: image, score map, 2-D maxima
   for (int l = 0; l < L; ++l) {
     okvfe_ctx* ch = ctx->layers[l];
-    hipStream_t ls = ((own_mask >> l) & 1) ? ch->stream : s;
+    hipStream_t ls = ch->stream;
     HIP_TRY(ctx, hipStreamWaitEvent(ls, ctx->layer_fork, 0));
     if (l == 1) {
       launch_twothird(img[0], ctx->layer_w[0], ctx->layer_h[0], n_images, ctx->d_layer_img[1], ls);
@@ -294,36 +287,25 @@ static okvfe_status detect_layers_concurrent(okvfe_ctx* ctx, const uint8_t* imag
       launch_halfsample(img[l - 2], ctx->layer_w[l - 2], ctx->layer_h[l - 2], n_images, ctx->d_layer_img[l], ls);
     }
     if (l >= 1) HIP_TRY(ctx, hipEventRecord(ev_img(l), ls));
-    static const int dbg_l1 = lab_env("OKVFE_SS_DBG_L1") ? atoi(lab_env("OKVFE_SS_DBG_L1")) : 0;  // bisecting knob
-    if (l == 1 && dbg_l1 == 1) (void)hipDeviceSynchronize();
-    static const bool dbg_memset = lab_env("OKVFE_SS_DBG_MEMSET") != nullptr;  // bisecting knob: the runtime's memset
-    if (dbg_memset)
-      HIP_TRY(ctx, hipMemsetAsync(ch->d_cand_count, 0, 2 * (size_t)ch->B * sizeof(int32_t), ls));
-    else  // counters cleared by a kernel of our own (stays in the layer's compute queue)
-      launch_param_copy(nullptr, nullptr, 0, ch->d_cand_count, 2 * ch->B, ls, nullptr, 0);
+    // counters cleared by a kernel of our own, not the runtime's memset (stays in the layer's compute queue)
+    launch_param_copy(nullptr, nullptr, 0, ch->d_cand_count, 2 * ch->B, ls, nullptr, 0);
     bool f;
     layer_score_nms(ch, img[l], n_images, ls, &f);
-    if (l == 1 && dbg_l1 == 2) (void)hipDeviceSynchronize();
     layer_nms_finish(ch, n_images, ls, f);
     HIP_TRY(ctx, hipEventRecord(ev_map(l), ls));
-    if (const char* m = lab_env("OKVFE_SS_DBG_A"))  // bisecting knob: device sync behind the layers of this bit mask
-      if ((atoi(m) >> l) & 1) (void)hipDeviceSynchronize();
   }
   // the FAST 5-8 map of c0 (the virtual layer below the first octave) is as large as c0's own score map: it runs on the
   // LAST layer's stream, whose own chain is the shortest, instead of behind c0's score kernel on the longest one
   hipEvent_t ev_virtual = ctx->layer_ev[3 * L];
   if (ctx->d_virtual) {
-    hipStream_t vs = ((own_mask >> (L - 1)) & 1) ? ctx->layers[L - 1]->stream : s;
+    hipStream_t vs = ctx->layers[L - 1]->stream;
     launch_fast58_score(img[0], ctx->layer_w[0], ctx->layer_h[0], n_images, ctx->d_virtual, vs);
     HIP_TRY(ctx, hipEventRecord(ev_virtual, vs));
   }
-  static const char* dbg = lab_env("OKVFE_SS_DBG");  // bisecting knob: 1 = device sync between the phases, 2 = after every layer too
-  if (dbg) (void)hipDeviceSynchronize();
   // ---- per layer: scale-space maxima against the finished maps below and above, order, selection / refinement
   for (int l = 0; l < L; ++l) {
     okvfe_ctx* ch = ctx->layers[l];
-    hipStream_t ls = ((own_mask >> l) & 1) ? ch->stream : s;
-    if (dbg && dbg[0] == '2') (void)hipDeviceSynchronize();
+    hipStream_t ls = ch->stream;
     if (l > 0) HIP_TRY(ctx, hipStreamWaitEvent(ls, ev_map(l - 1), 0));
     if (l + 1 < L) HIP_TRY(ctx, hipStreamWaitEvent(ls, ev_map(l + 1), 0));
     if (l == 0 && ctx->d_virtual) HIP_TRY(ctx, hipStreamWaitEvent(ls, ev_virtual, 0));
@@ -380,13 +362,10 @@ okvfe_status detect_stage(okvfe_ctx* ctx, const uint8_t* images_dev, int n_image
   okvfe_status st;
   ctx->setup_done = false;  // set by this call's selection launch only (a failed earlier call must not leak it)
   if (ctx->n_layers == 1) {
-    // priority lanes: the score kernel (and the clears in front of it) go to the owner's low-priority score stream,
-    // which runs the slices' score kernels back to back; this lane's stream picks up behind its k1_done
-    hipStream_t ks = ctx->lane_view && ctx->score_stream ? ctx->score_stream : s;
     if (!ctx->counters_cleared) {  // (cleared together with the parameter upload of the same call otherwise)
       if (ctx->lane_view) {
-        HIP_TRY(ctx, hipMemsetAsync(ctx->d_cand_count, 0, (size_t)ctx->B * sizeof(int32_t), ks));
-        HIP_TRY(ctx, hipMemsetAsync(ctx->d_fix_count, 0, (size_t)ctx->B * sizeof(int32_t), ks));
+        HIP_TRY(ctx, hipMemsetAsync(ctx->d_cand_count, 0, (size_t)ctx->B * sizeof(int32_t), s));
+        HIP_TRY(ctx, hipMemsetAsync(ctx->d_fix_count, 0, (size_t)ctx->B * sizeof(int32_t), s));
       } else {
         HIP_TRY(ctx, hipMemsetAsync(ctx->d_cand_count, 0, 2 * (size_t)ctx->B * sizeof(int32_t), s));
       }
@@ -396,13 +375,12 @@ okvfe_status detect_stage(okvfe_ctx* ctx, const uint8_t* images_dev, int n_image
     bool fused;
     // lanes inside one call: the score kernels run one after the other, so that the lanes proceed OUT OF PHASE -- the
     // (vector-ALU-bound) score kernel of lane l beside the selection / descriptor kernels of the lanes before it
-    if (ctx->k1_wait && ks == s) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->k1_wait, 0));
+    if (ctx->k1_wait) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->k1_wait, 0));
     {
-      StageTimer t(ctx, OKVFE_STAGE_HARRIS, ks);
-      layer_score_nms(ctx, images_dev, n_images, ks, &fused);
+      StageTimer t(ctx, OKVFE_STAGE_HARRIS, s);
+      layer_score_nms(ctx, images_dev, n_images, s, &fused);
     }
-    if (ctx->k1_done) HIP_TRY(ctx, hipEventRecord(ctx->k1_done, ks));
-    if (ks != s) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->k1_done, 0));
+    if (ctx->k1_done) HIP_TRY(ctx, hipEventRecord(ctx->k1_done, s));
     if ((st = heavy_end(ctx, s, 0, &token)) != OKVFE_OK) return st;
     {
       StageTimer t(ctx, OKVFE_STAGE_NMS, s);
@@ -416,8 +394,8 @@ okvfe_status detect_stage(okvfe_ctx* ctx, const uint8_t* images_dev, int n_image
       StageTimer t(ctx, OKVFE_STAGE_SELECT, s);
       layer_select(ctx, n_images, s);
     }
-  } else if (ctx->prof_mask == 0 && score_token_mode() == 0 && !scale_space_serial()) {  // (stage timers and the
-    // cross-context chaining of the heavy kernels belong to the one-stream form below)
+  } else if (ctx->prof_mask == 0 && score_token_mode() == 0) {  // (stage timers and the cross-context chaining of
+    // the heavy kernels belong to the one-stream form below)
     if ((st = detect_layers_concurrent(ctx, images_dev, n_images, s)) != OKVFE_OK) return st;
   } else {
     const int L = ctx->n_layers;
@@ -593,8 +571,7 @@ okvfe_status describe_stage(okvfe_ctx* ctx, const uint8_t* images_dev, int n_ima
 
 // ---- lanes inside one call (okvfe_ctx::internal_lanes) ---------------------------------------------------------------
 int lanes_for_call(const okvfe_ctx* ctx, int n_images) {
-  static const char* force = lab_env("OKVFE_INTERNAL_LANES");  // A/B knob
-  int k = force ? atoi(force) : ctx->internal_lanes;
+  int k = ctx->internal_lanes;
   if (ctx->n_layers != 1 || ctx->lane_view || ctx->child || !ctx->d_cand) return 1;
   // 0 = the library's choice, which is NOT to cut (measured, round 6, 3072 EuRoC stereo frames per call, one caller
   // stream): 1 / 2 / 3 / 4 / 6 lanes = 710 / 688 / 702 / 700 / 677 k stereo-frames/s, with the score kernels chained
@@ -618,23 +595,11 @@ okvfe_status ensure_join(okvfe_ctx* ctx) {
 
 okvfe_status ensure_lanes(okvfe_ctx* ctx, int k) {
   if (!ctx->lane_fork) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->lane_fork, hipEventDisableTiming));
-  static const bool prio_env = lab_env("OKVFE_LANES_PRIO") != nullptr;  // A/B knob
-  const bool prio = prio_env || ctx->lanes_prio;
-  int p_low = 0, p_high = 0;
-  if (prio) {
-    HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
-    HIP_TRY(ctx, hipDeviceGetStreamPriorityRange(&p_low, &p_high));  // (numerically: low >= high)
-    if (!ctx->score_stream) HIP_TRY(ctx, hipStreamCreateWithPriority(&ctx->score_stream, hipStreamNonBlocking, p_low));
-    ctx->lanes_prio = true;
-  }
   while ((int)ctx->lane_ctx.size() < k) {
     hipStream_t st = nullptr;
     hipEvent_t ev = nullptr;
     HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));  // (streams live on the context's device, whatever the caller's current one)
-    if (prio)
-      HIP_TRY(ctx, hipStreamCreateWithPriority(&st, hipStreamNonBlocking, p_high));
-    else
-      HIP_TRY(ctx, hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    HIP_TRY(ctx, hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
     hipError_t e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
     if (e != hipSuccess) {
       (void)hipStreamDestroy(st);
@@ -726,12 +691,9 @@ okvfe_status detect_describe_split(okvfe_ctx* ctx, const uint8_t* images_dev, in
     if (n <= 0) break;
     okvfe_ctx* v = ctx->lane_ctx[l];
     bind_lane(v, ctx, first, n);
-    static const bool no_chain = lab_env("OKVFE_LANES_NOCHAIN") != nullptr;  // A/B knob
     // (pipelined lanes are never chained: each follows its own previous call, like separate contexts)
-    v->k1_wait = l > 0 && !no_chain && !pipelined ? ctx->lane_ctx[l - 1]->k1_done : nullptr;
-    v->score_stream = ctx->score_stream;
+    v->k1_wait = l > 0 && !pipelined ? ctx->lane_ctx[l - 1]->k1_done : nullptr;
     HIP_TRY(ctx, hipStreamWaitEvent(v->stream, ctx->lane_fork, 0));
-    if (ctx->score_stream && l == 0) HIP_TRY(ctx, hipStreamWaitEvent(ctx->score_stream, ctx->lane_fork, 0));
     st = detect_stage(v, images_dev + first * P, n, v->stream);
     v->fuse_setup = false;
     if (st == OKVFE_OK) st = describe_stage(v, images_dev + first * P, n, v->stream);

@@ -228,7 +228,8 @@ __device__ __forceinline__ void describe_setup_one(const DescribeSetup& ds, int 
       }
     }
     *reinterpret_cast<int2*>(ds.desc_tmp + slot * OKVFE_DESC_BYTES + 16) = make_int2(g0, g1);
-    // ... and the samples beyond its 64 lanes, bytes 24.. of the slot (extra_box == 0: describe_extras_kernel does it)
+    // ... and the samples beyond its 64 lanes, bytes 24.. of the slot; a box outside the image drops the keypoint
+    // (extra_box == 0: the pattern has none, or describe_kernel serves the call)
     if (valid && ds.extra_box > 0) {
       const int extra = ds.pat->n_points - 64;  // 1 .. kAwareMaxExtra (host-checked)
       for (int e = 0; e < extra && valid; ++e)

@@ -236,16 +236,6 @@ __device__ __forceinline__ bool sample_pos(const float M[4], float kx, float ky,
   return (x_1 >= 0.0f && y_1 >= 0.0f && x1 < (float)(w - 1) && y1 < (float)(h - 1));
 }
 
-// A/B switches of the round-5 latency experiments (tools/lab/descab5.sh; defaults = the kept forms)
-#ifndef OKVFE_DESC_LATE_WAIT
-#define OKVFE_DESC_LATE_WAIT 1   // per-sample set-up runs under the patch loads' latency
-#endif
-#ifndef OKVFE_DESC_PAIRS_REG
-#define OKVFE_DESC_PAIRS_REG 1   // the lane's six pair entries live in registers (0: read from the LDS table per keypoint)
-#endif
-#ifndef OKVFE_DESC_PAIRS_OPAQUE
-#define OKVFE_DESC_PAIRS_OPAQUE 0  // 1: the gather addresses derived from them are recomputed per keypoint (no hoisting)
-#endif
 #ifndef OKVFE_DESC_WG_WAVES
 #define OKVFE_DESC_WG_WAVES 4
 #endif
@@ -435,10 +425,7 @@ __global__ __launch_bounds__(64 * kDescWaves) __attribute__((amdgpu_waves_per_eu
     // instructions for the same pixels.  The staging is bound by the number of vector-memory
     // requests in flight at L2 latency, not by bytes (stage-only 0.43 ms of the kernel's 0.51 with
     // dword requests), so fewer, wider requests are what shortens it.  Rows are padded to 16 B.
-    int nq = (pw + 15) >> 4;  // 16-byte chunks per patch row
-#ifdef OKVFE_DESC_ODD_PITCH
-    nq |= 1;  // A/B: odd chunk count = rows step through all bank phases (tools/lab: LDS bank conflicts of the box sums)
-#endif
+    const int nq = (pw + 15) >> 4;  // 16-byte chunks per patch row
     if (dword_ok && nq >= 1 && nq * 16 <= kZeroRowBytes - 8) {
       const int pitch = nq * 16;
       const uint32_t inv = (65536u + (uint32_t)nq - 1u) / (uint32_t)nq;
@@ -456,8 +443,8 @@ __global__ __launch_bounds__(64 * kDescWaves) __attribute__((amdgpu_waves_per_eu
                 img_rsrc, (__attribute__((address_space(3))) void*)(patch + it * R * pitch), 16,
                 (int)src_lane, src0 + it * R * w, 0, 0);
         }
-        if (AWARE && in_flight && OKVFE_DESC_LATE_WAIT) {
-          *in_flight = true;  // the caller's first box sum waits (smoothed_intensity<.., LATE_WAIT>)
+        if (AWARE && in_flight) {
+          *in_flight = true;  // the per-sample set-up runs under the loads' latency: the caller's first box sum waits (smoothed_intensity<.., LATE_WAIT>)
         } else {
           __builtin_amdgcn_s_waitcnt(0);
           __builtin_amdgcn_wave_barrier();
@@ -674,9 +661,6 @@ __global__ __launch_bounds__(64 * kDescWaves) __attribute__((amdgpu_waves_per_eu
   // opaque to the optimiser: expressions of the lane constants are NOT hoisted out of the loop
   // (they would cost ~25 more live VGPRs and push the kernel below 6 waves/SIMD)
   asm volatile("" : "+v"(px), "+v"(py), "+v"(sg), "+v"(bsc), "+v"(bsc2), "+v"(lane));
-#if OKVFE_DESC_PAIRS_OPAQUE
-  asm volatile("" : "+v"(my_pairs[0]), "+v"(my_pairs[1]), "+v"(my_pairs[2]));  // (nor the 12 gather addresses derived from these)
-#endif
   const size_t slot = (size_t)img * kp_cap + k;
   auto uni = [](float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); };
   kp.x = uni(nxt_x);
@@ -761,11 +745,7 @@ __global__ __launch_bounds__(64 * kDescWaves) __attribute__((amdgpu_waves_per_eu
     for (int j = 0; j < 6; ++j) {
       // this lane's pair of word j, held in registers for the whole wave (two pairs per dword): no table read in a
       // keypoint's chain, only the two value gathers
-#if OKVFE_DESC_PAIRS_REG
       const uint32_t pr = (j & 1) ? my_pairs[j >> 1] >> 16 : my_pairs[j >> 1] & 0xFFFFu;  // slots past n_short: 0 | 0
-#else
-      const uint32_t pr = short_pairs[j * 64 + lane];
-#endif
       const bool bit = vals[pr & 255u] > vals[pr >> 8];
       words[j] = __ballot(bit);
     }
@@ -850,7 +830,7 @@ void launch_describe(const uint8_t* img, int w, int h, int n_images, const Patte
   if (!setup_done)  // (done by select_lazy_kernel when detection and description were one call)
   hipLaunchKernelGGL(describe_setup_kernel, dim3((kp_cap + 255) / 256, n_images), dim3(256), 0,
                      stream, w, h, pat, prm, rays, jac, kps_in, kp_cap, kp_count_in, kps_tmp, desc_tmp,
-                     valid_tmp, scales, img, aware_extra_box > 0 && aware_extras_in_setup() ? (aware_extra_box & 0xFF) : 0);
+                     valid_tmp, scales, img, aware_extra_box > 0 ? (aware_extra_box & 0xFF) : 0);
   // blocks per image: enough waves to fill the machine with one image's ~300 keypoints spread
   // over them (a wave then describes ~9 keypoints of its image in a row)
   int tiles = (kp_cap + kDescWaves - 1) / kDescWaves;
@@ -869,14 +849,12 @@ void launch_describe(const uint8_t* img, int w, int h, int n_images, const Patte
   // have left the extra samples in the slots)
   if (all_camera_aware && aware_extra_box >= 0 && box_class <= 1) {
     launch_describe_aware(img, w, h, n_images, pat, kps_in, kp_cap, kp_count_in, desc_tmp, valid_tmp, box_class == 1,
-                          stream, aware_extra_box > 0 && !aware_extras_in_setup() ? (aware_extra_box >> 8) : 0,
-                          aware_extra_box & 0xFF);
+                          stream);
     return;
   }
   // round 6: upright / gradient-orientation calls (the BRISK scale-space path, callers without a camera) on the same box
   // sums: describe_rot_kernel (k_describe_aware.hip)
-  static const bool no_rot = lab_env("OKVFE_DESC_NO_ROT") != nullptr;  // A/B knob
-  if (rot_fast && !no_rot && !no_aware && box_class == 0 && scales == nullptr && w % 4 == 0 &&
+  if (rot_fast && !no_aware && box_class == 0 && scales == nullptr && w % 4 == 0 &&
       (reinterpret_cast<uintptr_t>(img) & 3) == 0) {
     launch_describe_rot(img, w, h, n_images, pat, prm, kps_in, kp_cap, kp_count_in, kps_tmp, desc_tmp, valid_tmp, stream);
     return;

@@ -444,7 +444,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) OKVFE_K1_WAVES void harris_ker
   // lines; lanes outside the row (and idle lanes of a packed wave) get a per-lane offset outside the
   // resource, which the hardware range check drops (the scalar offset is not range-checked)
   // (the stand-alone score kernel, NMS = false, writes the dense map: pitch == w, owners only)
-  // and so does the fused kernel under the OKVFE_K1_DENSE A/B knob (pitch == w)
+  // and so does the fused kernel on an image of a single strip (pitch == w)
   const bool slotted = NMS && pitch != w;
   const int slot_q = slotted ? d + 2 * strip : d;  // quad position within the (padded) row
   const bool st_on = slotted ? (lane_on && slot_q * 4 < pitch) : store;
@@ -911,8 +911,7 @@ ScoreLayout harris_nms_layout(int w, int h) {
   static const bool off = lab_env("OKVFE_NO_FUSED_NMS") != nullptr;  // A/B knob for profiling
   if (off || w % 4 != 0) return ScoreLayout{w, 0};
   const int strips = harris_strips(w);
-  static const bool dense = lab_env("OKVFE_K1_DENSE") != nullptr;  // A/B knob: fused kernel, dense map
-  if (strips == 1 || dense) return ScoreLayout{w, 1};
+  if (strips == 1) return ScoreLayout{w, 1};
   const int pitch = ((w + 8 * (strips - 1)) + 31) & ~31;
   return ScoreLayout{pitch, strips};
 }

@@ -169,9 +169,6 @@ __global__ __launch_bounds__(256) void nms_generic_kernel(const int32_t* __restr
   int pos = base_s + incl - cnt;
   for (int w2 = 0; w2 < wave; ++w2) pos += wtot[w2];
   if (cnt == 0) return;
-#ifdef OKVFE_NMS_TIMING_NOWRITE  // (timing experiment only: wrong results)
-  return;
-#endif
   Candidate* out = cand + (size_t)img * cand_cap;
 #pragma unroll 1
   for (int it = 0; it < kGenIters; ++it) {

@@ -1313,8 +1313,7 @@ LazyPlan lazy_plan(float radius, int max_kpts, int kp_cap, const uint8_t* occupa
                    int occ_rows, int occ_cols) {
   LazyPlan p{};
   static const bool legacy = lab_env("OKVFE_LEGACY_SELECT") != nullptr;  // A/B knob
-  static const bool grid = lab_env("OKVFE_SELECT_GRID") != nullptr;      // A/B knob: the occupancy-grid kernels
-  if (!(radius > 0.0f) || legacy || grid || occ_cols > 65535 || occ_rows > 65535) return p;
+  if (!(radius > 0.0f) || legacy || occ_cols > 65535 || occ_rows > 65535) return p;
   // lazy occupancy (no grid): any image size / radius whose bin heads and keypoint slots fit in LDS
   p.bins_x = (occ_cols + 15) >> 4;
   p.bins_y = (occ_rows + 15) >> 4;

@@ -1,5 +1,5 @@
 // k_select_grid.hip -- uniformity selection on an explicit occupancy grid (the fall-backs of launch_select:
-// lab knobs OKVFE_LEGACY_SELECT / OKVFE_SELECT_GRID, grids whose lazy form does not fit, radius 0).
+// lab knob OKVFE_LEGACY_SELECT, grids whose lazy form does not fit, radius 0).
 //
 //   select_greedy_kernel  occupancy grid in LDS (or HBM), one workgroup of 4 waves per image: the greedy is
 //                         serial in its accepted points only -- occupancy only grows, so a candidate that

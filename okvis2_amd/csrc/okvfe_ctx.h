@@ -106,10 +106,6 @@ struct okvfe_ctx {
   std::vector<okvfe_ctx*> lane_ctx;
   std::vector<hipEvent_t> lane_done;
   hipEvent_t lane_fork = nullptr;
-  // priority form of the lanes (lab knob OKVFE_LANES_PRIO / okvfe_set_internal_lanes(-k)): ONE low-priority stream runs the
-  // score kernels of all slices back to back, the slices' tails (fix-up .. compaction) run on high-priority lane streams
-  hipStream_t score_stream = nullptr;  // owner: the low-priority stream; lane view: where its score kernel goes (or null)
-  bool lanes_prio = false;             // owner: lane streams were created with priorities
   // PIPELINED lanes (okvfe_set_internal_lanes(ctx, -k)): the call does not join its lanes onto the caller's stream; the
   // slices' chains -- and those of the okvfe_match_stereo_batch_device call that follows -- stay on the lane streams, so
   // lane l starts the next call's score kernel behind ITS OWN previous work and the lanes drift out of phase, as separate

@@ -303,10 +303,7 @@ bool describe_patch_fits(float nx, float ny, int border);
 int describe_aware_patch_class(float nx, float ny, float reach);
 void launch_describe_aware(const uint8_t* img, int w, int h, int n_images, const Pattern* pat,
                            const okvfe_keypoint* kps_in, int kp_cap, const int32_t* kp_count_in, uint8_t* desc_tmp,
-                           uint8_t* valid_tmp, bool wide_boxes, hipStream_t stream, int extras_now, int extra_box);
-// true: the set-up threads (selection kernel's tail / describe_setup_kernel) evaluate the extra samples; false: a
-// kernel of their own does (describe_extras_kernel)
-bool aware_extras_in_setup();
+                           uint8_t* valid_tmp, bool wide_boxes, hipStream_t stream);
 // Quarter-wave lookup of the pattern's 1024-step rotation tables: sin(k) = +-Q[r or 256 - r] with Q = the first 257
 // entries of the sine table, cos(k) = sin(k + 256).  describe_rot_kernel keeps Q (ints and floats, 2 KB) in LDS instead
 // of gathering from the 16 KB of global tables inside every keypoint's chain; the host verifies once per pattern that the

@@ -28,4 +28,4 @@ for _ in range(3): fe.detect_describe_batch_device(d.data_ptr(), B, cam_ids, g, 
 torch.cuda.synchronize(); prof()
 for _ in range(10): fe.detect_describe_batch_device(d.data_ptr(), B, cam_ids, g, None)
 torch.cuda.synchronize()
-print(os.environ.get("OKVFE_DESC_TILES", "16"), prof())
+print(prof())

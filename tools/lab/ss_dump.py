@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""GPU box, lab library: buffers of every scale-space layer after a call, against a reference dump of the one-stream form.
-usage: OKVFE_SS_OWN=0 ss_dump.py ref   (writes /tmp/ss_ref.npz);   ss_dump.py cmp [runs]"""
+"""GPU box, lab library: buffers of every scale-space layer after a call, against a reference dump of an earlier run.
+usage: ss_dump.py ref   (writes /tmp/ss_ref.npz);   ss_dump.py cmp [runs]"""
 import ctypes as C, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 os.environ.setdefault("OKVFE_LIB", os.path.join(ROOT, "okvis2_amd", "libokvfe_lab.so"))
