@@ -758,6 +758,63 @@ okvfe_status okvfe_verify_place_blocks_device(okvfe_ctx* ctx, const void* blocks
                                               const okvfe_map_device* map, int32_t* k_min_dev,
                                               uint32_t* dist_min_dev, void* stream);
 
+/* ---- keyframe decision: keypoint coverage masks and their IoU ---------------- */
+/* Frontend::doWeNeedANewKeyframe (Frontend.cpp:1058-1167), the step between the map matchers and matchStereo whose
+ * answer is *asKeyframe.  Per camera image of size w x h (the context's) the reference keeps two zeroed u8 masks of
+ * rows = h / 10 by cols = w / 10 pixels, `detections` and `matches`, and for every keypoint paints
+ * cv::circle(mask, keypoint.pt * 0.1, radius, 255, cv::FILLED), radius = int(double(min(rows, cols)) * kptrad), into
+ * `detections` and, if the keypoint carries a landmark, into `matches`; it then counts the non-zero pixels of
+ * matches & detections and of matches | detections (:1074-1101, :1123-1149).  The coverage calls return these counts
+ * per image, okvfe_keyframe_decision turns the records of the current multiframe and of the other multiframes into
+ * the verdict.  The counts are exposed because ViSlamBackend::overlapFraction / trackingQuality
+ * (ViSlamBackend.cpp:157-196, 2341-2427) are a few host lines over the same primitive.
+ *
+ * What stays with the caller, because it needs estimator state: the two early returns at :1060-1065 (fewer than
+ * 4 frames in the estimator -> keyframe; front-end not initialised -> no keyframe), which come BEFORE anything here,
+ * and the choice of the other multiframes (keyframes, loop-closure frames, keyframes in the IMU window: :1105-1115).
+ *
+ * PARITY UNPINNED: cv::circle and the point conversion are not in the reference tree (OpenCV is an external
+ * dependency of it); they are restated from OpenCV's published source.  Centre: Point2f * double gives
+ * float(double(x) * 0.1) per coordinate, cv::Point rounds it with cvRound (half to even); a centre may lie outside
+ * the mask (cx == cols), the disc is clipped.  Disc: thickness FILLED, LINE_8, shift 0 is the integer midpoint
+ * routine -- a fixed stencil of half-widths per row offset (r = 4: 4 3 3 2 0, 49 pixels).  Keypoints whose
+ * coordinates are not finite paint nothing.  See DESIGN.md, "keyframe decision".
+ *
+ * Limits (OKVFE_ERR_UNSUPPORTED beyond them): radius <= 127 mask pixels, and the two bit masks of an image plus the
+ * id table must fit 64 KB of LDS -- every frame size okvfe_create accepts does at any radius up to 127, and so would
+ * 4096 x 4096. */
+typedef struct okvfe_coverage {      /* one camera image; 24 bytes */
+  int32_t n_keypoints, n_matched;    /* keypoints painted into detections / into matches */
+  int32_t detections_area, matches_area, intersection_area, union_area;  /* countNonZero of the four masks */
+} okvfe_coverage;
+/* :1074-1101 / :1123-1149 for n_frames gather blocks in one launch, one work-group per block.  landmark_ids_dev:
+ * device, n_frames x K (K = okvfe_device_outputs.max_keypoints), 0 = no landmark; rows past a block's count are not
+ * read.  id_set_dev == NULL: a keypoint counts as matched iff its id != 0 (the current frame); otherwise iff
+ * id != 0 and id is among the n_id_set values at id_set_dev (the other frames, :1138) -- in any order, duplicates and
+ * zeros allowed (zeros are ignored), n_id_set == 0 = the empty set.  ONE set per call, on purpose: the set is the
+ * current multiframe's, the same for every other frame it is compared with, and may simply be the current frame's
+ * own landmark_ids_dev rows, so the whole decision needs no host round trip but the final few records.
+ * kptrad: 0.09 in Frontend.cpp:104 (ViSlamBackend uses 0.09 * uniformityRadius / 36).  coverage_dev: device,
+ * n_frames records; nothing past them is written.  Nothing synchronises the host. */
+okvfe_status okvfe_keyframe_coverage_blocks_device(okvfe_ctx* ctx, const void* blocks_dev, int32_t n_frames,
+                                                   const uint64_t* landmark_ids_dev, const uint64_t* id_set_dev,
+                                                   int32_t n_id_set, double kptrad, okvfe_coverage* coverage_dev,
+                                                   void* stream);
+/* host containers in, host record out (the B = 1 seam; like okvfe_match_to_map): the same kernel on the context's
+ * own stream, n keypoints of any number, synchronous. */
+okvfe_status okvfe_keyframe_coverage(okvfe_ctx* ctx, const okvfe_keypoint* keypoints, int32_t n,
+                                     const uint64_t* landmark_ids, const uint64_t* id_set, int32_t n_id_set,
+                                     double kptrad, okvfe_coverage* out);
+/* pure host arithmetic, no context: :1103, :1116-1166 in the reference's expression order.  current: n_cameras
+ * records; others: n_others x n_cameras (multiframe-major), NULL if n_others == 0.  overlap_threshold: 0.55f
+ * (keyframeInsertionOverlapThreshold_, :145).  *overlap (may be NULL) receives std::min(overlapOthers, overlap) of
+ * :1154.  0 / 0 is NaN and goes through std::max / std::min / the comparisons as in the reference: a multiframe
+ * without a painted pixel does not raise overlapOthers, no other frames leave it 0, and a keyframe is then needed
+ * (unless the current multiframe has fewer than 7 keypoints per camera, :1157).  Negative counts are rejected. */
+okvfe_status okvfe_keyframe_decision(const okvfe_coverage* current, int32_t n_cameras, const okvfe_coverage* others,
+                                     int32_t n_others, float overlap_threshold, int32_t* need_keyframe,
+                                     double* overlap);
+
 /* ---- cross-camera gather collective (RCCL over xGMI) ---------------------- */
 /* The one exchange step of the path (okvis_frontend/src/Frontend.cpp:1990-2026 needs the keypoints
  * of BOTH cameras of a pair; with one camera per GPU they live on different ranks): an all-gather of

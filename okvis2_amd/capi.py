@@ -29,6 +29,10 @@ STEREO_MATCH_DTYPE = np.dtype([("k1", "<i4"), ("dist", "<i4"), ("initialisable",
 CAND_DTYPE = np.dtype([("i", "<i4"), ("j", "<i4"), ("dist", "<i4")])
 MOTION_MATCH_DTYPE = np.dtype([("k1", "<i4"), ("dist", "<i4"), ("initialisable", "<i4"),
                                ("accepted", "<i4"), ("cos_quality", "<f8"), ("hp_W", "<f8", (4,))])
+COVERAGE_DTYPE = np.dtype([("n_keypoints", "<i4"), ("n_matched", "<i4"), ("detections_area", "<i4"),
+                           ("matches_area", "<i4"), ("intersection_area", "<i4"), ("union_area", "<i4")])
+KPTRAD = 0.09  # Frontend.cpp:104
+KEYFRAME_OVERLAP_THRESHOLD = 0.55  # keyframeInsertionOverlapThreshold_, Frontend.cpp:145
 
 
 class Config(C.Structure):
@@ -109,6 +113,7 @@ EXPORTS = [
     "okvfe_stream_synchronize", "okvfe_copy_to_device", "okvfe_copy_to_host", "okvfe_device_fill",
     "okvfe_set_camera_ext", "okvfe_build_awareness_maps_ext", "okvfe_camera_overlap_ext",
     "okvfe_match_motion_stereo_ext",
+    "okvfe_keyframe_coverage_blocks_device", "okvfe_keyframe_coverage", "okvfe_keyframe_decision",
 ]
 
 STAGES = ["harris", "nms", "sort", "select", "map", "describe", "compact", "match"]
@@ -292,6 +297,25 @@ def bow_vector(word_ids, word_weight, weighting=0, normalise_l1=True):
     if st != OK:
         raise OkvfeError(st, "okvfe_bow_vector")
     return ids[:n.value].copy(), vals[:n.value].copy()
+
+
+def keyframe_decision(current, others=None, overlap_threshold=KEYFRAME_OVERLAP_THRESHOLD):
+    """okvfe_keyframe_decision (Frontend.cpp:1103, :1116-1166; host arithmetic, no context): current = the coverage
+    records of the current multiframe's cameras, others = (n_others, n_cameras) records of the multiframes it is
+    compared with.  Returns (need_keyframe, overlap).  The two early returns of :1060-1065 stay with the caller."""
+    cur = np.ascontiguousarray(current, dtype=COVERAGE_DTYPE).reshape(-1)
+    n_cam = len(cur)
+    oth = np.zeros((0, max(n_cam, 1)), dtype=COVERAGE_DTYPE) if others is None else \
+        np.ascontiguousarray(others, dtype=COVERAGE_DTYPE)
+    if oth.size and (n_cam == 0 or oth.size % n_cam):
+        raise ValueError("others: n_others x n_cameras records")
+    n_oth = oth.size // n_cam if n_cam else 0
+    need, overlap = C.c_int32(), C.c_double()
+    st = lib().okvfe_keyframe_decision(_p(cur) if n_cam else None, n_cam, _p(oth) if n_oth else None, n_oth,
+                                       C.c_float(overlap_threshold), C.byref(need), C.byref(overlap))
+    if st != OK:
+        raise OkvfeError(st, "okvfe_keyframe_decision")
+    return bool(need.value), overlap.value
 
 
 def set_heavy_kernel_chaining(mode: int):
@@ -774,6 +798,33 @@ class Frontend:
         self._check(lib().okvfe_verify_place_blocks_device(
             self._h, _p(blocks_ptr), int(n_frames), C.byref(map_dev), _p(k_min_ptr), _p(dist_min_ptr),
             _s(stream)))
+
+    # -- keyframe decision: coverage masks of doWeNeedANewKeyframe -------------------------
+    def keyframe_coverage_blocks_device(self, blocks_ptr, n_frames, landmark_ids_ptr, coverage_ptr, id_set_ptr=None,
+                                        n_id_set=0, kptrad=KPTRAD, stream=None):
+        """landmark_ids_ptr: device u64 [n_frames][max_keypoints]; coverage_ptr: device COVERAGE_DTYPE [n_frames];
+        id_set_ptr None: matched = id != 0, else id != 0 and among the n_id_set u64 at id_set_ptr (device)."""
+        self._check(lib().okvfe_keyframe_coverage_blocks_device(
+            self._h, _p(blocks_ptr), int(n_frames), _p(landmark_ids_ptr), _p(id_set_ptr), int(n_id_set),
+            C.c_double(kptrad), _p(coverage_ptr), _s(stream)))
+
+    def keyframe_coverage(self, keypoints, landmark_ids, id_set=None, kptrad=KPTRAD):
+        """The B = 1 host seam: one image's keypoints and landmark ids in, its COVERAGE_DTYPE record out."""
+        kps = np.ascontiguousarray(keypoints, dtype=KEYPOINT_DTYPE)
+        ids = np.ascontiguousarray(landmark_ids, dtype=np.uint64)
+        if len(ids) != len(kps):
+            raise ValueError("landmark_ids: one per keypoint")
+        s = None if id_set is None else np.ascontiguousarray(id_set, dtype=np.uint64).reshape(-1)
+        if s is not None and len(s) == 0:
+            s = np.zeros(1, dtype=np.uint64)  # the empty set, not "no set": a non-null pointer with n_id_set = 0
+            n_set = 0
+        else:
+            n_set = 0 if s is None else len(s)
+        out = np.zeros(1, dtype=COVERAGE_DTYPE)
+        self._check(lib().okvfe_keyframe_coverage(self._h, _p(kps) if len(kps) else None, len(kps),
+                                                  _p(ids) if len(ids) else None, _p(s), n_set,
+                                                  C.c_double(kptrad), _p(out)))
+        return out[0]
 
     # -- gather blocks --------------------------------------------------------------------
     def gather_block_bytes(self) -> int:

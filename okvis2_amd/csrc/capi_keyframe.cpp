@@ -1,0 +1,167 @@
+// capi_keyframe.cpp -- Frontend::doWeNeedANewKeyframe behind the C ABI (Frontend.cpp:1058-1167): the keypoint coverage
+// masks of a batch of frames on the device (k_keyframe.hip), their B = 1 host seam, and the decision as host arithmetic.
+#include "okvfe_ctx.h"
+
+using namespace okvfe;
+
+namespace okvfe {
+// cv::circle(img, c, r, colour, cv::FILLED, cv::LINE_8, 0) takes OpenCV's integer midpoint routine (imgproc/src/
+// drawing.cpp, Circle()): while dx >= dy the rows cy +- dy receive the span [cx - dx, cx + dx] and the rows cy +- dx the
+// span [cx - dy, cx + dy].  A row offset can be visited more than once; the widest span is what ends up painted.
+// Restated from the published source: OpenCV is not part of the reference tree (parity unpinned).
+void circle_half_widths(int r, uint8_t* hw) {
+  for (int j = 0; j <= r; ++j) hw[j] = 0;
+  int err = 0, dx = r, dy = 0, plus = 1, minus = (r << 1) - 1;
+  while (dx >= dy) {
+    hw[dy] = (uint8_t)std::max<int>(hw[dy], dx);
+    hw[dx] = (uint8_t)std::max<int>(hw[dx], dy);
+    ++dy;
+    err += plus;
+    plus += 2;
+    if (err > 0) {
+      err -= minus;
+      --dx;
+      minus -= 2;
+    }
+  }
+}
+}  // namespace okvfe
+
+namespace {
+// geometry, LDS budget and launch, shared by the device entry point and the host seam
+okvfe_status coverage_launch(okvfe_ctx* ctx, const char* who, CoverageArgs A, int n_frames, double kptrad,
+                             okvfe_coverage* out_dev, hipStream_t s) {
+  A.rows = ctx->h / 10;  // Frontend.cpp:1075-1076
+  A.cols = ctx->w / 10;
+  const double radius = double(std::min(A.rows, A.cols)) * kptrad;  // :1083
+  if (!(radius <= (double)kCoverageMaxRadius))
+    return fail(ctx, OKVFE_ERR_UNSUPPORTED, "%s: disc radius %g exceeds %d mask pixels", who, radius, kCoverageMaxRadius);
+  A.r = int(radius);
+  circle_half_widths(A.r, A.hw);
+  const size_t mask_bytes = (size_t)2 * A.rows * ((A.cols + 31) / 32) * sizeof(uint32_t);
+  A.log2_slots = 0;
+  if (A.has_set) {  // table of twice the set, 256 .. 4096 slots, smaller where the masks leave less room
+    A.log2_slots = 8;
+    while (A.log2_slots < 12 && (1 << A.log2_slots) < 2 * A.n_id_set) ++A.log2_slots;
+    while (A.log2_slots > 8 && mask_bytes + ((size_t)8 << A.log2_slots) > kCoverageLdsBudget) --A.log2_slots;
+  }
+  const size_t lds = mask_bytes + (A.has_set ? (size_t)8 << A.log2_slots : 0);
+  if (lds > kCoverageLdsBudget)
+    return fail(ctx, OKVFE_ERR_UNSUPPORTED, "%s: two %d x %d bit masks need %zu bytes of LDS (limit %zu)", who, A.rows,
+                A.cols, lds, kCoverageLdsBudget);
+  launch_keyframe_coverage(A, n_frames, lds, out_dev, s);
+  HIP_TRY(ctx, hipGetLastError());
+  return OKVFE_OK;
+}
+}  // namespace
+
+extern "C" {
+
+okvfe_status okvfe_keyframe_coverage_blocks_device(okvfe_ctx* ctx, const void* blocks_dev, int32_t n_frames,
+                                                   const uint64_t* landmark_ids_dev, const uint64_t* id_set_dev,
+                                                   int32_t n_id_set, double kptrad, okvfe_coverage* coverage_dev,
+                                                   void* stream) {
+  if (!ctx) return OKVFE_ERR_INVALID_ARGUMENT;
+  if (!blocks_dev || n_frames < 1 || !landmark_ids_dev || !coverage_dev || n_id_set < 0 ||
+      (!id_set_dev && n_id_set > 0) || !std::isfinite(kptrad) || kptrad < 0.0)
+    return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_keyframe_coverage_blocks_device: bad argument");
+  HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
+  hipStream_t s = pick_stream(ctx, stream);
+  const BlockLayout L = block_layout(ctx->kp_cap);
+  CoverageArgs A{};
+  A.base = static_cast<const uint8_t*>(blocks_dev);
+  A.frame_stride = L.total;
+  A.o_count = (int)L.o_count;
+  A.o_kps = (int)L.o_kps;
+  A.kp_limit = ctx->kp_cap;
+  A.ids = landmark_ids_dev;
+  A.id_stride = (size_t)ctx->kp_cap;
+  A.id_set = id_set_dev;
+  A.n_id_set = n_id_set;
+  A.has_set = id_set_dev ? 1 : 0;
+  okvfe_status st = coverage_launch(ctx, "okvfe_keyframe_coverage_blocks_device", A, n_frames, kptrad, coverage_dev, s);
+  if (st != OKVFE_OK) return st;
+  ctx->last_stream = s;
+  return OKVFE_OK;
+}
+
+okvfe_status okvfe_keyframe_coverage(okvfe_ctx* ctx, const okvfe_keypoint* keypoints, int32_t n,
+                                     const uint64_t* landmark_ids, const uint64_t* id_set, int32_t n_id_set,
+                                     double kptrad, okvfe_coverage* out) {
+  if (!ctx) return OKVFE_ERR_INVALID_ARGUMENT;
+  if (n < 0 || (n > 0 && (!keypoints || !landmark_ids)) || !out || n_id_set < 0 || (!id_set && n_id_set > 0) ||
+      !std::isfinite(kptrad) || kptrad < 0.0)
+    return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_keyframe_coverage: bad argument");
+  HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
+  hipStream_t s = pick_stream(ctx, nullptr);  // the context's own stream, behind pending pipelined lanes
+  size_t off = 0;
+  auto take = [&](size_t bytes) { const size_t o = off; off = align_up(off + std::max<size_t>(bytes, 1), 256); return o; };
+  const size_t o_n = take(4), o_k = take((size_t)n * sizeof(okvfe_keypoint)), o_id = take((size_t)n * 8),
+               o_set = take((size_t)n_id_set * 8), o_out = take(sizeof(okvfe_coverage));
+  okvfe_status st = ensure_scratch(ctx, off);
+  if (st != OKVFE_OK) return st;
+  uint8_t* base = static_cast<uint8_t*>(ctx->scratch);
+  auto up = [&](size_t o, const void* src, size_t bytes) -> hipError_t {
+    return bytes ? hipMemcpyAsync(base + o, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
+  };
+  HIP_TRY(ctx, up(o_n, &n, 4));
+  HIP_TRY(ctx, up(o_k, keypoints, (size_t)n * sizeof(okvfe_keypoint)));
+  HIP_TRY(ctx, up(o_id, landmark_ids, (size_t)n * 8));
+  HIP_TRY(ctx, up(o_set, id_set, (size_t)n_id_set * 8));
+  HIP_TRY(ctx, hipStreamSynchronize(s));  // pageable sources
+  CoverageArgs A{};
+  A.base = base;
+  A.frame_stride = 0;
+  A.o_count = (int)o_n;
+  A.o_kps = (int)o_k;
+  A.kp_limit = n;
+  A.ids = reinterpret_cast<const uint64_t*>(base + o_id);
+  A.id_stride = 0;
+  A.id_set = reinterpret_cast<const uint64_t*>(base + o_set);
+  A.n_id_set = n_id_set;
+  A.has_set = id_set ? 1 : 0;
+  st = coverage_launch(ctx, "okvfe_keyframe_coverage", A, 1, kptrad, reinterpret_cast<okvfe_coverage*>(base + o_out), s);
+  if (st != OKVFE_OK) return st;
+  HIP_TRY(ctx, hipMemcpyAsync(out, base + o_out, sizeof(okvfe_coverage), hipMemcpyDeviceToHost, s));
+  HIP_TRY(ctx, hipStreamSynchronize(s));
+  return OKVFE_OK;
+}
+
+okvfe_status okvfe_keyframe_decision(const okvfe_coverage* current, int32_t n_cameras, const okvfe_coverage* others,
+                                     int32_t n_others, float overlap_threshold, int32_t* need_keyframe,
+                                     double* overlap_out) {
+  if (!current || n_cameras < 1 || n_others < 0 || (n_others > 0 && !others) || !need_keyframe)
+    return OKVFE_ERR_INVALID_ARGUMENT;
+  for (size_t i = 0; i < (size_t)n_cameras * (size_t)(1 + n_others); ++i) {  // counts are counts
+    const okvfe_coverage& c = i < (size_t)n_cameras ? current[i] : others[i - (size_t)n_cameras];
+    if (c.n_keypoints < 0 || c.intersection_area < 0 || c.union_area < 0) return OKVFE_ERR_INVALID_ARGUMENT;
+  }
+  // Frontend.cpp:1067-1103: the current multiframe, counts summed over its cameras
+  int intersectionCount = 0, unionCount = 0;
+  size_t numKeypoints = 0;
+  for (int im = 0; im < n_cameras; ++im) {
+    numKeypoints += (size_t)current[im].n_keypoints;
+    intersectionCount += current[im].intersection_area;
+    unionCount += current[im].union_area;
+  }
+  double overlap = double(intersectionCount) / double(unionCount);
+  // :1116-1152: the best overlap with any other multiframe.  0 / 0 is NaN; std::max(a, NaN) keeps a
+  double overlapOthers = 0.0;
+  for (int f = 0; f < n_others; ++f) {
+    int intersectionOther = 0, unionOther = 0;
+    for (int im = 0; im < n_cameras; ++im) {
+      intersectionOther += others[(size_t)f * n_cameras + im].intersection_area;
+      unionOther += others[(size_t)f * n_cameras + im].union_area;
+    }
+    overlapOthers = std::max(overlapOthers, double(intersectionOther) / double(unionOther));
+  }
+  overlap = std::min(overlapOthers, overlap);  // :1154, this argument order: a NaN `overlap` yields overlapOthers
+  if (overlap_out) *overlap_out = overlap;
+  if (numKeypoints < (size_t)7 * (size_t)n_cameras)  // :1157: a respectable keyframe needs some detections
+    *need_keyframe = 0;
+  else
+    *need_keyframe = float(overlap) > overlap_threshold ? 0 : 1;  // :1161-1166
+  return OKVFE_OK;
+}
+
+}  // extern "C"

@@ -411,5 +411,26 @@ void launch_hamming_count(const uint8_t* A, int nA, const uint8_t* B, int nB, in
 void launch_hamming_emit(const uint8_t* A, int nA, const uint8_t* B, int nB, int thr,
                          const int32_t* row_offsets, okvfe_candidate* out, int cap,
                          hipStream_t stream);
+// keyframe coverage masks (k_keyframe.hip): one work-group per frame; frame f has its keypoint count at
+// base + f * frame_stride + o_count, its okvfe_keypoint rows at ... + o_kps and its landmark ids at ids + f * id_stride
+constexpr int kCoverageMaxRadius = 127;
+constexpr size_t kCoverageLdsBudget = 64 * 1024 - 256;  // dynamic LDS of a group; the kernel's static LDS is below 256 B
+struct CoverageArgs {
+  const uint8_t* base;
+  size_t frame_stride;
+  int o_count, o_kps;
+  int kp_limit;  // a frame's count is clamped to this
+  const uint64_t* ids;
+  size_t id_stride;
+  const uint64_t* id_set;  // has_set: a keypoint is matched iff its id != 0 and is among these n_id_set values
+  int n_id_set, has_set;
+  int log2_slots;  // LDS hash table of the id set: 2^log2_slots 8-byte slots, filled to half at most (has_set only)
+  int rows, cols, r;
+  uint8_t hw[kCoverageMaxRadius + 1];  // half-width of the disc's span at row offset |j| <= r
+};
+// OpenCV's filled midpoint circle of radius r as half-widths per row offset 0..r (capi_keyframe.cpp)
+void circle_half_widths(int r, uint8_t* hw);
+void launch_keyframe_coverage(const CoverageArgs& args, int n_frames, size_t lds_bytes, okvfe_coverage* out,
+                              hipStream_t stream);
 
 }  // namespace okvfe

@@ -8,6 +8,7 @@
 //     (okvis_frontend/src/Frontend.cpp:232-251)
 //   okvis::Frontend::detectAndDescribe            (okvis_frontend/src/Frontend.cpp:221-269)
 //   okvis::Frontend::matchStereo inner loops      (okvis_frontend/src/Frontend.cpp:2016-2076)
+//   okvis::Frontend::doWeNeedANewKeyframe         (okvis_frontend/src/Frontend.cpp:1058-1167)
 // okvfe_opencv_adapters.hpp wraps these in the real cv:: base classes when OpenCV is available.
 //
 // Every call goes to libokvfe.so (HIP kernels).  Failures throw okvfe::Exception, the analogue of
@@ -411,6 +412,46 @@ class HipFrontend {
         contexts_[cameraIndex]->get(), landmarkDescriptors.data(), descBegin.data(), int32_t(nl),
         frame.descriptors.data.data(), int32_t(frame.keypoints.size()), p.kMin.data(), p.distMin.data()));
     return p;
+  }
+
+  // Frontend::doWeNeedANewKeyframe(estimator, currentFrame) (Frontend.cpp:1058-1167) from :1067 on: the coverage
+  // masks of every camera image are painted and counted on the GPU (okvfe_keyframe_coverage), the decision is
+  // okvfe_keyframe_decision.  currentFrame / every entry of otherFrames: one FrameData per camera, whose landmarkIds
+  // say which keypoints carry a landmark (0 = none).  otherFrames are the multiframes the reference walks at
+  // :1105-1122 (keyframes, loop-closure frames, keyframes in the IMU window): that choice needs the estimator and
+  // stays with the caller, as do the two early returns at :1060-1065 (estimator.numFrames() < 4 -> true;
+  // !isInitialized_ -> false), which come before this call.  overlapOut: the value compared at :1161.
+  bool doWeNeedANewKeyframe(const std::vector<FrameData>& currentFrame,
+                            const std::vector<std::vector<FrameData>>& otherFrames,
+                            float keyframeInsertionOverlapThreshold = 0.55f, double* overlapOut = nullptr,
+                            double kptrad = 0.09) {
+    const size_t nc = cameras_.size();
+    if (currentFrame.size() != nc) throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "currentFrame: one FrameData per camera");
+    std::vector<uint64_t> lmIds;  // :1073, :1091 -- as a list: the library ignores order, duplicates and zeros
+    for (const FrameData& f : currentFrame) lmIds.insert(lmIds.end(), f.landmarkIds.begin(), f.landmarkIds.end());
+    if (lmIds.empty()) lmIds.push_back(0);  // an empty set is still a set (non-null pointer)
+    std::vector<okvfe_coverage> current(nc), others(otherFrames.size() * nc);
+    auto coverage = [&](size_t im, const FrameData& f, bool withSet, okvfe_coverage* out) {
+      if (f.landmarkIds.size() != f.keypoints.size())
+        throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "landmarkIds: one entry per keypoint");
+      std::lock_guard<std::mutex> lock(mutexes_[im]);
+      contexts_[im]->check(okvfe_keyframe_coverage(contexts_[im]->get(), f.keypoints.data(), int32_t(f.keypoints.size()),
+                                                   f.landmarkIds.data(), withSet ? lmIds.data() : nullptr,
+                                                   withSet ? int32_t(lmIds.size()) : 0, kptrad, out));
+    };
+    for (size_t im = 0; im < nc; ++im) coverage(im, currentFrame[im], false, &current[im]);
+    for (size_t o = 0; o < otherFrames.size(); ++o) {
+      if (otherFrames[o].size() != nc) throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "otherFrames: one FrameData per camera");
+      for (size_t im = 0; im < nc; ++im) coverage(im, otherFrames[o][im], true, &others[o * nc + im]);
+    }
+    int32_t need = 0;
+    double overlap = 0.0;
+    const okvfe_status st = okvfe_keyframe_decision(current.data(), int32_t(nc), others.empty() ? nullptr : others.data(),
+                                                    int32_t(otherFrames.size()), keyframeInsertionOverlapThreshold, &need,
+                                                    &overlap);
+    if (st != OKVFE_OK) throw Exception(st, "okvfe_keyframe_decision");
+    if (overlapOut) *overlapOut = overlap;
+    return need != 0;
   }
 
  private:
