@@ -519,6 +519,7 @@ okvfe_status create_impl(const okvfe_config* cfg, bool child, okvfe_ctx** out) {
     build_uniformity_lut(lut);
     build_pattern(&c->host_pattern);
     if (cfg->box_scale != 0.0f && cfg->box_scale != 1.0f) scale_pattern_boxes(&c->host_pattern, cfg->box_scale);
+    c->pattern_facts = pattern_facts(c->host_pattern);
     HIP_TRY(c, hipMemcpy(c->d_lut, lut, sizeof(lut), hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemcpy(c->d_pattern, &c->host_pattern, sizeof(Pattern), hipMemcpyHostToDevice));
     if (c->d_scales) {
@@ -803,6 +804,8 @@ okvfe_status okvfe_get_pattern(const okvfe_ctx* ctx, okvfe_pattern* out) {
   return OKVFE_OK;
 }
 
+int32_t okvfe_pattern_kernel_class(const okvfe_ctx* ctx) { return ctx ? ctx->pattern_facts.box_class : -1; }
+
 okvfe_status okvfe_set_pattern(okvfe_ctx* ctx, const okvfe_pattern* p) {
   if (!ctx || !p) return OKVFE_ERR_INVALID_ARGUMENT;
   ctx->ahead.valid = false;
@@ -853,6 +856,7 @@ okvfe_status okvfe_set_pattern(okvfe_ctx* ctx, const okvfe_pattern* p) {
     P.box_scaling2[i] = static_cast<int>(s2 / 1024.0f);
   }
   fill_aware_lanes(&P);
+  ctx->pattern_facts = pattern_facts(P);
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
   { const okvfe_status js = lanes_join_host(ctx); if (js != OKVFE_OK) return js; }
   if (ctx->last_stream) HIP_TRY(ctx, hipStreamSynchronize(ctx->last_stream));

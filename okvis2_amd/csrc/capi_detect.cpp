@@ -48,14 +48,14 @@ okvfe_status okvfe_harris_byte_mover_device(okvfe_ctx* ctx, const uint8_t* image
   return OKVFE_OK;
 }
 
-static okvfe_status upload_image_params(okvfe_ctx* ctx, int n_images, const int32_t* cam_ids,
-                                        const float* gravity, hipStream_t s, bool before_detect = false) {
+}  // extern "C"
+
+// Fills and uploads the ImageParams of a batch; `out` = what the batch is made of (nothing is kept in the context)
+static okvfe_status upload_image_params(okvfe_ctx* ctx, int n_images, const int32_t* cam_ids, const float* gravity,
+                                        hipStream_t s, bool before_detect, BatchFacts* out) {
   std::vector<ImageParams> prm(n_images);
-  ctx->wide_patches = false;
-  ctx->aware_fast = true;
-  ctx->all_aware = n_images > 0;
-  ctx->none_aware = true;
-  ctx->rt8_call = false;
+  BatchFacts b;
+  b.all_aware = n_images > 0;
   for (int i = 0; i < n_images; ++i) {
     ImageParams& p = prm[i];
     p.cam = cam_ids ? cam_ids[i] : -1;
@@ -67,96 +67,81 @@ static okvfe_status upload_image_params(okvfe_ctx* ctx, int n_images, const int3
         return fail(ctx, OKVFE_ERR_NOT_READY,
                     "camera-aware extraction requested for camera %d before okvfe_set_camera[_maps]", p.cam);
       p.mode = kCameraAware;
-      ctx->none_aware = false;
+      b.none_aware = false;
       p.dir[0] = gravity[3 * i];
       p.dir[1] = gravity[3 * i + 1];
       p.dir[2] = gravity[3 * i + 2];
       p.fu = ctx->cam_fu[p.cam];
-      if (ctx->cam_wide[p.cam]) ctx->wide_patches = true;
-      if (ctx->cam_aware_slow[p.cam]) ctx->aware_fast = false;
+      if (ctx->cam_wide[p.cam]) b.wide_patches = true;
+      if (ctx->cam_aware_slow[p.cam]) b.aware_fast = false;
     } else {
       p.mode = ctx->mode_default;
-      ctx->all_aware = false;
+      b.all_aware = false;
       p.dir[0] = 0.0f; p.dir[1] = 1.0f; p.dir[2] = 0.0f;
       p.fu = 1.0f;
     }
     if (p.cam >= 0 && !ctx->cam_has_intrinsics[p.cam]) p.cam = aware ? p.cam : -1;
-    if (p.cam >= 0 && ctx->h_cams[p.cam].distortion == OKVFE_DIST_RADTAN8) ctx->rt8_call = true;
+    if (p.cam >= 0 && ctx->h_cams[p.cam].distortion == OKVFE_DIST_RADTAN8) b.rt8 = true;
   }
   // intrinsics are needed for back-projection; a slot with maps only (set_camera_maps) keeps its
   // cam id for the maps and gets invalid back-projections (DeviceCamera zeroed -> fu = 0)
   void* d = nullptr;
   // (single-scale detector: its candidate / fix-up counters are cleared by the same launch)
-  ctx->counters_cleared = false;
   okvfe_status st = ring_upload(ctx, &ctx->prm_ring, prm.data(), n_images * sizeof(ImageParams), s, &d,
                                 &ctx->prm_slot, before_detect && ctx->n_layers == 1 ? ctx->d_cand_count : nullptr,
                                 before_detect && ctx->n_layers == 1 && ctx->d_cand_count ? 2 * ctx->B : 0,
-                                &ctx->counters_cleared);
+                                &b.counters_cleared);
   if (st != OKVFE_OK) return st;
   ctx->d_prm = static_cast<ImageParams*>(d);
+  *out = b;
   return OKVFE_OK;
 }
 
 // ---- batch pipeline ----------------------------------------------------------------------------
 // OKVFE_SCORE_TOKEN: see g_score_token.
-// The camera-aware-only descriptor kernel carries the fixed-trip box sum alone: every box of the installed pattern has
-// to fit its 11 x 11 slots (sigma_half <= 4.75: the built-in pattern; okvfe_set_pattern may install wider samples,
-// which take the all-modes kernel).
-// 0: every box of the installed pattern fits the fixed-trip slots of the fast descriptor kernels (first-pass samples
-// 11 x 11: sigma_half <= 4.75; second-pass samples = points 0 .. n - 65 of a pattern with more than 64 points, 5 x 5:
-// sigma_half <= 2.0); 1: the slots of the WIDE instantiations (21 x 21: <= 9.75, 10 x 10: <= 4.25); 2: wider still
-// (k_describe.hip: kMaxBox / kSmallBox / kWideBox / kWideSmallBox)
-static int pattern_box_class(const okvfe::Pattern& P) {
-  const int extra = P.n_points > 64 ? P.n_points - 64 : 0;
-  int cls = 0;
-  for (int i = 0; i < P.n_points && i < okvfe::kPatternPoints; ++i) {
-    const float s = P.sigma_half[i];
-    if (!(s <= (i < extra ? 2.0f : 4.75f))) cls = cls < 1 ? 1 : cls;
-    if (!(s <= (i < extra ? 4.25f : 9.75f))) cls = 2;
-    // half-widths below 0.5 are bilinear point samples: only the all-modes kernel carries that branch (and waits for
-    // its patch before it: ADVICE r5)
-    if (!(s >= 0.5f)) cls = 2;
-  }
-  return cls;
+
+namespace okvfe {
+// Which descriptor kernel serves a call, and what the set-up is told about the pattern's samples beyond 64.
+DescribeRoute describe_route(const RouteFacts& f, int* aware_extra_box) {
+  const bool dword_rows = f.w % 4 == 0 && f.aligned;
+  // describe_aware_kernel: every image camera-aware on a camera whose patches fit the kernel's LDS classes, the
+  // fixed-scale pattern with boxes inside the fixed-trip slots, dword-aligned images
+  int box = -1;
+  if (f.all_aware && f.aware_fast && f.box_class <= 1 && f.extra <= kAwareMaxExtra && !f.scale_invariant &&
+      f.n_layers == 1 && dword_rows && f.w < 4096 && f.h < 4096)
+    box = f.extra == 0 ? 0 : ((f.extra << 8) | (f.box_class == 0 ? 4 : 9));  // (samples beyond 64) << 8 | box side - 1
+  // scale-invariant extraction and unaligned images take the forms without the camera-aware specialisation
+  const bool aware = f.all_aware && !f.scale_invariant && dword_rows;
+  *aware_extra_box = box;
+  if (box >= 0) return DescribeRoute::kAwareBatched;  // (implies `aware` and box_class <= 1)
+  if (f.none_aware && f.rot_ok && f.box_class == 0 && !f.scale_invariant && dword_rows) return DescribeRoute::kRot;
+  if (f.box_class == 1 && !f.scale_invariant) return aware ? DescribeRoute::kAwareWideBoxes : DescribeRoute::kWideBoxes;
+  if (!aware || f.box_class != 0) return DescribeRoute::kAllModes;
+  return f.wide_patches ? DescribeRoute::kAware5 : DescribeRoute::kAware6;
 }
+}  // namespace okvfe
 
-// describe_rot_kernel (upright / gradient modes on the fast box sums) takes the installed pattern when its circle fits a
-// 64-byte row pitch, its samples beyond 64 lanes fit the kernel's table and its long-pair weights fit 16 bits
-static bool pattern_rot_ok(const okvfe::Pattern& P) {
-  const int extra = P.n_points > 64 ? P.n_points - 64 : 0;
-  if (P.border > 29 || extra > okvfe::kAwareMaxExtra || P.n_long > okvfe::kMaxLongPairs) return false;
-  for (int l = 0; l < P.n_long; ++l)
-    if (P.long_wdx[l] < -32768 || P.long_wdx[l] > 32767 || P.long_wdy[l] < -32768 || P.long_wdy[l] > 32767) return false;
-  // the rotation tables must follow the quarter-wave rule exactly (they do for the tables build_pattern computes)
-  static const bool sym = [&P] {
-    for (int k = 0; k < okvfe::kRot; ++k) {
-      if (okvfe::quarter_sin(P.rot_sin, k) != P.rot_sin[k] || okvfe::quarter_cos(P.rot_sin, k) != P.rot_cos[k]) return false;
-      // (float tables: sin(pi) and cos(pi / 2) are 1e-16, not 0, in double -- entries sin[512], cos[256], cos[768] are
-      // read from the global table by the kernel and exempt here)
-      const float fs = okvfe::quarter_sin(P.rot_sinf, k), fc = okvfe::quarter_cos(P.rot_sinf, k);
-      if (k != 512 && std::memcmp(&fs, &P.rot_sinf[k], 4) != 0) return false;
-      if (k != 256 && k != 768 && std::memcmp(&fc, &P.rot_cosf[k], 4) != 0) return false;
-    }
-    return true;
-  }();
-  return sym;
-}
-
-extern "C" int32_t okvfe_pattern_kernel_class(const okvfe_ctx* ctx) { return ctx ? pattern_box_class(ctx->host_pattern) : -1; }
-
-// Does describe_aware_kernel (k_describe_aware.hip) serve this call?  -1: no (describe_kernel does); otherwise
-// (samples beyond 64) << 8 | their largest box side minus one (0: the pattern has no such samples).
-// Every image camera-aware on a camera whose patches fit the kernel's LDS classes, the fixed-scale pattern with boxes
-// inside the fixed-trip slots, dword-aligned images.
-static int aware_box_for_call(const okvfe_ctx* ctx, const uint8_t* images_dev) {
-  const okvfe::Pattern& P = ctx->host_pattern;
-  const int cls = pattern_box_class(P);
-  const int extra = P.n_points > 64 ? P.n_points - 64 : 0;
-  if (!ctx->all_aware || !ctx->aware_fast || cls > 1 || extra > okvfe::kAwareMaxExtra || ctx->d_scales ||
-      ctx->n_layers != 1 || ctx->w % 4 != 0 || (reinterpret_cast<uintptr_t>(images_dev) & 3) != 0 || ctx->w >= 4096 ||
-      ctx->h >= 4096)
-    return -1;
-  return extra == 0 ? 0 : ((extra << 8) | (cls == 0 ? 4 : 9));  // (samples beyond 64) << 8 | box side - 1
+// The plan of a call that describes: built ONCE per call, by the entry point, from the batch, the installed pattern,
+// the context and the call's image pointer.  Deciding once is the same as deciding at every use because
+//  * a lane's image pointer is images_dev + first * w * h with `first` a multiple of 8, and every route that needs
+//    dword-aligned images also needs w % 4 == 0: the owner's alignment verdict holds for each of its lanes;
+//  * in the fused flow the selection kernel's set-up reads live_images, which layer_score_nms (Harris score) has just
+//    set to the call's images_dev: the aware_extra_box the set-up is told is the one the descriptor launch is given.
+//    (The AGAST score branch of layer_score_nms does not set live_images, before this plan existed or now.)
+static CallPlan make_call_plan(const okvfe_ctx* ctx, const BatchFacts& b, const uint8_t* images_dev, bool detects) {
+  static const bool no_fuse = lab_env("OKVFE_NO_FUSED_SETUP") != nullptr;  // A/B knob
+  const PatternFacts& pf = ctx->pattern_facts;
+  CallPlan p;
+  const RouteFacts f{.all_aware = b.all_aware, .none_aware = b.none_aware, .aware_fast = b.aware_fast,
+                     .wide_patches = b.wide_patches, .box_class = pf.box_class, .rot_ok = pf.rot_ok, .extra = pf.extra,
+                     .scale_invariant = ctx->d_scales != nullptr, .n_layers = ctx->n_layers, .w = ctx->w, .h = ctx->h,
+                     .aligned = (reinterpret_cast<uintptr_t>(images_dev) & 3) == 0};
+  p.route = describe_route(f, &p.aware_extra_box);
+  p.wide_boxes = pf.box_class == 1;
+  p.rt8 = b.rt8;
+  p.fuse_setup = detects && !no_fuse && ctx->n_layers == 1;
+  p.counters_cleared = b.counters_cleared;
+  return p;
 }
 
 namespace {
@@ -227,22 +212,22 @@ void layer_sort(okvfe_ctx* L, int n_images, hipStream_t s) {
     return;
   launch_sort(L->d_cand, L->cand_cap, L->d_cand_count, n_images, L->cfg.uniformity_radius, L->d_sort_ws, s);
 }
-void layer_select(okvfe_ctx* L, int n_images, hipStream_t s) {
-  // detection + description in one call (single scale): the selection kernel also prepares the
-  // extractor's per-keypoint inputs (describe_setup_dev.h)
-  if (!L->lane_view) L->aware_extra_box = aware_box_for_call(L, L->live_images);  // (a view: its owner decided)
+// -> the selection kernel also prepared the extractor's per-keypoint inputs (describe_setup_dev.h): asked for by the
+// plan of a single-scale call that describes what it detects
+bool layer_select(okvfe_ctx* L, int n_images, hipStream_t s, const CallPlan& plan) {
   const DescribeSetup setup{L->d_pattern, L->d_prm, L->d_rays_ptrs, L->d_jac_ptrs, L->d_kps_tmp, L->d_desc_tmp,
                             L->d_valid_tmp, L->d_scales, L->live_images,
-                            L->aware_extra_box > 0 ? (L->aware_extra_box & 0xFF) : 0};
-  const bool fuse = L->fuse_setup && L->n_layers == 1 && L->d_pattern && L->d_kps_tmp && L->d_prm;
-  L->setup_done = launch_select(L->d_scores, L->live_layout, L->w, L->h, n_images, L->d_cand, L->cand_cap,
-                                L->d_cand_count, L->cfg.uniformity_radius, L->cfg.max_keypoints, L->d_lut, L->d_occ,
-                                L->occ_image_bytes, L->occ_rows, L->occ_cols, L->d_kps_det, L->kp_cap, L->d_det_count,
-                                L->d_sort_ws, s, fuse ? &setup : nullptr, L->map_free_live ? L->live_images : nullptr);
+                            plan.aware_extra_box > 0 ? (plan.aware_extra_box & 0xFF) : 0};
+  const bool fuse = plan.fuse_setup && L->d_pattern && L->d_kps_tmp && L->d_prm;
+  return launch_select(L->d_scores, L->live_layout, L->w, L->h, n_images, L->d_cand, L->cand_cap, L->d_cand_count,
+                       L->cfg.uniformity_radius, L->cfg.max_keypoints, L->d_lut, L->d_occ, L->occ_image_bytes,
+                       L->occ_rows, L->occ_cols, L->d_kps_det, L->kp_cap, L->d_det_count, L->d_sort_ws, s,
+                       fuse ? &setup : nullptr, L->map_free_live ? L->live_images : nullptr);
 }
 
+// ---- scale space (octaves > 0): the steps of layer l of parent context `ctx`, shared by the two schedules below -----
 // scale of layer l relative to layer m, reduced (oracle: the layer ratios of detect_scale_space)
-static void layer_ratio(int l, int m, int out[2]) {
+void layer_ratio(int l, int m, int out[2]) {
   int sn, sd, mn, md;
   layer_scale(l, &sn, &sd);
   layer_scale(m, &mn, &md);
@@ -251,14 +236,89 @@ static void layer_ratio(int l, int m, int out[2]) {
     while (rn % g == 0 && rd % g == 0) { rn /= g; rd /= g; }
   out[0] = rn; out[1] = rd;
 }
+const uint8_t* layer_image(const okvfe_ctx* ctx, const uint8_t* images_dev, int l) {
+  return l == 0 ? images_dev : ctx->d_layer_img[l];
+}
+// image of layer l >= 1: two thirds of layer 0, or half of layer l - 2
+void layer_sample(okvfe_ctx* ctx, const uint8_t* images_dev, int l, int n_images, hipStream_t s) {
+  const int m = l == 1 ? 0 : l - 2;
+  (l == 1 ? launch_twothird : launch_halfsample)(layer_image(ctx, images_dev, m), ctx->layer_w[m], ctx->layer_h[m],
+                                                 n_images, ctx->d_layer_img[l], s);
+}
+// The score maps below and above layer l with their layouts, sizes and the reduced scale ratios of l to them.  Below
+// layer 0 lies the virtual FAST 5-8 layer (OKVFE_SCORE_BRISK_SCALESPACE only; c0's own grid: ratio 1, dense).
+struct LayerNeighbours {
+  const int32_t *below = nullptr, *above = nullptr;
+  ScoreLayout lb{0, 0}, la{0, 0};
+  int wb = 0, hb = 0, wa = 0, ha = 0;
+  int rb[2] = {1, 1}, ra[2] = {1, 1};
+};
+LayerNeighbours layer_neighbours(const okvfe_ctx* ctx, int l) {
+  LayerNeighbours n;
+  const int m = l > 0 ? l - 1 : 0, a = l + 1;
+  if (l > 0 || ctx->d_virtual) { n.wb = ctx->layer_w[m]; n.hb = ctx->layer_h[m]; }
+  if (l > 0) { n.below = ctx->layers[m]->d_scores; n.lb = ctx->layers[m]->live_layout; layer_ratio(l, m, n.rb); }
+  else if (ctx->d_virtual) { n.below = ctx->d_virtual; n.lb = ScoreLayout{n.wb, 0}; }
+  if (a < ctx->n_layers) {
+    n.above = ctx->layers[a]->d_scores; n.la = ctx->layers[a]->live_layout; layer_ratio(l, a, n.ra);
+    n.wa = ctx->layer_w[a]; n.ha = ctx->layer_h[a];
+  }
+  return n;
+}
+bool brisk_scale_space(const okvfe_ctx* ctx) { return ctx->cfg.score_type == OKVFE_SCORE_BRISK_SCALESPACE; }
+// scale-space maxima: the candidates of layer l against the finished score maps below and above
+void layer_scale_filter(okvfe_ctx* ctx, int l, int n_images, hipStream_t s) {
+  okvfe_ctx* ch = ctx->layers[l];
+  const LayerNeighbours n = layer_neighbours(ctx, l);
+  launch_scale_filter(ch->d_cand, ch->cand_cap, ch->d_cand_count, n_images, n.below, n.lb, n.wb, n.hb, n.rb[0], n.rb[1],
+                      n.above, n.la, n.wa, n.ha, n.ra[0], n.ra[1], s);
+}
+void scale_layer_sort(okvfe_ctx* ctx, int l, int n_images, hipStream_t s) {
+  okvfe_ctx* ch = ctx->layers[l];
+  if (brisk_scale_space(ctx))  // always ordered (score desc, y, x): there is no uniformity radius to switch the sort on
+    launch_sort(ch->d_cand, ch->cand_cap, ch->d_cand_count, n_images, 1.0f, ch->d_sort_ws, s);
+  else
+    layer_sort(ch, n_images, s);
+}
+// keypoints of layer l: uniformity selection, or (BRISK scale space) the strongest maxima with a continuous scale from
+// the scores of the layers below and above
+void scale_layer_keypoints(okvfe_ctx* ctx, int l, int n_images, hipStream_t s) {
+  okvfe_ctx* ch = ctx->layers[l];
+  if (!brisk_scale_space(ctx)) {
+    (void)layer_select(ch, n_images, s, CallPlan{});  // (a layer only detects: the parent context describes)
+    return;
+  }
+  const LayerNeighbours n = layer_neighbours(ctx, l);
+  // c_0: the virtual FAST 5-8 layer sits at 2/3 and the result is clamped to [0.7, 1.5] (published refine1D_2)
+  const double rel_b = (l & 1) || l == 0 ? 2.0 / 3.0 : 0.75, rel_a = (l & 1) ? 4.0 / 3.0 : 1.5;
+  const double rel_lo = l == 0 ? 0.7 : rel_b;
+  launch_brisk_refine(ch->d_scores, ch->w, ch->h, n_images, ch->cand_cap, ch->d_cand_count, ch->d_sort_ws,
+                      ch->cfg.max_keypoints, n.below, n.wb, n.hb, n.rb[0], n.rb[1], n.above, n.wa, n.ha, n.ra[0], n.ra[1],
+                      rel_b, rel_a, rel_lo, ch->d_kps_det, ch->kp_cap, ch->d_det_count, s);
+}
+// the layers' keypoints into image coordinates -> the parent's d_kps_det / d_det_count
+void merge_layers(okvfe_ctx* ctx, int n_images, hipStream_t s) {
+  const okvfe_keypoint* kps[8];
+  const int32_t* counts[8];
+  float scale[8];
+  for (int l = 0; l < ctx->n_layers; ++l) {
+    kps[l] = ctx->layers[l]->d_kps_det;
+    counts[l] = ctx->layers[l]->d_det_count;
+    int sn, sd;
+    layer_scale(l, &sn, &sd);
+    scale[l] = (float)sn / (float)sd;
+  }
+  launch_merge_layers(kps, counts, scale, ctx->n_layers, ctx->cfg.max_keypoints, n_images, ctx->d_kps_det, ctx->kp_cap,
+                      ctx->d_det_count, s);
+}
 
-// The scale space of one call with its layers SIDE BY SIDE (round 6): the kernels of the small layers are a few hundred
-// workgroups each -- one after the other on one stream they left most of the GPU idle (scale filter 4 x 0.1 ms,
-// refinement 4 x 0.05, NMS of the upper layers ...).  Layer l runs on the stream of its own layer context:
+// Schedule 1, layers SIDE BY SIDE (round 6): the kernels of the small layers are a few hundred workgroups each -- one
+// after the other on one stream they left most of the GPU idle (scale filter 4 x 0.1 ms, refinement 4 x 0.05, NMS of
+// the upper layers ...).  Layer l runs on the stream of its own layer context:
 //   sampler (behind the image it samples) -> score map -> NMS            | event "map l"
 //   (behind the maps of l - 1 and l + 1) scale filter -> sort -> selection / refinement | event "done l"
 // and the caller's stream picks up behind all "done" events for the merge.  Same kernels, same results.
-static okvfe_status detect_layers_concurrent(okvfe_ctx* ctx, const uint8_t* images_dev, int n_images, hipStream_t s) {
+okvfe_status detect_layers_concurrent(okvfe_ctx* ctx, const uint8_t* images_dev, int n_images, hipStream_t s) {
   const int L = ctx->n_layers;
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
   if (!ctx->layer_fork) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->layer_fork, hipEventDisableTiming));
@@ -270,27 +330,21 @@ static okvfe_status detect_layers_concurrent(okvfe_ctx* ctx, const uint8_t* imag
   auto ev_img = [&](int l) { return ctx->layer_ev[3 * l]; };
   auto ev_map = [&](int l) { return ctx->layer_ev[3 * l + 1]; };
   auto ev_done = [&](int l) { return ctx->layer_ev[3 * l + 2]; };
-  std::vector<const uint8_t*> img(L);
-  img[0] = images_dev;
-  for (int l = 1; l < L; ++l) img[l] = ctx->d_layer_img[l];
-  const bool brisk_ss = ctx->cfg.score_type == OKVFE_SCORE_BRISK_SCALESPACE;
   HIP_TRY(ctx, hipEventRecord(ctx->layer_fork, s));
   // ---- per layer: image, score map, 2-D maxima
   for (int l = 0; l < L; ++l) {
     okvfe_ctx* ch = ctx->layers[l];
     hipStream_t ls = ch->stream;
     HIP_TRY(ctx, hipStreamWaitEvent(ls, ctx->layer_fork, 0));
-    if (l == 1) {
-      launch_twothird(img[0], ctx->layer_w[0], ctx->layer_h[0], n_images, ctx->d_layer_img[1], ls);
-    } else if (l >= 2) {
+    if (l >= 1) {
       if (l - 2 >= 1) HIP_TRY(ctx, hipStreamWaitEvent(ls, ev_img(l - 2), 0));  // (layer 0 is the caller's image)
-      launch_halfsample(img[l - 2], ctx->layer_w[l - 2], ctx->layer_h[l - 2], n_images, ctx->d_layer_img[l], ls);
+      layer_sample(ctx, images_dev, l, n_images, ls);
+      HIP_TRY(ctx, hipEventRecord(ev_img(l), ls));
     }
-    if (l >= 1) HIP_TRY(ctx, hipEventRecord(ev_img(l), ls));
     // counters cleared by a kernel of our own, not the runtime's memset (stays in the layer's compute queue)
     launch_param_copy(nullptr, nullptr, 0, ch->d_cand_count, 2 * ch->B, ls, nullptr, 0);
     bool f;
-    layer_score_nms(ch, img[l], n_images, ls, &f);
+    layer_score_nms(ch, layer_image(ctx, images_dev, l), n_images, ls, &f);
     layer_nms_finish(ch, n_images, ls, f);
     HIP_TRY(ctx, hipEventRecord(ev_map(l), ls));
   }
@@ -299,70 +353,75 @@ static okvfe_status detect_layers_concurrent(okvfe_ctx* ctx, const uint8_t* imag
   hipEvent_t ev_virtual = ctx->layer_ev[3 * L];
   if (ctx->d_virtual) {
     hipStream_t vs = ctx->layers[L - 1]->stream;
-    launch_fast58_score(img[0], ctx->layer_w[0], ctx->layer_h[0], n_images, ctx->d_virtual, vs);
+    launch_fast58_score(images_dev, ctx->layer_w[0], ctx->layer_h[0], n_images, ctx->d_virtual, vs);
     HIP_TRY(ctx, hipEventRecord(ev_virtual, vs));
   }
   // ---- per layer: scale-space maxima against the finished maps below and above, order, selection / refinement
   for (int l = 0; l < L; ++l) {
-    okvfe_ctx* ch = ctx->layers[l];
-    hipStream_t ls = ch->stream;
+    hipStream_t ls = ctx->layers[l]->stream;
     if (l > 0) HIP_TRY(ctx, hipStreamWaitEvent(ls, ev_map(l - 1), 0));
     if (l + 1 < L) HIP_TRY(ctx, hipStreamWaitEvent(ls, ev_map(l + 1), 0));
     if (l == 0 && ctx->d_virtual) HIP_TRY(ctx, hipStreamWaitEvent(ls, ev_virtual, 0));
-    const int32_t *below = nullptr, *above = nullptr;
-    ScoreLayout lb{0, 0}, la{0, 0};
-    int rb[2] = {1, 1}, ra[2] = {1, 1};
-    if (l > 0) { below = ctx->layers[l - 1]->d_scores; lb = ctx->layers[l - 1]->live_layout; layer_ratio(l, l - 1, rb); }
-    if (l == 0 && ctx->d_virtual) { below = ctx->d_virtual; lb = ScoreLayout{ctx->layer_w[0], 0}; }  // same grid: ratio 1
-    if (l + 1 < L) { above = ctx->layers[l + 1]->d_scores; la = ctx->layers[l + 1]->live_layout; layer_ratio(l, l + 1, ra); }
-    launch_scale_filter(ch->d_cand, ch->cand_cap, ch->d_cand_count, n_images, below, lb,
-                        l > 0 ? ctx->layer_w[l - 1] : (below ? ctx->layer_w[0] : 0),
-                        l > 0 ? ctx->layer_h[l - 1] : (below ? ctx->layer_h[0] : 0), rb[0], rb[1], above, la,
-                        l + 1 < L ? ctx->layer_w[l + 1] : 0, l + 1 < L ? ctx->layer_h[l + 1] : 0, ra[0], ra[1], ls);
-    if (brisk_ss) {
-      launch_sort(ch->d_cand, ch->cand_cap, ch->d_cand_count, n_images, 1.0f, ch->d_sort_ws, ls);
-      const int32_t* rbelow = l == 0 ? ctx->d_virtual : ctx->layers[l - 1]->d_scores;
-      const int wb = l == 0 ? ctx->layer_w[0] : ctx->layer_w[l - 1], hb = l == 0 ? ctx->layer_h[0] : ctx->layer_h[l - 1];
-      const int32_t* rabove = l + 1 < L ? ctx->layers[l + 1]->d_scores : nullptr;
-      // c_0: the virtual FAST 5-8 layer sits at 2/3 and the result is clamped to [0.7, 1.5] (published refine1D_2)
-      const double rel_b = (l & 1) || l == 0 ? 2.0 / 3.0 : 0.75, rel_a = (l & 1) ? 4.0 / 3.0 : 1.5;
-      const double rel_lo = l == 0 ? 0.7 : rel_b;
-      launch_brisk_refine(ch->d_scores, ch->w, ch->h, n_images, ch->cand_cap, ch->d_cand_count, ch->d_sort_ws,
-                          ch->cfg.max_keypoints, rbelow, wb, hb, rb[0], rb[1], rabove,
-                          rabove ? ctx->layer_w[l + 1] : 0, rabove ? ctx->layer_h[l + 1] : 0, ra[0], ra[1], rel_b, rel_a,
-                          rel_lo, ch->d_kps_det, ch->kp_cap, ch->d_det_count, ls);
-    } else {
-      layer_sort(ch, n_images, ls);
-      layer_select(ch, n_images, ls);
-    }
+    layer_scale_filter(ctx, l, n_images, ls);
+    scale_layer_sort(ctx, l, n_images, ls);
+    scale_layer_keypoints(ctx, l, n_images, ls);
     HIP_TRY(ctx, hipEventRecord(ev_done(l), ls));
   }
   // ---- join and merge into image coordinates
   for (int l = 0; l < L; ++l) HIP_TRY(ctx, hipStreamWaitEvent(s, ev_done(l), 0));
-  const okvfe_keypoint* kps[8];
-  const int32_t* counts[8];
-  float scale[8];
-  for (int l = 0; l < L; ++l) {
-    kps[l] = ctx->layers[l]->d_kps_det;
-    counts[l] = ctx->layers[l]->d_det_count;
-    int sn, sd;
-    layer_scale(l, &sn, &sd);
-    scale[l] = (float)sn / (float)sd;
+  merge_layers(ctx, n_images, s);
+  return OKVFE_OK;
+}
+
+// Schedule 2, ONE STREAM, grouped by stage: the stage timers and the cross-context chaining of the heavy kernels
+// bracket whole stages (the score launches of all layers sit between heavy_begin and heavy_end)
+okvfe_status detect_layers_staged(okvfe_ctx* ctx, const uint8_t* images_dev, int n_images, hipStream_t s) {
+  const int L = ctx->n_layers;
+  TokenScope token;
+  okvfe_status st;
+  std::vector<bool> fused(L);
+  if ((st = heavy_begin(ctx, s, 0, &token)) != OKVFE_OK) return st;
+  {
+    StageTimer t(ctx, OKVFE_STAGE_HARRIS, s);
+    for (int l = 1; l < L; ++l) layer_sample(ctx, images_dev, l, n_images, s);
+    for (int l = 0; l < L; ++l) {
+      okvfe_ctx* ch = ctx->layers[l];
+      HIP_TRY(ctx, hipMemsetAsync(ch->d_cand_count, 0, 2 * (size_t)ch->B * sizeof(int32_t), s));
+      bool f;
+      layer_score_nms(ch, layer_image(ctx, images_dev, l), n_images, s, &f);
+      fused[l] = f;
+    }
+    if (ctx->d_virtual) launch_fast58_score(images_dev, ctx->layer_w[0], ctx->layer_h[0], n_images, ctx->d_virtual, s);
   }
-  launch_merge_layers(kps, counts, scale, L, ctx->cfg.max_keypoints, n_images, ctx->d_kps_det, ctx->kp_cap,
-                      ctx->d_det_count, s);
+  if ((st = heavy_end(ctx, s, 0, &token)) != OKVFE_OK) return st;
+  {
+    StageTimer t(ctx, OKVFE_STAGE_NMS, s);
+    for (int l = 0; l < L; ++l) layer_nms_finish(ctx->layers[l], n_images, s, fused[l]);
+    for (int l = 0; l < L; ++l) layer_scale_filter(ctx, l, n_images, s);
+  }
+  {
+    StageTimer t(ctx, OKVFE_STAGE_SORT, s);
+    for (int l = 0; l < L; ++l) scale_layer_sort(ctx, l, n_images, s);
+  }
+  {
+    StageTimer t(ctx, OKVFE_STAGE_SELECT, s);
+    for (int l = 0; l < L; ++l) scale_layer_keypoints(ctx, l, n_images, s);
+    merge_layers(ctx, n_images, s);
+  }
   return OKVFE_OK;
 }
 
 // K1..K4: score map + NMS, sort, uniformity selection, sub-pixel -> d_kps_det / d_det_count.
 // octaves > 0: the same per layer of the scale space (k_pyramid.hip), with the cross-layer maximum
 // test between NMS and selection and the merge into image coordinates at the end.
-okvfe_status detect_stage(okvfe_ctx* ctx, const uint8_t* images_dev, int n_images, hipStream_t s) {
-  TokenScope token;
+// *setup_done (may be null): the selection launch also ran the extractor's set-up, as plan.fuse_setup asked.
+okvfe_status detect_stage(okvfe_ctx* ctx, const uint8_t* images_dev, int n_images, hipStream_t s, const CallPlan& plan,
+                          bool* setup_done) {
   okvfe_status st;
-  ctx->setup_done = false;  // set by this call's selection launch only (a failed earlier call must not leak it)
+  if (setup_done) *setup_done = false;
   if (ctx->n_layers == 1) {
-    if (!ctx->counters_cleared) {  // (cleared together with the parameter upload of the same call otherwise)
+    TokenScope token;
+    if (!plan.counters_cleared) {  // (cleared together with the parameter upload of the same call otherwise)
       if (ctx->lane_view) {
         HIP_TRY(ctx, hipMemsetAsync(ctx->d_cand_count, 0, (size_t)ctx->B * sizeof(int32_t), s));
         HIP_TRY(ctx, hipMemsetAsync(ctx->d_fix_count, 0, (size_t)ctx->B * sizeof(int32_t), s));
@@ -370,7 +429,6 @@ okvfe_status detect_stage(okvfe_ctx* ctx, const uint8_t* images_dev, int n_image
         HIP_TRY(ctx, hipMemsetAsync(ctx->d_cand_count, 0, 2 * (size_t)ctx->B * sizeof(int32_t), s));
       }
     }
-    ctx->counters_cleared = false;
     if ((st = heavy_begin(ctx, s, 0, &token)) != OKVFE_OK) return st;
     bool fused;
     // lanes inside one call: the score kernels run one after the other, so that the lanes proceed OUT OF PHASE -- the
@@ -392,121 +450,14 @@ okvfe_status detect_stage(okvfe_ctx* ctx, const uint8_t* images_dev, int n_image
     }
     {
       StageTimer t(ctx, OKVFE_STAGE_SELECT, s);
-      layer_select(ctx, n_images, s);
+      const bool done = layer_select(ctx, n_images, s, plan);
+      if (setup_done) *setup_done = done;
     }
-  } else if (ctx->prof_mask == 0 && score_token_mode() == 0) {  // (stage timers and the cross-context chaining of
-    // the heavy kernels belong to the one-stream form below)
-    if ((st = detect_layers_concurrent(ctx, images_dev, n_images, s)) != OKVFE_OK) return st;
   } else {
-    const int L = ctx->n_layers;
-    std::vector<const uint8_t*> img(L);
-    std::vector<bool> fused(L);
-    img[0] = images_dev;
-    if ((st = heavy_begin(ctx, s, 0, &token)) != OKVFE_OK) return st;
-    {
-      StageTimer t(ctx, OKVFE_STAGE_HARRIS, s);
-      for (int l = 1; l < L; ++l) {
-        if (l == 1)
-          launch_twothird(img[0], ctx->layer_w[0], ctx->layer_h[0], n_images, ctx->d_layer_img[1], s);
-        else
-          launch_halfsample(img[l - 2], ctx->layer_w[l - 2], ctx->layer_h[l - 2], n_images, ctx->d_layer_img[l], s);
-        img[l] = ctx->d_layer_img[l];
-      }
-      for (int l = 0; l < L; ++l) {
-        okvfe_ctx* ch = ctx->layers[l];
-        HIP_TRY(ctx, hipMemsetAsync(ch->d_cand_count, 0, 2 * (size_t)ch->B * sizeof(int32_t), s));
-        bool f;
-        layer_score_nms(ch, img[l], n_images, s, &f);
-        fused[l] = f;
-      }
-      if (ctx->d_virtual) launch_fast58_score(img[0], ctx->layer_w[0], ctx->layer_h[0], n_images, ctx->d_virtual, s);
-    }
-    if ((st = heavy_end(ctx, s, 0, &token)) != OKVFE_OK) return st;
-    {
-      StageTimer t(ctx, OKVFE_STAGE_NMS, s);
-      for (int l = 0; l < L; ++l) layer_nms_finish(ctx->layers[l], n_images, s, fused[l]);
-      // scale-space maxima: every layer against the finished score maps below and above
-      for (int l = 0; l < L; ++l) {
-        okvfe_ctx* ch = ctx->layers[l];
-        int sn, sd;
-        layer_scale(l, &sn, &sd);
-        const int32_t *below = nullptr, *above = nullptr;
-        ScoreLayout lb{0, 0}, la{0, 0};
-        int rb[2] = {1, 1}, ra[2] = {1, 1};
-        auto ratio = [&](int m, int out[2]) {  // scale_l / scale_m, reduced
-          int mn, md;
-          layer_scale(m, &mn, &md);
-          int rn = sn * md, rd = sd * mn;
-          for (int g = 2; g <= 3; ++g)
-            while (rn % g == 0 && rd % g == 0) { rn /= g; rd /= g; }
-          out[0] = rn; out[1] = rd;
-        };
-        if (l > 0) { below = ctx->layers[l - 1]->d_scores; lb = ctx->layers[l - 1]->live_layout; ratio(l - 1, rb); }
-        if (l == 0 && ctx->d_virtual) { below = ctx->d_virtual; lb = ScoreLayout{ctx->layer_w[0], 0}; }  // same grid: ratio 1
-        if (l + 1 < L) { above = ctx->layers[l + 1]->d_scores; la = ctx->layers[l + 1]->live_layout; ratio(l + 1, ra); }
-        launch_scale_filter(ch->d_cand, ch->cand_cap, ch->d_cand_count, n_images, below, lb,
-                            l > 0 ? ctx->layer_w[l - 1] : (below ? ctx->layer_w[0] : 0),
-                            l > 0 ? ctx->layer_h[l - 1] : (below ? ctx->layer_h[0] : 0), rb[0], rb[1], above, la,
-                            l + 1 < L ? ctx->layer_w[l + 1] : 0, l + 1 < L ? ctx->layer_h[l + 1] : 0, ra[0], ra[1], s);
-      }
-    }
-    const bool brisk_ss = ctx->cfg.score_type == OKVFE_SCORE_BRISK_SCALESPACE;
-    {
-      StageTimer t(ctx, OKVFE_STAGE_SORT, s);
-      for (int l = 0; l < L; ++l) {
-        okvfe_ctx* ch = ctx->layers[l];
-        if (brisk_ss)  // always ordered (score desc, y, x): there is no uniformity radius to switch the sort on
-          launch_sort(ch->d_cand, ch->cand_cap, ch->d_cand_count, n_images, 1.0f, ch->d_sort_ws, s);
-        else
-          layer_sort(ch, n_images, s);
-      }
-    }
-    {
-      StageTimer t(ctx, OKVFE_STAGE_SELECT, s);
-      for (int l = 0; l < L; ++l) {
-        okvfe_ctx* ch = ctx->layers[l];
-        if (!brisk_ss) {
-          layer_select(ch, n_images, s);
-          continue;
-        }
-        // strongest maxima + continuous scale from the scores of the layers below and above
-        int sn, sd;
-        layer_scale(l, &sn, &sd);
-        auto ratio2 = [&](int m, int out[2]) {
-          int mn, md;
-          layer_scale(m, &mn, &md);
-          int rn = sn * md, rd = sd * mn;
-          for (int g = 2; g <= 3; ++g)
-            while (rn % g == 0 && rd % g == 0) { rn /= g; rd /= g; }
-          out[0] = rn; out[1] = rd;
-        };
-        int rb2[2] = {1, 1}, ra2[2] = {1, 1};
-        const int32_t* below = l == 0 ? ctx->d_virtual : ctx->layers[l - 1]->d_scores;
-        const int wb = l == 0 ? ctx->layer_w[0] : ctx->layer_w[l - 1], hb = l == 0 ? ctx->layer_h[0] : ctx->layer_h[l - 1];
-        if (l > 0) ratio2(l - 1, rb2);
-        const int32_t* above = l + 1 < L ? ctx->layers[l + 1]->d_scores : nullptr;
-        if (above) ratio2(l + 1, ra2);
-        // c_0: the virtual FAST 5-8 layer sits at 2/3 and the result is clamped to [0.7, 1.5] (published refine1D_2)
-        const double rel_b = (l & 1) || l == 0 ? 2.0 / 3.0 : 0.75, rel_a = (l & 1) ? 4.0 / 3.0 : 1.5;
-        const double rel_lo = l == 0 ? 0.7 : rel_b;
-        launch_brisk_refine(ch->d_scores, ch->w, ch->h, n_images, ch->cand_cap, ch->d_cand_count, ch->d_sort_ws,
-                            ch->cfg.max_keypoints, below, wb, hb, rb2[0], rb2[1], above,
-                            above ? ctx->layer_w[l + 1] : 0, above ? ctx->layer_h[l + 1] : 0, ra2[0], ra2[1], rel_b,
-                            rel_a, rel_lo, ch->d_kps_det, ch->kp_cap, ch->d_det_count, s);
-      }
-      const okvfe_keypoint* kps[8];
-      const int32_t* counts[8];
-      float scale[8];
-      for (int l = 0; l < L; ++l) {
-        kps[l] = ctx->layers[l]->d_kps_det;
-        counts[l] = ctx->layers[l]->d_det_count;
-        int sn, sd;
-        layer_scale(l, &sn, &sd);
-        scale[l] = (float)sn / (float)sd;
-      }
-      launch_merge_layers(kps, counts, scale, L, ctx->cfg.max_keypoints, n_images, ctx->d_kps_det, ctx->kp_cap,
-                          ctx->d_det_count, s);
-    }
+    // (stage timers and the cross-context chaining of the heavy kernels belong to the one-stream schedule)
+    const bool staged = ctx->prof_mask != 0 || score_token_mode() != 0;
+    st = staged ? detect_layers_staged(ctx, images_dev, n_images, s) : detect_layers_concurrent(ctx, images_dev, n_images, s);
+    if (st != OKVFE_OK) return st;
   }
   HIP_TRY(ctx, hipGetLastError());
   ctx->last_n_images = n_images;
@@ -537,29 +488,33 @@ okvfe_status find_overflow(okvfe_ctx* ctx, int first, int n_images, int* bad, in
   return OKVFE_OK;
 }
 
+// K6 and compaction + back-projection of the keypoints in d_kps_det, each one launch sequence without timers (the
+// batch flow brackets them in describe_stage; okvfe_compute issues them back to back)
+void run_describe(okvfe_ctx* ctx, const uint8_t* images_dev, int n_images, hipStream_t s, const CallPlan& plan,
+                  bool setup_done) {
+  launch_describe(images_dev, ctx->w, ctx->h, n_images, ctx->d_pattern, ctx->d_prm, ctx->d_rays_ptrs, ctx->d_jac_ptrs,
+                  ctx->d_kps_det, ctx->kp_cap, ctx->d_det_count, ctx->d_kps_tmp, ctx->d_desc_tmp, ctx->d_valid_tmp,
+                  ctx->d_scales, s, setup_done, plan.route, plan.wide_boxes, plan.aware_extra_box);
+}
+void run_compact(okvfe_ctx* ctx, int n_images, hipStream_t s, const CallPlan& plan) {
+  launch_compact(n_images, ctx->d_cams, ctx->d_prm, ctx->d_kps_tmp, ctx->d_desc_tmp, ctx->d_valid_tmp, ctx->d_det_count,
+                 ctx->kp_cap, ctx->d_kps, ctx->d_desc, ctx->d_bp, ctx->d_bpv, ctx->d_count, s, plan.rt8);
+}
+
 // K6 + compaction + back-projection of the keypoints detect_stage left in d_kps_det
-okvfe_status describe_stage(okvfe_ctx* ctx, const uint8_t* images_dev, int n_images, hipStream_t s) {
-  const int w = ctx->w, h = ctx->h;
+okvfe_status describe_stage(okvfe_ctx* ctx, const uint8_t* images_dev, int n_images, hipStream_t s, const CallPlan& plan,
+                            bool setup_done) {
   TokenScope token;
-  const bool setup_done = ctx->setup_done;  // consumed here, whatever happens below
-  ctx->setup_done = false;
   okvfe_status st = heavy_begin(ctx, s, 1, &token);
   if (st != OKVFE_OK) return st;
   {
     StageTimer t(ctx, OKVFE_STAGE_DESCRIBE, s);
-    launch_describe(images_dev, w, h, n_images, ctx->d_pattern, ctx->d_prm,
-                    ctx->d_rays_ptrs, ctx->d_jac_ptrs, ctx->d_kps_det, ctx->kp_cap, ctx->d_det_count,
-                    ctx->d_kps_tmp, ctx->d_desc_tmp, ctx->d_valid_tmp, ctx->d_scales, ctx->wide_patches, s, setup_done,
-                    ctx->all_aware, ctx->lane_view ? ctx->box_class_call : pattern_box_class(ctx->host_pattern),
-                    ctx->lane_view || setup_done ? ctx->aware_extra_box : aware_box_for_call(ctx, images_dev),
-                    ctx->none_aware && (ctx->lane_view ? ctx->rot_fast_call : pattern_rot_ok(ctx->host_pattern)));
+    run_describe(ctx, images_dev, n_images, s, plan, setup_done);
   }
   if ((st = heavy_end(ctx, s, 1, &token)) != OKVFE_OK) return st;
   {
     StageTimer t(ctx, OKVFE_STAGE_COMPACT, s);
-    launch_compact(n_images, ctx->d_cams, ctx->d_prm, ctx->d_kps_tmp, ctx->d_desc_tmp, ctx->d_valid_tmp,
-                   ctx->d_det_count, ctx->kp_cap, ctx->d_kps, ctx->d_desc, ctx->d_bp, ctx->d_bpv,
-                   ctx->d_count, s, ctx->rt8_call);
+    run_compact(ctx, n_images, s, plan);
   }
   HIP_TRY(ctx, hipGetLastError());
   ctx->last_stream = s;
@@ -623,7 +578,7 @@ okvfe_status ensure_lanes(okvfe_ctx* ctx, int k) {
   return OKVFE_OK;
 }
 
-// view `v` = images [first, first + n) of `p`'s buffers, with the state of the running call
+// view `v` = images [first, first + n) of `p`'s buffers (what the running call decided travels in its CallPlan)
 void bind_lane(okvfe_ctx* v, okvfe_ctx* p, int first, int n) {
   const size_t f = (size_t)first, K = (size_t)p->kp_cap;
   v->cfg = p->cfg;
@@ -647,41 +602,31 @@ void bind_lane(okvfe_ctx* v, okvfe_ctx* p, int first, int n) {
   v->d_bp = p->d_bp + f * K * 3; v->d_bpv = p->d_bpv + f * K; v->d_count = p->d_count + f;
   v->d_prm = p->d_prm + f;
   v->d_cams = p->d_cams; v->d_rays_ptrs = p->d_rays_ptrs; v->d_jac_ptrs = p->d_jac_ptrs;
-  v->wide_patches = p->wide_patches; v->all_aware = p->all_aware; v->aware_fast = p->aware_fast;
-  v->rt8_call = p->rt8_call;
-  v->aware_extra_box = p->aware_extra_box; v->box_class_call = p->box_class_call;
-  v->none_aware = p->none_aware; v->rot_fast_call = p->rot_fast_call;
-  v->fuse_setup = p->fuse_setup;
-  v->counters_cleared = p->counters_cleared;
   v->prof_mask = p->prof_mask;
   v->prm_slot = -1;
 }
 
 // detect + describe of a device-resident batch, in lanes when the call is large enough
 okvfe_status detect_describe_split(okvfe_ctx* ctx, const uint8_t* images_dev, int n_images, hipStream_t s,
-                                   bool pipelined = false) {
+                                   const CallPlan& plan, bool pipelined) {
   // (a context set to pipelined lanes splits only the calls that can stay un-joined; everything else runs unsplit)
   const int k = ctx->lanes_pipelined && !pipelined ? 1 : lanes_for_call(ctx, n_images);
   okvfe_status st;
+  bool setup_done = false;
   if (k <= 1) {
-    st = detect_stage(ctx, images_dev, n_images, s);
-    ctx->fuse_setup = false;
+    st = detect_stage(ctx, images_dev, n_images, s, plan, &setup_done);
     if (st != OKVFE_OK) {
-      ctx->setup_done = false;
       ctx->detected_images = 0;
       return st;
     }
     ctx->detected_images = n_images;
-    return describe_stage(ctx, images_dev, n_images, s);
+    return describe_stage(ctx, images_dev, n_images, s, plan, setup_done);
   }
   if ((st = ensure_lanes(ctx, k)) != OKVFE_OK) return st;
   // slices of whole stereo pairs, multiples of 8 images (the kernels' image -> XCD striping)
   int chunk = (n_images + k - 1) / k;
   chunk = (chunk + 7) & ~7;
   const size_t P = (size_t)ctx->w * ctx->h;
-  ctx->box_class_call = pattern_box_class(ctx->host_pattern);
-  ctx->rot_fast_call = pattern_rot_ok(ctx->host_pattern);
-  ctx->aware_extra_box = aware_box_for_call(ctx, images_dev);
   HIP_TRY(ctx, hipEventRecord(ctx->lane_fork, s));  // behind the parameter upload (and whatever the caller queued)
   okvfe_status first_err = OKVFE_OK;
   int used = 0;
@@ -694,9 +639,8 @@ okvfe_status detect_describe_split(okvfe_ctx* ctx, const uint8_t* images_dev, in
     // (pipelined lanes are never chained: each follows its own previous call, like separate contexts)
     v->k1_wait = l > 0 && !pipelined ? ctx->lane_ctx[l - 1]->k1_done : nullptr;
     HIP_TRY(ctx, hipStreamWaitEvent(v->stream, ctx->lane_fork, 0));
-    st = detect_stage(v, images_dev + first * P, n, v->stream);
-    v->fuse_setup = false;
-    if (st == OKVFE_OK) st = describe_stage(v, images_dev + first * P, n, v->stream);
+    st = detect_stage(v, images_dev + first * P, n, v->stream, plan, &setup_done);
+    if (st == OKVFE_OK) st = describe_stage(v, images_dev + first * P, n, v->stream, plan, setup_done);
     if (st != OKVFE_OK && first_err == OKVFE_OK) {
       first_err = st;
       ctx->err = v->err;
@@ -716,9 +660,6 @@ okvfe_status detect_describe_split(okvfe_ctx* ctx, const uint8_t* images_dev, in
   } else {
     for (int l = 0; l < used; ++l) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->lane_done[l], 0));
   }
-  ctx->fuse_setup = false;
-  ctx->setup_done = false;
-  ctx->counters_cleared = false;
   okvfe_ctx* v0 = ctx->lane_ctx[0];
   ctx->map_free_live = v0->map_free_live;
   ctx->live_layout = v0->live_layout;
@@ -738,6 +679,8 @@ okvfe_status detect_describe_split(okvfe_ctx* ctx, const uint8_t* images_dev, in
 }
 }  // namespace
 
+extern "C" {
+
 okvfe_status okvfe_detect_batch_device(okvfe_ctx* ctx, const uint8_t* images_dev, int32_t n_images,
                                        void* stream) {
   if (!ctx) return OKVFE_ERR_INVALID_ARGUMENT;
@@ -746,7 +689,7 @@ okvfe_status okvfe_detect_batch_device(okvfe_ctx* ctx, const uint8_t* images_dev
                 n_images, ctx->B);
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
   ctx->detected_images = 0;
-  okvfe_status st = detect_stage(ctx, images_dev, n_images, pick_stream(ctx, stream));
+  okvfe_status st = detect_stage(ctx, images_dev, n_images, pick_stream(ctx, stream), CallPlan{}, nullptr);
   if (st == OKVFE_OK) ctx->detected_images = n_images;
   return st;
 }
@@ -760,9 +703,10 @@ okvfe_status okvfe_describe_batch_device(okvfe_ctx* ctx, const uint8_t* images_d
                 "covered %d", n_images, ctx->detected_images);
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
   hipStream_t s = pick_stream(ctx, stream);
-  okvfe_status st = upload_image_params(ctx, n_images, cam_ids, gravity_C, s);
+  BatchFacts batch;
+  okvfe_status st = upload_image_params(ctx, n_images, cam_ids, gravity_C, s, false, &batch);
   if (st != OKVFE_OK) return st;
-  return describe_stage(ctx, images_dev, n_images, s);
+  return describe_stage(ctx, images_dev, n_images, s, make_call_plan(ctx, batch, images_dev, false), false);
 }
 
 okvfe_status okvfe_detect_describe_batch_device(okvfe_ctx* ctx, const uint8_t* images_dev,
@@ -787,11 +731,10 @@ okvfe_status okvfe_detect_describe_batch_device(okvfe_ctx* ctx, const uint8_t* i
   hipStream_t s = same_slices ? pick_stream_raw(ctx, stream) : pick_stream(ctx, stream);
   // (pipelined: the candidate counters are cleared by every lane on its own stream, not by the parameter upload on the
   // caller's -- a lane may still be reading last call's)
-  okvfe_status st = upload_image_params(ctx, n_images, cam_ids, gravity_C, s, !piped);
+  BatchFacts batch;
+  okvfe_status st = upload_image_params(ctx, n_images, cam_ids, gravity_C, s, !piped, &batch);
   if (st != OKVFE_OK) return st;
-  static const bool no_fuse = lab_env("OKVFE_NO_FUSED_SETUP") != nullptr;  // A/B knob
-  ctx->fuse_setup = !no_fuse;
-  return detect_describe_split(ctx, images_dev, n_images, s, piped);
+  return detect_describe_split(ctx, images_dev, n_images, s, make_call_plan(ctx, batch, images_dev, true), piped);
 }
 
 okvfe_status okvfe_detect_describe_batch_host(okvfe_ctx* ctx, const uint8_t* images_host, int32_t n_images,
@@ -839,10 +782,11 @@ okvfe_status okvfe_detect_describe_batch_host(okvfe_ctx* ctx, const uint8_t* ima
                               ctx->feed_stream));
   HIP_TRY(ctx, hipEventRecord(ctx->feed_copied[slot], ctx->feed_stream));
   HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->feed_copied[slot], 0));
-  okvfe_status st = upload_image_params(ctx, n_images, cam_ids, gravity_C, s, true);
+  BatchFacts batch;
+  okvfe_status st = upload_image_params(ctx, n_images, cam_ids, gravity_C, s, true, &batch);
   if (st != OKVFE_OK) return st;
-  ctx->fuse_setup = lab_env("OKVFE_NO_FUSED_SETUP") == nullptr;
-  if ((st = detect_describe_split(ctx, ctx->d_feed[slot], n_images, s)) != OKVFE_OK) return st;
+  const CallPlan plan = make_call_plan(ctx, batch, ctx->d_feed[slot], true);
+  if ((st = detect_describe_split(ctx, ctx->d_feed[slot], n_images, s, plan, false)) != OKVFE_OK) return st;
   HIP_TRY(ctx, hipEventRecord(ctx->feed_consumed[slot], s));
   ctx->feed_busy[slot] = true;
   return OKVFE_OK;
@@ -975,6 +919,16 @@ okvfe_status copy_results_out(okvfe_ctx* ctx, okvfe_keypoint* keypoints, uint8_t
   return OKVFE_OK;
 }
 
+// h_result -> the caller's array (the detector's keypoints)
+okvfe_status copy_detections_out(okvfe_ctx* ctx, okvfe_keypoint* keypoints, int32_t cap, int32_t* n_out) {
+  const int n = reinterpret_cast<const int32_t*>(ctx->h_result)[2];
+  *n_out = n;
+  if (n > cap) return fail(ctx, OKVFE_ERR_CAPACITY, "%d keypoints, caller capacity %d", n, cap);
+  if (n > 0 && keypoints)
+    std::memcpy(keypoints, ctx->h_result + result_layout(ctx->kp_cap).o_det, (size_t)n * sizeof(okvfe_keypoint));
+  return OKVFE_OK;
+}
+
 // the caller's image -> pinned staging -> d_img_stage on the context's stream (a copy kernel reads
 // the pinned rows in place: no hand-over between the DMA engine and the compute queue)
 okvfe_status stage_image(okvfe_ctx* ctx, const uint8_t* image, size_t stride, bool keep_shadow = false) {
@@ -1063,14 +1017,9 @@ okvfe_status okvfe_detect(okvfe_ctx* ctx, const uint8_t* image, size_t stride, o
   hipStream_t s = pick_stream(ctx, nullptr);  // (pipelined lanes may still write image slot 0)
   okvfe_status st = stage_image(ctx, image, stride);
   if (st != OKVFE_OK) return st;
-  if ((st = detect_stage(ctx, ctx->d_img_stage, 1, s)) != OKVFE_OK) return st;
+  if ((st = detect_stage(ctx, ctx->d_img_stage, 1, s, CallPlan{}, nullptr)) != OKVFE_OK) return st;
   if ((st = export_and_wait(ctx, 0, false, s)) != OKVFE_OK) return st;
-  const int n = reinterpret_cast<const int32_t*>(ctx->h_result)[2];
-  *n_out = n;
-  if (n > cap) return fail(ctx, OKVFE_ERR_CAPACITY, "%d keypoints, caller capacity %d", n, cap);
-  if (n > 0 && keypoints)
-    std::memcpy(keypoints, ctx->h_result + result_layout(ctx->kp_cap).o_det, (size_t)n * sizeof(okvfe_keypoint));
-  return OKVFE_OK;
+  return copy_detections_out(ctx, keypoints, cap, n_out);
 }
 
 okvfe_status okvfe_detect_ahead(okvfe_ctx* ctx, const uint8_t* image, size_t stride, int32_t cam,
@@ -1086,11 +1035,7 @@ okvfe_status okvfe_detect_ahead(okvfe_ctx* ctx, const uint8_t* image, size_t str
   st = okvfe_detect_describe_batch_device(ctx, ctx->d_img_stage, 1, &cam_id, aware ? gravity_C : nullptr, ctx->stream);
   if (st != OKVFE_OK) return st;
   if ((st = export_and_wait(ctx, 0, true, ctx->stream)) != OKVFE_OK) return st;
-  const int n = reinterpret_cast<const int32_t*>(ctx->h_result)[2];
-  *n_out = n;
-  if (n > cap) return fail(ctx, OKVFE_ERR_CAPACITY, "%d keypoints, caller capacity %d", n, cap);
-  if (n > 0 && keypoints)
-    std::memcpy(keypoints, ctx->h_result + result_layout(ctx->kp_cap).o_det, (size_t)n * sizeof(okvfe_keypoint));
+  if ((st = copy_detections_out(ctx, keypoints, cap, n_out)) != OKVFE_OK) return st;
   ctx->ahead.valid = true;
   ctx->ahead.image = image;
   ctx->ahead.stride = stride;
@@ -1128,8 +1073,10 @@ okvfe_status okvfe_compute(okvfe_ctx* ctx, const uint8_t* image, size_t stride, 
   okvfe_status st = stage_image(ctx, image, stride);
   if (st != OKVFE_OK) return st;
   const int32_t cam_id = cam;
-  st = upload_image_params(ctx, 1, &cam_id, aware ? gravity_C : nullptr, s);
+  BatchFacts batch;
+  st = upload_image_params(ctx, 1, &cam_id, aware ? gravity_C : nullptr, s, false, &batch);
   if (st != OKVFE_OK) return st;
+  const CallPlan plan = make_call_plan(ctx, batch, ctx->d_img_stage, false);
   const int w = ctx->w, h = ctx->h;
   // keypoints ride behind the image in the pinned staging buffer; the count is a kernel argument
   const size_t o_kp = align_up((size_t)w * h, 256) + 256;
@@ -1146,13 +1093,8 @@ okvfe_status okvfe_compute(okvfe_ctx* ctx, const uint8_t* image, size_t stride, 
     HIP_TRY(ctx, hipMemcpyAsync(ctx->d_det_count, ctx->h_pinned + o_kp - 256, sizeof(int32_t), hipMemcpyHostToDevice, s));
     HIP_TRY(ctx, hipMemsetAsync(ctx->d_cand_count, 0, sizeof(int32_t), s));
   }
-  launch_describe(ctx->d_img_stage, w, h, 1, ctx->d_pattern, ctx->d_prm, ctx->d_rays_ptrs,
-                  ctx->d_jac_ptrs, ctx->d_kps_det, ctx->kp_cap, ctx->d_det_count, ctx->d_kps_tmp,
-                  ctx->d_desc_tmp, ctx->d_valid_tmp, ctx->d_scales, ctx->wide_patches, s, false,
-                  ctx->all_aware, pattern_box_class(ctx->host_pattern), aware_box_for_call(ctx, ctx->d_img_stage),
-                  ctx->none_aware && pattern_rot_ok(ctx->host_pattern));
-  launch_compact(1, ctx->d_cams, ctx->d_prm, ctx->d_kps_tmp, ctx->d_desc_tmp, ctx->d_valid_tmp, ctx->d_det_count,
-                 ctx->kp_cap, ctx->d_kps, ctx->d_desc, ctx->d_bp, ctx->d_bpv, ctx->d_count, s, ctx->rt8_call);
+  run_describe(ctx, ctx->d_img_stage, 1, s, plan, false);
+  run_compact(ctx, 1, s, plan);
   HIP_TRY(ctx, hipGetLastError());
   ctx->last_n_images = 1;
   ctx->last_stream = s;
@@ -1183,5 +1125,14 @@ extern "C" long long okvfe_lab_dump_layer(okvfe_ctx* ctx, int layer, int what, v
   if (!src) return 0;
   if (host && hipMemcpy(host, src, bytes < n ? bytes : n, hipMemcpyDeviceToHost) != hipSuccess) return -2;
   return (long long)n;
+}
+// lab build only: describe_route on plain integers.  facts[12] = RouteFacts in declaration order (all_aware, none_aware,
+// aware_fast, wide_patches, box_class, rot_ok, extra, scale_invariant, n_layers, w, h, aligned); returns the
+// DescribeRoute value
+extern "C" int32_t okvfe_lab_describe_route(const int32_t* f, int32_t* aware_extra_box) {
+  const RouteFacts r{.all_aware = f[0] != 0, .none_aware = f[1] != 0, .aware_fast = f[2] != 0, .wide_patches = f[3] != 0,
+                     .box_class = f[4], .rot_ok = f[5] != 0, .extra = f[6], .scale_invariant = f[7] != 0, .n_layers = f[8],
+                     .w = f[9], .h = f[10], .aligned = f[11] != 0};
+  return (int32_t)describe_route(r, aware_extra_box);
 }
 #endif

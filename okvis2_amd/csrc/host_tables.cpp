@@ -153,6 +153,32 @@ void scale_pattern_boxes(Pattern* p, float s) {
   fill_aware_lanes(p);
 }
 
+PatternFacts pattern_facts(const Pattern& P) {
+  PatternFacts f;
+  f.extra = P.n_points > 64 ? P.n_points - 64 : 0;
+  for (int i = 0; i < P.n_points && i < kPatternPoints; ++i) {
+    const float s = P.sigma_half[i];
+    if (!(s <= (i < f.extra ? 2.0f : 4.75f))) f.box_class = f.box_class < 1 ? 1 : f.box_class;
+    if (!(s <= (i < f.extra ? 4.25f : 9.75f))) f.box_class = 2;
+    // half-widths below 0.5 are bilinear point samples: only the all-modes kernel carries that branch (and waits for
+    // its patch before it)
+    if (!(s >= 0.5f)) f.box_class = 2;
+  }
+  f.rot_ok = P.border <= 29 && f.extra <= kAwareMaxExtra && P.n_long <= kMaxLongPairs;
+  for (int l = 0; l < P.n_long && f.rot_ok; ++l)
+    f.rot_ok = P.long_wdx[l] >= -32768 && P.long_wdx[l] <= 32767 && P.long_wdy[l] >= -32768 && P.long_wdy[l] <= 32767;
+  // the rotation tables must follow the quarter-wave rule exactly (they do for the tables build_pattern computes)
+  for (int k = 0; k < kRot && f.rot_ok; ++k) {
+    if (quarter_sin(P.rot_sin, k) != P.rot_sin[k] || quarter_cos(P.rot_sin, k) != P.rot_cos[k]) f.rot_ok = false;
+    // (float tables: sin(pi) and cos(pi / 2) are 1e-16, not 0, in double -- entries sin[512], cos[256], cos[768] are
+    // read from the global table by the kernel and exempt here)
+    const float fs = quarter_sin(P.rot_sinf, k), fc = quarter_cos(P.rot_sinf, k);
+    if (k != 512 && std::memcmp(&fs, &P.rot_sinf[k], 4) != 0) f.rot_ok = false;
+    if (k != 256 && k != 768 && std::memcmp(&fc, &P.rot_cosf[k], 4) != 0) f.rot_ok = false;
+  }
+  return f;
+}
+
 int pattern_scale_index(float size) {
   const double lb_range = std::log(30.0) / std::log(2.0);
   if (!(size > 0.0f)) return 0;

@@ -822,11 +822,21 @@ void launch_describe(const uint8_t* img, int w, int h, int n_images, const Patte
                      const ImageParams* prm, const float* const* rays, const float* const* jac,
                      const okvfe_keypoint* kps_in, int kp_cap, const int32_t* kp_count_in,
                      okvfe_keypoint* kps_tmp, uint8_t* desc_tmp, uint8_t* valid_tmp,
-                     const PatternScales* scales, bool wide_patches, hipStream_t stream, bool setup_done,
-                     bool all_camera_aware, int box_class, int aware_extra_box, bool rot_fast) {
+                     const PatternScales* scales, hipStream_t stream, bool setup_done, DescribeRoute route,
+                     bool wide_boxes, int aware_extra_box) {
   if (n_images <= 0) return;
-  static const char* force = lab_env("OKVFE_DESC_WAVES");  // A/B knob: 5 / 6
-  if (force) wide_patches = force[0] == '5';
+  // The route is the caller's (describe_route, capi_detect.cpp).  Two A/B knobs are applied to it here:
+  // OKVFE_DESC_GENERIC sends a call to the all-modes form (its WIDE instantiation for a pattern of box class 1 outside
+  // scale-invariant extraction), OKVFE_DESC_WAVES=5 / 6 picks between the 5- and 6-wave camera-aware forms.
+  static const bool no_aware = lab_env("OKVFE_DESC_GENERIC") != nullptr;
+  if (no_aware) {
+    const bool wide = route == DescribeRoute::kAwareWideBoxes || route == DescribeRoute::kWideBoxes ||
+                      (route == DescribeRoute::kAwareBatched && wide_boxes);
+    route = wide ? DescribeRoute::kWideBoxes : DescribeRoute::kAllModes;
+  }
+  static const char* force = lab_env("OKVFE_DESC_WAVES");
+  if (force && (route == DescribeRoute::kAware5 || route == DescribeRoute::kAware6))
+    route = force[0] == '5' ? DescribeRoute::kAware5 : DescribeRoute::kAware6;
   if (!setup_done)  // (done by select_lazy_kernel when detection and description were one call)
   hipLaunchKernelGGL(describe_setup_kernel, dim3((kp_cap + 255) / 256, n_images), dim3(256), 0,
                      stream, w, h, pat, prm, rays, jac, kps_in, kp_cap, kp_count_in, kps_tmp, desc_tmp,
@@ -840,38 +850,24 @@ void launch_describe(const uint8_t* img, int w, int h, int n_images, const Patte
   hipLaunchKernelGGL((describe_kernel<WAVES, AWARE, WIDE>), dim3(tiles * n_images), dim3(64 * kDescWaves), 0, stream, \
                      img, w, h, pat, prm, rays, jac, kps_in, kp_cap, kp_count_in, kps_tmp, desc_tmp, valid_tmp,        \
                      n_images, tiles, inv_tiles, scales)
-  static const bool no_aware = lab_env("OKVFE_DESC_GENERIC") != nullptr;  // A/B knob: the all-modes kernel
-  if (no_aware || scales != nullptr || w % 4 != 0 || (reinterpret_cast<uintptr_t>(img) & 3) != 0)
-    all_camera_aware = false;  // (scale-invariant extraction, unaligned images: generic form)
-  // round 6: the production mode on cameras whose patches fit the two LDS classes -> k_describe_aware.hip (extra
-  // samples in batches, patch geometry from the set-up thread, compile-time row pitches)
-  // (aware_extra_box >= 0: capi_detect.cpp decided for it -- cameras, pattern, alignment -- and the set-up threads
-  // have left the extra samples in the slots)
-  if (all_camera_aware && aware_extra_box >= 0 && box_class <= 1) {
-    launch_describe_aware(img, w, h, n_images, pat, kps_in, kp_cap, kp_count_in, desc_tmp, valid_tmp, box_class == 1,
-                          stream);
-    return;
-  }
-  // round 6: upright / gradient-orientation calls (the BRISK scale-space path, callers without a camera) on the same box
-  // sums: describe_rot_kernel (k_describe_aware.hip)
-  if (rot_fast && !no_aware && box_class == 0 && scales == nullptr && w % 4 == 0 &&
-      (reinterpret_cast<uintptr_t>(img) & 3) == 0) {
-    launch_describe_rot(img, w, h, n_images, pat, prm, kps_in, kp_cap, kp_count_in, kps_tmp, desc_tmp, valid_tmp, stream);
-    return;
-  }
-  // box_class (capi_detect.cpp: pattern_box_class): 0 = every box fits the 11 x 11 / 5 x 5 slots, 1 = the 21 x 21 /
-  // 9 x 9 slots of the WIDE instantiations, 2 = wider still: the all-modes form's plain box loops
-  if (box_class == 1 && scales == nullptr) {
-    if (all_camera_aware) OKVFE_DESC_LAUNCH(4, true, true); else OKVFE_DESC_LAUNCH(4, false, true);
-  } else if (!all_camera_aware || box_class != 0) {
+  switch (route) {
+    case DescribeRoute::kAwareBatched:
+      // the production mode on cameras whose patches fit the two LDS classes (extra samples in batches, patch geometry
+      // from the set-up thread, compile-time row pitches); the set-up threads have left the extra samples in the slots
+      launch_describe_aware(img, w, h, n_images, pat, kps_in, kp_cap, kp_count_in, desc_tmp, valid_tmp, wide_boxes, stream);
+      break;
+    case DescribeRoute::kRot:
+      // upright / gradient-orientation calls (the BRISK scale-space path, callers without a camera) on the same box sums
+      launch_describe_rot(img, w, h, n_images, pat, prm, kps_in, kp_cap, kp_count_in, kps_tmp, desc_tmp, valid_tmp, stream);
+      break;
+    case DescribeRoute::kAwareWideBoxes: OKVFE_DESC_LAUNCH(4, true, true); break;
+    case DescribeRoute::kWideBoxes: OKVFE_DESC_LAUNCH(4, false, true); break;
     // the all-modes form: 128 registers, the long pairs in LDS: four workgroups per CU (measured on the BRISK
     // scale-space path, 512 images x 2780 keypoints in gradient mode: 5.5 ms with 80 registers and the long-pair /
     // rotation tables in global memory, 4.3 ms in this form; the 5- and 6-wave forms of it 4.7 ms)
-    OKVFE_DESC_LAUNCH(4, false, false);
-  } else if (wide_patches) {
-    OKVFE_DESC_LAUNCH(5, true, false);
-  } else {
-    OKVFE_DESC_LAUNCH(6, true, false);
+    case DescribeRoute::kAllModes: OKVFE_DESC_LAUNCH(4, false, false); break;
+    case DescribeRoute::kAware5: OKVFE_DESC_LAUNCH(5, true, false); break;
+    case DescribeRoute::kAware6: OKVFE_DESC_LAUNCH(6, true, false); break;
   }
 #undef OKVFE_DESC_LAUNCH
 }

@@ -17,6 +17,26 @@
 
 using namespace okvfe;  // internal header of the runtime's own translation units
 
+// The context holds what outlives a call.  A call's decisions travel in its CallPlan: built once by the entry point
+// (make_call_plan, capi_detect.cpp), handed down by const reference -- a lane view receives its owner's -- and gone
+// when the call returns.
+struct BatchFacts {  // of the images of one parameter upload (upload_image_params)
+  bool wide_patches = false;      // a camera-aware image comes from a camera whose patches often exceed the LDS buffer
+  bool aware_fast = true;         // none comes from a cam_aware_slow camera
+  bool all_aware = false;         // every image is extracted camera-aware
+  bool none_aware = true;         // no image is
+  bool rt8 = false;               // an image uses an OKVFE_DIST_RADTAN8 slot
+  bool counters_cleared = false;  // the upload zeroed d_cand_count / d_fix_count on the call's stream
+};
+struct CallPlan {  // (the default is a detect-only call's: nothing fused, no batch looked at)
+  DescribeRoute route = DescribeRoute::kAllModes;
+  int aware_extra_box = -1;       // what describe_route says of the samples beyond 64
+  bool wide_boxes = false;        // pattern of box class 1
+  bool rt8 = false;               // compact_kernel<true>
+  bool fuse_setup = false;        // the call describes what it detects: the set-up rides in the selection kernel
+  bool counters_cleared = false;  // BatchFacts::counters_cleared
+};
+
 struct okvfe_ctx {
   okvfe_config cfg{};
   hipStream_t stream = nullptr;
@@ -28,6 +48,7 @@ struct okvfe_ctx {
   size_t occ_image_bytes = 0;
   int mode_default = kUpright;
   Pattern host_pattern{};
+  PatternFacts pattern_facts{};  // of host_pattern, refreshed wherever it changes
 
   std::vector<void*> allocs;
   int32_t* d_scores = nullptr;
@@ -153,17 +174,6 @@ struct okvfe_ctx {
   // class of describe_aware_kernel (k_describe_aware.hip) -> such a camera keeps describe_kernel
   std::vector<std::vector<float>> cam_norms;
   std::vector<uint8_t> cam_aware_slow;
-  bool aware_fast = false;        // of the images of the current batch: none from a cam_aware_slow camera
-  bool none_aware = false;        // no image of the last parameter upload is camera-aware (describe_rot_kernel's call)
-  bool rot_fast_call = false;     // lane view: pattern_rot_ok of the owner's pattern
-  int box_class_call = 0;         // lane view: pattern_box_class of the owner's pattern
-  int aware_extra_box = -1;       // of the running call (aware_box_for_call): >= 0 = describe_aware_kernel serves it
-  bool wide_patches = false;      // of the images of the current batch
-  bool all_aware = false;         // every image of the current batch is extracted camera-aware
-  bool rt8_call = false;          // an image of the current batch uses an OKVFE_DIST_RADTAN8 slot (compact_kernel<true>)
-  bool counters_cleared = false;  // upload_image_params zeroed d_cand_count on the call's stream
-  bool fuse_setup = false;        // the current call describes what it detects: setup rides in the selection kernel
-  bool setup_done = false;        // ... and did
   std::vector<DeviceCamera> h_cams;
   std::vector<bool> cam_has_intrinsics;
   int last_n_images = 0;

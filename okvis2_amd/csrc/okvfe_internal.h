@@ -82,6 +82,20 @@ void fill_aware_lanes(Pattern* p);
 void build_pattern(Pattern* p);
 void scale_pattern_boxes(Pattern* p, float s);
 float pattern_reach(const Pattern& p);
+// What the descriptor kernels may assume of a pattern; computed where a pattern is installed (okvfe_create,
+// okvfe_set_pattern) and kept next to it, so that no call walks the pattern.
+struct PatternFacts {
+  // 0: every box fits the fixed-trip slots of the fast descriptor kernels (first-pass samples 11 x 11: sigma_half <=
+  // 4.75; second-pass samples = points 0 .. n - 65 of a pattern with more than 64 points, 5 x 5: sigma_half <= 2.0);
+  // 1: the slots of the WIDE instantiations (21 x 21: <= 9.75, 10 x 10: <= 4.25); 2: wider still, or a half-width
+  // below 0.5 (k_describe.hip: kMaxBox / kSmallBox / kWideBox / kWideSmallBox)
+  int32_t box_class = 0;
+  // describe_rot_kernel takes the pattern: its circle fits a 64-byte row pitch, its samples beyond 64 lanes fit the
+  // kernel's table, its long-pair weights fit 16 bits and its rotation tables follow the quarter-wave rule exactly
+  bool rot_ok = false;
+  int32_t extra = 0;  // samples beyond 64 lanes
+};
+PatternFacts pattern_facts(const Pattern& p);
 // scale_invariant = true (Frontend.hpp:235-237): the published BRISK extractor keeps the pattern at 64
 // scales spanning a factor of 30 and picks index max(int(64 / lb(30) * lb(size / 7.2) + 0.5), 0)
 // (<= 63) from the keypoint's diameter; the fixed-scale extractor is index 17 of the same ladder.
@@ -290,14 +304,33 @@ bool launch_select(const int32_t* score, ScoreLayout layout, int w, int h, int n
                    const uint8_t* images = nullptr);  // images != null: map-free call, see select_recomputes_scores
 bool select_recomputes_scores(float radius, int max_kpts, int kp_cap, const uint8_t* occupancy, size_t occ_image_bytes,
                               int occ_rows, int occ_cols);
+// Which descriptor kernel serves a call, one value per form launch_describe can launch: describe_aware_kernel (every
+// image camera-aware, extra samples batched), describe_rot_kernel (no image camera-aware), describe_kernel<4, true, true>,
+// <4, false, true>, <4, false, false> (all modes), <5, true, false>, <6, true, false>
+enum class DescribeRoute : int32_t { kAwareBatched, kRot, kAwareWideBoxes, kWideBoxes, kAllModes, kAware5, kAware6 };
+// Everything the choice depends on, as plain numbers (no pointer, no HIP type): the batch (upload_image_params), the
+// installed pattern (PatternFacts), the context and the alignment of the call's image pointer.
+struct RouteFacts {
+  bool all_aware, none_aware, aware_fast, wide_patches;  // of the images of the batch
+  int32_t box_class;
+  bool rot_ok;
+  int32_t extra;
+  bool scale_invariant;  // the context extracts with the pattern at 64 scales (d_scales)
+  int32_t n_layers, w, h;
+  bool aligned;  // the call's image pointer is a multiple of 4
+};
+// *aware_extra_box = -1: the batched camera-aware kernel cannot serve the call; otherwise (samples beyond 64) << 8 |
+// their largest box side minus one (0: no such samples).  Its low byte is what the set-up (describe_setup_kernel or the
+// selection kernel's fused set-up) is told, whichever route serves the call.
+DescribeRoute describe_route(const RouteFacts& f, int* aware_extra_box);
+// setup_done: the selection kernel has prepared the per-keypoint inputs (detection and description in one call);
+// wide_boxes: the pattern is of box class 1 (the WIDE slots of describe_aware_kernel)
 void launch_describe(const uint8_t* img, int w, int h, int n_images, const Pattern* pat,
                      const ImageParams* prm, const float* const* rays, const float* const* jac,
                      const okvfe_keypoint* kps_in, int kp_cap, const int32_t* kp_count_in,
                      okvfe_keypoint* kps_tmp, uint8_t* desc_tmp, uint8_t* valid_tmp,
-                     const PatternScales* scales, bool wide_patches, hipStream_t stream, bool setup_done = false,
-                     bool all_camera_aware = false, int box_class = 0,  // (every image of the call has mode kCameraAware)
-                     int aware_extra_box = -1,  // >= 0: describe_aware_kernel serves the call (capi_detect.cpp: aware_box_for_call)
-                     bool rot_fast = false);    // no image of the call is camera-aware and the pattern suits describe_rot_kernel
+                     const PatternScales* scales, hipStream_t stream, bool setup_done, DescribeRoute route,
+                     bool wide_boxes, int aware_extra_box);
 bool describe_patch_fits(float nx, float ny, int border);
 // k_describe_aware.hip: the camera-aware-only extractor with batched extra samples (round 6)
 int describe_aware_patch_class(float nx, float ny, float reach);
@@ -307,7 +340,7 @@ void launch_describe_aware(const uint8_t* img, int w, int h, int n_images, const
 // Quarter-wave lookup of the pattern's 1024-step rotation tables: sin(k) = +-Q[r or 256 - r] with Q = the first 257
 // entries of the sine table, cos(k) = sin(k + 256).  describe_rot_kernel keeps Q (ints and floats, 2 KB) in LDS instead
 // of gathering from the 16 KB of global tables inside every keypoint's chain; the host verifies once per pattern that the
-// rule reproduces all 4096 table entries bit for bit (pattern_rot_ok, capi_detect.cpp) and keeps the all-modes kernel
+// rule reproduces all 4096 table entries bit for bit (pattern_facts, host_tables.cpp) and keeps the all-modes kernel
 // otherwise.
 template <typename V>
 __host__ __device__ inline V quarter_sin(const V* Q, int k) {
