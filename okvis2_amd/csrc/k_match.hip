@@ -920,8 +920,9 @@ __global__ __launch_bounds__(64 * kMapSegs) void match_to_map_kernel(
     ky = (double)kps[k].y;
   }
   // bounding box of the wave's keypoints, grown by the radius (+1 px for the float rounding): a
-  // landmark outside it is near no keypoint of the wave.  NaN coordinates pass (as they pass the
-  // reference's "!(dd > thr)").
+  // landmark outside it is near no keypoint of the wave.  A keypoint with a NaN coordinate is near
+  // EVERY landmark in the reference (dd is NaN and "dd > thr" false), but fminf / fmaxf drop a NaN
+  // lane from the box: a wave that holds one takes the whole plane as its box.
   float bx0 = active ? (float)kx : INFINITY, bx1 = active ? (float)kx : -INFINITY;
   float by0 = active ? (float)ky : INFINITY, by1 = active ? (float)ky : -INFINITY;
 #pragma unroll
@@ -933,6 +934,10 @@ __global__ __launch_bounds__(64 * kMapSegs) void match_to_map_kernel(
   }
   const float rad = sqrtf((float)thr_sq) * 1.0001f + 1.0f;
   bx0 -= rad; by0 -= rad; bx1 += rad; by1 += rad;
+  if (__any(active && (kx != kx || ky != ky))) {  // wave-uniform
+    bx0 = by0 = -INFINITY;
+    bx1 = by1 = INFINITY;
+  }
   const int per_seg = (n_lm + kMapSegs - 1) / kMapSegs;
   const int l_lo = min(seg * per_seg, n_lm), l_hi = min(l_lo + per_seg, n_lm);
   uint4* chunk = seg_desc[seg];
@@ -949,9 +954,11 @@ __global__ __launch_bounds__(64 * kMapSegs) void match_to_map_kernel(
       e = desc_begin[l0 + lane + 1];
     }
     // ONE vector test for the 64 landmarks of the chunk: inside the wave's box?
-    const float fpx = (float)px, fpy = (float)py;
-    const unsigned long long cmask =
-        __ballot(lane < cnt && !(fpx < bx0) && !(fpx > bx1) && !(fpy < by0) && !(fpy > by1));
+    // (a projection with a NaN coordinate is near every keypoint, wherever its other coordinate lies: the sum
+    // of the two is NaN then -- and for (inf, -inf), which the exact test below sorts out)
+    const float fpx = (float)px, fpy = (float)py, fps = fpx + fpy;
+    const bool in_box = !(fpx < bx0) && !(fpx > bx1) && !(fpy < by0) && !(fpy > by1);
+    const unsigned long long cmask = __ballot(lane < cnt && (in_box || fps != fps));
     if (cmask == 0) continue;  // wave-uniform: nothing of this chunk is near the wave
     const int d_lo = __builtin_amdgcn_readfirstlane(b);
     const int d_hi = __builtin_amdgcn_readlane(e, cnt - 1);

@@ -216,6 +216,66 @@ void orc_match_to_map_uninit(const uint8_t* desc, const double* bp, const uint8_
                              int32_t* best_lm, int32_t* best_d, double* hps_W, uint8_t* hp_set,
                              int32_t* ctr_out);
 
+/* ---- gate census: which branches of the gate chain a scene reaches ---------------------------
+ * The *_census entry points run the very loop of their plain counterpart (one shared static
+ * function) and add, into counters[ORC_CEN_COUNT] when it is not null, one count per gate
+ * evaluation AS THE SEQUENTIAL LOOP MAKES IT (a pair the running minimum never lets through is
+ * not counted).  Outputs are the plain entry point's, byte for byte. */
+enum {
+  ORC_CEN_BP_INVALID = 0,  /* back-projection invalid on either side (gated pair dropped) */
+  ORC_CEN_DET_SINGULAR,    /* !(|det| > 1e-12) */
+  ORC_CEN_L_SMALL,         /* l0 < 0.01 || l1 < 0.01 */
+  ORC_CEN_TN_SMALL,        /* |t12| < 0.01 inside midpoint_parallel */
+  ORC_CEN_PAR_COS26_E1,    /* midpoint_parallel: first cos 2.6 sigma test fails */
+  ORC_CEN_PAR_COS26_E2,    /* midpoint_parallel: second fails */
+  ORC_CEN_TRI_COS26_E1,    /* plain triangulation: first cos 2.6 sigma test fails */
+  ORC_CEN_TRI_COS26_E2,    /* plain triangulation: second fails */
+  ORC_CEN_COS6_PARALLEL,   /* dot(n2, n1) > cos 6 sigma */
+  ORC_CEN_DEPTH0,          /* depth in camera 0 below 0.05 (stereo) / 0.2 (motion) */
+  ORC_CEN_DEPTH1,          /* depth in camera 1 below it */
+  ORC_CEN_EE_05,           /* ee < 0.5 (motion) */
+  ORC_CEN_EE_08,           /* ee < 0.8 */
+  ORC_CEN_PX4_ACCEPT,      /* winner passes the 4 px check */
+  ORC_CEN_PX4_REJECT,      /* winner fails it */
+  ORC_CEN_PROJ_STATUS,     /* winner's projection status != 0 */
+  ORC_CEN_EPIPOLAR,        /* uninitialised: not in the epipolar plane */
+  ORC_CEN_DIVERGENT,       /* uninitialised: divergent rays */
+  ORC_CEN_NEAR_PARALLEL,   /* uninitialised: near-parallel rays bypass both tests */
+  ORC_CEN_DIST0,           /* uninitialised: point within 0.2 m of the observation centre */
+  ORC_CEN_DIST1,           /* uninitialised: within 0.2 m of the current centre */
+  ORC_CEN_PREVIOUS,        /* uninitialised: l == previous[k] counted */
+  ORC_CEN_WIN_HP,          /* uninitialised: winner replaced, hp stored */
+  ORC_CEN_WIN_NO_HP,       /* uninitialised: winner replaced, parallel: no hp */
+  ORC_CEN_RADIUS_PASS,     /* 3-D map: inside the reprojection radius */
+  ORC_CEN_RADIUS_FAIL,     /* 3-D map: outside */
+  ORC_CEN_MIN_REPLACED,    /* 3-D map: a running minimum replaced by a LATER landmark */
+  ORC_CEN_NAN_OPERAND,     /* a comparison of the chain saw a NaN operand */
+  ORC_CEN_COUNT
+};
+const char* orc_census_label(int label); /* NULL outside [0, ORC_CEN_COUNT) */
+
+void orc_match_stereo_census(const uint8_t* desc0, const orc_keypoint* kp0, const double* bp0,
+                             const uint8_t* bpv0, int n0, const uint8_t* desc1, const orc_keypoint* kp1,
+                             const double* bp1, const uint8_t* bpv1, int n1, const orc_pose* T_WC0,
+                             const orc_pose* T_WC1, double f0, double f1, double threshold,
+                             orc_stereo_match* out /* n0 */, int64_t* counters);
+void orc_match_motion_stereo_census(const uint8_t* desc0, const orc_keypoint* kp0, const double* bp0,
+                                    const uint8_t* bpv0, const uint8_t* skip0, int n0,
+                                    const uint8_t* desc1, const orc_keypoint* kp1, const double* bp1,
+                                    const uint8_t* bpv1, const uint8_t* matched1, int n1,
+                                    const orc_pose* T_WC0, const orc_pose* T_WC1, const orc_camera* cam,
+                                    uint32_t threshold, orc_motion_match* out /* n0 */, int64_t* counters);
+void orc_match_to_map_census(const uint8_t* desc, const orc_keypoint* kps, const uint8_t* use, int n_k,
+                             const double* proj, const int32_t* desc_begin, int n_lm, const uint8_t* pool,
+                             double reprojection_threshold, double threshold, int32_t* best_lm,
+                             int32_t* best_d, int64_t* counters);
+void orc_match_to_map_uninit_census(const uint8_t* desc, const double* bp, const uint8_t* use,
+                                    const int32_t* previous, int n_k, const int32_t* desc_begin, int n_lm,
+                                    const uint8_t* pool, const double* e0_W, const double* r0_W,
+                                    const orc_pose* T_WC1, double focal, double threshold,
+                                    int32_t* best_lm, int32_t* best_d, double* hps_W, uint8_t* hp_set,
+                                    int32_t* ctr_out, int64_t* counters);
+
 /* candidates: all (i, j) with popcnt(A[i]^B[j]) < thr in (i, j) order */
 typedef struct orc_cand {
   int32_t i, j, dist;

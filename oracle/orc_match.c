@@ -95,12 +95,30 @@ static inline void inv_transform_h(const orc_pose* T, const double hp[4], double
   out[3] = s;
 }
 
+/* ---- gate census (okvfe_oracle.h): counters are touched only behind `cen != NULL`, the arithmetic
+ * and the control flow of the loops are the same with and without them. */
+static const char* const k_census_labels[ORC_CEN_COUNT] = {
+    "bp_invalid", "det_singular", "l_small", "tn_small", "par_cos26_e1", "par_cos26_e2",
+    "tri_cos26_e1", "tri_cos26_e2", "cos6_parallel", "depth0", "depth1", "ee_05", "ee_08",
+    "px4_accept", "px4_reject", "proj_status", "epipolar", "divergent", "near_parallel", "dist0",
+    "dist1", "previous", "win_hp", "win_no_hp", "radius_pass", "radius_fail", "min_replaced",
+    "nan_operand"};
+const char* orc_census_label(int label) {
+  return label >= 0 && label < ORC_CEN_COUNT ? k_census_labels[label] : NULL;
+}
+#define CEN(label) do { if (cen) ++cen[label]; } while (0)
+#define CEN_IF(cond, label) do { if (cen && (cond)) ++cen[label]; } while (0)
+/* operand of a comparison: counted when it is a NaN */
+#define SEEN(x) do { if (cen && (x) != (x)) ++cen[ORC_CEN_NAN_OPERAND]; } while (0)
+
 static void midpoint_parallel(const double p1[3], const double e1[3], const double p2[3],
                               const double e2[3], const double t12[3], double sigma, double hp[4],
-                              int* is_valid) {
+                              int* is_valid, int64_t* cen) {
   *is_valid = 1;
   double m[3], mid[3], d[3], dn[3];
   const double tn = sqrt(dot3(t12, t12));
+  SEEN(tn);
+  CEN_IF(0.01 > tn, ORC_CEN_TN_SMALL);
   const double f = 40.0 * (0.01 > tn ? 0.01 : tn);
   for (int i = 0; i < 3; ++i) {
     m[i] = p1[i] + 0.5 * t12[i];
@@ -110,15 +128,19 @@ static void midpoint_parallel(const double p1[3], const double e1[3], const doub
   const double c26 = cos(2.6 * sigma);
   for (int i = 0; i < 3; ++i) d[i] = mid[i] - p1[i];
   normalize3(d, dn);
+  SEEN(dot3(e1, dn));
+  CEN_IF(dot3(e1, dn) < c26, ORC_CEN_PAR_COS26_E1);
   if (dot3(e1, dn) < c26) *is_valid = 0;
   for (int i = 0; i < 3; ++i) d[i] = mid[i] - p2[i];
   normalize3(d, dn);
+  SEEN(dot3(e2, dn));
+  CEN_IF(dot3(e2, dn) < c26, ORC_CEN_PAR_COS26_E2);
   if (dot3(e2, dn) < c26) *is_valid = 0;
 }
 
-void orc_triangulate_fast(const double p1[3], const double e1[3], const double p2[3],
-                          const double e2[3], double sigma, double hp[4], int* is_valid,
-                          int* is_parallel) {
+static void triangulate_fast(const double p1[3], const double e1[3], const double p2[3],
+                             const double e2[3], double sigma, double hp[4], int* is_valid,
+                             int* is_parallel, int64_t* cen) {
   *is_parallel = 0;
   *is_valid = 1;
   double t12[3] = {p2[0] - p1[0], p2[1] - p1[1], p2[2] - p1[2]};
@@ -130,18 +152,23 @@ void orc_triangulate_fast(const double p1[3], const double e1[3], const double p
   /* computeInverseWithCheck(A_inverse, invertible, 1e-12) for a 2x2 */
   const double det = a00 * a11 - a01 * a10;
   const int invertible = fabs(det) > 1.0e-12;
+  SEEN(det);
   if (!invertible) {
+    CEN(ORC_CEN_DET_SINGULAR);
     *is_parallel = 1;
-    midpoint_parallel(p1, e1, p2, e2, t12, sigma, hp, is_valid);
+    midpoint_parallel(p1, e1, p2, e2, t12, sigma, hp, is_valid, cen);
     return;
   }
   const double invdet = 1.0 / det;
   const double i00 = a11 * invdet, i10 = -a10 * invdet, i01 = -a01 * invdet, i11 = a00 * invdet;
   const double l0 = i00 * b0 + i01 * b1;
   const double l1 = i10 * b0 + i11 * b1;
+  SEEN(l0);
+  if (!(l0 < 0.01)) SEEN(l1);
   if (l0 < 0.01 || l1 < 0.01) {
+    CEN(ORC_CEN_L_SMALL);
     *is_parallel = 1;
-    midpoint_parallel(p1, e1, p2, e2, t12, sigma, hp, is_valid);
+    midpoint_parallel(p1, e1, p2, e2, t12, sigma, hp, is_valid, cen);
     return;
   }
   double mid[3], d1[3], d2[3], n1[3], n2[3];
@@ -155,18 +182,30 @@ void orc_triangulate_fast(const double p1[3], const double e1[3], const double p
   normalize3(d1, n1);
   normalize3(d2, n2);
   const double c26 = cos(2.6 * sigma);
+  SEEN(dot3(e1, n1));
+  SEEN(dot3(e2, n2));
+  SEEN(dot3(n2, n1));
+  CEN_IF(dot3(e1, n1) < c26, ORC_CEN_TRI_COS26_E1);
+  CEN_IF(dot3(e2, n2) < c26, ORC_CEN_TRI_COS26_E2);
+  CEN_IF(dot3(n2, n1) > cos(6.0 * sigma), ORC_CEN_COS6_PARALLEL);
   if (dot3(e1, n1) < c26) *is_valid = 0;
   if (dot3(e2, n2) < c26) *is_valid = 0;
   if (dot3(n2, n1) > cos(6.0 * sigma)) *is_parallel = 1;
   hp[0] = mid[0]; hp[1] = mid[1]; hp[2] = mid[2]; hp[3] = 1.0;
 }
 
+void orc_triangulate_fast(const double p1[3], const double e1[3], const double p2[3],
+                          const double e2[3], double sigma, double hp[4], int* is_valid,
+                          int* is_parallel) {
+  triangulate_fast(p1, e1, p2, e2, sigma, hp, is_valid, is_parallel, NULL);
+}
+
 /* ---- matchStereo (Frontend.cpp:2016-2076): k0 ascending, k1 ascending, strict < ------------ */
-void orc_match_stereo(const uint8_t* desc0, const orc_keypoint* kp0, const double* bp0,
-                      const uint8_t* bpv0, int n0, const uint8_t* desc1, const orc_keypoint* kp1,
-                      const double* bp1, const uint8_t* bpv1, int n1, const orc_pose* T_WC0,
-                      const orc_pose* T_WC1, double f0, double f1, double threshold,
-                      orc_stereo_match* out) {
+static void match_stereo(const uint8_t* desc0, const orc_keypoint* kp0, const double* bp0,
+                         const uint8_t* bpv0, int n0, const uint8_t* desc1, const orc_keypoint* kp1,
+                         const double* bp1, const uint8_t* bpv1, int n1, const orc_pose* T_WC0,
+                         const orc_pose* T_WC1, double f0, double f1, double threshold,
+                         orc_stereo_match* out, int64_t* cen) {
   for (int k0 = 0; k0 < n0; ++k0) {
     double distances = threshold;
     int initialisable = 0;
@@ -179,6 +218,9 @@ void orc_match_stereo(const uint8_t* desc0, const orc_keypoint* kp0, const doubl
         const double s0 = size0 / f0, s1 = size1 / f1;
         const double sigma = (s0 > s1 ? s0 : s1) * 0.125; /* std::max(a,b): a<b ? b : a */
         int is_valid = 0, is_parallel = 0;
+        SEEN(s0);
+        SEEN(s1);
+        CEN_IF(!bpv0[k0] || !bpv1[k1], ORC_CEN_BP_INVALID);
         if (!bpv0[k0]) continue;
         if (!bpv1[k1]) continue;
         double v[3], e0_W[3], e1_W[3], hp_W[4], hp_C0[4], hp_C1[4];
@@ -186,13 +228,18 @@ void orc_match_stereo(const uint8_t* desc0, const orc_keypoint* kp0, const doubl
         normalize3(v, e0_W);
         rot(T_WC1->C, bp1 + 3 * (size_t)k1, v);
         normalize3(v, e1_W);
-        orc_triangulate_fast(T_WC0->r, e0_W, T_WC1->r, e1_W, sigma, hp_W, &is_valid,
-                             &is_parallel);
+        triangulate_fast(T_WC0->r, e0_W, T_WC1->r, e1_W, sigma, hp_W, &is_valid, &is_parallel, cen);
         inv_transform_h(T_WC0, hp_W, hp_C0);
         inv_transform_h(T_WC1, hp_W, hp_C1);
         if (!is_parallel) {
           const double w4 = hp_W[3];
           hp_W[0] /= w4; hp_W[1] /= w4; hp_W[2] /= w4; hp_W[3] /= w4;
+          SEEN(hp_C0[2] / hp_C0[3]);
+          SEEN(hp_C1[2] / hp_C1[3]);
+          SEEN(dot3(e0_W, e1_W));
+          CEN_IF(hp_C0[2] / hp_C0[3] < 0.05, ORC_CEN_DEPTH0);
+          CEN_IF(hp_C1[2] / hp_C1[3] < 0.05, ORC_CEN_DEPTH1);
+          CEN_IF(dot3(e0_W, e1_W) < 0.8, ORC_CEN_EE_08);
           if (hp_C0[2] / hp_C0[3] < 0.05) is_valid = 0;
           if (hp_C1[2] / hp_C1[3] < 0.05) is_valid = 0;
           if (dot3(e0_W, e1_W) < 0.8) is_valid = 0;
@@ -218,6 +265,22 @@ void orc_match_stereo(const uint8_t* desc0, const orc_keypoint* kp0, const doubl
     }
   }
 }
+void orc_match_stereo(const uint8_t* desc0, const orc_keypoint* kp0, const double* bp0,
+                      const uint8_t* bpv0, int n0, const uint8_t* desc1, const orc_keypoint* kp1,
+                      const double* bp1, const uint8_t* bpv1, int n1, const orc_pose* T_WC0,
+                      const orc_pose* T_WC1, double f0, double f1, double threshold,
+                      orc_stereo_match* out) {
+  match_stereo(desc0, kp0, bp0, bpv0, n0, desc1, kp1, bp1, bpv1, n1, T_WC0, T_WC1, f0, f1, threshold, out,
+               NULL);
+}
+void orc_match_stereo_census(const uint8_t* desc0, const orc_keypoint* kp0, const double* bp0,
+                             const uint8_t* bpv0, int n0, const uint8_t* desc1, const orc_keypoint* kp1,
+                             const double* bp1, const uint8_t* bpv1, int n1, const orc_pose* T_WC0,
+                             const orc_pose* T_WC1, double f0, double f1, double threshold,
+                             orc_stereo_match* out, int64_t* counters) {
+  match_stereo(desc0, kp0, bp0, bpv0, n0, desc1, kp1, bp1, bpv1, n1, T_WC0, T_WC1, f0, f1, threshold, out,
+               counters);
+}
 
 /* ---- matchMotionStereo (Frontend.cpp:1789-1905) --------------------------------------------
  * Frame 0 = older frame, frame 1 = current frame, same camera `cam`.
@@ -226,12 +289,12 @@ void orc_match_stereo(const uint8_t* desc0, const orc_keypoint* kp0, const doubl
  * matched1[k1] != 0 = current keypoint already carries a landmark (:1795-1798)
  * and is left out of the packed candidate set (the packed order is k1
  * ascending, so iterating k1 ascending and skipping is the same loop). */
-void orc_match_motion_stereo(const uint8_t* desc0, const orc_keypoint* kp0, const double* bp0,
-                             const uint8_t* bpv0, const uint8_t* skip0, int n0,
-                             const uint8_t* desc1, const orc_keypoint* kp1, const double* bp1,
-                             const uint8_t* bpv1, const uint8_t* matched1, int n1,
-                             const orc_pose* T_WC0, const orc_pose* T_WC1, const orc_camera* cam,
-                             uint32_t threshold, orc_motion_match* out) {
+static void match_motion_stereo(const uint8_t* desc0, const orc_keypoint* kp0, const double* bp0,
+                                const uint8_t* bpv0, const uint8_t* skip0, int n0,
+                                const uint8_t* desc1, const orc_keypoint* kp1, const double* bp1,
+                                const uint8_t* bpv1, const uint8_t* matched1, int n1,
+                                const orc_pose* T_WC0, const orc_pose* T_WC1, const orc_camera* cam,
+                                uint32_t threshold, orc_motion_match* out, int64_t* cen) {
   const double f0 = 0.5 * (cam->fu + cam->fv);
   for (int k0 = 0; k0 < n0; ++k0) {
     orc_motion_match* o = &out[k0];
@@ -244,6 +307,7 @@ void orc_match_motion_stereo(const uint8_t* desc0, const orc_keypoint* kp0, cons
     double quality = 0.0;
     double hps_W[4] = {0, 0, 0, 0};
     int k1_max = 1000;
+    CEN_IF(!bpv0[k0], ORC_CEN_BP_INVALID);
     if (!bpv0[k0]) continue;
     double v[3], e0_W[3];
     rot(T_WC0->C, bp0 + 3 * (size_t)k0, v);
@@ -254,21 +318,28 @@ void orc_match_motion_stereo(const uint8_t* desc0, const orc_keypoint* kp0, cons
       const uint32_t dist = popc48(desc0 + 48 * (size_t)k0, desc1 + 48 * (size_t)k1);
       if (dist < distances) {
         int is_valid = 0, is_parallel = 0;
+        CEN_IF(!bpv1[k1], ORC_CEN_BP_INVALID);
         if (!bpv1[k1]) continue;
         double e1_W[3], hp_W[4], hp_C0[4], hp_C1[4];
         rot(T_WC1->C, bp1 + 3 * (size_t)k1, v);
         normalize3(v, e1_W);
         const double ee = dot3(e0_W, e1_W);
+        SEEN(ee);
+        CEN_IF(ee < 0.5, ORC_CEN_EE_05);
         if (ee < 0.5) continue;
-        orc_triangulate_fast(T_WC0->r, e0_W, T_WC1->r, e1_W, sigma, hp_W, &is_valid,
-                             &is_parallel);
+        triangulate_fast(T_WC0->r, e0_W, T_WC1->r, e1_W, sigma, hp_W, &is_valid, &is_parallel, cen);
         if (!is_valid) continue;
         inv_transform_h(T_WC0, hp_W, hp_C0);
         inv_transform_h(T_WC1, hp_W, hp_C1);
+        CEN_IF(ee < 0.8, ORC_CEN_EE_08);
         if (ee < 0.8) is_valid = 0;
         if (!is_parallel) {
           const double w4 = hp_W[3];
           hp_W[0] /= w4; hp_W[1] /= w4; hp_W[2] /= w4; hp_W[3] /= w4;
+          SEEN(hp_C0[2] / hp_C0[3]);
+          SEEN(hp_C1[2] / hp_C1[3]);
+          CEN_IF(hp_C0[2] / hp_C0[3] < 0.2, ORC_CEN_DEPTH0);
+          CEN_IF(hp_C1[2] / hp_C1[3] < 0.2, ORC_CEN_DEPTH1);
           if (hp_C0[2] / hp_C0[3] < 0.2) is_valid = 0;
           if (hp_C1[2] / hp_C1[3] < 0.2) is_valid = 0;
         }
@@ -305,8 +376,30 @@ void orc_match_motion_stereo(const uint8_t* desc0, const orc_keypoint* kp0, cons
       const int status = orc_cam_project(cam, head, pt1p, NULL);
       const double ex = (double)kp1[k1_max].x - pt1p[0], ey = (double)kp1[k1_max].y - pt1p[1];
       o->accepted = (status == 0 && sqrt(ex * ex + ey * ey) < 4.0) ? 1 : 0;
+      SEEN(hp_C1[3]);
+      CEN_IF(status != 0, ORC_CEN_PROJ_STATUS);
+      if (status == 0) SEEN(sqrt(ex * ex + ey * ey));
+      CEN(o->accepted ? ORC_CEN_PX4_ACCEPT : ORC_CEN_PX4_REJECT);
     }
   }
+}
+void orc_match_motion_stereo(const uint8_t* desc0, const orc_keypoint* kp0, const double* bp0,
+                             const uint8_t* bpv0, const uint8_t* skip0, int n0,
+                             const uint8_t* desc1, const orc_keypoint* kp1, const double* bp1,
+                             const uint8_t* bpv1, const uint8_t* matched1, int n1,
+                             const orc_pose* T_WC0, const orc_pose* T_WC1, const orc_camera* cam,
+                             uint32_t threshold, orc_motion_match* out) {
+  match_motion_stereo(desc0, kp0, bp0, bpv0, skip0, n0, desc1, kp1, bp1, bpv1, matched1, n1, T_WC0, T_WC1,
+                      cam, threshold, out, NULL);
+}
+void orc_match_motion_stereo_census(const uint8_t* desc0, const orc_keypoint* kp0, const double* bp0,
+                                    const uint8_t* bpv0, const uint8_t* skip0, int n0,
+                                    const uint8_t* desc1, const orc_keypoint* kp1, const double* bp1,
+                                    const uint8_t* bpv1, const uint8_t* matched1, int n1,
+                                    const orc_pose* T_WC0, const orc_pose* T_WC1, const orc_camera* cam,
+                                    uint32_t threshold, orc_motion_match* out, int64_t* counters) {
+  match_motion_stereo(desc0, kp0, bp0, bpv0, skip0, n0, desc1, kp1, bp1, bpv1, matched1, n1, T_WC0, T_WC1,
+                      cam, threshold, out, counters);
 }
 
 /* ---- candidate list and ungated arg-min ----------------------------------------------------- */
@@ -351,10 +444,10 @@ void orc_hamming_argmin(const uint8_t* A, int nA, const uint8_t* B, int nB, uint
  * Landmarks in the given order (the reference iterates a std::map by ascending LandmarkId);
  * landmark l owns pool rows desc_begin[l] .. desc_begin[l+1]-1.  distances[k] starts at the
  * threshold (double, fresh vector at Frontend.cpp:1365) and is updated with strict '<'. */
-void orc_match_to_map(const uint8_t* desc, const orc_keypoint* kps, const uint8_t* use, int n_k,
-                      const double* proj, const int32_t* desc_begin, int n_lm, const uint8_t* pool,
-                      double reprojection_threshold, double threshold, int32_t* best_lm,
-                      int32_t* best_d) {
+static void match_to_map(const uint8_t* desc, const orc_keypoint* kps, const uint8_t* use, int n_k,
+                         const double* proj, const int32_t* desc_begin, int n_lm, const uint8_t* pool,
+                         double reprojection_threshold, double threshold, int32_t* best_lm,
+                         int32_t* best_d, int64_t* cen) {
   const double thr_sq = reprojection_threshold * reprojection_threshold;
   for (int k = 0; k < n_k; ++k) {
     best_lm[k] = -1;
@@ -364,16 +457,34 @@ void orc_match_to_map(const uint8_t* desc, const orc_keypoint* kps, const uint8_
     for (int k = 0; k < n_k; ++k) {
       if (!use[k]) continue;
       const double dx = proj[2 * l] - (double)kps[k].x, dy = proj[2 * l + 1] - (double)kps[k].y;
+      SEEN(dx * dx + dy * dy);
+      SEEN(thr_sq);
+      CEN(dx * dx + dy * dy > thr_sq ? ORC_CEN_RADIUS_FAIL : ORC_CEN_RADIUS_PASS);
       if (dx * dx + dy * dy > thr_sq) continue;
       for (int d = desc_begin[l]; d < desc_begin[l + 1]; ++d) {
         const double dist = (double)popc48(desc + 48 * (size_t)k, pool + 48 * (size_t)d);
         if (dist < (double)best_d[k]) {
+          CEN_IF(best_lm[k] >= 0 && best_lm[k] < l, ORC_CEN_MIN_REPLACED);
           best_d[k] = (int32_t)dist;
           best_lm[k] = l;
         }
       }
     }
   }
+}
+void orc_match_to_map(const uint8_t* desc, const orc_keypoint* kps, const uint8_t* use, int n_k,
+                      const double* proj, const int32_t* desc_begin, int n_lm, const uint8_t* pool,
+                      double reprojection_threshold, double threshold, int32_t* best_lm,
+                      int32_t* best_d) {
+  match_to_map(desc, kps, use, n_k, proj, desc_begin, n_lm, pool, reprojection_threshold, threshold,
+               best_lm, best_d, NULL);
+}
+void orc_match_to_map_census(const uint8_t* desc, const orc_keypoint* kps, const uint8_t* use, int n_k,
+                             const double* proj, const int32_t* desc_begin, int n_lm, const uint8_t* pool,
+                             double reprojection_threshold, double threshold, int32_t* best_lm,
+                             int32_t* best_d, int64_t* counters) {
+  match_to_map(desc, kps, use, n_k, proj, desc_begin, n_lm, pool, reprojection_threshold, threshold,
+               best_lm, best_d, counters);
 }
 
 /* ---- matchToMapByThreadUnitialised (Frontend.cpp:1616-1719) -------------------------------------
@@ -384,12 +495,12 @@ void orc_match_to_map(const uint8_t* desc, const orc_keypoint* kps, const uint8_
  * either centre -> if the landmark is the one the keypoint already carries: count and leave this
  * landmark's descriptor loop; else update distances[k], landmark, and hp (only when not parallel).
  * previous[k] = index of the landmark keypoint k already carries, or -1. */
-void orc_match_to_map_uninit(const uint8_t* desc, const double* bp, const uint8_t* use,
-                             const int32_t* previous, int n_k, const int32_t* desc_begin, int n_lm,
-                             const uint8_t* pool, const double* e0_W, const double* r0_W,
-                             const orc_pose* T_WC1, double focal, double threshold,
-                             int32_t* best_lm, int32_t* best_d, double* hps_W, uint8_t* hp_set,
-                             int32_t* ctr_out) {
+static void match_to_map_uninit(const uint8_t* desc, const double* bp, const uint8_t* use,
+                                const int32_t* previous, int n_k, const int32_t* desc_begin, int n_lm,
+                                const uint8_t* pool, const double* e0_W, const double* r0_W,
+                                const orc_pose* T_WC1, double focal, double threshold,
+                                int32_t* best_lm, int32_t* best_d, double* hps_W, uint8_t* hp_set,
+                                int32_t* ctr_out, int64_t* cen) {
   const double sigma = 1.0 / focal;
   const double cos6 = cos(6.0 * sigma);
   int ctr = 0;
@@ -410,6 +521,8 @@ void orc_match_to_map_uninit(const uint8_t* desc, const double* bp, const uint8_
         if (dist < (double)best_d[k]) {
           const double* e0 = e0_W + 3 * (size_t)d;
           const double* r0 = r0_W + 3 * (size_t)d;
+          SEEN(dot3(e0, e1_W));
+          CEN_IF(!(dot3(e0, e1_W) < cos6), ORC_CEN_NEAR_PARALLEL);
           if (dot3(e0, e1_W) < cos6) {
             double t[3], et[3], c0[3], c1[3], n0[3], n1[3], cx[3], nn[3], nnn[3];
             for (int i = 0; i < 3; ++i) t[i] = T_WC1->r[i] - r0[i];
@@ -422,17 +535,21 @@ void orc_match_to_map_uninit(const uint8_t* desc, const double* bp, const uint8_
             c1[1] = e1_W[2] * et[0] - e1_W[0] * et[2];
             c1[2] = e1_W[0] * et[1] - e1_W[1] * et[0];
             normalize3(c1, n1);
+            SEEN(dot3(n0, n1));
+            CEN_IF(dot3(n0, n1) < cos6, ORC_CEN_EPIPOLAR);
             if (dot3(n0, n1) < cos6) continue; /* not in epipolar plane */
             cx[0] = e0[1] * e1_W[2] - e0[2] * e1_W[1];
             cx[1] = e0[2] * e1_W[0] - e0[0] * e1_W[2];
             cx[2] = e0[0] * e1_W[1] - e0[1] * e1_W[0];
             for (int i = 0; i < 3; ++i) nn[i] = n0[i] + n0[i];
             normalize3(nn, nnn);
+            SEEN(dot3(cx, nnn));
+            CEN_IF(dot3(cx, nnn) > 0.0, ORC_CEN_DIVERGENT);
             if (dot3(cx, nnn) > 0.0) continue; /* divergent rays */
           }
           double hp[4];
           int is_valid = 0, is_parallel = 0;
-          orc_triangulate_fast(r0, e0, T_WC1->r, e1_W, sigma, hp, &is_valid, &is_parallel);
+          triangulate_fast(r0, e0, T_WC1->r, e1_W, sigma, hp, &is_valid, &is_parallel, cen);
           if (!is_valid) continue;
           if (!is_parallel) {
             double p[3], a[3], b[3];
@@ -441,16 +558,22 @@ void orc_match_to_map_uninit(const uint8_t* desc, const double* bp, const uint8_
               a[i] = p[i] - r0[i];
               b[i] = p[i] - T_WC1->r[i];
             }
+            SEEN(sqrt(dot3(a, a)));
+            SEEN(sqrt(dot3(b, b)));
+            CEN_IF(sqrt(dot3(a, a)) < 0.2, ORC_CEN_DIST0);
+            CEN_IF(sqrt(dot3(b, b)) < 0.2, ORC_CEN_DIST1);
             if (sqrt(dot3(a, a)) < 0.2) is_valid = 0;
             if (sqrt(dot3(b, b)) < 0.2) is_valid = 0;
           }
           if (!is_valid) continue;
           if (l == previous[k]) {
+            CEN(ORC_CEN_PREVIOUS);
             ++ctr;
             break;
           }
           best_d[k] = (int32_t)dist;
           best_lm[k] = l;
+          CEN(is_parallel ? ORC_CEN_WIN_NO_HP : ORC_CEN_WIN_HP);
           if (!is_parallel) {
             memcpy(hps_W + 4 * (size_t)k, hp, 4 * sizeof(double));
             hp_set[k] = 1;
@@ -460,6 +583,24 @@ void orc_match_to_map_uninit(const uint8_t* desc, const double* bp, const uint8_
     }
   }
   *ctr_out = ctr;
+}
+void orc_match_to_map_uninit(const uint8_t* desc, const double* bp, const uint8_t* use,
+                             const int32_t* previous, int n_k, const int32_t* desc_begin, int n_lm,
+                             const uint8_t* pool, const double* e0_W, const double* r0_W,
+                             const orc_pose* T_WC1, double focal, double threshold,
+                             int32_t* best_lm, int32_t* best_d, double* hps_W, uint8_t* hp_set,
+                             int32_t* ctr_out) {
+  match_to_map_uninit(desc, bp, use, previous, n_k, desc_begin, n_lm, pool, e0_W, r0_W, T_WC1, focal,
+                      threshold, best_lm, best_d, hps_W, hp_set, ctr_out, NULL);
+}
+void orc_match_to_map_uninit_census(const uint8_t* desc, const double* bp, const uint8_t* use,
+                                    const int32_t* previous, int n_k, const int32_t* desc_begin, int n_lm,
+                                    const uint8_t* pool, const double* e0_W, const double* r0_W,
+                                    const orc_pose* T_WC1, double focal, double threshold,
+                                    int32_t* best_lm, int32_t* best_d, double* hps_W, uint8_t* hp_set,
+                                    int32_t* ctr_out, int64_t* counters) {
+  match_to_map_uninit(desc, bp, use, previous, n_k, desc_begin, n_lm, pool, e0_W, r0_W, T_WC1, focal,
+                      threshold, best_lm, best_d, hps_W, hp_set, ctr_out, counters);
 }
 
 /* ---- verifyRecognisedPlace, all landmarks of one camera (Frontend.cpp:330-355) ------------------

@@ -295,29 +295,59 @@ def triangulate_fast(p1, e1, p2, e2, sigma):
     return np.array(hp[:]), bool(v.value), bool(par.value)
 
 
-def match_stereo(desc0, kp0, bp0, bpv0, desc1, kp1, bp1, bpv1, T0, T1, f0, f1, thr):
+def census_labels():
+    """names of the gate-census counters (oracle/okvfe_oracle.h, ORC_CEN_*), in counter order"""
+    f = lib().orc_census_label
+    f.restype, f.argtypes = C.c_char_p, [C.c_int]
+    out = []
+    while f(len(out)) is not None:
+        out.append(f(len(out)).decode())
+    return out
+
+
+def new_census() -> np.ndarray:
+    """a zeroed counters array for the census= argument of the four gated matchers: they then run
+    the orc_*_census entry point (same loop, same bytes) and add their counts to it"""
+    return np.zeros(len(census_labels()), dtype=np.int64)
+
+
+def census_dict(counters) -> dict:
+    return dict(zip(census_labels(), (int(v) for v in counters)))
+
+
+def _census_call(name, census, args):
+    if census is None:
+        getattr(lib(), name)(*args)
+    else:
+        assert census.dtype == np.int64 and census.flags.c_contiguous and len(census) == len(census_labels())
+        getattr(lib(), name + "_census")(*args, _p(census))
+
+
+def match_stereo(desc0, kp0, bp0, bpv0, desc1, kp1, bp1, bpv1, T0, T1, f0, f1, thr, census=None):
     n0, n1 = len(kp0), len(kp1)
     out = np.zeros(max(n0, 1), dtype=STEREO_MATCH_DTYPE)
     P0, P1 = make_pose(*T0), make_pose(*T1)
     arrs = [np.ascontiguousarray(a) for a in (desc0, kp0, bp0, bpv0, desc1, kp1, bp1, bpv1)]
-    lib().orc_match_stereo(_p(arrs[0]), _p(arrs[1]), _p(arrs[2]), _p(arrs[3]), n0, _p(arrs[4]),
-                           _p(arrs[5]), _p(arrs[6]), _p(arrs[7]), n1, C.byref(P0), C.byref(P1),
-                           C.c_double(f0), C.c_double(f1), C.c_double(thr), _p(out))
+    _census_call("orc_match_stereo", census,
+                 (_p(arrs[0]), _p(arrs[1]), _p(arrs[2]), _p(arrs[3]), n0, _p(arrs[4]),
+                  _p(arrs[5]), _p(arrs[6]), _p(arrs[7]), n1, C.byref(P0), C.byref(P1),
+                  C.c_double(f0), C.c_double(f1), C.c_double(thr), _p(out)))
     return out[:n0]
 
 
 def match_motion_stereo(desc0, kp0, bp0, bpv0, skip0, desc1, kp1, bp1, bpv1, matched1, T0, T1, cam,
-                        thr):
+                        thr, census=None):
     n0, n1 = len(kp0), len(kp1)
     out = np.zeros(max(n0, 1), dtype=MOTION_MATCH_DTYPE)
     P0, P1 = make_pose(*T0), make_pose(*T1)
     c = make_camera(cam)
     arrs = [None if a is None else np.ascontiguousarray(a)
             for a in (desc0, kp0, bp0, bpv0, skip0, desc1, kp1, bp1, bpv1, matched1)]
-    lib().orc_match_motion_stereo(_p(arrs[0]), _p(arrs[1]), _p(arrs[2]), _p(arrs[3]), _p(arrs[4]),
-                                  n0, _p(arrs[5]), _p(arrs[6]), _p(arrs[7]), _p(arrs[8]),
-                                  _p(arrs[9]), n1, C.byref(P0), C.byref(P1), C.byref(c),
-                                  C.c_uint32(int(thr)), _p(out))
+    _census_call("orc_match_motion_stereo", census,
+                 (_p(arrs[0]), _p(arrs[1]), _p(arrs[2]), _p(arrs[3]), _p(arrs[4]),
+                  n0, _p(arrs[5]), _p(arrs[6]), _p(arrs[7]), _p(arrs[8]),
+                  _p(arrs[9]), n1, C.byref(P0), C.byref(P1), C.byref(c),
+                  C.c_uint32(int(thr)), _p(out)))
     return out[:n0]
 
 
@@ -339,19 +369,21 @@ def hamming_argmin(A, B, thr):
     return bj[:len(A)], bd[:len(A)]
 
 
-def match_to_map(desc, kps, use, proj, desc_begin, pool, repr_thr, thr):
+def match_to_map(desc, kps, use, proj, desc_begin, pool, repr_thr, thr, census=None):
     n, nl = len(kps), len(desc_begin) - 1
     bl = np.zeros(max(n, 1), dtype=np.int32)
     bd = np.zeros(max(n, 1), dtype=np.int32)
     arrs = [np.ascontiguousarray(a) for a in (desc, kps, np.asarray(use, dtype=np.uint8),
                                              np.asarray(proj, dtype=np.float64),
                                              np.asarray(desc_begin, dtype=np.int32), pool)]
-    lib().orc_match_to_map(_p(arrs[0]), _p(arrs[1]), _p(arrs[2]), n, _p(arrs[3]), _p(arrs[4]), nl,
-                           _p(arrs[5]), C.c_double(repr_thr), C.c_double(thr), _p(bl), _p(bd))
+    _census_call("orc_match_to_map", census,
+                 (_p(arrs[0]), _p(arrs[1]), _p(arrs[2]), n, _p(arrs[3]), _p(arrs[4]), nl,
+                  _p(arrs[5]), C.c_double(repr_thr), C.c_double(thr), _p(bl), _p(bd)))
     return bl[:n], bd[:n]
 
 
-def match_to_map_uninit(desc, bp, use, previous, desc_begin, pool, e0_W, r0_W, T1, focal, thr):
+def match_to_map_uninit(desc, bp, use, previous, desc_begin, pool, e0_W, r0_W, T1, focal, thr,
+                        census=None):
     n, nl = len(desc), len(desc_begin) - 1
     bl = np.zeros(max(n, 1), dtype=np.int32)
     bd = np.zeros(max(n, 1), dtype=np.int32)
@@ -363,10 +395,11 @@ def match_to_map_uninit(desc, bp, use, previous, desc_begin, pool, e0_W, r0_W, T
             np.ascontiguousarray(desc_begin, dtype=np.int32), np.ascontiguousarray(pool, dtype=np.uint8),
             np.ascontiguousarray(e0_W, dtype=np.float64), np.ascontiguousarray(r0_W, dtype=np.float64)]
     P1 = make_pose(*T1)
-    lib().orc_match_to_map_uninit(_p(arrs[0]), _p(arrs[1]), _p(arrs[2]), _p(arrs[3]), n, _p(arrs[4]),
-                                  nl, _p(arrs[5]), _p(arrs[6]), _p(arrs[7]), C.byref(P1),
-                                  C.c_double(focal), C.c_double(thr), _p(bl), _p(bd), _p(hp), _p(hs),
-                                  C.byref(ctr))
+    _census_call("orc_match_to_map_uninit", census,
+                 (_p(arrs[0]), _p(arrs[1]), _p(arrs[2]), _p(arrs[3]), n, _p(arrs[4]),
+                  nl, _p(arrs[5]), _p(arrs[6]), _p(arrs[7]), C.byref(P1),
+                  C.c_double(focal), C.c_double(thr), _p(bl), _p(bd), _p(hp), _p(hs),
+                  C.byref(ctr)))
     return bl[:n], bd[:n], hp[:n], hs[:n], ctr.value
 
 
