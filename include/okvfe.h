@@ -692,7 +692,8 @@ okvfe_status okvfe_match_stereo_blocks_device(okvfe_ctx* ctx, const void* block0
  * point (n_points - 64) + l; the FIRST n_points - 64 points of a pattern with more than 64 are the extra samples
  * (evaluated beside the wave), so put the smallest boxes first -- the built-in pattern has the centre and one
  * hexagon point there.
- *   class 0: extra samples' half-width <= 2.0 (5 x 5 row slots), all others <= 4.75 (11 x 11): the fast kernels;
+ *   class 0: extra samples' half-width < 2.0 (5 x 5 row slots; in float32 a box of exactly 2.0 can span 6 pixels),
+ *            all others <= 4.75 (11 x 11): the fast kernels;
  *   class 1: <= 4.25 / <= 9.75 (10 x 10 / 21 x 21 row slots): the WIDE instantiations of the same kernels;
  *   class 2: wider still, or any half-width below 0.5 (bilinear point samples): the all-modes kernel with plain
  *            box loops -- correct for every pattern, several times slower. */

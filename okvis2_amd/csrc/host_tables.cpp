@@ -158,7 +158,10 @@ PatternFacts pattern_facts(const Pattern& P) {
   f.extra = P.n_points > 64 ? P.n_points - 64 : 0;
   for (int i = 0; i < P.n_points && i < kPatternPoints; ++i) {
     const float s = P.sigma_half[i];
-    if (!(s <= (i < f.extra ? 2.0f : 4.75f))) f.box_class = f.box_class < 1 ? 1 : f.box_class;
+    // (an extra of half-width EXACTLY 2.0 belongs to the wide class: at xf = k + 0.5 - 1 ulp the float sum xf + 2 ties
+    // up to k + 2.5, the box spans 6 pixels and x_right - x_left = 5 exceeds the 5 x 5 form.  The other thresholds
+    // hold with equality: 4.25 spans at most 10 pixels, 4.75 at most 11, 9.75 at most 21.)
+    if (!(i < f.extra ? s < 2.0f : s <= 4.75f)) f.box_class = f.box_class < 1 ? 1 : f.box_class;
     if (!(s <= (i < f.extra ? 4.25f : 9.75f))) f.box_class = 2;
     // half-widths below 0.5 are bilinear point samples: only the all-modes kernel carries that branch (and waits for
     // its patch before it)

@@ -41,7 +41,7 @@ namespace {
 // float operation sequence as the published BRISK smoothedIntensity (sub-pixel rim weights); the
 // interior / edge sums are taken directly over the pixels (identical to integral-image sums).
 [[maybe_unused]] constexpr int kMaxBox = 10;  // fast path: boxes of at most 11 x 11 pixels (sigma_half <= 4.75)
-constexpr int kSmallBox = 4;  // second pass of the camera-aware-only kernel: boxes of at most 5 x 5 (sigma_half <= 2.0)
+constexpr int kSmallBox = 4;  // second pass of the camera-aware-only kernel: boxes of at most 5 x 5 (sigma_half < 2.0: exactly 2.0 can span 6 pixels)
 // WIDE-box instantiations (round 5: a pattern with wider smoothing -- what the vocabulary's statistics favour,
 // tools/pattern/README.md -- must not fall off the fast path): boxes up to 21 x 21 (sigma_half <= 9.75) in the
 // first pass, up to 10 x 10 (sigma_half <= 4.25) in the second
@@ -558,7 +558,7 @@ __global__ __launch_bounds__(64 * kDescWaves) __attribute__((amdgpu_waves_per_eu
         v = smoothed_intensity<AWARE, kFirstBox, AWARE, WIDE>(ppx, xf, yf, sg, bsc, bsc2);
       else
         v = smoothed_intensity<AWARE, kFirstBox, false, WIDE>(ppx, xf, yf, sg, bsc, bsc2);
-      if (extra > 0) {  // wave-uniform; AWARE: the host checked sigma_half <= 2.0 for these points (5 x 5 boxes)
+      if (extra > 0) {  // wave-uniform; AWARE: the host checked sigma_half < 2.0 for these points (5 x 5 boxes)
         const int b1 = ladder ? scales->box_scaling[sc2][l2] : second_i[0][l2];
         const int b2 = ladder ? scales->box_scaling2[sc2][l2] : second_i[1][l2];
         asm volatile("" : "+v"(l2));  // opaque: the position is recomputed, not carried over the first pass

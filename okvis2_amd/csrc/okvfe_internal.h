@@ -86,7 +86,7 @@ float pattern_reach(const Pattern& p);
 // okvfe_set_pattern) and kept next to it, so that no call walks the pattern.
 struct PatternFacts {
   // 0: every box fits the fixed-trip slots of the fast descriptor kernels (first-pass samples 11 x 11: sigma_half <=
-  // 4.75; second-pass samples = points 0 .. n - 65 of a pattern with more than 64 points, 5 x 5: sigma_half <= 2.0);
+  // 4.75; second-pass samples = points 0 .. n - 65 of a pattern with more than 64 points, 5 x 5: sigma_half < 2.0);
   // 1: the slots of the WIDE instantiations (21 x 21: <= 9.75, 10 x 10: <= 4.25); 2: wider still, or a half-width
   // below 0.5 (k_describe.hip: kMaxBox / kSmallBox / kWideBox / kWideSmallBox)
   int32_t box_class = 0;
