@@ -316,6 +316,60 @@ void orc_prepare_landmarks(const double* hp_W, const double* quality, const int3
                            double repr_threshold, int exclusive, int32_t* status, int32_t* n_desc,
                            int32_t* obs_rows, double* projection, double* e_W, double* r_W);
 
+/* ---- census of the landmark preparation: which branches of Frontend.cpp:1219-1359 a table reaches.
+ * orc_prepare_landmarks_census runs the very loop of orc_prepare_landmarks (one shared static
+ * function) and adds one count per event into counters[ORC_PCEN_COUNT]; its outputs are the plain
+ * entry point's, byte for byte.  Per landmark unless it says per observation. */
+enum {
+  ORC_PCEN_HEAD_NEGATED = 0, /* hp_C[3] < 0: the head of hp_C is negated before it is projected */
+  ORC_PCEN_PROJ_INVALID,     /* projection status Invalid (|z| < 1e-12) */
+  ORC_PCEN_PROJ_BEHIND,      /* status Behind */
+  ORC_PCEN_PROJ_OUTSIDE_KEPT,/* status OutsideImage, and inside the reprojection margin */
+  ORC_PCEN_PROJ_SUCCESSFUL,  /* status Successful */
+  ORC_PCEN_MARGIN_U_LOW,     /* kp[0] < -thr */
+  ORC_PCEN_MARGIN_V_LOW,     /* kp[1] < -thr */
+  ORC_PCEN_MARGIN_U_HIGH,    /* kp[0] > w + thr */
+  ORC_PCEN_MARGIN_V_HIGH,    /* kp[1] > h + thr */
+  ORC_PCEN_CLAMP_R,          /* max(0.01, |r_W|) takes 0.01 (landmarks past the FoV check) */
+  ORC_PCEN_IS3D_FIRST,       /* is3d set at the first observation */
+  ORC_PCEN_IS3D_LATER,       /* is3d set at a later observation */
+  ORC_PCEN_IS3D_NEVER,       /* at least one observation, is3d never set */
+  ORC_PCEN_VP_REJECT,        /* per observation: cosVC < cos(0.6), dropped */
+  ORC_PCEN_VP_KEPT_EXCL,     /* per observation: cosVC < cos(0.6), kept because the call is exclusive */
+  ORC_PCEN_SCALE_REJECT,     /* per observation: scaleChange > 0.5, dropped */
+  ORC_PCEN_SCALE_KEPT_EXCL,  /* per observation: scaleChange > 0.5, kept because the call is exclusive */
+  ORC_PCEN_ACOS_TINY,        /* per scored observation: |x| < 2^-57 */
+  ORC_PCEN_ACOS_SMALL,       /* 2^-57 <= |x| < 0.5 */
+  ORC_PCEN_ACOS_NEG,         /* -1 <= x <= -0.5 */
+  ORC_PCEN_ACOS_POS,         /* 0.5 <= x <= 1 */
+  ORC_PCEN_ACOS_ABOVE_ONE,   /* |x| > 1: NaN */
+  ORC_PCEN_NOT_STORED,       /* per scored observation: !(score < best[worst]) */
+  ORC_PCEN_NOT_STORED_TIE,   /*   of those: score == best[worst] */
+  ORC_PCEN_NOT_STORED_GE1,   /*   of those: score >= 1 */
+  ORC_PCEN_NOT_STORED_NAN,   /*   of those: score is a NaN */
+  ORC_PCEN_WRITE_S0_O0,      /* per stored observation: slot `worst` replaced, descriptor written at row o */
+  ORC_PCEN_WRITE_S0_O1,
+  ORC_PCEN_WRITE_S0_O2,
+  ORC_PCEN_WRITE_S1_O0,
+  ORC_PCEN_WRITE_S1_O1,
+  ORC_PCEN_WRITE_S1_O2,
+  ORC_PCEN_WRITE_S2_O0,
+  ORC_PCEN_WRITE_S2_O1,
+  ORC_PCEN_WRITE_S2_O2,
+  ORC_PCEN_FINAL_O0_STORED,  /* final o == 0 with one stored view: "no observations -- weird", status 0 */
+  ORC_PCEN_FINAL_O1,         /* final o == 1 */
+  ORC_PCEN_FINAL_O2,         /* final o == 2, three views stored */
+  ORC_PCEN_FINAL_O2_CROPPED, /* final o == 2 and a third row written, then cropped */
+  ORC_PCEN_COUNT
+};
+const char* orc_prepare_census_label(int label); /* NULL outside [0, ORC_PCEN_COUNT) */
+void orc_prepare_landmarks_census(const double* hp_W, const double* quality, const int32_t* obs_begin,
+                                  int n_landmarks, const int32_t* obs_pose, const double* obs_bp,
+                                  const orc_pose* poses_old, const orc_pose* T_WC1, const orc_camera* cam,
+                                  double repr_threshold, int exclusive, int32_t* status, int32_t* n_desc,
+                                  int32_t* obs_rows, double* projection, double* e_W, double* r_W,
+                                  int64_t* counters);
+
 #ifdef __cplusplus
 }
 #endif

@@ -715,12 +715,33 @@ double orc_acos_fixed(double x) {
   return 2.0 * (df + w);
 }
 
-void orc_prepare_landmarks(const double* hp_W, const double* quality, const int32_t* obs_begin,
-                           int n_landmarks, const int32_t* obs_pose, const double* obs_bp,
-                           const orc_pose* poses_old, const orc_pose* T_WC1, const orc_camera* cam,
-                           double repr_threshold, int exclusive, int32_t* status, int32_t* n_desc,
-                           int32_t* obs_rows /* n*3 */, double* projection /* n*2 */,
-                           double* e_W /* n*2*3 */, double* r_W /* n*2*3 */) {
+static const char* const k_prepare_census_labels[ORC_PCEN_COUNT] = {
+    "head_negated", "proj_invalid", "proj_behind", "proj_outside_kept", "proj_successful",
+    "margin_u_low", "margin_v_low", "margin_u_high", "margin_v_high", "clamp_r", "is3d_first",
+    "is3d_later", "is3d_never", "vp_reject", "vp_kept_excl", "scale_reject", "scale_kept_excl",
+    "acos_tiny", "acos_small", "acos_neg", "acos_pos", "acos_above_one", "not_stored",
+    "not_stored_tie", "not_stored_ge1", "not_stored_nan", "write_s0_o0", "write_s0_o1", "write_s0_o2",
+    "write_s1_o0", "write_s1_o1", "write_s1_o2", "write_s2_o0", "write_s2_o1", "write_s2_o2",
+    "final_o0_stored", "final_o1", "final_o2", "final_o2_cropped"};
+const char* orc_prepare_census_label(int label) {
+  return label >= 0 && label < ORC_PCEN_COUNT ? k_prepare_census_labels[label] : NULL;
+}
+/* which branch of orc_acos_fixed an argument takes (census only; a NaN argument takes none) */
+static int acos_branch(double x) {
+  const double ax = x < 0.0 ? -x : x;
+  if (x != x) return -1;
+  if (ax > 1.0) return ORC_PCEN_ACOS_ABOVE_ONE;
+  if (ax < 6.938893903907228e-18) return ORC_PCEN_ACOS_TINY;
+  if (ax < 0.5) return ORC_PCEN_ACOS_SMALL;
+  return x < 0.0 ? ORC_PCEN_ACOS_NEG : ORC_PCEN_ACOS_POS;
+}
+
+static void prepare_landmarks(const double* hp_W, const double* quality, const int32_t* obs_begin,
+                              int n_landmarks, const int32_t* obs_pose, const double* obs_bp,
+                              const orc_pose* poses_old, const orc_pose* T_WC1, const orc_camera* cam,
+                              double repr_threshold, int exclusive, int32_t* status, int32_t* n_desc,
+                              int32_t* obs_rows /* n*3 */, double* projection /* n*2 */,
+                              double* e_W /* n*2*3 */, double* r_W /* n*2*3 */, int64_t* cen) {
   const double maxU = (double)cam->w + repr_threshold, maxV = (double)cam->h + repr_threshold;
   const double focal = cam->fu + cam->fv; /* sum, as at Frontend.cpp:1213-1215 */
   const double cos10 = cos(10.0 / focal), cos06 = cos(0.6);
@@ -744,11 +765,24 @@ void orc_prepare_landmarks(const double* hp_W, const double* quality, const int3
     } else {
       head[0] = hp_C[0]; head[1] = hp_C[1]; head[2] = hp_C[2];
     }
+    CEN_IF(hp_C[3] < 0, ORC_PCEN_HEAD_NEGATED);
     const int st = orc_cam_project(cam, head, kp, NULL);
+    CEN_IF(st == 4, ORC_PCEN_PROJ_INVALID);
+    CEN_IF(st == 3, ORC_PCEN_PROJ_BEHIND);
+    CEN_IF(st == 0, ORC_PCEN_PROJ_SUCCESSFUL);
     if (st == 4 || st == 3) continue; /* Invalid, Behind */
+    if (cen) { /* the reference's four tests, in its order (Frontend.cpp:1250-1257) */
+      if (kp[0] < -repr_threshold) ++cen[ORC_PCEN_MARGIN_U_LOW];
+      else if (kp[1] < -repr_threshold) ++cen[ORC_PCEN_MARGIN_V_LOW];
+      else if (kp[0] > maxU) ++cen[ORC_PCEN_MARGIN_U_HIGH];
+      else if (kp[1] > maxV) ++cen[ORC_PCEN_MARGIN_V_HIGH];
+      else if (st == 1) ++cen[ORC_PCEN_PROJ_OUTSIDE_KEPT];
+    }
     if (kp[0] < -repr_threshold || kp[1] < -repr_threshold || kp[0] > maxU || kp[1] > maxV) continue;
+    CEN_IF(0.01 > rn, ORC_PCEN_CLAMP_R);
     projection[2 * l] = kp[0];
     projection[2 * l + 1] = kp[1];
+    int n_stored = 0;
     int is3d = 0, o = 0, rows[3] = {-1, -1, -1};
     double best[3] = {1.0, 1.0, 1.0}, ew[3][3], rw[3][3];
     for (int ob = obs_begin[l]; ob < obs_begin[l + 1]; ++ob) {
@@ -761,13 +795,17 @@ void orc_prepare_landmarks(const double* hp_W, const double* quality, const int3
         normalize3(r_Wv, a);
         normalize3(rc, b);
         if (dot3(a, b) > cos10) is3d = 1;
+        CEN_IF(is3d, ob == obs_begin[l] ? ORC_PCEN_IS3D_FIRST : ORC_PCEN_IS3D_LATER);
       }
       double eo[3];
       normalize3(r_old, eo);
       const double cosVC = dot3(e_Wv, eo);
+      CEN_IF(cosVC < cos06, exclusive ? ORC_PCEN_VP_KEPT_EXCL : ORC_PCEN_VP_REJECT);
       if (cosVC < cos06 && !exclusive) continue;
       const double scaleChange = fabs(r - sqrt(dot3(r_old, r_old))) / r;
+      CEN_IF(scaleChange > 0.5, exclusive ? ORC_PCEN_SCALE_KEPT_EXCL : ORC_PCEN_SCALE_REJECT);
       if (scaleChange > 0.5 && !exclusive) continue;
+      CEN_IF(acos_branch(cosVC) >= 0, acos_branch(cosVC));
       const double score = 0.5 * ((orc_get_libm() ? acos(cosVC) : orc_acos_fixed(cosVC)) / 0.6 + scaleChange / 0.5);
       double worst = 0.0;
       int wi = 0;
@@ -776,7 +814,15 @@ void orc_prepare_landmarks(const double* hp_W, const double* quality, const int3
           worst = best[n];
           wi = n;
         }
+      if (cen && !(score < best[wi])) {
+        ++cen[ORC_PCEN_NOT_STORED];
+        if (score == best[wi]) ++cen[ORC_PCEN_NOT_STORED_TIE];
+        if (score >= 1.0) ++cen[ORC_PCEN_NOT_STORED_GE1];
+        if (score != score) ++cen[ORC_PCEN_NOT_STORED_NAN];
+      }
       if (score < best[wi]) {
+        CEN(ORC_PCEN_WRITE_S0_O0 + 3 * wi + o);
+        ++n_stored;
         rows[o] = ob;
         double en[3];
         normalize3(obs_bp + 3 * (size_t)ob, en);
@@ -786,6 +832,10 @@ void orc_prepare_landmarks(const double* hp_W, const double* quality, const int3
         best[wi] = score;
       }
     }
+    CEN_IF(!is3d && obs_begin[l + 1] > obs_begin[l], ORC_PCEN_IS3D_NEVER);
+    CEN_IF(o == 0 && n_stored > 0, ORC_PCEN_FINAL_O0_STORED);
+    CEN_IF(o == 1, ORC_PCEN_FINAL_O1);
+    CEN_IF(o == 2, n_stored > 3 ? ORC_PCEN_FINAL_O2_CROPPED : ORC_PCEN_FINAL_O2);
     if (o == 0) continue; /* "no observations -- weird" */
     status[l] = is3d ? 1 : 2;
     n_desc[l] = o;
@@ -796,6 +846,23 @@ void orc_prepare_landmarks(const double* hp_W, const double* quality, const int3
         r_W[6 * l + 3 * k + i] = rw[k][i];
       }
   }
+}
+void orc_prepare_landmarks(const double* hp_W, const double* quality, const int32_t* obs_begin,
+                           int n_landmarks, const int32_t* obs_pose, const double* obs_bp,
+                           const orc_pose* poses_old, const orc_pose* T_WC1, const orc_camera* cam,
+                           double repr_threshold, int exclusive, int32_t* status, int32_t* n_desc,
+                           int32_t* obs_rows, double* projection, double* e_W, double* r_W) {
+  prepare_landmarks(hp_W, quality, obs_begin, n_landmarks, obs_pose, obs_bp, poses_old, T_WC1, cam,
+                    repr_threshold, exclusive, status, n_desc, obs_rows, projection, e_W, r_W, NULL);
+}
+void orc_prepare_landmarks_census(const double* hp_W, const double* quality, const int32_t* obs_begin,
+                                  int n_landmarks, const int32_t* obs_pose, const double* obs_bp,
+                                  const orc_pose* poses_old, const orc_pose* T_WC1, const orc_camera* cam,
+                                  double repr_threshold, int exclusive, int32_t* status, int32_t* n_desc,
+                                  int32_t* obs_rows, double* projection, double* e_W, double* r_W,
+                                  int64_t* counters) {
+  prepare_landmarks(hp_W, quality, obs_begin, n_landmarks, obs_pose, obs_bp, poses_old, T_WC1, cam,
+                    repr_threshold, exclusive, status, n_desc, obs_rows, projection, e_W, r_W, counters);
 }
 
 

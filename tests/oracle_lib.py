@@ -93,6 +93,16 @@ def make_pose(Cm, r) -> Pose:
     return p
 
 
+def pose_array(poses):
+    """a C array of Pose from [(C, r)], filled through one numpy buffer (a table may hold thousands of poses)"""
+    n = max(len(poses), 1)
+    buf = np.zeros((n, 12), dtype=np.float64)
+    for i, (Cm, r) in enumerate(poses):
+        buf[i, :9] = np.asarray(Cm, dtype=np.float64).reshape(-1)
+        buf[i, 9:] = r
+    return (Pose * n).from_buffer_copy(buf.tobytes())
+
+
 _PATTERN = None
 
 
@@ -447,24 +457,49 @@ def acos_fixed(x) -> np.ndarray:
     return np.array([f(float(v)) for v in np.atleast_1d(np.asarray(x, dtype=np.float64))])
 
 
-def prepare_landmarks(hp_W, quality, obs_begin, obs_pose, obs_bp, poses, T_WC1, cam, repr_thr, exclusive):
-    """orc_prepare_landmarks: Frontend.cpp:1219-1359 (projection + descriptor-view pooling)."""
+def prepare_census_labels():
+    """names of the landmark-preparation census counters (oracle/okvfe_oracle.h, ORC_PCEN_*), in counter order"""
+    f = lib().orc_prepare_census_label
+    f.restype, f.argtypes = C.c_char_p, [C.c_int]
+    out = []
+    while f(len(out)) is not None:
+        out.append(f(len(out)).decode())
+    return out
+
+
+def new_prepare_census() -> np.ndarray:
+    """a zeroed counters array for prepare_landmarks(census=...)"""
+    return np.zeros(len(prepare_census_labels()), dtype=np.int64)
+
+
+def prepare_census_dict(counters) -> dict:
+    return dict(zip(prepare_census_labels(), (int(v) for v in counters)))
+
+
+def prepare_landmarks(hp_W, quality, obs_begin, obs_pose, obs_bp, poses, T_WC1, cam, repr_thr, exclusive,
+                      census=None):
+    """orc_prepare_landmarks: Frontend.cpp:1219-1359 (projection + descriptor-view pooling).  census: a
+    counters array (new_prepare_census) makes the call take orc_prepare_landmarks_census and add to it."""
     hp = np.ascontiguousarray(hp_W, dtype=np.float64).reshape(-1, 4)
     q = np.ascontiguousarray(quality, dtype=np.float64)
     ob = np.ascontiguousarray(obs_begin, dtype=np.int32)
     op = np.ascontiguousarray(obs_pose, dtype=np.int32)
     obp = np.ascontiguousarray(obs_bp, dtype=np.float64).reshape(-1, 3)
-    P = (Pose * max(len(poses), 1))(*[make_pose(*p) for p in poses])
+    P = pose_array(poses)
     T1 = make_pose(*T_WC1)
     c = make_camera(cam)
     nl = len(hp)
     out = {"status": np.zeros(max(nl, 1), np.int32), "n_desc": np.zeros(max(nl, 1), np.int32),
            "obs_rows": np.zeros((max(nl, 1), 3), np.int32), "projection": np.zeros((max(nl, 1), 2)),
            "e_W": np.zeros((max(nl, 1), 2, 3)), "r_W": np.zeros((max(nl, 1), 2, 3))}
-    lib().orc_prepare_landmarks(_p(hp), _p(q), _p(ob), nl, _p(op), _p(obp), P, C.byref(T1), C.byref(c),
-                                C.c_double(repr_thr), int(bool(exclusive)), _p(out["status"]),
-                                _p(out["n_desc"]), _p(out["obs_rows"]), _p(out["projection"]),
-                                _p(out["e_W"]), _p(out["r_W"]))
+    args = (_p(hp), _p(q), _p(ob), nl, _p(op), _p(obp), P, C.byref(T1), C.byref(c), C.c_double(repr_thr),
+            int(bool(exclusive)), _p(out["status"]), _p(out["n_desc"]), _p(out["obs_rows"]),
+            _p(out["projection"]), _p(out["e_W"]), _p(out["r_W"]))
+    if census is None:
+        lib().orc_prepare_landmarks(*args)
+    else:
+        assert census.dtype == np.int64 and census.flags.c_contiguous and len(census) == len(prepare_census_labels())
+        lib().orc_prepare_landmarks_census(*args, _p(census))
     return {k: v[:nl] for k, v in out.items()}
 
 
