@@ -759,6 +759,68 @@ okvfe_status okvfe_verify_place_blocks_device(okvfe_ctx* ctx, const void* blocks
                                               const okvfe_map_device* map, int32_t* k_min_dev,
                                               uint32_t* dist_min_dev, void* stream);
 
+/* ---- matchToMap from the raw landmark table, device-resident and batched -------------------
+ * okvfe_match_to_map_landmarks for n_frames frames against ONE landmark table that lives in device memory: the table
+ * is uploaded when the map changes (at keyframes: okvfe_device_alloc / okvfe_copy_to_device), every frame then costs
+ * one call that uploads 112 bytes per frame (pose, camera slot) through the pinned parameter ring and synchronises
+ * nothing.  Frame f = gather block f; its result is exactly what okvfe_match_to_map_landmarks returns for that frame's
+ * keypoints with T_WC1[f], camera slot cam_ids[f], the same threshold and the same `exclusive`: projection, view
+ * pooling and the three-slot buffer depend on the frame's pose, so every frame gets a pooled set of its own
+ * (okvfe_match_to_map_blocks_device shares one set among all frames and takes the projections from the caller).
+ *
+ * okvfe_landmark_table with every pointer a DEVICE pointer (obs_desc 16-byte aligned, as okvfe_device_alloc returns
+ * it).  The matcher does not check the table: call okvfe_landmark_table_check_device once per upload.  An unchecked,
+ * malformed table (obs_begin not monotone or outside [0, n_observations], a pose index outside [0, n_poses)) is
+ * undefined behaviour, exactly as a bad device pointer is. */
+typedef struct okvfe_landmark_table_device {
+  int32_t n_landmarks, n_observations, n_poses;
+  const double* hp_W;
+  const double* quality;
+  const int32_t* obs_begin;
+  const int32_t* obs_pose;
+  const uint8_t* obs_desc;
+  const double* obs_backproj;
+  const okvfe_pose* poses;
+} okvfe_landmark_table_device;
+
+/* okvfe_landmark_pool per frame: device arrays, frame-major n_frames x L rows (obs_rows x 3, projection x 2, e_W / r_W
+ * x 6), holding the bytes of the B = 1 call's okvfe_landmark_pool: landmarks that are not kept are zero and their
+ * obs_rows -1.  The struct pointer and every member may be NULL.  status, e_W and r_W stay on the device: they are the
+ * input of a later, batched pass over the not-yet-3-D landmarks. */
+typedef struct okvfe_landmark_pool_device {
+  int32_t* status;
+  int32_t* n_desc;
+  int32_t* obs_rows;
+  double* projection;
+  double* e_W;
+  double* r_W;
+} okvfe_landmark_pool_device;
+
+/* The structural checks okvfe_match_to_map_landmarks runs on its host arrays, by one kernel on the device table.  The
+ * ONLY call of this group that synchronises the host; meant to run once per upload.  OKVFE_ERR_INVALID_ARGUMENT and an
+ * okvfe_last_error that names the first offending row ("obs_begin not monotone at L", "observation O: pose index out of
+ * range") if the table is malformed. */
+okvfe_status okvfe_landmark_table_check_device(okvfe_ctx* ctx, const okvfe_landmark_table_device* table, void* stream);
+
+/* cam_ids, T_WC1: HOST arrays of n_frames camera slots (with intrinsics: okvfe_set_camera; else OKVFE_ERR_NOT_READY)
+ * and poses.  use_dev: device n_frames x K flags or NULL (every keypoint).  Outputs (device, n_frames x K):
+ * best_landmark = row of the TABLE (-1 = none), best_dist (match_threshold if none); rows at or past a block's keypoint
+ * count are untouched; with n_landmarks == 0 the rows below it still receive -1 / match_threshold.  Ties: the first
+ * landmark in ascending table order, pooled row 0 before row 1 (the cropped third row never matches).  Both orders of
+ * okvfe_set_fp64_reduction apply.
+ * Nothing synchronises the host.  The workspace (32 bytes per (frame, landmark) pair plus the keypoint order) is kept
+ * per stream, so calls on different streams of one context may be in flight together; growing it or the parameter
+ * ring -- the first call on a stream, or a larger batch -- frees the old buffer, which waits for the device once.  A call that would need more
+ * than 1 GiB of workspace runs its frames in slices, one after another on the same stream.
+ * A NULL or negative argument: OKVFE_ERR_INVALID_ARGUMENT before anything is launched.
+ * Not covered: the second pass of Frontend::matchToMap over the landmarks that are not 3-D yet with per-frame pools
+ * (pool_out leaves its inputs on the device), RANSAC and outlier removal (Frontend.cpp:1411-1430). */
+okvfe_status okvfe_match_to_map_table_blocks_device(
+    okvfe_ctx* ctx, const okvfe_landmark_table_device* table, const void* blocks_dev, int32_t n_frames,
+    const int32_t* cam_ids /* HOST, n_frames */, const okvfe_pose* T_WC1 /* HOST, n_frames */,
+    double reprojection_threshold, int32_t exclusive, const uint8_t* use_dev /* n_frames x K or NULL */,
+    const okvfe_landmark_pool_device* pool_out, int32_t* best_landmark_dev, int32_t* best_dist_dev, void* stream);
+
 /* ---- keyframe decision: keypoint coverage masks and their IoU ---------------- */
 /* Frontend::doWeNeedANewKeyframe (Frontend.cpp:1058-1167), the step between the map matchers and matchStereo whose
  * answer is *asKeyframe.  Per camera image of size w x h (the context's) the reference keeps two zeroed u8 masks of

@@ -114,6 +114,7 @@ EXPORTS = [
     "okvfe_set_camera_ext", "okvfe_build_awareness_maps_ext", "okvfe_camera_overlap_ext",
     "okvfe_match_motion_stereo_ext",
     "okvfe_keyframe_coverage_blocks_device", "okvfe_keyframe_coverage", "okvfe_keyframe_decision",
+    "okvfe_landmark_table_check_device", "okvfe_match_to_map_table_blocks_device",
 ]
 
 STAGES = ["harris", "nms", "sort", "select", "map", "describe", "compact", "match"]
@@ -131,6 +132,16 @@ class LandmarkTable(C.Structure):
 class LandmarkPool(C.Structure):
     _fields_ = [("status", C.c_void_p), ("n_desc", C.c_void_p), ("obs_rows", C.c_void_p),
                 ("projection", C.c_void_p), ("e_W", C.c_void_p), ("r_W", C.c_void_p)]
+
+
+class LandmarkTableDevice(C.Structure):
+    """okvfe_landmark_table_device: the landmark table in device memory (every pointer a device pointer)."""
+    _fields_ = LandmarkTable._fields_
+
+
+class LandmarkPoolDevice(C.Structure):
+    """okvfe_landmark_pool_device: per-frame pooling results, device arrays n_frames x L (any member may be None)."""
+    _fields_ = LandmarkPool._fields_
 
 
 class OkvfeError(RuntimeError):
@@ -793,6 +804,46 @@ class Frontend:
             self._h, _p(blocks_ptr), int(n_frames), _p(use_ptr), _p(previous_ptr), C.byref(map_dev), P,
             C.c_double(focal), _p(best_lm_ptr), _p(best_d_ptr), _p(hps_ptr), _p(hp_set_ptr), _p(ctr_ptr),
             _s(stream)))
+
+    # -- matchToMap from a device-resident landmark table, a batch of frames ---------------
+    @staticmethod
+    def make_landmark_table_device(n_landmarks, n_observations, n_poses, hp_ptr, quality_ptr, obs_begin_ptr,
+                                   obs_pose_ptr, obs_desc_ptr, obs_backproj_ptr, poses_ptr) -> LandmarkTableDevice:
+        """Device pointers (ints; 0 / None = NULL) of a table uploaded once per map change."""
+        return LandmarkTableDevice(int(n_landmarks), int(n_observations), int(n_poses),
+                                   *[int(p) if p else None for p in (hp_ptr, quality_ptr, obs_begin_ptr, obs_pose_ptr,
+                                                                     obs_desc_ptr, obs_backproj_ptr, poses_ptr)])
+
+    @staticmethod
+    def make_landmark_pool_device(status_ptr=None, n_desc_ptr=None, obs_rows_ptr=None, projection_ptr=None,
+                                  e_W_ptr=None, r_W_ptr=None) -> LandmarkPoolDevice:
+        return LandmarkPoolDevice(*[int(p) if p else None for p in (status_ptr, n_desc_ptr, obs_rows_ptr,
+                                                                    projection_ptr, e_W_ptr, r_W_ptr)])
+
+    def landmark_table_check_device(self, table: LandmarkTableDevice, stream=None):
+        """The structural checks of the table on the device; synchronises.  Raises OkvfeError naming the first bad row."""
+        self._check(lib().okvfe_landmark_table_check_device(self._h, C.byref(table), _s(stream)))
+
+    def match_to_map_table_blocks_device(self, table: LandmarkTableDevice, blocks_ptr, n_frames, cam_ids, poses_T_WC1,
+                                         repr_thr, exclusive, use_ptr, pool_out, best_lm_ptr, best_d_ptr,
+                                         stream=None):
+        """okvfe_match_to_map_landmarks for n_frames gather blocks against one device-resident table.  cam_ids /
+        poses_T_WC1: host sequences of n_frames camera slots / (C, r); pool_out: LandmarkPoolDevice or None."""
+        n = int(n_frames)
+        cams = np.ascontiguousarray(cam_ids, dtype=np.int32)
+        if len(cams) != n or len(poses_T_WC1) != n:
+            raise ValueError("cam_ids and poses_T_WC1: one per frame")
+        P = (Pose * max(n, 1))(*[make_pose(*T) for T in poses_T_WC1])
+        self._check(lib().okvfe_match_to_map_table_blocks_device(
+            self._h, C.byref(table), _p(blocks_ptr), n, _p(cams) if n else _p(np.zeros(1, np.int32)), P,
+            C.c_double(repr_thr), int(bool(exclusive)), _p(use_ptr), C.byref(pool_out) if pool_out is not None else None,
+            _p(best_lm_ptr), _p(best_d_ptr), _s(stream)))
+
+    def _test_set_map_table_workspace_limit(self, nbytes):
+        """test hook (not part of include/okvfe.h): the workspace size above which the call above slices its frames"""
+        f = lib().okvfe_test_set_map_table_workspace_limit
+        f.argtypes = [C.c_void_p, C.c_uint64]
+        self._check(f(self._h, int(nbytes)))
 
     def verify_place_blocks_device(self, blocks_ptr, n_frames, map_dev, k_min_ptr, dist_min_ptr, stream=None):
         self._check(lib().okvfe_verify_place_blocks_device(

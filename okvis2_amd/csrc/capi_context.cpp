@@ -628,6 +628,8 @@ void okvfe_destroy(okvfe_ctx* ctx) {
   if (ctx->d_virtual) (void)hipFree(ctx->d_virtual);
   for (auto& m : ctx->map_perm)
     if (m.d) (void)hipFree(m.d);
+  for (auto& m : ctx->map_table_ws)
+    if (m.d) (void)hipFree(m.d);
   for (void* p : ctx->allocs) (void)hipFree(p);
   for (float* p : ctx->cam_rays)
     if (p) (void)hipFree(p);

@@ -515,6 +515,156 @@ okvfe_status okvfe_match_to_map_uninitialised_blocks_device(okvfe_ctx* ctx, cons
   return rel;
 }
 
+// ---- matchToMap from a device-resident landmark table, a batch of frames -----------------------
+namespace {
+// the per-stream workspace of the two entry points below, at least `bytes` large (growing frees the old buffer, which
+// synchronises the device once; at most eight streams keep one, as for MapPerm above)
+okvfe_status map_table_workspace(okvfe_ctx* ctx, hipStream_t s, size_t bytes, uint8_t** out) {
+  okvfe_ctx::MapTableWs* ws = nullptr;
+  for (auto& m : ctx->map_table_ws)
+    if (m.stream == s) ws = &m;
+  if (!ws) {
+    constexpr size_t kMaxStreams = 8;
+    if (ctx->map_table_ws.size() >= kMaxStreams) {
+      okvfe_ctx::MapTableWs old = ctx->map_table_ws.front();
+      ctx->map_table_ws.erase(ctx->map_table_ws.begin());
+      HIP_TRY(ctx, hipDeviceSynchronize());  // a launch may still read it
+      if (old.d) HIP_TRY(ctx, hipFree(old.d));
+    }
+    ctx->map_table_ws.push_back(okvfe_ctx::MapTableWs{s, nullptr, 0});
+    ws = &ctx->map_table_ws.back();
+  }
+  bytes = std::max<size_t>(bytes, 256);
+  if (bytes > ws->bytes) {
+    if (ws->d) HIP_TRY(ctx, hipFree(ws->d));
+    ws->d = nullptr;
+    ws->bytes = 0;
+    void* q = nullptr;
+    HIP_TRY(ctx, hipMalloc(&q, bytes));
+    ws->d = static_cast<uint8_t*>(q);
+    ws->bytes = bytes;
+  }
+  *out = ws->d;
+  return OKVFE_OK;
+}
+
+bool table_pointers_ok(const okvfe_landmark_table_device* T) {
+  return T && T->n_landmarks >= 0 && T->n_observations >= 0 && T->n_poses >= 0 && T->obs_begin &&
+         !(T->n_landmarks > 0 && (!T->hp_W || !T->quality)) &&
+         !(T->n_observations > 0 && (!T->obs_pose || !T->obs_desc || !T->obs_backproj || !T->poses));
+}
+}  // namespace
+
+okvfe_status okvfe_landmark_table_check_device(okvfe_ctx* ctx, const okvfe_landmark_table_device* T, void* stream) {
+  if (!ctx) return OKVFE_ERR_INVALID_ARGUMENT;
+  if (!table_pointers_ok(T)) return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_landmark_table_check_device: bad argument");
+  HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
+  hipStream_t s = pick_stream(ctx, stream);
+  uint8_t* ws = nullptr;
+  okvfe_status st = map_table_workspace(ctx, s, 256, &ws);
+  if (st != OKVFE_OK) return st;
+  uint32_t* bad = reinterpret_cast<uint32_t*>(ws);
+  uint32_t h_bad[2] = {0, 0};
+  HIP_TRY(ctx, hipMemsetAsync(bad, 0xff, sizeof(h_bad), s));
+  launch_check_landmark_table(T->obs_begin, T->n_landmarks, T->obs_pose, T->n_observations, T->n_poses, bad, s);
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipMemcpyAsync(h_bad, bad, sizeof(h_bad), hipMemcpyDeviceToHost, s));
+  HIP_TRY(ctx, hipStreamSynchronize(s));
+  ctx->last_stream = s;
+  if (h_bad[0] != 0xffffffffu)
+    return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_landmark_table_check_device: obs_begin not monotone at %d", (int)h_bad[0]);
+  if (h_bad[1] != 0xffffffffu)
+    return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_landmark_table_check_device: observation %d: pose index out of range", (int)h_bad[1]);
+  return OKVFE_OK;
+}
+
+okvfe_status okvfe_match_to_map_table_blocks_device(okvfe_ctx* ctx, const okvfe_landmark_table_device* T,
+                                                    const void* blocks_dev, int32_t n_frames, const int32_t* cam_ids,
+                                                    const okvfe_pose* T_WC1, double reprojection_threshold,
+                                                    int32_t exclusive, const uint8_t* use_dev,
+                                                    const okvfe_landmark_pool_device* pool_out,
+                                                    int32_t* best_landmark_dev, int32_t* best_dist_dev, void* stream) {
+  if (!ctx) return OKVFE_ERR_INVALID_ARGUMENT;
+  if (!table_pointers_ok(T) || !blocks_dev || n_frames < 0 || !cam_ids || !T_WC1 || !(reprojection_threshold >= 0.0) ||
+      !best_landmark_dev || !best_dist_dev)
+    return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_match_to_map_table_blocks_device: bad argument");
+  bool rt8 = false;  // the 8-coefficient form of the projection only when a slot this call uses holds that model
+  for (int f = 0; f < n_frames; ++f) {
+    const int cam = cam_ids[f];
+    if (cam < 0 || cam >= (int)ctx->h_cams.size() || !(ctx->h_cams[cam].fu > 0.0))
+      return fail(ctx, OKVFE_ERR_NOT_READY,
+                  "okvfe_match_to_map_table_blocks_device: frame %d: camera slot %d has no intrinsics (okvfe_set_camera)", f, cam);
+    rt8 = rt8 || ctx->h_cams[cam].distortion == OKVFE_DIST_RADTAN8;
+  }
+  if (n_frames == 0) return OKVFE_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
+  hipStream_t s = pick_stream(ctx, stream);
+  const BlockLayout L = block_layout(ctx->kp_cap);
+  const int offs[6] = {(int)L.o_count, (int)L.o_kps, (int)L.o_desc, (int)L.o_bp, (int)L.o_bpv, (int)L.total};
+  const size_t nl = (size_t)T->n_landmarks, K = (size_t)ctx->kp_cap;
+  // workspace per frame: the packed records, the keypoint order and the count of 3-D landmarks; a call that would need
+  // more than the limit runs its frames in slices, one after another on the same stream
+  const size_t per_frame = nl * sizeof(MapPacked) + K * sizeof(int32_t) + sizeof(int32_t);
+  const int slice = map_table_slice_frames(per_frame, ctx->map_table_ws_limit, n_frames);
+  const size_t o_perm = align_up((size_t)slice * nl * sizeof(MapPacked), 256),
+               o_cnt = align_up(o_perm + (size_t)slice * K * sizeof(int32_t), 256),
+               total = o_cnt + (size_t)slice * sizeof(int32_t);
+  uint8_t* ws = nullptr;
+  okvfe_status st = map_table_workspace(ctx, s, total, &ws);
+  if (st != OKVFE_OK) return st;
+  // poses and camera slots: one record per frame through the pinned parameter ring (one asynchronous copy, no host sync)
+  std::vector<MapFrameParams> fp((size_t)n_frames);
+  for (int f = 0; f < n_frames; ++f) {
+    const DeviceCamera& dc = ctx->h_cams[cam_ids[f]];
+    fp[(size_t)f] = MapFrameParams{};
+    fp[(size_t)f].T1 = T_WC1[f];
+    fp[(size_t)f].cos10 = std::cos(10.0 / (dc.fu + dc.fv));  // the SUM, as at Frontend.cpp:1213-1215
+    fp[(size_t)f].cam = cam_ids[f];
+  }
+  void* d_fp = nullptr;
+  int slot = -1;
+  st = ring_upload(ctx, &ctx->pair_ring, fp.data(), fp.size() * sizeof(MapFrameParams), s, &d_fp, &slot);
+  if (st != OKVFE_OK) return st;
+  hipError_t e = hipSuccess;
+  {
+    StageTimer t(ctx, OKVFE_STAGE_MAP, s);
+    MapPacked* packed = reinterpret_cast<MapPacked*>(ws);
+    int32_t* perm = reinterpret_cast<int32_t*>(ws + o_perm);
+    int32_t* counts = reinterpret_cast<int32_t*>(ws + o_cnt);
+    for (int f0 = 0; f0 < n_frames && e == hipSuccess; f0 += slice) {
+      const int nf = std::min(slice, n_frames - f0);
+      const size_t row = (size_t)f0 * nl;  // first row of the slice in the caller's frame-major pool arrays
+      auto at = [&](auto* p, size_t per_row) { return p ? p + row * per_row : p; };
+      launch_prepare_landmarks_frames(
+          T->hp_W, T->quality, T->obs_begin, T->n_landmarks, T->obs_pose, T->obs_backproj, T->poses,
+          static_cast<const MapFrameParams*>(d_fp) + f0, nf, ctx->d_cams, ctx->w, ctx->h, reprojection_threshold,
+          exclusive ? 1 : 0, std::cos(0.6), at(pool_out ? pool_out->status : nullptr, 1),
+          at(pool_out ? pool_out->n_desc : nullptr, 1), at(pool_out ? pool_out->obs_rows : nullptr, 3),
+          at(pool_out ? pool_out->projection : nullptr, 2), at(pool_out ? pool_out->e_W : nullptr, 6),
+          at(pool_out ? pool_out->r_W : nullptr, 6), packed, counts, s, rt8);
+      launch_match_to_map_table_blocks(offs, static_cast<const uint8_t*>(blocks_dev) + (size_t)f0 * L.total, nf,
+                                       ctx->kp_cap, use_dev ? use_dev + (size_t)f0 * K : nullptr, packed, counts,
+                                       T->n_landmarks, T->obs_desc, reprojection_threshold * reprojection_threshold,
+                                       ctx->cfg.match_threshold, best_landmark_dev + (size_t)f0 * K,
+                                       best_dist_dev + (size_t)f0 * K, perm, s);
+      e = hipGetLastError();
+    }
+  }
+  const okvfe_status rel = ring_release(ctx, &ctx->pair_ring, slot, s);  // on every path: the slot has a reader or not
+  HIP_TRY(ctx, e);
+  ctx->last_stream = s;
+  return rel;
+}
+
+// Test hook, deliberately not in include/okvfe.h: lowers the workspace limit above which
+// okvfe_match_to_map_table_blocks_device cuts a call into slices of frames, so that a test reaches that path with a small
+// batch (0 restores the default of 1 GiB).
+okvfe_status okvfe_test_set_map_table_workspace_limit(okvfe_ctx* ctx, uint64_t bytes) {
+  if (!ctx) return OKVFE_ERR_INVALID_ARGUMENT;
+  ctx->map_table_ws_limit = bytes ? (size_t)bytes : (size_t)1 << 30;
+  return OKVFE_OK;
+}
+
 okvfe_status okvfe_verify_place_blocks_device(okvfe_ctx* ctx, const void* blocks_dev, int32_t n_frames,
                                               const okvfe_map_device* map, int32_t* k_min_dev,
                                               uint32_t* dist_min_dev, void* stream) {

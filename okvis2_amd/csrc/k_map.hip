@@ -5,7 +5,12 @@
 //                              "keep the best" buffer with the reference's exact write / crop rules
 //                              (oracle: orc_prepare_landmarks documents the quirks);
 //   compact_landmarks_kernel   the 3-D landmarks as the packed set the matcher kernel reads
-//                              (projections, <= 2 pooled descriptors each), in landmark order.
+//                              (projections, <= 2 pooled descriptors each), in landmark order;
+//   prepare_landmarks_frames_kernel / pack_landmarks_frames_kernel   the same two steps for a batch of
+//                              frames against one device-resident table: blockIdx.y resp. the work-group
+//                              is the frame, the packed record names observation rows instead of copying
+//                              descriptors, and the count of 3-D landmarks stays on the device;
+//   check_landmark_table_kernel   the structural checks of a device-resident table.
 // FP64, 3-term sums in the order of okvfe_set_fp64_reduction, no FMA; acos / cos through atan_fixed.h resp. host-computed constants.
 #include "camera_dev.h"
 #include "okvfe_internal.h"
@@ -34,24 +39,26 @@ __device__ __forceinline__ void normalize3m(const double v[3], double out[3]) {
   out[2] = v[2] / n;
 }
 
+// what the pooling leaves of one landmark: the row of okvfe_landmark_pool (zero / -1 when the landmark is not kept)
+struct Prepared {
+  int32_t status, n_desc, rows[3];
+  double proj[2], ew[2][3], rw[2][3];
+};
+
+// One landmark of Frontend.cpp:1219-1359.  The ONE copy of the reference's FP64 expression order: both
+// prepare_landmarks_kernel (B = 1) and prepare_landmarks_frames_kernel (a batch of frames) compile it.
 template <bool kRT8>  // camera_dev.h: the form that also knows OKVFE_DIST_RADTAN8
-__global__ __launch_bounds__(128) void prepare_landmarks_kernel(
-    const double* __restrict__ hp_W, const double* __restrict__ quality,
-    const int32_t* __restrict__ obs_begin, int n_landmarks, const int32_t* __restrict__ obs_pose,
-    const double* __restrict__ obs_bp, const okvfe_pose* __restrict__ poses, okvfe_pose T1,
-    const DeviceCamera* __restrict__ camera, int w, int h, double repr, int exclusive, double cos10,
-    double cos06, int32_t* __restrict__ status, int32_t* __restrict__ n_desc,
-    int32_t* __restrict__ obs_rows, double* __restrict__ projection, double* __restrict__ e_W,
-    double* __restrict__ r_W) {
-  const int l = blockIdx.x * 128 + threadIdx.x;
-  if (l >= n_landmarks) return;
-  const DeviceCamera cam = *camera;
-  status[l] = 0;
-  n_desc[l] = 0;
-  obs_rows[3 * l] = obs_rows[3 * l + 1] = obs_rows[3 * l + 2] = -1;
-  projection[2 * l] = projection[2 * l + 1] = 0.0;
-  for (int i = 0; i < 6; ++i) e_W[6 * l + i] = r_W[6 * l + i] = 0.0;
-  const double hp[4] = {hp_W[4 * l], hp_W[4 * l + 1], hp_W[4 * l + 2], hp_W[4 * l + 3]};
+__device__ __forceinline__ void prepare_landmark(
+    int l, const double* __restrict__ hp_W, const double* __restrict__ quality,
+    const int32_t* __restrict__ obs_begin, const int32_t* __restrict__ obs_pose,
+    const double* __restrict__ obs_bp, const okvfe_pose* __restrict__ poses, const okvfe_pose& T1,
+    const DeviceCamera& cam, int w, int h, double repr, int exclusive, double cos10, double cos06, Prepared& P) {
+  P.status = P.n_desc = 0;
+  P.rows[0] = P.rows[1] = P.rows[2] = -1;
+  P.proj[0] = P.proj[1] = 0.0;
+  for (int k = 0; k < 2; ++k)
+    for (int i = 0; i < 3; ++i) P.ew[k][i] = P.rw[k][i] = 0.0;
+  const double hp[4] = {hp_W[4 * (size_t)l], hp_W[4 * (size_t)l + 1], hp_W[4 * (size_t)l + 2], hp_W[4 * (size_t)l + 3]};
   const double p_W[3] = {hp[0] / hp[3], hp[1] / hp[3], hp[2] / hp[3]};
   const double r_Wv[3] = {p_W[0] - T1.r[0], p_W[1] - T1.r[1], p_W[2] - T1.r[2]};
   double e_Wv[3];
@@ -76,8 +83,8 @@ __global__ __launch_bounds__(128) void prepare_landmarks_kernel(
   if (st == 4 || st == 3) return;  // Invalid, Behind
   const double maxU = (double)w + repr, maxV = (double)h + repr;
   if (kp[0] < -repr || kp[1] < -repr || kp[0] > maxU || kp[1] > maxV) return;
-  projection[2 * l] = kp[0];
-  projection[2 * l + 1] = kp[1];
+  P.proj[0] = kp[0];
+  P.proj[1] = kp[1];
   const double focal = cam.fu + cam.fv;
   bool is3d = false;
   int o = 0, rows[3] = {-1, -1, -1};
@@ -127,14 +134,141 @@ __global__ __launch_bounds__(128) void prepare_landmarks_kernel(
     }
   }
   if (o == 0) return;
-  status[l] = is3d ? 1 : 2;
-  n_desc[l] = o;
-  for (int k = 0; k < 3; ++k) obs_rows[3 * l + k] = rows[k];
-  for (int k = 0; k < o && k < 2; ++k)
+  P.status = is3d ? 1 : 2;
+  P.n_desc = o;
+  for (int k = 0; k < 3; ++k) P.rows[k] = rows[k];
+  for (int k = 0; k < 2; ++k)
+    if (k < o)
+      for (int i = 0; i < 3; ++i) {
+        P.ew[k][i] = ew[k][i];
+        P.rw[k][i] = rw[k][i];
+      }
+}
+
+__device__ __forceinline__ void store_prepared(const Prepared& P, size_t l, int32_t* __restrict__ status,
+                                               int32_t* __restrict__ n_desc, int32_t* __restrict__ obs_rows,
+                                               double* __restrict__ projection, double* __restrict__ e_W,
+                                               double* __restrict__ r_W) {
+  if (status) status[l] = P.status;
+  if (n_desc) n_desc[l] = P.n_desc;
+  if (obs_rows)
+    for (int k = 0; k < 3; ++k) obs_rows[3 * l + k] = P.rows[k];
+  if (projection) {
+    projection[2 * l] = P.proj[0];
+    projection[2 * l + 1] = P.proj[1];
+  }
+  for (int k = 0; k < 2; ++k)
     for (int i = 0; i < 3; ++i) {
-      e_W[6 * l + 3 * k + i] = ew[k][i];
-      r_W[6 * l + 3 * k + i] = rw[k][i];
+      if (e_W) e_W[6 * l + 3 * k + i] = P.ew[k][i];
+      if (r_W) r_W[6 * l + 3 * k + i] = P.rw[k][i];
     }
+}
+
+template <bool kRT8>
+__global__ __launch_bounds__(128) void prepare_landmarks_kernel(
+    const double* __restrict__ hp_W, const double* __restrict__ quality,
+    const int32_t* __restrict__ obs_begin, int n_landmarks, const int32_t* __restrict__ obs_pose,
+    const double* __restrict__ obs_bp, const okvfe_pose* __restrict__ poses, okvfe_pose T1,
+    const DeviceCamera* __restrict__ camera, int w, int h, double repr, int exclusive, double cos10,
+    double cos06, int32_t* __restrict__ status, int32_t* __restrict__ n_desc,
+    int32_t* __restrict__ obs_rows, double* __restrict__ projection, double* __restrict__ e_W,
+    double* __restrict__ r_W) {
+  const int l = blockIdx.x * 128 + threadIdx.x;
+  if (l >= n_landmarks) return;
+  const DeviceCamera cam = *camera;
+  Prepared P;
+  prepare_landmark<kRT8>(l, hp_W, quality, obs_begin, obs_pose, obs_bp, poses, T1, cam, w, h, repr, exclusive, cos10,
+                         cos06, P);
+  store_prepared(P, (size_t)l, status, n_desc, obs_rows, projection, e_W, r_W);
+}
+
+// The same for a batch of frames against one device-resident table (okvfe_match_to_map_table_blocks_device):
+// blockIdx.y = frame, whose pose, camera slot and cos(10 / focal) come from the parameter block.  The pooling rows go to
+// the caller's frame-major arrays (each may be null); what the matcher needs -- projection, table index (-1 = not 3-D)
+// and the observation rows of the <= 2 pooled descriptors -- goes to the frame's MapPacked records, unpacked.
+template <bool kRT8>
+__global__ __launch_bounds__(128) void prepare_landmarks_frames_kernel(
+    const double* __restrict__ hp_W, const double* __restrict__ quality,
+    const int32_t* __restrict__ obs_begin, int n_landmarks, const int32_t* __restrict__ obs_pose,
+    const double* __restrict__ obs_bp, const okvfe_pose* __restrict__ poses,
+    const MapFrameParams* __restrict__ frames, const DeviceCamera* __restrict__ cameras, int w, int h, double repr,
+    int exclusive, double cos06, int32_t* __restrict__ status, int32_t* __restrict__ n_desc,
+    int32_t* __restrict__ obs_rows, double* __restrict__ projection, double* __restrict__ e_W,
+    double* __restrict__ r_W, MapPacked* __restrict__ packed) {
+  const int l = blockIdx.x * 128 + threadIdx.x;
+  if (l >= n_landmarks) return;
+  const MapFrameParams& fp = frames[blockIdx.y];
+  const DeviceCamera cam = cameras[fp.cam];
+  Prepared P;
+  prepare_landmark<kRT8>(l, hp_W, quality, obs_begin, obs_pose, obs_bp, poses, fp.T1, cam, w, h, repr, exclusive,
+                         fp.cos10, cos06, P);
+  const size_t i = (size_t)blockIdx.y * (size_t)n_landmarks + (size_t)l;
+  store_prepared(P, i, status, n_desc, obs_rows, projection, e_W, r_W);
+  MapPacked rec;
+  rec.px = P.proj[0];
+  rec.py = P.proj[1];
+  rec.index = P.status == 1 ? l : -1;
+  rec.row0 = P.rows[0];
+  rec.row1 = P.n_desc > 1 ? P.rows[1] : -1;
+  rec.pad = 0;
+  packed[i] = rec;
+}
+
+// The 3-D landmarks of every frame moved to the front of the frame's records, in landmark order and IN PLACE: one
+// work-group per frame, the chunked scan of compact_landmarks_kernel below.  A chunk is read into registers before any
+// of it is written, and its records land at or below their own place, so no unread record is overwritten.  The count
+// stays in device memory (counts[frame]): the matcher reads it there.
+__global__ __launch_bounds__(1024) void pack_landmarks_frames_kernel(MapPacked* __restrict__ packed, int n_landmarks,
+                                                                      int32_t* __restrict__ counts) {
+  __shared__ int s_lm[1024];
+  __shared__ int base_lm;
+  MapPacked* P = packed + (size_t)blockIdx.x * (size_t)n_landmarks;
+  const int tid = threadIdx.x;
+  if (tid == 0) base_lm = 0;
+  __syncthreads();
+  for (int c0 = 0; c0 < n_landmarks; c0 += 1024) {
+    const int l = c0 + tid;
+    uint4 lo = make_uint4(0, 0, 0, 0), hi = make_uint4(0xffffffffu, 0, 0, 0);  // the record as two 16-byte halves
+    if (l < n_landmarks) {
+      lo = reinterpret_cast<const uint4*>(P + l)[0];
+      hi = reinterpret_cast<const uint4*>(P + l)[1];
+    }
+    const bool take = (int32_t)hi.x >= 0;  // MapPacked::index
+    s_lm[tid] = take ? 1 : 0;
+    __syncthreads();
+    for (int d = 1; d < 1024; d <<= 1) {  // inclusive scan
+      const int a = tid >= d ? s_lm[tid - d] : 0;
+      __syncthreads();
+      s_lm[tid] += a;
+      __syncthreads();
+    }
+    if (take) {
+      uint4* dst = reinterpret_cast<uint4*>(P + (base_lm + s_lm[tid] - 1));
+      dst[0] = lo;
+      dst[1] = hi;
+    }
+    __syncthreads();
+    if (tid == 1023) base_lm += s_lm[1023];
+    __syncthreads();
+  }
+  if (tid == 0) counts[blockIdx.x] = base_lm;
+}
+
+// okvfe_landmark_table_check_device: what the host form checks on its host arrays.  bad[0] / bad[1] = first offending
+// landmark row of obs_begin / first observation with a pose index out of range (0xffffffff = none).
+__global__ __launch_bounds__(256) void check_landmark_table_kernel(const int32_t* __restrict__ obs_begin, int n_landmarks,
+                                                                    const int32_t* __restrict__ obs_pose,
+                                                                    int n_observations, int n_poses,
+                                                                    uint32_t* __restrict__ bad) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n_landmarks) {
+    const int b = obs_begin[i], e = obs_begin[i + 1];
+    if (e < b || b < 0 || e > n_observations) atomicMin(&bad[0], (uint32_t)i);
+  }
+  if (i < n_observations) {
+    const int p = obs_pose[i];
+    if (p < 0 || p >= n_poses) atomicMin(&bad[1], (uint32_t)i);
+  }
 }
 
 // the landmarks with status == want as a packed set, in landmark order (single workgroup: the
@@ -209,6 +343,29 @@ void launch_compact_landmarks(const int32_t* status, const int32_t* n_desc, cons
                               int32_t* n_out, hipStream_t stream) {
   hipLaunchKernelGGL(compact_landmarks_kernel, dim3(1), dim3(1024), 0, stream, status, n_desc, obs_rows,
                      projection, obs_desc, n_landmarks, want, index_out, proj_out, begin_out, pool_out, n_out);
+}
+
+void launch_prepare_landmarks_frames(const double* hp_W, const double* quality, const int32_t* obs_begin,
+                                     int n_landmarks, const int32_t* obs_pose, const double* obs_bp,
+                                     const okvfe_pose* poses, const MapFrameParams* frames, int n_frames,
+                                     const DeviceCamera* cameras, int w, int h, double repr, int exclusive,
+                                     double cos06, int32_t* status, int32_t* n_desc, int32_t* obs_rows,
+                                     double* projection, double* e_W, double* r_W, MapPacked* packed,
+                                     int32_t* counts, hipStream_t stream, bool rt8) {
+  if (n_frames <= 0) return;
+  if (n_landmarks > 0)
+    hipLaunchKernelGGL(rt8 ? prepare_landmarks_frames_kernel<true> : prepare_landmarks_frames_kernel<false>,
+                       dim3((n_landmarks + 127) / 128, n_frames), dim3(128), 0, stream, hp_W, quality, obs_begin,
+                       n_landmarks, obs_pose, obs_bp, poses, frames, cameras, w, h, repr, exclusive, cos06, status,
+                       n_desc, obs_rows, projection, e_W, r_W, packed);
+  hipLaunchKernelGGL(pack_landmarks_frames_kernel, dim3(n_frames), dim3(1024), 0, stream, packed, n_landmarks, counts);
+}
+void launch_check_landmark_table(const int32_t* obs_begin, int n_landmarks, const int32_t* obs_pose,
+                                 int n_observations, int n_poses, uint32_t* bad, hipStream_t stream) {
+  const int n = n_landmarks > n_observations ? n_landmarks : n_observations;
+  if (n <= 0) return;
+  hipLaunchKernelGGL(check_landmark_table_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, obs_begin, n_landmarks,
+                     obs_pose, n_observations, n_poses, bad);
 }
 
 bool set_fp64_tree_map(int tree) {

@@ -1010,6 +1010,126 @@ __global__ __launch_bounds__(64 * kMapSegs) void match_to_map_kernel(
   }
 }
 
+// match_to_map_kernel for okvfe_match_to_map_table_blocks_device: the landmark set of frame blockIdx.y is that frame's
+// packed records (k_map.hip: pack_landmarks_frames_kernel) and its length counts[frame], both read from device memory.
+// A record names the observation rows of its <= 2 pooled descriptors; the descriptors of the chunk's landmarks that
+// passed the box test are staged from table.obs_desc into LDS (slot 2 j + r), nothing is copied per frame.  The result
+// is the landmark's row in the TABLE.  Region order, box test and its NaN rules, segment merge and the strict `<` are
+// those of match_to_map_kernel.
+constexpr int kMapTableChunkDesc = 2 * kMapChunk;
+
+__global__ __launch_bounds__(64 * kMapSegs) void match_to_map_table_kernel(
+    MapBatch mb, const uint8_t* __restrict__ use, const MapPacked* __restrict__ packed,
+    const int32_t* __restrict__ counts, int n_table, const uint8_t* __restrict__ obs_desc, double thr_sq,
+    int threshold, int32_t* __restrict__ best_lm, int32_t* __restrict__ best_d) {
+  __shared__ uint4 seg_desc[kMapSegs][kMapTableChunkDesc * 3];
+  __shared__ int2 seg_best[kMapSegs - 1][64];
+  const uint8_t* base = mb.blocks + (size_t)blockIdx.y * mb.block_bytes;
+  const int n_k = *reinterpret_cast<const int32_t*>(base);
+  const uint8_t* desc_k = base + mb.o_desc;
+  const okvfe_keypoint* kps = reinterpret_cast<const okvfe_keypoint*>(base + mb.o_kps);
+  if (use) use += (size_t)blockIdx.y * mb.kp_cap;
+  packed += (size_t)blockIdx.y * (size_t)n_table;
+  best_lm += (size_t)blockIdx.y * mb.kp_cap;
+  best_d += (size_t)blockIdx.y * mb.kp_cap;
+  const int n_lm = min(max(counts[blockIdx.y], 0), n_table);
+  const int lane = threadIdx.x, seg = threadIdx.y;
+  const int pos = blockIdx.x * 64 + lane;
+  const bool in_range = pos < n_k;
+  const int k = (in_range && mb.perm) ? mb.perm[(size_t)blockIdx.y * mb.kp_cap + pos] : pos;
+  const bool active = in_range && (use == nullptr || use[k] != 0);
+  Desc12 dk = {};
+  double kx = 0.0, ky = 0.0;
+  if (active) {
+    dk = load_desc(desc_k + (size_t)k * OKVFE_DESC_BYTES);
+    kx = (double)kps[k].x;
+    ky = (double)kps[k].y;
+  }
+  // the wave's bounding box, as in match_to_map_kernel (a NaN keypoint takes the whole plane)
+  float bx0 = active ? (float)kx : INFINITY, bx1 = active ? (float)kx : -INFINITY;
+  float by0 = active ? (float)ky : INFINITY, by1 = active ? (float)ky : -INFINITY;
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) {
+    bx0 = fminf(bx0, __shfl_xor(bx0, d));
+    bx1 = fmaxf(bx1, __shfl_xor(bx1, d));
+    by0 = fminf(by0, __shfl_xor(by0, d));
+    by1 = fmaxf(by1, __shfl_xor(by1, d));
+  }
+  const float rad = sqrtf((float)thr_sq) * 1.0001f + 1.0f;
+  bx0 -= rad; by0 -= rad; bx1 += rad; by1 += rad;
+  if (__any(active && (kx != kx || ky != ky))) {  // wave-uniform
+    bx0 = by0 = -INFINITY;
+    bx1 = by1 = INFINITY;
+  }
+  const int per_seg = (n_lm + kMapSegs - 1) / kMapSegs;
+  const int l_lo = min(seg * per_seg, n_lm), l_hi = min(l_lo + per_seg, n_lm);
+  uint4* chunk = seg_desc[seg];
+  int best = threshold, lm = -1;
+  for (int l0 = l_lo; l0 < l_hi; l0 += kMapChunk) {
+    const int cnt = min(kMapChunk, l_hi - l0);
+    // lane j holds packed landmark l0 + j
+    double px = 0.0, py = 0.0;
+    int idx = -1, r0 = -1, r1 = -1;
+    if (lane < cnt) {
+      const MapPacked rec = packed[l0 + lane];
+      px = rec.px;
+      py = rec.py;
+      idx = rec.index;
+      r0 = rec.row0;
+      r1 = rec.row1;
+    }
+    const float fpx = (float)px, fpy = (float)py, fps = fpx + fpy;
+    const bool in_box = !(fpx < bx0) && !(fpx > bx1) && !(fpy < by0) && !(fpy > by1);
+    const unsigned long long cmask = __ballot(lane < cnt && (in_box || fps != fps));
+    if (cmask == 0) continue;  // wave-uniform: nothing of this chunk is near the wave
+    __builtin_amdgcn_wave_barrier();
+    // descriptors of the landmarks of cmask: 3 uint4 per slot, slot = 2 j + r
+    for (int i0 = 0; i0 < cnt * 6; i0 += 64) {  // (wave-uniform trip count: every lane takes part in the shuffles)
+      const int i = i0 + lane, slot = i / 3, part = i - 3 * slot, j = slot >> 1;  // i < 384: j < 64
+      const int ra = __shfl(r0, j), rb = __shfl(r1, j);
+      const int row = (slot & 1) ? rb : ra;
+      if (i < cnt * 6 && ((cmask >> j) & 1ull) && row >= 0)
+        chunk[i] = reinterpret_cast<const uint4*>(obs_desc + (size_t)row * OKVFE_DESC_BYTES)[part];
+    }
+    __builtin_amdgcn_wave_barrier();
+    for (unsigned long long cm = cmask; cm != 0; cm &= cm - 1) {
+      const int j = (int)__ffsll((long long)cm) - 1;
+      const double lpx = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(px), j),
+                                          __builtin_amdgcn_readlane(__double2loint(px), j));
+      const double lpy = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(py), j),
+                                          __builtin_amdgcn_readlane(__double2loint(py), j));
+      const int lidx = __builtin_amdgcn_readlane(idx, j);
+      const int nd = (__builtin_amdgcn_readlane(r0, j) >= 0 ? 1 : 0) + (__builtin_amdgcn_readlane(r1, j) >= 0 ? 1 : 0);
+      const double dx = lpx - kx, dy = lpy - ky;
+      const double dd = dx * dx + dy * dy;
+      const bool near = active && !(dd > thr_sq);
+      if (!__any(near)) continue;  // wave-uniform: no keypoint of this wave near the landmark
+      for (int d = 0; d < nd; ++d) {
+        const int dist = hamming(dk, reinterpret_cast<const uint32_t*>(chunk + 3 * (2 * j + d)));
+        if (near && dist < best) {
+          best = dist;
+          lm = lidx;
+        }
+      }
+    }
+  }
+  if (seg > 0) seg_best[seg - 1][lane] = make_int2(best, lm);
+  __syncthreads();
+  if (seg > 0) return;
+#pragma unroll
+  for (int sgm = 0; sgm < kMapSegs - 1; ++sgm) {
+    const int2 o = seg_best[sgm][lane];
+    if (o.x < best) {  // strict: ties stay with the lower segment = lower landmark row
+      best = o.x;
+      lm = o.y;
+    }
+  }
+  if (in_range) {
+    best_lm[k] = lm;
+    best_d[k] = best;
+  }
+}
+
 
 // ---- matchToMapByThreadUnitialised (Frontend.cpp:1616-1719) --------------------------------------
 // Landmarks that are not 3-D yet: pooled descriptor d carries the observing ray e0_W[d] and camera
@@ -1374,6 +1494,18 @@ void launch_match_to_map_blocks(const int offs[6], const uint8_t* blocks, int n_
   hipLaunchKernelGGL(match_to_map_kernel, dim3((kp_cap + 63) / 64, n_frames), dim3(64, kMapSegs), 0, stream,
                      nullptr, nullptr, use, 0, projections, desc_begin, n_lm, pool, thr_sq, threshold, best_lm,
                      best_d, mb);
+}
+
+void launch_match_to_map_table_blocks(const int offs[6], const uint8_t* blocks, int n_frames, int kp_cap,
+                                      const uint8_t* use, const MapPacked* packed, const int32_t* counts,
+                                      int n_landmarks, const uint8_t* obs_desc, double thr_sq, int threshold,
+                                      int32_t* best_lm, int32_t* best_d, int32_t* perm_ws, hipStream_t stream) {
+  if (n_frames <= 0 || kp_cap <= 0) return;
+  MapBatch mb{blocks, offs[1], offs[2], offs[3], offs[5], kp_cap, 0, nullptr};
+  hipLaunchKernelGGL(keypoint_order_kernel, dim3(n_frames), dim3(256), 0, stream, mb, perm_ws);
+  mb.perm = perm_ws;
+  hipLaunchKernelGGL(match_to_map_table_kernel, dim3((kp_cap + 63) / 64, n_frames), dim3(64, kMapSegs), 0, stream,
+                     mb, use, packed, counts, n_landmarks, obs_desc, thr_sq, threshold, best_lm, best_d);
 }
 
 void launch_match_stereo(const PairParams* pairs, int n_pairs, const okvfe_keypoint* kps,

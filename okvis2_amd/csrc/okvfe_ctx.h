@@ -61,6 +61,15 @@ struct okvfe_ctx {
     size_t frames = 0;  // frames d holds
   };
   std::vector<MapPerm> map_perm;
+  // okvfe_match_to_map_table_blocks_device / okvfe_landmark_table_check_device: packed records, counts and keypoint
+  // order of a slice of frames, ONE workspace PER STREAM as above (grown on demand, never shrunk)
+  struct MapTableWs {
+    hipStream_t stream = nullptr;
+    uint8_t* d = nullptr;
+    size_t bytes = 0;
+  };
+  std::vector<MapTableWs> map_table_ws;
+  size_t map_table_ws_limit = (size_t)1 << 30;  // more than this per call: the frames go in slices
   ScoreLayout score_layout{0, 0};  // of d_scores: slotted where the fused score+NMS kernel applies
   ScoreLayout live_layout{0, 0};   // the layout the LAST score launch actually wrote (dense when the fused kernel refused the call)
   // Map-free detection (round 4): single-scale Harris calls whose selection kernel can recompute the nine
@@ -294,5 +303,12 @@ struct BlockLayout {
   size_t o_count, o_kps, o_desc, o_bp, o_bpv, total;
 };
 BlockLayout block_layout(int kp_cap);
+
+// okvfe_match_to_map_table_blocks_device: frames per slice when a frame needs `per_frame` bytes of workspace and a call
+// may hold `limit`: all of them if they fit, never fewer than one, never more than a launch's grid.y
+inline int map_table_slice_frames(size_t per_frame, size_t limit, int n_frames) {
+  const size_t fit = per_frame ? limit / per_frame : (size_t)n_frames;
+  return (int)std::min<size_t>(std::max<size_t>(fit, 1), std::min<size_t>((size_t)std::max(n_frames, 1), 65535));
+}
 
 }  // namespace okvfe

@@ -1,6 +1,7 @@
 // okvfe_internal.h -- shared declarations of the libokvfe.so runtime (host + HIP kernels).
 // Product code; never includes or links anything under oracle/.
 #pragma once
+#include <cstddef>
 #include <atomic>
 #include <cstdlib>
 
@@ -164,6 +165,23 @@ struct PairParams {  // one stereo pair on device
   const double* cls;
 };
 constexpr int kSizeClasses = 8;
+
+// okvfe_match_to_map_table_blocks_device: one frame's record in the parameter block (host-filled, one upload per call)
+struct MapFrameParams {
+  okvfe_pose T1;  // T_WC1 of the frame
+  double cos10;   // cos(10 / (fu + fv)) of the frame's camera slot (Frontend.cpp:1213-1215)
+  int32_t cam;    // camera slot
+  int32_t pad;
+};
+// ... and its workspace record per (frame, landmark): written unpacked by prepare_landmarks_frames_kernel (index -1 =
+// not a 3-D landmark), packed in place to the frame's 3-D landmarks in table order by pack_landmarks_frames_kernel
+struct MapPacked {
+  double px, py;        // projection into the frame
+  int32_t index;        // landmark row of the table
+  int32_t row0, row1;   // observation rows of the pooled descriptors (row1 = -1: one descriptor)
+  int32_t pad;
+};
+static_assert(sizeof(MapPacked) == 32 && offsetof(MapPacked, index) == 16, "two 16-byte halves, index first in the second");
 
 // Layout of a context's int32 score map in HBM.
 //   dense   (strips <= 1): pixel (x, y) at y * pitch + x, pitch == w;
@@ -427,6 +445,20 @@ void launch_compact_landmarks(const int32_t* status, const int32_t* n_desc, cons
                               const double* projection, const uint8_t* obs_desc, int n_landmarks, int want,
                               int32_t* index_out, double* proj_out, int32_t* begin_out, uint8_t* pool_out,
                               int32_t* n_out, hipStream_t stream);
+void launch_prepare_landmarks_frames(const double* hp_W, const double* quality, const int32_t* obs_begin,
+                                     int n_landmarks, const int32_t* obs_pose, const double* obs_bp,
+                                     const okvfe_pose* poses, const MapFrameParams* frames, int n_frames,
+                                     const DeviceCamera* cameras, int w, int h, double repr, int exclusive,
+                                     double cos06, int32_t* status, int32_t* n_desc, int32_t* obs_rows,
+                                     double* projection, double* e_W, double* r_W, MapPacked* packed,
+                                     int32_t* counts, hipStream_t stream, bool rt8);
+void launch_check_landmark_table(const int32_t* obs_begin, int n_landmarks, const int32_t* obs_pose,
+                                 int n_observations, int n_poses, uint32_t* bad, hipStream_t stream);
+// the matcher on the frames' packed records (k_match.hip, match_to_map_table_kernel)
+void launch_match_to_map_table_blocks(const int offs[6], const uint8_t* blocks, int n_frames, int kp_cap,
+                                      const uint8_t* use, const MapPacked* packed, const int32_t* counts,
+                                      int n_landmarks, const uint8_t* obs_desc, double thr_sq, int threshold,
+                                      int32_t* best_lm, int32_t* best_d, int32_t* perm_ws, hipStream_t stream);
 // scale space (k_pyramid.hip)
 void launch_halfsample(const uint8_t* src, int w, int h, int n_images, uint8_t* dst, hipStream_t stream);
 void launch_twothird(const uint8_t* src, int w, int h, int n_images, uint8_t* dst, hipStream_t stream);

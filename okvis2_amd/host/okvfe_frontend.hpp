@@ -217,7 +217,7 @@ class HipFrontend {
   HipFrontend(const std::vector<okvfe_camera>& cameras, const FrontendParameters& p, int device = 0)
       : HipFrontend(extendCameras(cameras), p, device) {}
   HipFrontend(const std::vector<okvfe_camera_ext>& cameras, const FrontendParameters& p, int device = 0)
-      : cameras_(cameras), mutexes_(cameras.size()), bp_scratch_(cameras.size()) {
+      : cameras_(cameras), mutexes_(cameras.size()), bp_scratch_(cameras.size()), device_(device) {
     if (cameras.empty()) throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "no cameras");
     for (size_t i = 0; i < cameras.size(); ++i) {
       okvfe_config cfg{};
@@ -341,6 +341,79 @@ class HipFrontend {
         frame.descriptors.data.data(), frame.keypoints.data(), use.empty() ? all.data() : use.data(), int32_t(n),
         poolOut, m.landmark.data(), m.distance.data()));
     return m;
+  }
+  // A landmark table in device memory: uploaded when the map changes (at keyframes), read by every matchToMapBlocks
+  // until the next upload.  Owns its device copies (okvfe_device_alloc / okvfe_copy_to_device / okvfe_device_free).
+  class DeviceLandmarkTable {
+   public:
+    DeviceLandmarkTable() = default;
+    DeviceLandmarkTable(const DeviceLandmarkTable&) = delete;
+    DeviceLandmarkTable& operator=(const DeviceLandmarkTable&) = delete;
+    ~DeviceLandmarkTable() {
+      for (void* p : allocs_) okvfe_device_free(p);
+    }
+    const okvfe_landmark_table_device& get() const { return view_; }
+
+   private:
+    friend class HipFrontend;
+    okvfe_landmark_table_device view_{};
+    std::vector<void*> allocs_;
+  };
+  // Copies `table` to the device of camera `cameraIndex`'s context and runs okvfe_landmark_table_check_device on the
+  // copy: throws (OKVFE_ERR_INVALID_ARGUMENT, the first offending row named) if the table is malformed.  Synchronises;
+  // meant to run once per map change.
+  std::shared_ptr<DeviceLandmarkTable> uploadLandmarkTable(size_t cameraIndex, const okvfe_landmark_table& table) {
+    if (cameraIndex >= cameras_.size())
+      throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "Camera index exceeds number of cameras.");
+    if (table.n_landmarks < 0 || table.n_observations < 0 || table.n_poses < 0 || !table.obs_begin)
+      throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "uploadLandmarkTable: bad table");
+    std::lock_guard<std::mutex> lock(mutexes_[cameraIndex]);
+    Context& c = *contexts_[cameraIndex];
+    auto out = std::make_shared<DeviceLandmarkTable>();
+    auto up = [&](const void* src, size_t bytes) -> const void* {
+      void* d = nullptr;
+      c.check(okvfe_device_alloc(device_, bytes ? bytes : 1, &d));
+      out->allocs_.push_back(d);
+      if (bytes) {
+        if (!src) throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "uploadLandmarkTable: null array");
+        c.check(okvfe_copy_to_device(d, src, bytes, nullptr));
+      }
+      return d;
+    };
+    const size_t nl = size_t(table.n_landmarks), no = size_t(table.n_observations), np = size_t(table.n_poses);
+    okvfe_landmark_table_device& v = out->view_;
+    v.n_landmarks = table.n_landmarks;
+    v.n_observations = table.n_observations;
+    v.n_poses = table.n_poses;
+    v.hp_W = static_cast<const double*>(up(table.hp_W, nl * 32));
+    v.quality = static_cast<const double*>(up(table.quality, nl * 8));
+    v.obs_begin = static_cast<const int32_t*>(up(table.obs_begin, (nl + 1) * 4));
+    v.obs_pose = static_cast<const int32_t*>(up(table.obs_pose, no * 4));
+    v.obs_desc = static_cast<const uint8_t*>(up(table.obs_desc, no * OKVFE_DESC_BYTES));
+    v.obs_backproj = static_cast<const double*>(up(table.obs_backproj, no * 24));
+    v.poses = static_cast<const okvfe_pose*>(up(table.poses, np * sizeof(okvfe_pose)));
+    c.check(okvfe_stream_synchronize(nullptr));  // (the copies ran on the null stream)
+    c.check(okvfe_landmark_table_check_device(c.get(), &v, nullptr));
+    return out;
+  }
+  // matchToMap (above) for nFrames frames that live in device memory as gather blocks, against an uploaded table: one
+  // call per frame batch, nothing synchronises the host.  T_WC1: one pose per frame; useDev: device nFrames x K flags
+  // or null; outputs device nFrames x K (K = the context's row capacity); poolOut and its members may be null.  All
+  // frames are camera `cameraIndex`'s.  The results are ready when `stream` (null = the context's own) has drained.
+  void matchToMapBlocks(size_t cameraIndex, const DeviceLandmarkTable& table, const void* blocksDev, int nFrames,
+                        const std::vector<okvfe_pose>& T_WC1, double reprojectionThreshold, bool exclusive,
+                        const uint8_t* useDev, const okvfe_landmark_pool_device* poolOut, int32_t* bestLandmarkDev,
+                        int32_t* bestDistDev, void* stream = nullptr) {
+    if (cameraIndex >= cameras_.size())
+      throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "Camera index exceeds number of cameras.");
+    if (nFrames < 0 || T_WC1.size() != size_t(nFrames))
+      throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "matchToMapBlocks: one pose per frame");
+    std::lock_guard<std::mutex> lock(mutexes_[cameraIndex]);
+    if (!extractors_[cameraIndex].isCameraAware()) extractors_[cameraIndex].setCamera(cameras_[cameraIndex]);
+    const std::vector<int32_t> cams(size_t(nFrames) + 1, 0);  // slot 0 of the camera's own context
+    contexts_[cameraIndex]->check(okvfe_match_to_map_table_blocks_device(
+        contexts_[cameraIndex]->get(), &table.get(), blocksDev, nFrames, cams.data(), T_WC1.data(),
+        reprojectionThreshold, exclusive ? 1 : 0, useDev, poolOut, bestLandmarkDev, bestDistDev, stream));
   }
   // Frontend::matchToMapByThread on an already pooled 3-D landmark set (Frontend.cpp:1552-1589)
   MapMatches matchToMapPooled(size_t cameraIndex, const FrameData& frame, const std::vector<uint8_t>& use,
@@ -467,6 +540,7 @@ class HipFrontend {
   std::vector<HipBriskDetector> detectors_;
   std::vector<HipBriskExtractor> extractors_;
   std::vector<std::vector<double>> bp_scratch_;  // per camera (one thread per camera)
+  int device_ = 0;
 };
 
 }  // namespace okvfe
