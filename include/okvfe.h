@@ -785,8 +785,9 @@ typedef struct okvfe_landmark_table_device {
 
 /* okvfe_landmark_pool per frame: device arrays, frame-major n_frames x L rows (obs_rows x 3, projection x 2, e_W / r_W
  * x 6), holding the bytes of the B = 1 call's okvfe_landmark_pool: landmarks that are not kept are zero and their
- * obs_rows -1.  The struct pointer and every member may be NULL.  status, e_W and r_W stay on the device: they are the
- * input of a later, batched pass over the not-yet-3-D landmarks. */
+ * obs_rows -1.  The struct pointer and every member may be NULL.  status, n_desc, obs_rows, e_W and r_W stay on the
+ * device: they are the input of okvfe_match_to_map_table_uninitialised_blocks_device, the batched second pass over the
+ * landmarks that are not 3-D yet. */
 typedef struct okvfe_landmark_pool_device {
   int32_t* status;
   int32_t* n_desc;
@@ -813,13 +814,54 @@ okvfe_status okvfe_landmark_table_check_device(okvfe_ctx* ctx, const okvfe_landm
  * ring -- the first call on a stream, or a larger batch -- frees the old buffer, which waits for the device once.  A call that would need more
  * than 1 GiB of workspace runs its frames in slices, one after another on the same stream.
  * A NULL or negative argument: OKVFE_ERR_INVALID_ARGUMENT before anything is launched.
- * Not covered: the second pass of Frontend::matchToMap over the landmarks that are not 3-D yet with per-frame pools
- * (pool_out leaves its inputs on the device), RANSAC and outlier removal (Frontend.cpp:1411-1430). */
+ * The second pass of Frontend::matchToMap over the landmarks that are not 3-D yet is
+ * okvfe_match_to_map_table_uninitialised_blocks_device below, on what pool_out leaves on the device.  Not covered: RANSAC
+ * and outlier removal between the two passes (Frontend.cpp:1411-1430). */
 okvfe_status okvfe_match_to_map_table_blocks_device(
     okvfe_ctx* ctx, const okvfe_landmark_table_device* table, const void* blocks_dev, int32_t n_frames,
     const int32_t* cam_ids /* HOST, n_frames */, const okvfe_pose* T_WC1 /* HOST, n_frames */,
     double reprojection_threshold, int32_t exclusive, const uint8_t* use_dev /* n_frames x K or NULL */,
     const okvfe_landmark_pool_device* pool_out, int32_t* best_landmark_dev, int32_t* best_dist_dev, void* stream);
+
+/* The second pass of Frontend::matchToMap (Frontend.cpp:1434-1496): matchToMapByThreadUnitialised (:1594-1720) for
+ * n_frames frames, each over the landmarks that ITS first pass left as not 3-D yet, with the pose as it is NOW (after
+ * RANSAC and optimiseRealtimeGraph, which stay with the caller).  table: the table of the first pass; pool: what
+ * okvfe_match_to_map_table_blocks_device wrote for these frames (device, n_frames x L, L = table->n_landmarks).
+ *
+ * Landmark set of frame f: the landmarks l with pool->status[f L + l] == 2, in ascending table order.  Landmark l has
+ * pool->n_desc[f L + l] (1 or 2) pooled descriptors: the rows pool->obs_rows[3 (f L + l) + d] of table->obs_desc (the
+ * cropped third row is never read); pooled row d carries the ray pool->e_W[6 (f L + l) + 3 d ..] and the centre
+ * pool->r_W[6 (f L + l) + 3 d ..].  pool->projection is not read and may be NULL; the other five members are required
+ * when L > 0 (else OKVFE_ERR_INVALID_ARGUMENT).  Of the table only obs_desc and n_landmarks are read.  The pool is not
+ * checked: a malformed pool (a row outside obs_desc) is undefined behaviour, as a malformed table is.
+ *
+ * Keypoint k of block f takes part iff k < count, the block's backproj_valid[k] != 0 (:1625), use_dev == NULL or
+ * use[k] != 0, and exclusive != 0 or previous[k] < 0 (:1630): the first pass's best_landmark_dev may be passed as
+ * previous_landmark_dev unchanged.  previous: device n_frames x K TABLE rows (-1 = none) or NULL (none).
+ *
+ * cam_ids, T_WC1: HOST arrays of n_frames camera slots and poses.  sigma = 1 / (0.5 (fu + fv)) of slot cam_ids[f];
+ * cos(2.6 sigma) and cos(6 sigma) are computed on the host (std::cos); a slot without intrinsics:
+ * OKVFE_ERR_NOT_READY, the frame and the slot named.  One record per frame (240 bytes) goes through the pinned
+ * parameter ring.
+ *
+ * Gate chain, acceptance and outputs are those of okvfe_match_to_map_uninitialised_blocks_device: epipolar plane and
+ * divergence (unless nearly parallel), triangulateFast, not within 0.2 m of either centre; a gated hit on the landmark
+ * the keypoint carries (previous, with exclusive != 0) is counted in already_matched[f], ends that landmark's descriptor
+ * loop and is never accepted; `<` is strict (the first pooled row in table order reaching the smallest distance); hps_W
+ * is stored, and hp_set is 1, only when the winning triangulation is not parallel.  best_landmark = row of the TABLE.
+ * Outputs (device): best_landmark / best_dist n_frames x K, hps_W n_frames x K x 4, hp_set n_frames x K,
+ * already_matched n_frames (zeroed by this call).  Rows at or past a block's count are untouched; with L == 0 or an
+ * empty set the rows below it still receive -1, match_threshold, a zero hp and hp_set 0.  Both orders of
+ * okvfe_set_fp64_reduction apply.
+ * Nothing synchronises the host.  The workspace (16 bytes per (frame, landmark) pair plus 4 per frame) is the
+ * per-stream one of the first pass; a call above its limit runs in slices of frames.  A NULL or negative argument:
+ * OKVFE_ERR_INVALID_ARGUMENT before anything is launched; n_frames == 0 is OK and launches nothing. */
+okvfe_status okvfe_match_to_map_table_uninitialised_blocks_device(
+    okvfe_ctx* ctx, const okvfe_landmark_table_device* table, const okvfe_landmark_pool_device* pool,
+    const void* blocks_dev, int32_t n_frames, const int32_t* cam_ids /* HOST, n_frames */,
+    const okvfe_pose* T_WC1 /* HOST, n_frames */, int32_t exclusive, const uint8_t* use_dev /* n_frames x K or NULL */,
+    const int32_t* previous_landmark_dev /* n_frames x K or NULL */, int32_t* best_landmark_dev, int32_t* best_dist_dev,
+    double* hps_W_dev, uint8_t* hp_set_dev, int32_t* already_matched_dev, void* stream);
 
 /* ---- keyframe decision: keypoint coverage masks and their IoU ---------------- */
 /* Frontend::doWeNeedANewKeyframe (Frontend.cpp:1058-1167), the step between the map matchers and matchStereo whose

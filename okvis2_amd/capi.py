@@ -115,6 +115,7 @@ EXPORTS = [
     "okvfe_match_motion_stereo_ext",
     "okvfe_keyframe_coverage_blocks_device", "okvfe_keyframe_coverage", "okvfe_keyframe_decision",
     "okvfe_landmark_table_check_device", "okvfe_match_to_map_table_blocks_device",
+    "okvfe_match_to_map_table_uninitialised_blocks_device",
 ]
 
 STAGES = ["harris", "nms", "sort", "select", "map", "describe", "compact", "match"]
@@ -178,6 +179,10 @@ def lib():
         L.okvfe_comm_destroy.restype = None
         L.okvfe_gather_blocks.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.okvfe_comm_create.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
+        V = C.c_void_p
+        L.okvfe_match_to_map_table_uninitialised_blocks_device.restype = C.c_int32
+        L.okvfe_match_to_map_table_uninitialised_blocks_device.argtypes = [
+            V, V, V, V, C.c_int32, V, V, C.c_int32, V, V, V, V, V, V, V, V]
         _LIB = L
     return _LIB
 
@@ -838,6 +843,24 @@ class Frontend:
             self._h, C.byref(table), _p(blocks_ptr), n, _p(cams) if n else _p(np.zeros(1, np.int32)), P,
             C.c_double(repr_thr), int(bool(exclusive)), _p(use_ptr), C.byref(pool_out) if pool_out is not None else None,
             _p(best_lm_ptr), _p(best_d_ptr), _s(stream)))
+
+    def match_to_map_table_uninitialised_blocks_device(self, table: LandmarkTableDevice, pool: LandmarkPoolDevice,
+                                                       blocks_ptr, n_frames, cam_ids, poses_T_WC1, exclusive, use_ptr,
+                                                       previous_ptr, best_lm_ptr, best_d_ptr, hps_ptr, hp_set_ptr,
+                                                       ctr_ptr, stream=None):
+        """The second pass of matchToMap for n_frames gather blocks: every frame over the landmarks its first pass
+        (match_to_map_table_blocks_device with `pool` as pool_out) left with status 2.  cam_ids / poses_T_WC1: host
+        sequences of n_frames camera slots / (C, r), the poses as they are NOW; previous_ptr: device n_frames x K table
+        rows or None."""
+        n = int(n_frames)
+        cams = np.ascontiguousarray(cam_ids, dtype=np.int32)
+        if len(cams) != n or len(poses_T_WC1) != n:
+            raise ValueError("cam_ids and poses_T_WC1: one per frame")
+        P = (Pose * max(n, 1))(*[make_pose(*T) for T in poses_T_WC1])
+        self._check(lib().okvfe_match_to_map_table_uninitialised_blocks_device(
+            self._h, C.byref(table), C.byref(pool) if pool is not None else None, _p(blocks_ptr), n,
+            _p(cams) if n else _p(np.zeros(1, np.int32)), P, int(bool(exclusive)), _p(use_ptr), _p(previous_ptr),
+            _p(best_lm_ptr), _p(best_d_ptr), _p(hps_ptr), _p(hp_set_ptr), _p(ctr_ptr), _s(stream)))
 
     def _test_set_map_table_workspace_limit(self, nbytes):
         """test hook (not part of include/okvfe.h): the workspace size above which the call above slices its frames"""

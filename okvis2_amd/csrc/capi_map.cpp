@@ -656,9 +656,83 @@ okvfe_status okvfe_match_to_map_table_blocks_device(okvfe_ctx* ctx, const okvfe_
   return rel;
 }
 
+okvfe_status okvfe_match_to_map_table_uninitialised_blocks_device(
+    okvfe_ctx* ctx, const okvfe_landmark_table_device* T, const okvfe_landmark_pool_device* pool, const void* blocks_dev,
+    int32_t n_frames, const int32_t* cam_ids, const okvfe_pose* T_WC1, int32_t exclusive, const uint8_t* use_dev,
+    const int32_t* previous_landmark_dev, int32_t* best_landmark_dev, int32_t* best_dist_dev, double* hps_W_dev,
+    uint8_t* hp_set_dev, int32_t* already_matched_dev, void* stream) {
+  if (!ctx) return OKVFE_ERR_INVALID_ARGUMENT;
+  if (!T || T->n_landmarks < 0 || !pool || !blocks_dev || n_frames < 0 || !cam_ids || !T_WC1 || !best_landmark_dev ||
+      !best_dist_dev || !hps_W_dev || !hp_set_dev || !already_matched_dev ||
+      (T->n_landmarks > 0 && (!T->obs_desc || !pool->status || !pool->n_desc || !pool->obs_rows || !pool->e_W || !pool->r_W)))
+    return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_match_to_map_table_uninitialised_blocks_device: bad argument");
+  for (int f = 0; f < n_frames; ++f) {
+    const int cam = cam_ids[f];
+    if (cam < 0 || cam >= (int)ctx->h_cams.size() || !(ctx->h_cams[cam].fu > 0.0))
+      return fail(ctx, OKVFE_ERR_NOT_READY,
+                  "okvfe_match_to_map_table_uninitialised_blocks_device: frame %d: camera slot %d has no intrinsics (okvfe_set_camera)",
+                  f, cam);
+  }
+  if (n_frames == 0) return OKVFE_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
+  hipStream_t s = pick_stream(ctx, stream);
+  const BlockLayout L = block_layout(ctx->kp_cap);
+  const int offs[6] = {(int)L.o_count, (int)L.o_kps, (int)L.o_desc, (int)L.o_bp, (int)L.o_bpv, (int)L.total};
+  const size_t nl = (size_t)T->n_landmarks, K = (size_t)ctx->kp_cap;
+  // workspace per frame: one packed record per landmark and the count of the status-2 set; slices as in the first pass
+  const size_t per_frame = nl * sizeof(MapUninitPacked) + sizeof(int32_t);
+  const int slice = map_table_slice_frames(per_frame, ctx->map_table_ws_limit, n_frames);
+  const size_t o_cnt = align_up((size_t)slice * nl * sizeof(MapUninitPacked), 256),
+               total = o_cnt + (size_t)slice * sizeof(int32_t);
+  uint8_t* ws = nullptr;
+  okvfe_status st = map_table_workspace(ctx, s, total, &ws);
+  if (st != OKVFE_OK) return st;
+  // the pose NOW and the gate constants of the frame's camera slot: one record per frame through the pinned parameter
+  // ring (one asynchronous copy, no host sync)
+  std::vector<PairParams> pp((size_t)n_frames);
+  for (int f = 0; f < n_frames; ++f) {
+    const DeviceCamera& dc = ctx->h_cams[cam_ids[f]];
+    const double sigma = 1.0 / (0.5 * (dc.fu + dc.fv));  // Frontend.cpp:1636
+    pp[(size_t)f] = PairParams{};
+    std::memcpy(pp[(size_t)f].C1, T_WC1[f].C, sizeof(pp[(size_t)f].C1));
+    std::memcpy(pp[(size_t)f].r1, T_WC1[f].r, sizeof(pp[(size_t)f].r1));
+    pp[(size_t)f].cos26 = std::cos(2.6 * sigma);
+    pp[(size_t)f].cos6 = std::cos(6.0 * sigma);
+  }
+  void* d_pairs = nullptr;
+  int slot = -1;
+  st = ring_upload(ctx, &ctx->pair_ring, pp.data(), pp.size() * sizeof(PairParams), s, &d_pairs, &slot);
+  if (st != OKVFE_OK) return st;
+  hipError_t e = hipMemsetAsync(already_matched_dev, 0, (size_t)n_frames * sizeof(int32_t), s);
+  if (e == hipSuccess) {
+    StageTimer t(ctx, OKVFE_STAGE_MAP, s);
+    MapUninitPacked* packed = reinterpret_cast<MapUninitPacked*>(ws);
+    int32_t* counts = reinterpret_cast<int32_t*>(ws + o_cnt);
+    for (int f0 = 0; f0 < n_frames && e == hipSuccess; f0 += slice) {
+      const int nf = std::min(slice, n_frames - f0);
+      const size_t row = (size_t)f0 * nl;  // first row of the slice in the caller's frame-major pool arrays
+      auto at = [&](auto* p, size_t per_row) { return p ? p + row * per_row : p; };
+      launch_pack_uninit_frames(at(pool->status, 1), at(pool->n_desc, 1), at(pool->obs_rows, 3), T->n_landmarks, nf,
+                                packed, counts, s);
+      launch_match_to_map_table_uninit_blocks(
+          static_cast<const PairParams*>(d_pairs) + f0, offs, static_cast<const uint8_t*>(blocks_dev) + (size_t)f0 * L.total,
+          nf, ctx->kp_cap, use_dev ? use_dev + (size_t)f0 * K : nullptr,
+          previous_landmark_dev ? previous_landmark_dev + (size_t)f0 * K : nullptr, exclusive ? 1 : 0, packed, counts,
+          T->n_landmarks, T->obs_desc, at(pool->e_W, 6), at(pool->r_W, 6), ctx->cfg.match_threshold,
+          best_landmark_dev + (size_t)f0 * K, best_dist_dev + (size_t)f0 * K, hps_W_dev + 4 * (size_t)f0 * K,
+          hp_set_dev + (size_t)f0 * K, already_matched_dev + f0, s);
+      e = hipGetLastError();
+    }
+  }
+  const okvfe_status rel = ring_release(ctx, &ctx->pair_ring, slot, s);  // on every path: the slot has a reader or not
+  HIP_TRY(ctx, e);
+  ctx->last_stream = s;
+  return rel;
+}
+
 // Test hook, deliberately not in include/okvfe.h: lowers the workspace limit above which
-// okvfe_match_to_map_table_blocks_device cuts a call into slices of frames, so that a test reaches that path with a small
-// batch (0 restores the default of 1 GiB).
+// okvfe_match_to_map_table_blocks_device and okvfe_match_to_map_table_uninitialised_blocks_device cut a call into slices of
+// frames, so that a test reaches that path with a small batch (0 restores the default of 1 GiB).
 okvfe_status okvfe_test_set_map_table_workspace_limit(okvfe_ctx* ctx, uint64_t bytes) {
   if (!ctx) return OKVFE_ERR_INVALID_ARGUMENT;
   ctx->map_table_ws_limit = bytes ? (size_t)bytes : (size_t)1 << 30;

@@ -10,6 +10,8 @@
 //                              frames against one device-resident table: blockIdx.y resp. the work-group
 //                              is the frame, the packed record names observation rows instead of copying
 //                              descriptors, and the count of 3-D landmarks stays on the device;
+//   pack_uninit_frames_kernel   the landmarks a frame's first pass left with status 2 (not 3-D yet), packed in
+//                              table order for the second pass (okvfe_match_to_map_table_uninitialised_blocks_device);
 //   check_landmark_table_kernel   the structural checks of a device-resident table.
 // FP64, 3-term sums in the order of okvfe_set_fp64_reduction, no FMA; acos / cos through atan_fixed.h resp. host-computed constants.
 #include "camera_dev.h"
@@ -254,6 +256,49 @@ __global__ __launch_bounds__(1024) void pack_landmarks_frames_kernel(MapPacked* 
   if (tid == 0) counts[blockIdx.x] = base_lm;
 }
 
+// okvfe_match_to_map_table_uninitialised_blocks_device: the landmarks of every frame that the first pass left with
+// status 2 (not 3-D yet), as one MapUninitPacked record each at the front of the frame's records, in table order: one
+// work-group per frame, the chunked scan of pack_landmarks_frames_kernel.  Reads the frame's rows of the caller's pool
+// (status, n_desc, obs_rows; the cropped third row is never read); the count stays in device memory (counts[frame]).
+__global__ __launch_bounds__(1024) void pack_uninit_frames_kernel(const int32_t* __restrict__ status,
+                                                                   const int32_t* __restrict__ n_desc,
+                                                                   const int32_t* __restrict__ obs_rows, int n_landmarks,
+                                                                   MapUninitPacked* __restrict__ packed,
+                                                                   int32_t* __restrict__ counts) {
+  __shared__ int s_lm[1024];
+  __shared__ int base_lm;
+  const size_t row0 = (size_t)blockIdx.x * (size_t)n_landmarks;
+  MapUninitPacked* P = packed + row0;
+  const int tid = threadIdx.x;
+  if (tid == 0) base_lm = 0;
+  __syncthreads();
+  for (int c0 = 0; c0 < n_landmarks; c0 += 1024) {
+    const int l = c0 + tid;
+    const bool take = l < n_landmarks && status[row0 + l] == 2;
+    s_lm[tid] = take ? 1 : 0;
+    __syncthreads();
+    for (int d = 1; d < 1024; d <<= 1) {  // inclusive scan
+      const int a = tid >= d ? s_lm[tid - d] : 0;
+      __syncthreads();
+      s_lm[tid] += a;
+      __syncthreads();
+    }
+    if (take) {
+      const int nd = n_desc[row0 + l];
+      int4 rec;
+      rec.x = l;
+      rec.y = nd > 0 ? obs_rows[3 * (row0 + l)] : -1;
+      rec.z = nd > 1 ? obs_rows[3 * (row0 + l) + 1] : -1;
+      rec.w = 0;
+      *reinterpret_cast<int4*>(P + (base_lm + s_lm[tid] - 1)) = rec;
+    }
+    __syncthreads();
+    if (tid == 1023) base_lm += s_lm[1023];
+    __syncthreads();
+  }
+  if (tid == 0) counts[blockIdx.x] = base_lm;
+}
+
 // okvfe_landmark_table_check_device: what the host form checks on its host arrays.  bad[0] / bad[1] = first offending
 // landmark row of obs_begin / first observation with a pose index out of range (0xffffffff = none).
 __global__ __launch_bounds__(256) void check_landmark_table_kernel(const int32_t* __restrict__ obs_begin, int n_landmarks,
@@ -359,6 +404,12 @@ void launch_prepare_landmarks_frames(const double* hp_W, const double* quality, 
                        n_landmarks, obs_pose, obs_bp, poses, frames, cameras, w, h, repr, exclusive, cos06, status,
                        n_desc, obs_rows, projection, e_W, r_W, packed);
   hipLaunchKernelGGL(pack_landmarks_frames_kernel, dim3(n_frames), dim3(1024), 0, stream, packed, n_landmarks, counts);
+}
+void launch_pack_uninit_frames(const int32_t* status, const int32_t* n_desc, const int32_t* obs_rows, int n_landmarks,
+                               int n_frames, MapUninitPacked* packed, int32_t* counts, hipStream_t stream) {
+  if (n_frames <= 0) return;
+  hipLaunchKernelGGL(pack_uninit_frames_kernel, dim3(n_frames), dim3(1024), 0, stream, status, n_desc, obs_rows,
+                     n_landmarks, packed, counts);
 }
 void launch_check_landmark_table(const int32_t* obs_begin, int n_landmarks, const int32_t* obs_pose,
                                  int n_observations, int n_poses, uint32_t* bad, hipStream_t stream) {

@@ -1164,6 +1164,119 @@ struct UninitSegResult {
   double hp[4];
 };
 
+// Gate of one (keypoint, pooled descriptor) pair in the reference's order; pure.  e1_W: the keypoint's ray in the world
+// frame; e0v / r0v: the pooled descriptor's observing ray and camera centre; P.C1 / P.r1 = T_WC1, P.cos26 / P.cos6 for
+// sigma = 1 / f.  The one copy of the chain: match_to_map_uninit_kernel and match_to_map_table_uninit_kernel compile it.
+__device__ __forceinline__ bool uninit_gate(const PairParams& P, const double e1_W[3], const double e0v[3],
+                                            const double r0v[3], double hp[4], bool* is_parallel) {
+  if (dot3(e0v, e1_W) < P.cos6) {
+    double t[3], et[3], c0[3], c1[3], n0[3], n1[3], cx[3], nn[3], nnn[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) t[i] = P.r1[i] - r0v[i];
+    normalize3(t, et);
+    cross3(e0v, et, c0);
+    normalize3(c0, n0);
+    cross3(e1_W, et, c1);
+    normalize3(c1, n1);
+    if (dot3(n0, n1) < P.cos6) return false;
+    cross3(e0v, e1_W, cx);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) nn[i] = n0[i] + n0[i];
+    normalize3(nn, nnn);
+    if (dot3(cx, nnn) > 0.0) return false;
+  }
+  bool is_valid;
+  triangulate_fast(r0v, e0v, P.r1, e1_W, P.cos26, P.cos6, hp, &is_valid, is_parallel);
+  if (!is_valid) return false;
+  if (!*is_parallel) {
+    double a[3], bb[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const double p = hp[i] / hp[3];
+      a[i] = p - r0v[i];
+      bb[i] = p - P.r1[i];
+    }
+    if (sqrt(dot3(a, a)) < 0.2) is_valid = false;
+    if (sqrt(dot3(bb, bb)) < 0.2) is_valid = false;
+  }
+  return is_valid;
+}
+
+// What one range keeps per keypoint (the three items above), and the step for a pair whose distance is below the
+// range's running best: gate, then counted (the carried landmark `prev`, never accepted) or accepted.
+struct UninitRange {
+  int best, lm, np_dist, prev_min;
+  double h0, h1, h2, h3;  // hp of the last accepted non-parallel pair
+};
+__device__ __forceinline__ UninitRange uninit_range_start(int threshold) {
+  UninitRange R;
+  R.best = threshold; R.lm = -1; R.np_dist = INT_MAX; R.prev_min = INT_MAX;
+  R.h0 = 0.0; R.h1 = 0.0; R.h2 = 0.0; R.h3 = 0.0;
+  return R;
+}
+__device__ __forceinline__ void uninit_visit(const PairParams& P, const double e1_W[3], const double e0v[3],
+                                             const double r0v[3], int dist, int l, int prev, UninitRange& R) {
+  double hp[4];
+  bool is_parallel;
+  if (!uninit_gate(P, e1_W, e0v, r0v, hp, &is_parallel)) return;
+  if (l == prev) {  // counted, never accepted: `best` stays as it is for the whole landmark
+    R.prev_min = dist < R.prev_min ? dist : R.prev_min;
+    return;
+  }
+  R.best = dist;
+  R.lm = l;
+  if (!is_parallel) {
+    R.np_dist = dist;
+    R.h0 = hp[0]; R.h1 = hp[1]; R.h2 = hp[2]; R.h3 = hp[3];
+  }
+}
+
+// Ranges 1 .. kUninitSegs - 1 leave their result in seg_res; range 0 (the wave that returns from here, the others
+// leave the kernel) folds them in landmark order -- range 0 started from the threshold itself -- writes the keypoint's
+// rows and adds the wave's count of hits on carried landmarks to *ctr_total.  (R by value and the fold on locals: with
+// a reference the range state stayed in scratch.)
+__device__ __forceinline__ void uninit_fold_and_store(UninitSegResult (*seg_res)[64], int seg, int lane, int threshold,
+                                                      const UninitRange R, bool in_range, int k,
+                                                      int32_t* __restrict__ best_lm, int32_t* __restrict__ best_d,
+                                                      double* __restrict__ hps_W, uint8_t* __restrict__ hp_set,
+                                                      int32_t* __restrict__ ctr_total) {
+  int best = R.best, lm = R.lm;
+  double hps[4] = {R.h0, R.h1, R.h2, R.h3};
+  if (seg > 0) {
+    UninitSegResult& r = seg_res[seg - 1][lane];
+    r.best = best; r.lm = lm; r.np_dist = R.np_dist; r.prev_min = R.prev_min;
+    r.hp[0] = hps[0]; r.hp[1] = hps[1]; r.hp[2] = hps[2]; r.hp[3] = hps[3];
+  }
+  __syncthreads();
+  if (seg > 0) return;
+  int ctr = R.prev_min < threshold ? 1 : 0;
+  bool have_hp = R.np_dist != INT_MAX;
+  for (int sg = 0; sg < kUninitSegs - 1; ++sg) {
+    const UninitSegResult& r = seg_res[sg][lane];
+    if (r.prev_min < best) ++ctr;
+    if (r.best < best) {
+      if (r.np_dist < best) {
+        hps[0] = r.hp[0]; hps[1] = r.hp[1]; hps[2] = r.hp[2]; hps[3] = r.hp[3];
+        have_hp = true;
+      }
+      best = r.best;
+      lm = r.lm;
+    }
+  }
+  if (in_range) {
+    best_lm[k] = lm;
+    best_d[k] = best;
+    hp_set[k] = have_hp ? 1 : 0;
+    hps_W[4 * (size_t)k + 0] = hps[0];
+    hps_W[4 * (size_t)k + 1] = hps[1];
+    hps_W[4 * (size_t)k + 2] = hps[2];
+    hps_W[4 * (size_t)k + 3] = hps[3];
+  }
+#pragma unroll
+  for (int dlt = 32; dlt > 0; dlt >>= 1) ctr += __shfl_xor(ctr, dlt);
+  if (lane == 0 && ctr) atomicAdd(ctr_total, ctr);
+}
+
 __global__ __launch_bounds__(64 * kUninitSegs) void match_to_map_uninit_kernel(
     const PairParams* __restrict__ pair, const uint8_t* __restrict__ desc_k,
     const double* __restrict__ bp, const uint8_t* __restrict__ use,
@@ -1202,104 +1315,116 @@ __global__ __launch_bounds__(64 * kUninitSegs) void match_to_map_uninit_kernel(
     rot(P.C1, en, e1_W);
     prev = previous ? previous[k] : -1;
   }
-  // gate of one (keypoint, pooled descriptor) pair in the reference's order; pure
-  auto gate = [&](int d, double hp[4], bool* is_parallel) -> bool {
-    const double* e0 = e0_W + 3 * (size_t)d;
-    const double* r0 = r0_W + 3 * (size_t)d;
-    const double e0v[3] = {e0[0], e0[1], e0[2]}, r0v[3] = {r0[0], r0[1], r0[2]};
-    if (dot3(e0v, e1_W) < P.cos6) {
-      double t[3], et[3], c0[3], c1[3], n0[3], n1[3], cx[3], nn[3], nnn[3];
-#pragma unroll
-      for (int i = 0; i < 3; ++i) t[i] = P.r1[i] - r0v[i];
-      normalize3(t, et);
-      cross3(e0v, et, c0);
-      normalize3(c0, n0);
-      cross3(e1_W, et, c1);
-      normalize3(c1, n1);
-      if (dot3(n0, n1) < P.cos6) return false;
-      cross3(e0v, e1_W, cx);
-#pragma unroll
-      for (int i = 0; i < 3; ++i) nn[i] = n0[i] + n0[i];
-      normalize3(nn, nnn);
-      if (dot3(cx, nnn) > 0.0) return false;
-    }
-    bool is_valid;
-    triangulate_fast(r0v, e0v, P.r1, e1_W, P.cos26, P.cos6, hp, &is_valid, is_parallel);
-    if (!is_valid) return false;
-    if (!*is_parallel) {
-      double a[3], bb[3];
-#pragma unroll
-      for (int i = 0; i < 3; ++i) {
-        const double p = hp[i] / hp[3];
-        a[i] = p - r0v[i];
-        bb[i] = p - P.r1[i];
-      }
-      if (sqrt(dot3(a, a)) < 0.2) is_valid = false;
-      if (sqrt(dot3(bb, bb)) < 0.2) is_valid = false;
-    }
-    return is_valid;
-  };
   const int per_seg = (n_lm + kUninitSegs - 1) / kUninitSegs;
   const int l_lo = min(seg * per_seg, n_lm), l_hi = min(l_lo + per_seg, n_lm);
-  int best = threshold, lm = -1, np_dist = INT_MAX, prev_min = INT_MAX;
-  double hps[4] = {0, 0, 0, 0};
+  UninitRange R = uninit_range_start(threshold);
   for (int l = l_lo; l < l_hi; ++l) {
     const int b = desc_begin[l], e = desc_begin[l + 1];
     for (int d = b; d < e; ++d) {
       const uint32_t* dd = reinterpret_cast<const uint32_t*>(pool + (size_t)d * OKVFE_DESC_BYTES);
       if (!active) continue;
       const int dist = hamming(dk, dd);
-      if (dist < best) {
-        double hp[4];
-        bool is_parallel;
-        if (!gate(d, hp, &is_parallel)) continue;
-        if (l == prev) {  // counted, never accepted: `best` stays as it is for the whole landmark
-          prev_min = dist < prev_min ? dist : prev_min;
-          continue;
-        }
-        best = dist;
-        lm = l;
-        if (!is_parallel) {
-          np_dist = dist;
-          hps[0] = hp[0]; hps[1] = hp[1]; hps[2] = hp[2]; hps[3] = hp[3];
-        }
+      if (dist < R.best) {
+        const double* e0 = e0_W + 3 * (size_t)d;
+        const double* r0 = r0_W + 3 * (size_t)d;
+        const double e0v[3] = {e0[0], e0[1], e0[2]}, r0v[3] = {r0[0], r0[1], r0[2]};
+        uninit_visit(P, e1_W, e0v, r0v, dist, l, prev, R);
       }
     }
   }
-  if (seg > 0) {
-    UninitSegResult& r = seg_res[seg - 1][lane];
-    r.best = best; r.lm = lm; r.np_dist = np_dist; r.prev_min = prev_min;
-    r.hp[0] = hps[0]; r.hp[1] = hps[1]; r.hp[2] = hps[2]; r.hp[3] = hps[3];
+  uninit_fold_and_store(seg_res, seg, lane, threshold, R, in_range, k, best_lm, best_d, hps_W, hp_set, ctr_total);
+}
+
+// match_to_map_uninit_kernel for okvfe_match_to_map_table_uninitialised_blocks_device: the landmark set of frame
+// blockIdx.y is that frame's packed records (k_map.hip: pack_uninit_frames_kernel: the landmarks the first pass left
+// with status 2, in table order) and its length counts[frame], both read from device memory.  A record names the
+// landmark's table row and the observation rows of its <= 2 pooled descriptors; pooled row d of landmark l carries the
+// ray e_W[6 l + 3 d ..] and the centre r_W[6 l + 3 d ..] of the frame's pool rows.  Lane = keypoint; a wave walks its
+// range in chunks of kUninitChunk landmarks: lane j fetches record l0 + j, the chunk's descriptors are staged from
+// table.obs_desc into LDS (slot 2 j + r), and the ray and centre of a pooled row are fetched (wave-uniform address) only
+// when some keypoint of the wave has a distance below its running best.  Gate, acceptance, the carried landmark and the
+// fold of the ranges are the shared functions above; the result is the landmark's row in the TABLE.
+constexpr int kUninitChunk = 32;
+
+__global__ __launch_bounds__(64 * kUninitSegs) void match_to_map_table_uninit_kernel(
+    const PairParams* __restrict__ pairs, MapBatch mb, int o_bpv, const uint8_t* __restrict__ use,
+    const int32_t* __restrict__ previous, int exclusive, const MapUninitPacked* __restrict__ packed,
+    const int32_t* __restrict__ counts, int n_table, const uint8_t* __restrict__ obs_desc,
+    const double* __restrict__ e_W, const double* __restrict__ r_W, int threshold, int32_t* __restrict__ best_lm,
+    int32_t* __restrict__ best_d, double* __restrict__ hps_W, uint8_t* __restrict__ hp_set,
+    int32_t* __restrict__ ctr_total) {
+  __shared__ uint4 seg_desc[kUninitSegs][2 * kUninitChunk * 3];
+  __shared__ UninitSegResult seg_res[kUninitSegs - 1][64];
+  const uint8_t* base = mb.blocks + (size_t)blockIdx.y * mb.block_bytes;
+  const PairParams& P = pairs[blockIdx.y];  // C1/r1 = T_WC1 of the frame; cos26/cos6 of its camera slot
+  const int n_k = min(*reinterpret_cast<const int32_t*>(base), mb.kp_cap);
+  const uint8_t* desc_k = base + mb.o_desc;
+  const double* bp = reinterpret_cast<const double*>(base + mb.o_bp);
+  const uint8_t* bpv = base + o_bpv;
+  if (use) use += (size_t)blockIdx.y * mb.kp_cap;
+  if (previous) previous += (size_t)blockIdx.y * mb.kp_cap;
+  packed += (size_t)blockIdx.y * (size_t)n_table;
+  e_W += 6 * (size_t)blockIdx.y * (size_t)n_table;
+  r_W += 6 * (size_t)blockIdx.y * (size_t)n_table;
+  best_lm += (size_t)blockIdx.y * mb.kp_cap;
+  best_d += (size_t)blockIdx.y * mb.kp_cap;
+  hps_W += 4 * (size_t)blockIdx.y * mb.kp_cap;
+  hp_set += (size_t)blockIdx.y * mb.kp_cap;
+  ctr_total += blockIdx.y;
+  const int n_lm = min(max(counts[blockIdx.y], 0), n_table);
+  const int lane = threadIdx.x, seg = threadIdx.y;
+  const int k = blockIdx.x * 64 + lane;
+  const bool in_range = k < n_k;
+  // Frontend.cpp:1623-1635: a valid back-projection, the caller's flag, and no landmark yet unless `exclusive`
+  const int prev = (in_range && previous) ? previous[k] : -1;
+  const bool active = in_range && bpv[k] != 0 && (use == nullptr || use[k] != 0) && (exclusive != 0 || prev < 0);
+  Desc12 dk = {};
+  double e1_W[3] = {0, 0, 0};
+  if (active) {
+    dk = load_desc(desc_k + (size_t)k * OKVFE_DESC_BYTES);
+    double en[3];
+    normalize3(bp + 3 * (size_t)k, en);
+    rot(P.C1, en, e1_W);
   }
-  __syncthreads();
-  if (seg > 0) return;
-  // fold the ranges in landmark order; range 0 started from the threshold itself
-  int ctr = prev_min < threshold ? 1 : 0;
-  bool have_hp = np_dist != INT_MAX;
-  for (int sg = 0; sg < kUninitSegs - 1; ++sg) {
-    const UninitSegResult& r = seg_res[sg][lane];
-    if (r.prev_min < best) ++ctr;
-    if (r.best < best) {
-      if (r.np_dist < best) {
-        hps[0] = r.hp[0]; hps[1] = r.hp[1]; hps[2] = r.hp[2]; hps[3] = r.hp[3];
-        have_hp = true;
+  const int per_seg = (n_lm + kUninitSegs - 1) / kUninitSegs;
+  const int l_lo = min(seg * per_seg, n_lm), l_hi = min(l_lo + per_seg, n_lm);
+  uint4* chunk = seg_desc[seg];
+  UninitRange R = uninit_range_start(threshold);
+  for (int l0 = l_lo; l0 < l_hi; l0 += kUninitChunk) {
+    const int cnt = min(kUninitChunk, l_hi - l0);
+    // lane j < cnt holds packed landmark l0 + j
+    int idx = -1, r0 = -1, r1 = -1;
+    if (lane < cnt) {
+      const MapUninitPacked rec = packed[l0 + lane];
+      idx = rec.index;
+      r0 = rec.row0;
+      r1 = rec.row1;
+    }
+    __builtin_amdgcn_wave_barrier();
+    // descriptors of the chunk: 3 uint4 per slot, slot = 2 j + r
+    for (int i0 = 0; i0 < cnt * 6; i0 += 64) {  // (wave-uniform trip count: every lane takes part in the shuffles)
+      const int i = i0 + lane, slot = i / 3, part = i - 3 * slot, j = (slot >> 1) & 63;  // i < 192 + 64: j < 64
+      const int ra = __shfl(r0, j), rb = __shfl(r1, j);
+      const int row = (slot & 1) ? rb : ra;
+      if (i < cnt * 6 && row >= 0)
+        chunk[i] = reinterpret_cast<const uint4*>(obs_desc + (size_t)row * OKVFE_DESC_BYTES)[part];
+    }
+    __builtin_amdgcn_wave_barrier();
+    for (int j = 0; j < cnt; ++j) {
+      const int lidx = __builtin_amdgcn_readlane(idx, j);
+      const int nd = (__builtin_amdgcn_readlane(r0, j) >= 0 ? 1 : 0) + (__builtin_amdgcn_readlane(r1, j) >= 0 ? 1 : 0);
+      for (int d = 0; d < nd; ++d) {
+        const int dist = hamming(dk, reinterpret_cast<const uint32_t*>(chunk + 3 * (2 * j + d)));
+        const bool below = active && dist < R.best;
+        if (!__any(below)) continue;  // wave-uniform: no keypoint of this wave reaches the gate
+        const double* e0 = e_W + 6 * (size_t)lidx + 3 * d;
+        const double* c0 = r_W + 6 * (size_t)lidx + 3 * d;
+        const double e0v[3] = {e0[0], e0[1], e0[2]}, r0v[3] = {c0[0], c0[1], c0[2]};
+        if (below) uninit_visit(P, e1_W, e0v, r0v, dist, lidx, prev, R);
       }
-      best = r.best;
-      lm = r.lm;
     }
   }
-  if (in_range) {
-    best_lm[k] = lm;
-    best_d[k] = best;
-    hp_set[k] = have_hp ? 1 : 0;
-    hps_W[4 * (size_t)k + 0] = hps[0];
-    hps_W[4 * (size_t)k + 1] = hps[1];
-    hps_W[4 * (size_t)k + 2] = hps[2];
-    hps_W[4 * (size_t)k + 3] = hps[3];
-  }
-#pragma unroll
-  for (int dlt = 32; dlt > 0; dlt >>= 1) ctr += __shfl_xor(ctr, dlt);
-  if (lane == 0 && ctr) atomicAdd(ctr_total, ctr);
+  uninit_fold_and_store(seg_res, seg, lane, threshold, R, in_range, k, best_lm, best_d, hps_W, hp_set, ctr_total);
 }
 
 // ---- gather blocks (cross-camera exchange) ---------------------------------------
@@ -1506,6 +1631,19 @@ void launch_match_to_map_table_blocks(const int offs[6], const uint8_t* blocks, 
   mb.perm = perm_ws;
   hipLaunchKernelGGL(match_to_map_table_kernel, dim3((kp_cap + 63) / 64, n_frames), dim3(64, kMapSegs), 0, stream,
                      mb, use, packed, counts, n_landmarks, obs_desc, thr_sq, threshold, best_lm, best_d);
+}
+
+void launch_match_to_map_table_uninit_blocks(const PairParams* pairs, const int offs[6], const uint8_t* blocks,
+                                             int n_frames, int kp_cap, const uint8_t* use, const int32_t* previous,
+                                             int exclusive, const MapUninitPacked* packed, const int32_t* counts,
+                                             int n_landmarks, const uint8_t* obs_desc, const double* e_W,
+                                             const double* r_W, int threshold, int32_t* best_lm, int32_t* best_d,
+                                             double* hps_W, uint8_t* hp_set, int32_t* ctr_total, hipStream_t stream) {
+  if (n_frames <= 0 || kp_cap <= 0) return;
+  MapBatch mb{blocks, offs[1], offs[2], offs[3], offs[5], kp_cap, 0, nullptr};
+  hipLaunchKernelGGL(match_to_map_table_uninit_kernel, dim3((kp_cap + 63) / 64, n_frames), dim3(64, kUninitSegs), 0,
+                     stream, pairs, mb, offs[4], use, previous, exclusive, packed, counts, n_landmarks, obs_desc, e_W,
+                     r_W, threshold, best_lm, best_d, hps_W, hp_set, ctr_total);
 }
 
 void launch_match_stereo(const PairParams* pairs, int n_pairs, const okvfe_keypoint* kps,

@@ -182,6 +182,14 @@ struct MapPacked {
   int32_t pad;
 };
 static_assert(sizeof(MapPacked) == 32 && offsetof(MapPacked, index) == 16, "two 16-byte halves, index first in the second");
+// okvfe_match_to_map_table_uninitialised_blocks_device: its workspace record per status-2 landmark of a frame, written
+// packed in table order by pack_uninit_frames_kernel
+struct MapUninitPacked {
+  int32_t index;       // landmark row of the table
+  int32_t row0, row1;  // observation rows of the pooled descriptors (row1 = -1: one descriptor)
+  int32_t pad;
+};
+static_assert(sizeof(MapUninitPacked) == 16, "one 16-byte store");
 
 // Layout of a context's int32 score map in HBM.
 //   dense   (strips <= 1): pixel (x, y) at y * pitch + x, pitch == w;
@@ -459,6 +467,16 @@ void launch_match_to_map_table_blocks(const int offs[6], const uint8_t* blocks, 
                                       const uint8_t* use, const MapPacked* packed, const int32_t* counts,
                                       int n_landmarks, const uint8_t* obs_desc, double thr_sq, int threshold,
                                       int32_t* best_lm, int32_t* best_d, int32_t* perm_ws, hipStream_t stream);
+// the second pass on the frames' status-2 landmarks (k_map.hip, pack_uninit_frames_kernel; k_match.hip,
+// match_to_map_table_uninit_kernel)
+void launch_pack_uninit_frames(const int32_t* status, const int32_t* n_desc, const int32_t* obs_rows, int n_landmarks,
+                               int n_frames, MapUninitPacked* packed, int32_t* counts, hipStream_t stream);
+void launch_match_to_map_table_uninit_blocks(const PairParams* pairs, const int offs[6], const uint8_t* blocks,
+                                             int n_frames, int kp_cap, const uint8_t* use, const int32_t* previous,
+                                             int exclusive, const MapUninitPacked* packed, const int32_t* counts,
+                                             int n_landmarks, const uint8_t* obs_desc, const double* e_W,
+                                             const double* r_W, int threshold, int32_t* best_lm, int32_t* best_d,
+                                             double* hps_W, uint8_t* hp_set, int32_t* ctr_total, hipStream_t stream);
 // scale space (k_pyramid.hip)
 void launch_halfsample(const uint8_t* src, int w, int h, int n_images, uint8_t* dst, hipStream_t stream);
 void launch_twothird(const uint8_t* src, int w, int h, int n_images, uint8_t* dst, hipStream_t stream);

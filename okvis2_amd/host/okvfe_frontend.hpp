@@ -415,6 +415,29 @@ class HipFrontend {
         contexts_[cameraIndex]->get(), &table.get(), blocksDev, nFrames, cams.data(), T_WC1.data(),
         reprojectionThreshold, exclusive ? 1 : 0, useDev, poolOut, bestLandmarkDev, bestDistDev, stream));
   }
+  // The second pass of matchToMap (Frontend.cpp:1434-1496) after matchToMapBlocks: every frame over the landmarks its
+  // first pass left as not 3-D yet.  pool: what matchToMapBlocks wrote as poolOut for these frames (status, n_desc,
+  // obs_rows, e_W and r_W are required); T_WC1: one pose per frame, as it is NOW; previousLandmarkDev: device nFrames x
+  // K table rows (the first pass's bestLandmarkDev may be passed as it is) or null; outputs device: nFrames x K,
+  // hpsWDev x 4, alreadyMatchedDev nFrames.  Nothing synchronises the host.
+  void matchToMapUninitialisedBlocks(size_t cameraIndex, const DeviceLandmarkTable& table,
+                                     const okvfe_landmark_pool_device& pool, const void* blocksDev, int nFrames,
+                                     const std::vector<okvfe_pose>& T_WC1, bool exclusive, const uint8_t* useDev,
+                                     const int32_t* previousLandmarkDev, int32_t* bestLandmarkDev, int32_t* bestDistDev,
+                                     double* hpsWDev, uint8_t* hpSetDev, int32_t* alreadyMatchedDev,
+                                     void* stream = nullptr) {
+    if (cameraIndex >= cameras_.size())
+      throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "Camera index exceeds number of cameras.");
+    if (nFrames < 0 || T_WC1.size() != size_t(nFrames))
+      throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "matchToMapUninitialisedBlocks: one pose per frame");
+    std::lock_guard<std::mutex> lock(mutexes_[cameraIndex]);
+    if (!extractors_[cameraIndex].isCameraAware()) extractors_[cameraIndex].setCamera(cameras_[cameraIndex]);
+    const std::vector<int32_t> cams(size_t(nFrames) + 1, 0);  // slot 0 of the camera's own context
+    contexts_[cameraIndex]->check(okvfe_match_to_map_table_uninitialised_blocks_device(
+        contexts_[cameraIndex]->get(), &table.get(), &pool, blocksDev, nFrames, cams.data(), T_WC1.data(),
+        exclusive ? 1 : 0, useDev, previousLandmarkDev, bestLandmarkDev, bestDistDev, hpsWDev, hpSetDev,
+        alreadyMatchedDev, stream));
+  }
   // Frontend::matchToMapByThread on an already pooled 3-D landmark set (Frontend.cpp:1552-1589)
   MapMatches matchToMapPooled(size_t cameraIndex, const FrameData& frame, const std::vector<uint8_t>& use,
                               const std::vector<double>& projections, const std::vector<int32_t>& descBegin,
