@@ -815,8 +815,9 @@ okvfe_status okvfe_landmark_table_check_device(okvfe_ctx* ctx, const okvfe_landm
  * than 1 GiB of workspace runs its frames in slices, one after another on the same stream.
  * A NULL or negative argument: OKVFE_ERR_INVALID_ARGUMENT before anything is launched.
  * The second pass of Frontend::matchToMap over the landmarks that are not 3-D yet is
- * okvfe_match_to_map_table_uninitialised_blocks_device below, on what pool_out leaves on the device.  Not covered: RANSAC
- * and outlier removal between the two passes (Frontend.cpp:1411-1430). */
+ * okvfe_match_to_map_table_uninitialised_blocks_device below, on what pool_out leaves on the device.  Between the two
+ * passes (Frontend.cpp:1411-1430): okvfe_ransac3d2d_consensus_blocks_device and okvfe_remove_outliers_blocks_device
+ * further below.  Not covered: the minimal solver and the sampler of the RANSAC, and optimiseRealtimeGraph. */
 okvfe_status okvfe_match_to_map_table_blocks_device(
     okvfe_ctx* ctx, const okvfe_landmark_table_device* table, const void* blocks_dev, int32_t n_frames,
     const int32_t* cam_ids /* HOST, n_frames */, const okvfe_pose* T_WC1 /* HOST, n_frames */,
@@ -862,6 +863,81 @@ okvfe_status okvfe_match_to_map_table_uninitialised_blocks_device(
     const okvfe_pose* T_WC1 /* HOST, n_frames */, int32_t exclusive, const uint8_t* use_dev /* n_frames x K or NULL */,
     const int32_t* previous_landmark_dev /* n_frames x K or NULL */, int32_t* best_landmark_dev, int32_t* best_dist_dev,
     double* hps_W_dev, uint8_t* hp_set_dev, int32_t* already_matched_dev, void* stream);
+
+/* ---- between matchToMap's two passes: RANSAC consensus and outlier removal ------------------
+ * The consensus step of Frontend::runRansac3d2d (Frontend.cpp:2208-2261) for n_multiframes multiframes of n_cams
+ * cameras each: multiframe m owns the gather blocks m n_cams + c, c = 0 .. n_cams - 1, and the rows
+ * (m n_cams + c) K .. of landmark_dev (device, TABLE rows, -1 = none; the first pass's best_landmark_dev as it is).
+ * cam_ids, T_SC: HOST arrays of n_cams camera slots (with intrinsics, else OKVFE_ERR_NOT_READY) and sensor-from-camera
+ * poses (p_S = C p_C + r), one rig per call as the adapter takes frame->T_SC(im).  Of the table hp_W, obs_begin and
+ * n_landmarks are read.
+ *
+ * Correspondences (FrameNoncentralAbsoluteAdapter.cpp:50-148), camera-major with keypoints ascending: keypoint k of
+ * block (m, c) with k < count and l = landmark[k] >= 0, unless fabs(hp_W[4 l + 3]) < 1.0e-8 (:116; a NaN stays in) or
+ * the landmark has no observation in the table, obs_begin[l + 1] - obs_begin[l] < 1.  The reference asks for
+ * observations.size() >= 2 (:109) AFTER the frame added its own observation at Frontend.cpp:1404; the table holds the
+ * observations before that, so one is the floor here.  A row l >= n_landmarks is no correspondence.  Point
+ * p = hp.head<3>() / hp[3]; bearing = the block's back-projection, or (1, 0, 0) where backproj_valid[k] == 0
+ * (:129-132), normalised as Eigen's normalize() (z = squaredNorm; divided by sqrt(z) iff z > 0);
+ * sigma = ((sqrt2 s) s) / (fu fu), s = (0.8 double(size)) / 12.0, fu of slot cam_ids[c] (:128, 135).
+ *
+ * hypotheses_dev: n_multiframes x n_hyp x 12 doubles, each a row-major 3 x 4 [R | t] = T_WS (ransac.model_coefficients_);
+ * hyp_valid_dev: n_multiframes x n_hyp bytes or NULL (all valid), 0 = a sample whose solver failed (opengv skips it).
+ * n_hyp in 1 .. OKVFE_RANSAC_MAX_HYPOTHESES (the reference: max_iterations_ 50); threshold: the reference's 16.
+ * Distance (FrameAbsolutePoseSacProblem.hpp:140-165): Ri = R^T, ti = (-Ri) t, body = Ri p + ti (four terms),
+ * rep = C_SC^T (body - r_SC), rep /= |rep|, e = rep - bearing, dist = e.e / sigma; inlier iff dist < threshold (a NaN
+ * is an outlier).  Three- and four-term sums follow okvfe_set_fp64_reduction: Eigen's x0 + (x1 + x2) and
+ * (x0 + x1) + (x2 + x3), or left to right.
+ *
+ * Verdict (Frontend.cpp:2226, 2242-2261): with fewer than 10 correspondences nothing is scored (best_hypothesis -1,
+ * n_inliers 0, accepted 0).  Otherwise the winner is the valid hypothesis with the most inliers, more than 0, the first
+ * such in list order; accepted = n_inliers >= 10 && double(n_inliers) / double(n_correspondences) > 0.7.  The winning
+ * pose is hypotheses[best_hypothesis], which the caller owns.
+ *
+ * NOT restated: the minimal solver (opengv's gp3p) and the sampler, which work on three correspondences at a time and
+ * stay with the caller; opengv's adaptive stop, which only ever shortens the list (this call scores every hypothesis
+ * it is given).  PARITY UNPINNED: opengv is not in the reference tree; the winner rule (replace on strictly more
+ * inliers) is restated from the published source of opengv::sac::Ransac::computeModel.
+ *
+ * Results (device; each optional one may be NULL): n_correspondences / best_hypothesis / n_inliers int32 and accepted
+ * u8 per multiframe; optional hyp_inliers n_multiframes x n_hyp (-1: skipped or, below 10 correspondences, not scored);
+ * optional state blocks x K (0 no correspondence, 1 outlier of the winner, 2 inlier; only 0 and 1 without a winner);
+ * optional distance blocks x K (the winner's distance at correspondences; untouched elsewhere and without a winner);
+ * optional landmark_out blocks x K, which may be landmark_dev itself: the input, -1 where accepted && remove_outliers
+ * && state == 1.  Rows at or past a block's keypoint count are untouched.
+ * Nothing synchronises the host; no workspace; 112 bytes per camera go through the pinned parameter ring.  A NULL or
+ * negative argument: OKVFE_ERR_INVALID_ARGUMENT before anything is launched; n_multiframes == 0 is OK and launches
+ * nothing. */
+#define OKVFE_RANSAC_MAX_HYPOTHESES 64
+typedef struct okvfe_ransac_result_device {
+  int32_t* n_correspondences;
+  int32_t* best_hypothesis;
+  int32_t* n_inliers;
+  uint8_t* accepted;
+  int32_t* hyp_inliers;  /* optional */
+  uint8_t* state;        /* optional */
+  double* distance;      /* optional */
+  int32_t* landmark_out; /* optional */
+} okvfe_ransac_result_device;
+okvfe_status okvfe_ransac3d2d_consensus_blocks_device(
+    okvfe_ctx* ctx, const okvfe_landmark_table_device* table, const void* blocks_dev, int32_t n_multiframes,
+    int32_t n_cams, const int32_t* cam_ids /* HOST, n_cams */, const okvfe_pose* T_SC /* HOST, n_cams */,
+    const int32_t* landmark_dev, const double* hypotheses_dev, const uint8_t* hyp_valid_dev /* or NULL */, int32_t n_hyp,
+    double threshold, int32_t remove_outliers, const okvfe_ransac_result_device* result, void* stream);
+
+/* Frontend::removeOutliers (Frontend.cpp:2152-2205) for n_frames frames (frame f = gather block f).  cam_ids, T_WC:
+ * HOST arrays of n_frames camera slots and poses, T_WC = T_WS T_SC as the caller's Transformation class computes it.
+ * Of the table hp_W and n_landmarks are read (hp_W may point at refreshed positions after the caller's optimisation).
+ * Per keypoint k < count with l = landmark[k] in [0, n_landmarks): hp_C = T_WC^-1 hp_W in the expression order of the
+ * first pass, projectHomogeneous (the head negated when hp_C[3] < 0), the camera's project; the row becomes -1 iff the
+ * status is not Successful or sqrt(dx dx + dy dy) > max_error (the reference's 4.0), dx = projection - double(keypoint);
+ * a NaN norm is kept.  kept_dev[f] (int32, zeroed by this call) counts the kept ones: the reference's return value.
+ * Rows with l < 0 (or outside the table) pass through; rows at or past the count are untouched.  landmark_out_dev may
+ * be landmark_dev.  Nothing synchronises the host; 112 bytes per frame go through the pinned parameter ring. */
+okvfe_status okvfe_remove_outliers_blocks_device(
+    okvfe_ctx* ctx, const okvfe_landmark_table_device* table, const void* blocks_dev, int32_t n_frames,
+    const int32_t* cam_ids /* HOST, n_frames */, const okvfe_pose* T_WC /* HOST, n_frames */, double max_error,
+    const int32_t* landmark_dev, int32_t* landmark_out_dev, int32_t* kept_dev, void* stream);
 
 /* ---- keyframe decision: keypoint coverage masks and their IoU ---------------- */
 /* Frontend::doWeNeedANewKeyframe (Frontend.cpp:1058-1167), the step between the map matchers and matchStereo whose

@@ -116,6 +116,7 @@ EXPORTS = [
     "okvfe_keyframe_coverage_blocks_device", "okvfe_keyframe_coverage", "okvfe_keyframe_decision",
     "okvfe_landmark_table_check_device", "okvfe_match_to_map_table_blocks_device",
     "okvfe_match_to_map_table_uninitialised_blocks_device",
+    "okvfe_ransac3d2d_consensus_blocks_device", "okvfe_remove_outliers_blocks_device",
 ]
 
 STAGES = ["harris", "nms", "sort", "select", "map", "describe", "compact", "match"]
@@ -143,6 +144,18 @@ class LandmarkTableDevice(C.Structure):
 class LandmarkPoolDevice(C.Structure):
     """okvfe_landmark_pool_device: per-frame pooling results, device arrays n_frames x L (any member may be None)."""
     _fields_ = LandmarkPool._fields_
+
+
+class RansacResultDevice(C.Structure):
+    """okvfe_ransac_result_device: device pointers; the last four are optional (None)."""
+    _fields_ = [("n_correspondences", C.c_void_p), ("best_hypothesis", C.c_void_p), ("n_inliers", C.c_void_p),
+                ("accepted", C.c_void_p), ("hyp_inliers", C.c_void_p), ("state", C.c_void_p),
+                ("distance", C.c_void_p), ("landmark_out", C.c_void_p)]
+
+
+RANSAC_MAX_HYPOTHESES = 64  # OKVFE_RANSAC_MAX_HYPOTHESES
+RANSAC_THRESHOLD = 16.0     # Frontend.cpp:2235
+REMOVE_OUTLIERS_MAX_ERROR = 4.0  # Frontend.cpp:2185
 
 
 class OkvfeError(RuntimeError):
@@ -183,6 +196,11 @@ def lib():
         L.okvfe_match_to_map_table_uninitialised_blocks_device.restype = C.c_int32
         L.okvfe_match_to_map_table_uninitialised_blocks_device.argtypes = [
             V, V, V, V, C.c_int32, V, V, C.c_int32, V, V, V, V, V, V, V, V]
+        L.okvfe_ransac3d2d_consensus_blocks_device.restype = C.c_int32
+        L.okvfe_ransac3d2d_consensus_blocks_device.argtypes = [
+            V, V, V, C.c_int32, C.c_int32, V, V, V, V, V, C.c_int32, C.c_double, C.c_int32, V, V]
+        L.okvfe_remove_outliers_blocks_device.restype = C.c_int32
+        L.okvfe_remove_outliers_blocks_device.argtypes = [V, V, V, C.c_int32, V, V, C.c_double, V, V, V, V]
         _LIB = L
     return _LIB
 
@@ -861,6 +879,54 @@ class Frontend:
             self._h, C.byref(table), C.byref(pool) if pool is not None else None, _p(blocks_ptr), n,
             _p(cams) if n else _p(np.zeros(1, np.int32)), P, int(bool(exclusive)), _p(use_ptr), _p(previous_ptr),
             _p(best_lm_ptr), _p(best_d_ptr), _p(hps_ptr), _p(hp_set_ptr), _p(ctr_ptr), _s(stream)))
+
+    # -- between the two passes: RANSAC consensus and outlier removal ------------------------
+    @staticmethod
+    def make_ransac_result_device(n_correspondences_ptr, best_hypothesis_ptr, n_inliers_ptr, accepted_ptr,
+                                  hyp_inliers_ptr=None, state_ptr=None, distance_ptr=None,
+                                  landmark_out_ptr=None) -> RansacResultDevice:
+        return RansacResultDevice(*[int(p) if p else None for p in (
+            n_correspondences_ptr, best_hypothesis_ptr, n_inliers_ptr, accepted_ptr, hyp_inliers_ptr, state_ptr,
+            distance_ptr, landmark_out_ptr)])
+
+    def ransac3d2d_consensus_blocks_device(self, table: LandmarkTableDevice, blocks_ptr, n_multiframes, cam_ids,
+                                           poses_T_SC, landmark_ptr, hypotheses_ptr, hyp_valid_ptr, n_hyp,
+                                           result: RansacResultDevice, threshold=RANSAC_THRESHOLD,
+                                           remove_outliers=True, stream=None):
+        """The consensus step of runRansac3d2d for n_multiframes multiframes of len(cam_ids) gather blocks each.
+        cam_ids / poses_T_SC: host sequences of the rig's camera slots / (C, r); hypotheses_ptr: device
+        n_multiframes x n_hyp x 12 doubles ([R | t] = T_WS, row-major); hyp_valid_ptr: device bytes or None."""
+        cams = np.ascontiguousarray(cam_ids, dtype=np.int32)
+        n_cams = len(cams)
+        if len(poses_T_SC) != n_cams:
+            raise ValueError("cam_ids and poses_T_SC: one per camera")
+        P = (Pose * max(n_cams, 1))(*[make_pose(*T) for T in poses_T_SC])
+        self._check(lib().okvfe_ransac3d2d_consensus_blocks_device(
+            self._h, C.byref(table), _p(blocks_ptr), int(n_multiframes), n_cams,
+            _p(cams) if n_cams else _p(np.zeros(1, np.int32)), P, _p(landmark_ptr), _p(hypotheses_ptr),
+            _p(hyp_valid_ptr), int(n_hyp), C.c_double(threshold), int(bool(remove_outliers)),
+            C.byref(result) if result is not None else None, _s(stream)))
+
+    def remove_outliers_blocks_device(self, table: LandmarkTableDevice, blocks_ptr, n_frames, cam_ids, poses_T_WC,
+                                      landmark_ptr, landmark_out_ptr, kept_ptr, max_error=REMOVE_OUTLIERS_MAX_ERROR,
+                                      stream=None):
+        """Frontend::removeOutliers for n_frames gather blocks.  cam_ids / poses_T_WC: host sequences of n_frames camera
+        slots / (C, r); landmark_out_ptr may be landmark_ptr; kept_ptr: device n_frames int32."""
+        n = int(n_frames)
+        cams = np.ascontiguousarray(cam_ids, dtype=np.int32)
+        if len(cams) != n or len(poses_T_WC) != n:
+            raise ValueError("cam_ids and poses_T_WC: one per frame")
+        P = (Pose * max(n, 1))(*[make_pose(*T) for T in poses_T_WC])
+        self._check(lib().okvfe_remove_outliers_blocks_device(
+            self._h, C.byref(table), _p(blocks_ptr), n, _p(cams) if n else _p(np.zeros(1, np.int32)), P,
+            C.c_double(max_error), _p(landmark_ptr), _p(landmark_out_ptr), _p(kept_ptr), _s(stream)))
+
+    @staticmethod
+    def _test_ransac_chunk_records() -> int:
+        """test hook (not part of include/okvfe.h): correspondences the consensus kernel scores at a time"""
+        f = lib().okvfe_test_ransac_chunk_records
+        f.restype = C.c_int32
+        return int(f())
 
     def _test_set_map_table_workspace_limit(self, nbytes):
         """test hook (not part of include/okvfe.h): the workspace size above which the call above slices its frames"""

@@ -1,0 +1,115 @@
+// capi_ransac.cpp -- what Frontend::matchToMap does between its two matcher passes, behind the C ABI: the consensus
+// step of runRansac3d2d (Frontend.cpp:2208-2261) and removeOutliers (:2152-2205), on device-resident batches.
+#include "okvfe_ctx.h"
+
+using namespace okvfe;
+
+namespace {
+const DeviceCamera* slot_camera(okvfe_ctx* ctx, int cam) {
+  if (cam < 0 || cam >= (int)ctx->h_cams.size() || !(ctx->h_cams[cam].fu > 0.0)) return nullptr;
+  return &ctx->h_cams[cam];
+}
+}  // namespace
+
+extern "C" {
+
+okvfe_status okvfe_ransac3d2d_consensus_blocks_device(
+    okvfe_ctx* ctx, const okvfe_landmark_table_device* T, const void* blocks_dev, int32_t n_multiframes, int32_t n_cams,
+    const int32_t* cam_ids, const okvfe_pose* T_SC, const int32_t* landmark_dev, const double* hypotheses_dev,
+    const uint8_t* hyp_valid_dev, int32_t n_hyp, double threshold, int32_t remove_outliers,
+    const okvfe_ransac_result_device* result, void* stream) {
+  if (!ctx) return OKVFE_ERR_INVALID_ARGUMENT;
+  if (!T || T->n_landmarks < 0 || (T->n_landmarks > 0 && (!T->hp_W || !T->obs_begin)) || !blocks_dev ||
+      n_multiframes < 0 || n_cams < 1 || n_cams > (int)ctx->h_cams.size() || !cam_ids || !T_SC || !landmark_dev ||
+      !hypotheses_dev || n_hyp < 1 || n_hyp > OKVFE_RANSAC_MAX_HYPOTHESES || !(threshold >= 0.0) || !result ||
+      !result->n_correspondences || !result->best_hypothesis || !result->n_inliers || !result->accepted)
+    return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_ransac3d2d_consensus_blocks_device: bad argument");
+  if ((int64_t)n_cams * ctx->kp_cap >= (int64_t)1 << 30)
+    return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_ransac3d2d_consensus_blocks_device: too many keypoints per multiframe");
+  std::vector<RansacCamParams> cp((size_t)n_cams);
+  for (int c = 0; c < n_cams; ++c) {
+    const DeviceCamera* dc = slot_camera(ctx, cam_ids[c]);
+    if (!dc)
+      return fail(ctx, OKVFE_ERR_NOT_READY,
+                  "okvfe_ransac3d2d_consensus_blocks_device: frame %d: camera slot %d has no intrinsics (okvfe_set_camera)",
+                  c, cam_ids[c]);
+    cp[(size_t)c] = RansacCamParams{};
+    std::memcpy(cp[(size_t)c].C, T_SC[c].C, sizeof(cp[(size_t)c].C));
+    std::memcpy(cp[(size_t)c].r, T_SC[c].r, sizeof(cp[(size_t)c].r));
+    cp[(size_t)c].fu = dc->fu;
+    cp[(size_t)c].cam = cam_ids[c];
+  }
+  if (n_multiframes == 0) return OKVFE_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
+  hipStream_t s = pick_stream(ctx, stream);
+  const BlockLayout L = block_layout(ctx->kp_cap);
+  const int offs[6] = {(int)L.o_count, (int)L.o_kps, (int)L.o_desc, (int)L.o_bp, (int)L.o_bpv, (int)L.total};
+  // the rig: one record per camera through the pinned parameter ring (one asynchronous copy, no host sync)
+  void* d_cp = nullptr;
+  int slot = -1;
+  okvfe_status st = ring_upload(ctx, &ctx->pair_ring, cp.data(), cp.size() * sizeof(RansacCamParams), s, &d_cp, &slot);
+  if (st != OKVFE_OK) return st;
+  hipError_t e = hipSuccess;
+  {
+    StageTimer t(ctx, OKVFE_STAGE_MAP, s);
+    launch_ransac_consensus(T->hp_W, T->obs_begin, T->n_landmarks, offs, static_cast<const uint8_t*>(blocks_dev),
+                            n_multiframes, n_cams, ctx->kp_cap, static_cast<const RansacCamParams*>(d_cp), landmark_dev,
+                            hypotheses_dev, hyp_valid_dev, n_hyp, threshold, remove_outliers ? 1 : 0, *result, s);
+    e = hipGetLastError();
+  }
+  const okvfe_status rel = ring_release(ctx, &ctx->pair_ring, slot, s);  // on every path: the slot has a reader or not
+  HIP_TRY(ctx, e);
+  ctx->last_stream = s;
+  return rel;
+}
+
+okvfe_status okvfe_remove_outliers_blocks_device(okvfe_ctx* ctx, const okvfe_landmark_table_device* T,
+                                                 const void* blocks_dev, int32_t n_frames, const int32_t* cam_ids,
+                                                 const okvfe_pose* T_WC, double max_error, const int32_t* landmark_dev,
+                                                 int32_t* landmark_out_dev, int32_t* kept_dev, void* stream) {
+  if (!ctx) return OKVFE_ERR_INVALID_ARGUMENT;
+  if (!T || T->n_landmarks < 0 || (T->n_landmarks > 0 && !T->hp_W) || !blocks_dev || n_frames < 0 || !cam_ids || !T_WC ||
+      !(max_error >= 0.0) || !landmark_dev || !landmark_out_dev || !kept_dev)
+    return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_remove_outliers_blocks_device: bad argument");
+  bool rt8 = false;  // the 8-coefficient form of the projection only when a slot this call uses holds that model
+  std::vector<MapFrameParams> fp((size_t)n_frames);
+  for (int f = 0; f < n_frames; ++f) {
+    const DeviceCamera* dc = slot_camera(ctx, cam_ids[f]);
+    if (!dc)
+      return fail(ctx, OKVFE_ERR_NOT_READY,
+                  "okvfe_remove_outliers_blocks_device: frame %d: camera slot %d has no intrinsics (okvfe_set_camera)", f,
+                  cam_ids[f]);
+    rt8 = rt8 || dc->distortion == OKVFE_DIST_RADTAN8;
+    fp[(size_t)f] = MapFrameParams{};
+    fp[(size_t)f].T1 = T_WC[f];
+    fp[(size_t)f].cam = cam_ids[f];
+  }
+  if (n_frames == 0) return OKVFE_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
+  hipStream_t s = pick_stream(ctx, stream);
+  const BlockLayout L = block_layout(ctx->kp_cap);
+  const int offs[6] = {(int)L.o_count, (int)L.o_kps, (int)L.o_desc, (int)L.o_bp, (int)L.o_bpv, (int)L.total};
+  // pose and camera slot: one record per frame through the pinned parameter ring (one asynchronous copy, no host sync)
+  void* d_fp = nullptr;
+  int slot = -1;
+  okvfe_status st = ring_upload(ctx, &ctx->pair_ring, fp.data(), fp.size() * sizeof(MapFrameParams), s, &d_fp, &slot);
+  if (st != OKVFE_OK) return st;
+  hipError_t e = hipMemsetAsync(kept_dev, 0, (size_t)n_frames * sizeof(int32_t), s);
+  if (e == hipSuccess) {
+    StageTimer t(ctx, OKVFE_STAGE_MAP, s);
+    launch_remove_outliers_frames(T->hp_W, T->n_landmarks, static_cast<const MapFrameParams*>(d_fp), n_frames, ctx->d_cams,
+                                  ctx->w, ctx->h, offs, static_cast<const uint8_t*>(blocks_dev), ctx->kp_cap, max_error,
+                                  landmark_dev, landmark_out_dev, kept_dev, s, rt8);
+    e = hipGetLastError();
+  }
+  const okvfe_status rel = ring_release(ctx, &ctx->pair_ring, slot, s);  // on every path: the slot has a reader or not
+  HIP_TRY(ctx, e);
+  ctx->last_stream = s;
+  return rel;
+}
+
+// Test hook, deliberately not in include/okvfe.h: the number of correspondences the consensus kernel scores at a time,
+// so that the tests straddle it whatever it is.
+int32_t okvfe_test_ransac_chunk_records(void) { return ransac_chunk_records(); }
+
+}  // extern "C"

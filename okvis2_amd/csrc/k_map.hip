@@ -41,6 +41,18 @@ __device__ __forceinline__ void normalize3m(const double v[3], double out[3]) {
   out[2] = v[2] / n;
 }
 
+// hp_C = T_WC^-1 * hp_W as the reference's Transformation::inverse() * hp evaluates it.  The ONE copy of this expression
+// order: prepare_landmark and remove_outliers_frames_kernel compile it.
+__device__ __forceinline__ void pose_inverse_times(const okvfe_pose& T1, const double hp[4], double hp_C[4]) {
+  double cr[3], hh[3];
+  for (int i = 0; i < 3; ++i) {
+    cr[i] = sum3m(T1.C[i] * T1.r[0], T1.C[3 + i] * T1.r[1], T1.C[6 + i] * T1.r[2]);
+    hh[i] = sum3m(T1.C[i] * hp[0], T1.C[3 + i] * hp[1], T1.C[6 + i] * hp[2]);
+  }
+  for (int i = 0; i < 3; ++i) hp_C[i] = hh[i] + (-cr[i]) * hp[3];
+  hp_C[3] = hp[3];
+}
+
 // what the pooling leaves of one landmark: the row of okvfe_landmark_pool (zero / -1 when the landmark is not kept)
 struct Prepared {
   int32_t status, n_desc, rows[3];
@@ -67,14 +79,8 @@ __device__ __forceinline__ void prepare_landmark(
   normalize3m(r_Wv, e_Wv);
   const double rn = sqrt(dot3m(r_Wv, r_Wv));
   const double r = 0.01 > rn ? 0.01 : rn;
-  // hp_C = T_WC1^-1 * hp_W
-  double cr[3], hh[3], hp_C[4];
-  for (int i = 0; i < 3; ++i) {
-    cr[i] = sum3m(T1.C[i] * T1.r[0], T1.C[3 + i] * T1.r[1], T1.C[6 + i] * T1.r[2]);
-    hh[i] = sum3m(T1.C[i] * hp[0], T1.C[3 + i] * hp[1], T1.C[6 + i] * hp[2]);
-  }
-  for (int i = 0; i < 3; ++i) hp_C[i] = hh[i] + (-cr[i]) * hp[3];
-  hp_C[3] = hp[3];
+  double hp_C[4];
+  pose_inverse_times(T1, hp, hp_C);
   double head[3], kp[2];
   if (hp_C[3] < 0) {
     head[0] = -hp_C[0]; head[1] = -hp_C[1]; head[2] = -hp_C[2];
@@ -299,6 +305,53 @@ __global__ __launch_bounds__(1024) void pack_uninit_frames_kernel(const int32_t*
   if (tid == 0) counts[blockIdx.x] = base_lm;
 }
 
+// okvfe_remove_outliers_blocks_device: Frontend::removeOutliers (Frontend.cpp:2152-2205) for a batch of frames.  One
+// thread per keypoint, blockIdx.y = frame (pose and camera slot from the parameter block).  A keypoint that carries table
+// row l is removed (landmark_out = -1) iff the landmark does not project successfully or lands more than max_error
+// pixels from the keypoint; a kept one counts into kept[frame].  Rows without a landmark, or with one outside the table
+// (:2177 fails), pass through.  landmark_out may be landmark: a thread reads and writes its own row only.
+template <bool kRT8>
+__global__ __launch_bounds__(128) void remove_outliers_frames_kernel(
+    const double* __restrict__ hp_W, int n_landmarks, const MapFrameParams* __restrict__ frames,
+    const DeviceCamera* __restrict__ cameras, int w, int h, const uint8_t* __restrict__ blocks, int o_count, int o_kps,
+    size_t block_bytes, int kp_cap, double max_error, const int32_t* landmark, int32_t* landmark_out,
+    int32_t* __restrict__ kept) {
+  const int k = blockIdx.x * 128 + threadIdx.x;
+  const size_t f = blockIdx.y;
+  const uint8_t* blk = blocks + f * block_bytes;
+  int count = *reinterpret_cast<const int32_t*>(blk + o_count);
+  count = count < 0 ? 0 : (count > kp_cap ? kp_cap : count);
+  bool keep = false;
+  if (k < count) {
+    const size_t row = f * (size_t)kp_cap + (size_t)k;
+    const int l = landmark[row];
+    int out = l;
+    if (l >= 0 && l < n_landmarks) {
+      const MapFrameParams& fp = frames[f];
+      const DeviceCamera cam = cameras[fp.cam];
+      const double hp[4] = {hp_W[4 * (size_t)l], hp_W[4 * (size_t)l + 1], hp_W[4 * (size_t)l + 2], hp_W[4 * (size_t)l + 3]};
+      double hp_C[4], head[3], proj[2];
+      pose_inverse_times(fp.T1, hp, hp_C);
+      if (hp_C[3] < 0) {  // projectHomogeneous
+        head[0] = -hp_C[0]; head[1] = -hp_C[1]; head[2] = -hp_C[2];
+      } else {
+        head[0] = hp_C[0]; head[1] = hp_C[1]; head[2] = hp_C[2];
+      }
+      bool remove = true;
+      if (cam::project<kRT8>(cam, w, h, head, proj) == 0) {
+        const okvfe_keypoint kp = reinterpret_cast<const okvfe_keypoint*>(blk + o_kps)[k];
+        const double dx = proj[0] - (double)kp.x, dy = proj[1] - (double)kp.y;
+        remove = sqrt(dx * dx + dy * dy) > max_error;  // :2185 (a NaN norm is kept)
+      }
+      keep = !remove;
+      if (remove) out = -1;
+    }
+    landmark_out[row] = out;
+  }
+  const unsigned long long kb = __ballot(keep);
+  if ((threadIdx.x & 63) == 0 && kb) atomicAdd(&kept[f], (int)__popcll(kb));
+}
+
 // okvfe_landmark_table_check_device: what the host form checks on its host arrays.  bad[0] / bad[1] = first offending
 // landmark row of obs_begin / first observation with a pose index out of range (0xffffffff = none).
 __global__ __launch_bounds__(256) void check_landmark_table_kernel(const int32_t* __restrict__ obs_begin, int n_landmarks,
@@ -410,6 +463,20 @@ void launch_pack_uninit_frames(const int32_t* status, const int32_t* n_desc, con
   if (n_frames <= 0) return;
   hipLaunchKernelGGL(pack_uninit_frames_kernel, dim3(n_frames), dim3(1024), 0, stream, status, n_desc, obs_rows,
                      n_landmarks, packed, counts);
+}
+void launch_remove_outliers_frames(const double* hp_W, int n_landmarks, const MapFrameParams* frames, int n_frames,
+                                   const DeviceCamera* cameras, int w, int h, const int offs[6], const uint8_t* blocks,
+                                   int kp_cap, double max_error, const int32_t* landmark, int32_t* landmark_out,
+                                   int32_t* kept, hipStream_t stream, bool rt8) {
+  if (kp_cap <= 0) return;
+  for (int f0 = 0; f0 < n_frames; f0 += 65535) {  // a launch's grid.y
+    const int nf = n_frames - f0 < 65535 ? n_frames - f0 : 65535;
+    const size_t row = (size_t)f0 * (size_t)kp_cap;
+    hipLaunchKernelGGL(rt8 ? remove_outliers_frames_kernel<true> : remove_outliers_frames_kernel<false>,
+                       dim3((kp_cap + 127) / 128, nf), dim3(128), 0, stream, hp_W, n_landmarks, frames + f0, cameras, w, h,
+                       blocks + (size_t)f0 * (size_t)offs[5], offs[0], offs[1], (size_t)offs[5], kp_cap, max_error,
+                       landmark + row, landmark_out + row, kept + f0);
+  }
 }
 void launch_check_landmark_table(const int32_t* obs_begin, int n_landmarks, const int32_t* obs_pose,
                                  int n_observations, int n_poses, uint32_t* bad, hipStream_t stream) {

@@ -190,6 +190,14 @@ struct MapUninitPacked {
   int32_t pad;
 };
 static_assert(sizeof(MapUninitPacked) == 16, "one 16-byte store");
+// okvfe_ransac3d2d_consensus_blocks_device: one camera of the rig in the parameter block (host-filled, one upload per call)
+struct RansacCamParams {
+  double C[9], r[3];  // T_SC: p_S = C p_C + r
+  double fu;          // of the camera slot (FrameNoncentralAbsoluteAdapter.cpp:73-100)
+  int32_t cam;        // camera slot
+  int32_t pad;
+};
+static_assert(sizeof(RansacCamParams) == 112, "112 bytes per camera");
 
 // Layout of a context's int32 score map in HBM.
 //   dense   (strips <= 1): pixel (x, y) at y * pitch + x, pitch == w;
@@ -247,6 +255,7 @@ namespace okvfe {
 // 3-term FP64 sum order of the matcher / landmark kernels (one device flag per translation unit)
 bool set_fp64_tree_match(int tree);
 bool set_fp64_tree_map(int tree);
+bool set_fp64_tree_ransac(int tree);
 void launch_bow_query_l1(const int32_t* db_begin, const int32_t* db_ids, const double* db_values, int n_entries,
                          const int32_t* q_ids, const double* q_values, int n_q, double* scores,
                          hipStream_t stream);
@@ -477,6 +486,18 @@ void launch_match_to_map_table_uninit_blocks(const PairParams* pairs, const int 
                                              int n_landmarks, const uint8_t* obs_desc, const double* e_W,
                                              const double* r_W, int threshold, int32_t* best_lm, int32_t* best_d,
                                              double* hps_W, uint8_t* hp_set, int32_t* ctr_total, hipStream_t stream);
+// Frontend::removeOutliers for a batch of frames (k_map.hip, remove_outliers_frames_kernel); kept is zeroed by the caller
+void launch_remove_outliers_frames(const double* hp_W, int n_landmarks, const MapFrameParams* frames, int n_frames,
+                                   const DeviceCamera* cameras, int w, int h, const int offs[6], const uint8_t* blocks,
+                                   int kp_cap, double max_error, const int32_t* landmark, int32_t* landmark_out,
+                                   int32_t* kept, hipStream_t stream, bool rt8);
+// the consensus step of runRansac3d2d for a batch of multiframes (k_ransac.hip)
+void launch_ransac_consensus(const double* hp_W, const int32_t* obs_begin, int n_landmarks, const int offs[6],
+                             const uint8_t* blocks, int n_multiframes, int n_cams, int kp_cap,
+                             const RansacCamParams* cams, const int32_t* landmark, const double* hypotheses,
+                             const uint8_t* hyp_valid, int n_hyp, double threshold, int remove_outliers,
+                             const okvfe_ransac_result_device& out, hipStream_t stream);
+int ransac_chunk_records();  // correspondences the consensus kernel scores at a time
 // scale space (k_pyramid.hip)
 void launch_halfsample(const uint8_t* src, int w, int h, int n_images, uint8_t* dst, hipStream_t stream);
 void launch_twothird(const uint8_t* src, int w, int h, int n_images, uint8_t* dst, hipStream_t stream);

@@ -217,7 +217,8 @@ class HipFrontend {
   HipFrontend(const std::vector<okvfe_camera>& cameras, const FrontendParameters& p, int device = 0)
       : HipFrontend(extendCameras(cameras), p, device) {}
   HipFrontend(const std::vector<okvfe_camera_ext>& cameras, const FrontendParameters& p, int device = 0)
-      : cameras_(cameras), mutexes_(cameras.size()), bp_scratch_(cameras.size()), device_(device) {
+      : cameras_(cameras), mutexes_(cameras.size()), bp_scratch_(cameras.size()), hyp_scratch_(cameras.size()),
+        device_(device) {
     if (cameras.empty()) throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "no cameras");
     for (size_t i = 0; i < cameras.size(); ++i) {
       okvfe_config cfg{};
@@ -438,6 +439,66 @@ class HipFrontend {
         exclusive ? 1 : 0, useDev, previousLandmarkDev, bestLandmarkDev, bestDistDev, hpsWDev, hpSetDev,
         alreadyMatchedDev, stream));
   }
+  // Between the two passes (Frontend.cpp:1411-1430): the consensus step of runRansac3d2d for nMultiframes frames of
+  // camera `cameraIndex` (a context of this class holds ONE camera, so a multiframe is one gather block here; a rig
+  // whose cameras share a context calls okvfe_ransac3d2d_consensus_blocks_device itself).  hypotheses: host,
+  // nMultiframes x nHyp x 12 doubles ([R | t] = T_WS, row-major), what the caller's minimal solver produced from its
+  // samples; hypValid: host nMultiframes x nHyp bytes or empty (all valid).  Both are uploaded on `stream` into a buffer
+  // this object keeps per camera (growing it waits for the device once), with asynchronous copies: the two vectors
+  // stay valid and unchanged until `stream` has drained, and a second call for the same camera waits for the first
+  // one's stream to drain (the buffer is one per camera).  landmarkDev: device nMultiframes x K table
+  // rows, the first pass's bestLandmarkDev as it is; result: device pointers, landmark_out may be landmarkDev.  Nothing
+  // else synchronises the host.
+  void ransac3d2dBlocks(size_t cameraIndex, const DeviceLandmarkTable& table, const void* blocksDev, int nMultiframes,
+                        const okvfe_pose& T_SC, const int32_t* landmarkDev, const std::vector<double>& hypotheses,
+                        const std::vector<uint8_t>& hypValid, int nHyp, const okvfe_ransac_result_device& result,
+                        bool removeOutliers = true, double threshold = 16.0, void* stream = nullptr) {
+    if (cameraIndex >= cameras_.size())
+      throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "Camera index exceeds number of cameras.");
+    if (nMultiframes < 0 || nHyp < 1 || hypotheses.size() != size_t(nMultiframes) * size_t(nHyp) * 12 ||
+        (!hypValid.empty() && hypValid.size() != size_t(nMultiframes) * size_t(nHyp)))
+      throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "ransac3d2dBlocks: nHyp hypotheses (and flags) per multiframe");
+    std::lock_guard<std::mutex> lock(mutexes_[cameraIndex]);
+    if (!extractors_[cameraIndex].isCameraAware()) extractors_[cameraIndex].setCamera(cameras_[cameraIndex]);
+    Context& c = *contexts_[cameraIndex];
+    HypothesisScratch& hs = hyp_scratch_[cameraIndex];
+    const size_t hypBytes = hypotheses.size() * sizeof(double), bytes = hypBytes + hypValid.size();
+    if (bytes > hs.bytes) {
+      if (hs.d) {
+        c.check(okvfe_stream_synchronize(nullptr));
+        if (stream) c.check(okvfe_stream_synchronize(stream));
+        okvfe_device_free(hs.d);
+        hs.d = nullptr;
+        hs.bytes = 0;
+      }
+      c.check(okvfe_device_alloc(device_, bytes, &hs.d));
+      hs.bytes = bytes;
+    }
+    uint8_t* d = static_cast<uint8_t*>(hs.d);
+    if (hypBytes) c.check(okvfe_copy_to_device(d, hypotheses.data(), hypBytes, stream));
+    if (!hypValid.empty()) c.check(okvfe_copy_to_device(d + hypBytes, hypValid.data(), hypValid.size(), stream));
+    const int32_t cam = 0;  // slot 0 of the camera's own context
+    c.check(okvfe_ransac3d2d_consensus_blocks_device(
+        c.get(), &table.get(), blocksDev, nMultiframes, 1, &cam, &T_SC, landmarkDev, reinterpret_cast<const double*>(d),
+        hypValid.empty() ? nullptr : d + hypBytes, nHyp, threshold, removeOutliers ? 1 : 0, &result, stream));
+  }
+  // Frontend::removeOutliers (Frontend.cpp:2152-2205) for nFrames frames of camera `cameraIndex`: T_WC one pose per
+  // frame (T_WS T_SC as the caller's Transformation computes it); landmarkOutDev may be landmarkDev; keptDev: device
+  // nFrames int32, the reference's return value per frame.  Nothing synchronises the host.
+  void removeOutliersBlocks(size_t cameraIndex, const DeviceLandmarkTable& table, const void* blocksDev, int nFrames,
+                            const std::vector<okvfe_pose>& T_WC, const int32_t* landmarkDev, int32_t* landmarkOutDev,
+                            int32_t* keptDev, double maxError = 4.0, void* stream = nullptr) {
+    if (cameraIndex >= cameras_.size())
+      throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "Camera index exceeds number of cameras.");
+    if (nFrames < 0 || T_WC.size() != size_t(nFrames))
+      throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "removeOutliersBlocks: one pose per frame");
+    std::lock_guard<std::mutex> lock(mutexes_[cameraIndex]);
+    if (!extractors_[cameraIndex].isCameraAware()) extractors_[cameraIndex].setCamera(cameras_[cameraIndex]);
+    const std::vector<int32_t> cams(size_t(nFrames) + 1, 0);  // slot 0 of the camera's own context
+    contexts_[cameraIndex]->check(okvfe_remove_outliers_blocks_device(
+        contexts_[cameraIndex]->get(), &table.get(), blocksDev, nFrames, cams.data(), T_WC.data(), maxError, landmarkDev,
+        landmarkOutDev, keptDev, stream));
+  }
   // Frontend::matchToMapByThread on an already pooled 3-D landmark set (Frontend.cpp:1552-1589)
   MapMatches matchToMapPooled(size_t cameraIndex, const FrameData& frame, const std::vector<uint8_t>& use,
                               const std::vector<double>& projections, const std::vector<int32_t>& descBegin,
@@ -563,6 +624,17 @@ class HipFrontend {
   std::vector<HipBriskDetector> detectors_;
   std::vector<HipBriskExtractor> extractors_;
   std::vector<std::vector<double>> bp_scratch_;  // per camera (one thread per camera)
+  struct HypothesisScratch {  // ransac3d2dBlocks: the device copy of a call's hypotheses and flags
+    void* d = nullptr;
+    size_t bytes = 0;
+    HypothesisScratch() = default;
+    HypothesisScratch(const HypothesisScratch&) = delete;
+    HypothesisScratch& operator=(const HypothesisScratch&) = delete;
+    ~HypothesisScratch() {
+      if (d) okvfe_device_free(d);
+    }
+  };
+  std::vector<HypothesisScratch> hyp_scratch_;  // per camera
   int device_ = 0;
 };
 

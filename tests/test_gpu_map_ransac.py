@@ -1,0 +1,229 @@
+"""GPU: okvfe_ransac3d2d_consensus_blocks_device (ransac_consensus_kernel) and okvfe_remove_outliers_blocks_device
+(remove_outliers_frames_kernel) against ransac_ref.py under both orders of the FP64 sums: counts, verdicts, states and
+landmark rows for equality, distances as uint64 patterns; rows at or past a block's keypoint count keep their
+sentinels.  Scenes: ransac_scenes.py (general rigs of 1, 2 and 5 cameras over the four camera models, the directed
+cases, both knife edges, the verdict table, the chunk edges; the projection statuses, the max_error edge and mixed
+camera slots of removeOutliers)."""
+import ctypes as C
+import dataclasses
+
+import numpy as np
+import pytest
+
+import gpu_common as G
+import ransac_ref as R
+import ransac_scenes as S
+from okvis2_amd import capi, synth
+
+pytestmark = [pytest.mark.gpu]
+torch = pytest.importorskip("torch")
+
+_FRONTENDS = {}
+
+
+def _frontend(cams, n_set=None):
+    """a context of the first camera's size with K = ransac_scenes.K whose first n_set slots hold `cams`"""
+    n_set = len(cams) if n_set is None else n_set
+    key = tuple((c.w, c.h, c.fu, c.fv, c.cu, c.cv, c.dist_type, tuple(c.d)) for c in cams) + (n_set,)
+    if key not in _FRONTENDS:
+        cfg = dataclasses.replace(synth.euroc_config(), w=cams[0].w, h=cams[0].h, cams=list(cams), max_kpts=S.K)
+        fe = G.make_frontend(cfg)
+        for i, c in enumerate(cams[:n_set]):
+            fe.set_camera(i, c)
+        _FRONTENDS[key] = fe
+    return _FRONTENDS[key]
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _close_frontends():
+    yield
+    while _FRONTENDS:
+        _FRONTENDS.popitem()[1].close()
+
+
+def _tree(fp64_order):
+    return fp64_order == "eigen_tree"
+
+
+def _run(fe, sc, refs, what, **kw):
+    tab = S.DeviceTable(fe, sc["hp"], sc["obs_begin"])
+    alias = kw.pop("alias", False)
+    T = S.prepare_consensus(fe, sc, optional=kw.pop("optional", True), alias=alias)
+    S.launch_consensus(fe, tab, sc, T, **kw)
+    return S.check_consensus(sc, T, refs, what, alias=alias)
+
+
+@pytest.mark.parametrize("spec", S.GENERAL_SPECS, ids=S.spec_id)
+def test_general_scene(oracle, fp64_order, spec):
+    tree = _tree(fp64_order)
+    sc = S.general_scene(oracle, spec)
+    fe = _frontend(sc["cams"])
+    assert fe.max_keypoints == S.K
+    refs = S.reference(tree, sc)
+    what = (sc["name"], fp64_order)
+    got = _run(fe, sc, refs, what)
+    # (inliers and outliers of a winner both occur: the floor test_map_ransac_host.py holds the scenes to)
+    assert int((got["state"] == 2).sum()) >= S.STATE_FLOOR and int((got["state"] == 1).sum()) >= S.STATE_FLOOR
+    _run(fe, sc, refs, what + ("in place",), alias=True)
+    _run(fe, sc, refs, what + ("verdicts only",), optional=False)
+    _run(fe, sc, S.reference(tree, sc, remove_outliers=False), what + ("no removal",), remove_outliers=False)
+    _run(fe, sc, S.reference(tree, sc, use_valid=False), what + ("hyp_valid NULL",), use_valid=False)
+
+
+def test_directed_scene(oracle, fp64_order):
+    tree = _tree(fp64_order)
+    sc = S.directed_scene(oracle)
+    refs = S.reference(tree, sc)
+    got = _run(_frontend(sc["cams"]), sc, refs, (sc["name"], fp64_order))
+    assert got["hyp_inliers"][0, 0] == refs[0]["hyp_inliers"][0] >= 0  # [I | 0]: the NaN distances are outliers
+    _run(_frontend(sc["cams"]), sc, refs, (sc["name"], fp64_order, "in place"), alias=True)
+
+
+def test_knife_edges(oracle, fp64_order):
+    tree = _tree(fp64_order)
+    for sc in (S.knife_translation(oracle, tree), S.knife_size(oracle, tree)):
+        refs = S.reference(tree, sc)
+        got = _run(_frontend(sc["cams"]), sc, refs, (sc["name"], fp64_order))
+        print(sc["name"], got["hyp_inliers"][0], got["state"][0, :3])
+    assert list(got["state"][0, :2]) == [1, 2]  # the two sizes
+
+
+def test_verdict_table(oracle, fp64_order):
+    tree = _tree(fp64_order)
+    true_first = lambda T, rng: np.array([S.pose_matrix(T), S.far_pose(T, rng)])
+    variants = (("true first", true_first, None), ("twice", lambda T, rng: np.array([S.pose_matrix(T)] * 2), None),
+                ("better later", lambda T, rng: np.array([S.far_pose(T, rng), S.pose_matrix(T)]), None),
+                ("nothing beats zero", lambda T, rng: np.array([S.far_pose(T, rng)] * 2), None),
+                ("all invalid", true_first, np.zeros(2, np.uint8)))
+    for name, H_of, valid in variants:
+        sc = S.verdict_scene(oracle, H_of, valid)
+        fe = _frontend(sc["cams"])
+        refs = S.reference(tree, sc)
+        got = _run(fe, sc, refs, (name, fp64_order))
+        if name == "true first":
+            heads = list(zip(got["best"].tolist(), got["n_inl"].tolist(), got["accepted"].tolist()))
+            assert heads == [S.VERDICT_EXPECT[c] for c in S.VERDICT_CASES], heads
+            _run(fe, sc, refs, (name, fp64_order, "in place"), alias=True)
+            _run(fe, sc, S.reference(tree, sc, remove_outliers=False), (name, "no removal"), remove_outliers=False)
+        if name == "twice":
+            assert got["best"].tolist()[1:] == [0] * 6
+        if name == "better later":
+            assert got["best"].tolist()[1:] == [1] * 6
+
+
+def test_chunk_edges(oracle, fp64_order):
+    tree = _tree(fp64_order)
+    chunk = capi.Frontend._test_ransac_chunk_records()
+    sc = S.chunk_scene(oracle, chunk)
+    refs = S.reference(tree, sc)
+    got = _run(_frontend(sc["cams"]), sc, refs, (sc["name"], fp64_order))
+    assert got["n_corr"].tolist() == [chunk - 1, chunk, chunk + 1, 2 * chunk + 1]
+
+
+def test_batches_slices_and_a_side_stream(oracle, fp64_order):
+    """batches of 1, 3 and 17 multiframes (ragged and empty blocks); a call on a part of a batch touches that part
+    only; consensus in place and removeOutliers on a non-default stream with nothing waited for in between"""
+    tree = _tree(fp64_order)
+    base = S.general_scene(oracle, ("euroc", "euroc1"))
+    fe = _frontend(base["cams"])
+    refs3 = S.reference(tree, base)
+    tab = S.DeviceTable(fe, base["hp"], base["obs_begin"])
+    for B in (1, 3, 17):
+        sc = dict(base, mfs=[base["mfs"][i % 3] for i in range(B)])
+        refs = [refs3[i % 3] for i in range(B)]
+        T = S.prepare_consensus(fe, sc)
+        S.launch_consensus(fe, tab, sc, T)
+        S.check_consensus(sc, T, refs, ("batch", B, fp64_order))
+    # slices of the batch of 17: [5, 9) first, the rest untouched; then the rest
+    T = S.prepare_consensus(fe, sc)
+    S.launch_consensus(fe, tab, sc, T, first=5, count=4)
+    got = S.check_consensus(sc, T, refs, ("slice",), only=range(5, 9))
+    untouched = [i for i in range(17) if not 5 <= i < 9]
+    assert np.all(got["n_corr"][untouched] == S.SENTINEL) and np.all(got["state"][:10] == S.STATE_SENTINEL)
+    assert np.all(got["state"][18:] == S.STATE_SENTINEL) and np.all(got["hyp_inliers"][untouched] == S.SENTINEL)
+    S.launch_consensus(fe, tab, sc, T, first=0, count=5)
+    S.launch_consensus(fe, tab, sc, T, first=9, count=8)
+    S.check_consensus(sc, T, refs, ("slices",))
+    # a side stream: consensus in place, then removeOutliers on its output, no host synchronisation in between
+    stream = torch.cuda.Stream()
+    T = S.prepare_consensus(fe, sc, alias=True)
+    frames = [f for mf in sc["mfs"] for f in mf["frames"]]
+    n_cams = len(sc["cams"])
+    poses = [S.compose(mf["T_WS"], sc["T_SC"][c]) for mf in sc["mfs"] for c in range(n_cams)]
+    kept = torch.full((len(frames),), S.SENTINEL, dtype=torch.int32, device="cuda")
+    out = torch.full(T["lm"].shape, S.SENTINEL, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    S.launch_consensus(fe, tab, sc, T, stream=stream)
+    fe.remove_outliers_blocks_device(tab.desc, T["blocks"].data_ptr(), len(frames), [i % n_cams for i in range(len(frames))],
+                                     poses, T["lm"].data_ptr(), out.data_ptr(), kept.data_ptr(), stream=stream)
+    stream.synchronize()
+    S.check_consensus(sc, T, refs, ("side stream",), alias=True)
+    out, kept = out.cpu().numpy(), kept.cpu().numpy()
+    for i, fr in enumerate(frames):
+        ref = refs[i // n_cams]["landmark_out"][i % n_cams]
+        rl, rk = R.remove_outliers(oracle, tree, sc["hp"], fr["kps"], ref, sc["cams"][i % n_cams], poses[i])
+        assert np.array_equal(out[i, :len(rl)], rl) and int(kept[i]) == rk, ("side stream", i)
+
+
+def test_argument_errors_and_an_empty_batch(oracle):
+    sc = S.general_scene(oracle, ("euroc", "euroc1"))
+    fe = _frontend(sc["cams"])
+    tab = S.DeviceTable(fe, sc["hp"], sc["obs_begin"])
+    T = S.prepare_consensus(fe, sc)
+    res = fe.make_ransac_result_device(*[T[k].data_ptr() for k in ("n_corr", "best", "n_inl", "accepted")])
+    good = dict(table=tab.desc, blocks_ptr=T["blocks"].data_ptr(), n_multiframes=3, cam_ids=[0, 1], poses_T_SC=sc["T_SC"],
+                landmark_ptr=T["lm"].data_ptr(), hypotheses_ptr=T["H"].data_ptr(), hyp_valid_ptr=None, n_hyp=50, result=res)
+    bad = (dict(n_hyp=0), dict(n_hyp=capi.RANSAC_MAX_HYPOTHESES + 1), dict(n_multiframes=-1), dict(blocks_ptr=None),
+           dict(landmark_ptr=None), dict(hypotheses_ptr=None), dict(result=None), dict(threshold=float("nan")),
+           dict(cam_ids=[], poses_T_SC=[]), dict(cam_ids=[0, 1, 0], poses_T_SC=sc["T_SC"] + sc["T_SC"][:1]),
+           dict(result=fe.make_ransac_result_device(T["n_corr"].data_ptr(), None, T["n_inl"].data_ptr(), T["accepted"].data_ptr())))
+    for change in bad:
+        with pytest.raises(capi.OkvfeError) as e:
+            fe.ransac3d2d_consensus_blocks_device(**dict(good, **change))
+        assert e.value.status == capi.ERR_INVALID_ARGUMENT, change
+    fe.ransac3d2d_consensus_blocks_device(**dict(good, n_multiframes=0))
+    rgood = dict(table=tab.desc, blocks_ptr=T["blocks"].data_ptr(), n_frames=2, cam_ids=[0, 1],
+                 poses_T_WC=[S.compose(sc["mfs"][0]["T_WS"], t) for t in sc["T_SC"]], landmark_ptr=T["lm"].data_ptr(),
+                 landmark_out_ptr=T["lm_out"].data_ptr(), kept_ptr=T["n_inl"].data_ptr())
+    for change in (dict(blocks_ptr=None), dict(landmark_ptr=None), dict(landmark_out_ptr=None), dict(kept_ptr=None),
+                   dict(max_error=-1.0), dict(max_error=float("nan"))):
+        with pytest.raises(capi.OkvfeError) as e:
+            fe.remove_outliers_blocks_device(**dict(rgood, **change))
+        assert e.value.status == capi.ERR_INVALID_ARGUMENT, change
+    st = capi.lib().okvfe_remove_outliers_blocks_device(fe._h, C.byref(tab.desc), T["blocks"].data_ptr(), -1, None, None, 4.0, None,
+                                                        None, None, None)
+    assert st == capi.ERR_INVALID_ARGUMENT
+    fe.remove_outliers_blocks_device(**dict(rgood, n_frames=0, cam_ids=[], poses_T_WC=[]))
+    torch.cuda.synchronize()
+    assert np.all(T["n_corr"].cpu().numpy() == S.SENTINEL) and np.all(T["n_inl"].cpu().numpy() == S.SENTINEL)
+    assert np.all(T["lm_out"].cpu().numpy() == S.SENTINEL)
+    # a slot without intrinsics: the frame and the slot are named
+    half = _frontend(sc["cams"], n_set=1)
+    for call, args in ((half.ransac3d2d_consensus_blocks_device, good), (half.remove_outliers_blocks_device, rgood)):
+        with pytest.raises(capi.OkvfeError) as e:
+            call(**args)
+        assert e.value.status == capi.ERR_NOT_READY and "frame 1: camera slot 1" in str(e.value), str(e.value)
+
+
+def _run_remove(fe, sc, refs, what, alias=False, **kw):
+    tab = S.DeviceTable(fe, sc["hp"])
+    T = S.prepare_remove(fe, sc, alias=alias)
+    S.launch_remove(fe, tab, sc, T, **kw)
+    S.check_remove(sc, T, refs, what, alias=alias)
+    return T
+
+
+def test_remove_outliers(oracle, fp64_order):
+    tree = _tree(fp64_order)
+    fe = _frontend(S.remove_cameras())
+    sc = S.remove_scene(oracle)
+    refs = S.remove_reference(oracle, tree, sc)
+    T = _run_remove(fe, sc, refs, (sc["name"], fp64_order))
+    kept = T["kept"].cpu().numpy()
+    assert np.all(kept[:-1] >= 10) and kept[-1] == 0
+    _run_remove(fe, sc, refs, (sc["name"], fp64_order, "in place"), alias=True)
+    st = S.remove_status_scene(oracle)
+    _run_remove(fe, st, S.remove_reference(oracle, tree, st), (st["name"], fp64_order))
+    edge, keep, drop = S.remove_edge_scene(oracle, tree)
+    _run_remove(fe, edge, S.remove_reference(oracle, tree, edge, keep), ("edge kept",), max_error=keep)
+    _run_remove(fe, edge, S.remove_reference(oracle, tree, edge, drop), ("edge removed",), max_error=drop)
