@@ -7,15 +7,41 @@
 
 namespace okvfe {
 
+// Lab builds of k_select.hip only (tools/lab/select_traffic.sh): ONE source of the selection kernel's memory traffic is
+// switched off per build so that the byte counters and the kernel time price it.  Results of such a build are wrong by
+// design.  Bits: 1 = the tail (K4) is skipped, 2 = no extra samples, 4 = the key workspace is no longer written once the
+// first batches have filled it (same images every step), 8 = every image reads image 0's candidate list (L2-resident),
+// 16 = ray and Jacobian from one fixed pixel, 32 = the tail computes but stores nothing.
+#if defined(OKVFE_LAB) && defined(OKVFE_SELECT_OFF)
+constexpr int kSelectOff = OKVFE_SELECT_OFF;
+__device__ int g_select_off_flag;  // 1: the key workspace is filled (bit 4); never 2 (keeps the unstored values alive, bit 32)
+#define OKVFE_TAIL_STORE(stmt)                                   \
+  do {                                                           \
+    if (!(kSelectOff & 32) || g_select_off_flag == 2) { stmt; } \
+  } while (0)
+#else
+constexpr int kSelectOff = 0;
+#define OKVFE_TAIL_STORE(stmt) \
+  do {                         \
+    stmt;                      \
+  } while (0)
+#endif
+
 // M = J * [e_x e_y] / fu on the tangent plane of the keypoint's ray, e_y along `dir`
 __device__ __forceinline__ bool camera_aware_matrix(const float* __restrict__ rays,
                                                     const float* __restrict__ jac, int w, float fu,
                                                     const float dir[3], float kx, float ky,
                                                     float M[4]) {
-  const int u = (int)(kx + 0.5f), v = (int)(ky + 0.5f);
+  int u = (int)(kx + 0.5f), v = (int)(ky + 0.5f);
+  if (kSelectOff & 16) {
+    u = w / 2;
+    v = w / 4;
+  }
   const float* r = rays + ((size_t)v * w + u) * 3;
   const float* J = jac + ((size_t)v * w + u) * 6;
   const float r0 = r[0], r1 = r[1], r2 = r[2];
+  // (requested with the ray, ahead of the tests below: behind them the Jacobian was a memory round trip of its own)
+  const float J0 = J[0], J1 = J[1], J2 = J[2], J3 = J[3], J4 = J[4], J5 = J[5];
   if (r0 == 0.0f && r1 == 0.0f && r2 == 0.0f) return false;
   float ey0 = 0.f, ey1 = 0.f, ey2 = 0.f, n2 = 0.0f;
 #pragma unroll
@@ -48,10 +74,10 @@ __device__ __forceinline__ bool camera_aware_matrix(const float* __restrict__ ra
   t1 = ey2 * r0; t2 = ey0 * r2; const float ex1 = t1 - t2;
   t1 = ey0 * r1; t2 = ey1 * r0; const float ex2 = t1 - t2;
   float s;
-  s = J[0] * ex0; t1 = J[1] * ex1; s = s + t1; t1 = J[2] * ex2; s = s + t1; M[0] = s / fu;
-  s = J[0] * ey0; t1 = J[1] * ey1; s = s + t1; t1 = J[2] * ey2; s = s + t1; M[1] = s / fu;
-  s = J[3] * ex0; t1 = J[4] * ex1; s = s + t1; t1 = J[5] * ex2; s = s + t1; M[2] = s / fu;
-  s = J[3] * ey0; t1 = J[4] * ey1; s = s + t1; t1 = J[5] * ey2; s = s + t1; M[3] = s / fu;
+  s = J0 * ex0; t1 = J1 * ex1; s = s + t1; t1 = J2 * ex2; s = s + t1; M[0] = s / fu;
+  s = J0 * ey0; t1 = J1 * ey1; s = s + t1; t1 = J2 * ey2; s = s + t1; M[1] = s / fu;
+  s = J3 * ex0; t1 = J4 * ex1; s = s + t1; t1 = J5 * ex2; s = s + t1; M[2] = s / fu;
+  s = J3 * ey0; t1 = J4 * ey1; s = s + t1; t1 = J5 * ey2; s = s + t1; M[3] = s / fu;
   return true;
 }
 
@@ -157,11 +183,20 @@ __device__ __forceinline__ bool extra_sample_value(const uint8_t* __restrict__ i
   return true;
 }
 
+// the constants of extra sample e (uniform over the workgroup: every lane reads the same five words)
+struct ExtraSampleParams {
+  float px, py, sigma_half;
+  int scaling, scaling2;
+};
+__device__ __forceinline__ ExtraSampleParams extra_sample_params(const Pattern* __restrict__ pat, int e) {
+  return ExtraSampleParams{pat->px[e], pat->py[e], pat->sigma_half[e], pat->box_scaling[e], pat->box_scaling2[e]};
+}
+
 // extra sample e of the keypoint at (kx, ky) under M -> bytes 24 + 4 e of its descriptor slot; false: box outside the image
-__device__ __forceinline__ bool extra_sample_one(const Pattern* __restrict__ pat, const uint8_t* __restrict__ im, int w,
+__device__ __forceinline__ bool extra_sample_one(const ExtraSampleParams& sp, const uint8_t* __restrict__ im, int w,
                                                  int h, int extra_box, int e, const float M[4], float kx, float ky,
                                                  uint8_t* __restrict__ slot_bytes) {
-  const float px = pat->px[e], py = pat->py[e], sg = pat->sigma_half[e];
+  const float px = sp.px, py = sp.py, sg = sp.sigma_half;
   float a = M[0] * px, b2 = M[1] * py;  // (the sequence of sample_pos, k_describe_aware.hip)
   a = a + b2;
   const float xf = kx + a;
@@ -169,32 +204,60 @@ __device__ __forceinline__ bool extra_sample_one(const Pattern* __restrict__ pat
   c = c + d2;
   const float yf = ky + c;
   int v = 0;
-  const bool ok = extra_box <= 4
-                      ? extra_sample_value<4>(im, w, h, xf, yf, sg, pat->box_scaling[e], pat->box_scaling2[e], &v)
-                      : extra_sample_value<9>(im, w, h, xf, yf, sg, pat->box_scaling[e], pat->box_scaling2[e], &v);
-  *reinterpret_cast<int*>(slot_bytes + 24 + 4 * e) = v;
+  const bool ok = extra_box <= 4 ? extra_sample_value<4>(im, w, h, xf, yf, sg, sp.scaling, sp.scaling2, &v)
+                                 : extra_sample_value<9>(im, w, h, xf, yf, sg, sp.scaling, sp.scaling2, &v);
+  OKVFE_TAIL_STORE(*reinterpret_cast<int*>(slot_bytes + 24 + 4 * e) = v);
   return ok;
+}
+
+// What describe_setup_one needs that is the same for every keypoint of an image: the image's launch parameters, its
+// camera's maps and three fields of the pattern.  Every address is uniform over the workgroup, so a caller that loads
+// them before its first store (the selection kernels: at their start) gets scalar loads whose latency nothing waits
+// for; read per keypoint, in the tail, they were six dependent memory round trips of every lane.
+struct DescribeImageParams {
+  ImageParams ip;
+  const float* rays;
+  const float* jac;
+  int border;   // of the fixed-scale pattern
+  float reach;
+  int extra;    // samples beyond describe_aware_kernel's 64 lanes
+};
+__device__ __forceinline__ DescribeImageParams describe_image_params(const DescribeSetup& ds, int img) {
+  DescribeImageParams p;
+  p.ip = ds.prm[img];
+  const bool aware = p.ip.mode == kCameraAware;
+  p.rays = aware ? ds.rays[p.ip.cam] : nullptr;
+  p.jac = aware ? ds.jac[p.ip.cam] : nullptr;
+  p.border = ds.pat->border;
+  p.reach = ds.pat->reach;
+  p.extra = ds.pat->n_points - 64;
+  return p;
 }
 
 // One keypoint: valid byte (bit 0 = inside the rim and a usable ray, bits 1..6 = scale index of the
 // scale-invariant extractor), M into the first 16 bytes of the (not yet written) descriptor slot, the
 // record into kps_tmp.
-__device__ __forceinline__ void describe_setup_one(const DescribeSetup& ds, int w, int h, int img, size_t slot,
-                                                   const okvfe_keypoint& kp) {
-  const ImageParams ip = ds.prm[img];
+__device__ __forceinline__ void describe_setup_one(const DescribeSetup& ds, const DescribeImageParams& dp, int w, int h,
+                                                   int img, size_t slot, const okvfe_keypoint& kp) {
+  const ImageParams& ip = dp.ip;
   int scale = 0;
   if (ds.scales) {
     for (int i = 1; i < kPatternScales; ++i) scale += kp.size >= ds.scales->size_from[i] ? 1 : 0;
   }
-  const int border = ds.scales ? ds.scales->border[scale] : ds.pat->border;
+  const int border = ds.scales ? ds.scales->border[scale] : dp.border;
   bool valid = !(kp.x < (float)border || kp.x >= (float)(w - border) || kp.y < (float)border ||
                  kp.y >= (float)(h - border));
   float M[4] = {1.0f, 0.0f, 0.0f, 1.0f};
+  // (the first extra sample's constants travel with the ray and the Jacobian, each further one's with the rows of the
+  // sample before it: read where they are used, every sample began with a round trip for five uniform words)
+  const bool extras = ip.mode == kCameraAware && !ds.scales && ds.extra_box > 0 && dp.extra > 0 && !(kSelectOff & 2);
+  ExtraSampleParams sp{};
+  if (extras) sp = extra_sample_params(ds.pat, 0);
   if (valid && ip.mode == kCameraAware) {
     const float dir[3] = {ip.dir[0], ip.dir[1], ip.dir[2]};
-    valid = camera_aware_matrix(ds.rays[ip.cam], ds.jac[ip.cam], w, ip.fu, dir, kp.x, kp.y, M);
+    valid = camera_aware_matrix(dp.rays, dp.jac, w, ip.fu, dir, kp.x, kp.y, M);
   }
-  *reinterpret_cast<float4*>(ds.desc_tmp + slot * OKVFE_DESC_BYTES) = make_float4(M[0], M[1], M[2], M[3]);
+  OKVFE_TAIL_STORE(*reinterpret_cast<float4*>(ds.desc_tmp + slot * OKVFE_DESC_BYTES) = make_float4(M[0], M[1], M[2], M[3]));
   if (ip.mode == kCameraAware && !ds.scales) {
     // patch geometry for describe_aware_kernel (k_describe_aware.hip), bytes 16..23 of the slot: a superset of every
     // sample box under M -- |M p|_x <= |row_x(M)| |p|, boxes are not scaled by M, a box spans at most half a pixel
@@ -202,7 +265,7 @@ __device__ __forceinline__ void describe_setup_one(const DescribeSetup& ds, int 
     // the image (boxes that leave it drop the keypoint).  Class 0 / 1: rows of 64 / 80 bytes in LDS; 3: neither.
     int g0 = 0, g1 = 3 << 29;
     if (valid) {
-      const float reach = ds.pat->reach;
+      const float reach = dp.reach;
       float nx = M[0] * M[0], t = M[1] * M[1];
       nx = sqrtf(nx + t) * 1.001f;
       float ny = M[2] * M[2];
@@ -227,18 +290,27 @@ __device__ __forceinline__ void describe_setup_one(const DescribeSetup& ds, int 
         }
       }
     }
-    *reinterpret_cast<int2*>(ds.desc_tmp + slot * OKVFE_DESC_BYTES + 16) = make_int2(g0, g1);
+    OKVFE_TAIL_STORE(*reinterpret_cast<int2*>(ds.desc_tmp + slot * OKVFE_DESC_BYTES + 16) = make_int2(g0, g1));
     // ... and the samples beyond its 64 lanes, bytes 24.. of the slot; a box outside the image drops the keypoint
     // (extra_box == 0: the pattern has none, or describe_kernel serves the call)
-    if (valid && ds.extra_box > 0) {
-      const int extra = ds.pat->n_points - 64;  // 1 .. kAwareMaxExtra (host-checked)
-      for (int e = 0; e < extra && valid; ++e)
-        valid = extra_sample_one(ds.pat, ds.images + (size_t)img * w * h, w, h, ds.extra_box, e, M, kp.x, kp.y,
+    if (valid && extras) {
+      const int extra = dp.extra;  // 1 .. kAwareMaxExtra (host-checked)
+      for (int e = 0; e < extra && valid; ++e) {
+        const ExtraSampleParams next = extra_sample_params(ds.pat, e + 1 < extra ? e + 1 : e);
+        valid = extra_sample_one(sp, ds.images + (size_t)img * w * h, w, h, ds.extra_box, e, M, kp.x, kp.y,
                                  ds.desc_tmp + slot * OKVFE_DESC_BYTES);
+        sp = next;
+      }
     }
   }
-  ds.valid_tmp[slot] = (uint8_t)((valid ? 1 : 0) | (scale << 1));
-  ds.kps_tmp[slot] = kp;  // the record travels on from here; describe_kernel only rewrites the angle
+  OKVFE_TAIL_STORE(ds.valid_tmp[slot] = (uint8_t)((valid ? 1 : 0) | (scale << 1)));
+  OKVFE_TAIL_STORE(ds.kps_tmp[slot] = kp);  // the record travels on from here; describe_kernel only rewrites the angle
+}
+
+// (describe_setup_kernel, k_describe.hip: one keypoint per thread of any image)
+__device__ __forceinline__ void describe_setup_one(const DescribeSetup& ds, int w, int h, int img, size_t slot,
+                                                   const okvfe_keypoint& kp) {
+  describe_setup_one(ds, describe_image_params(ds, img), w, h, img, slot, kp);
 }
 
 }  // namespace okvfe

@@ -12,7 +12,16 @@
 //   select_list_kernel         the same over linked lists (fine grids with few keypoints per bin)
 // launch_select picks the form; sorts: k_sort.hip, grid fall-backs: k_select_grid.hip, BRISK scale
 // refinement: k_brisk_refine.hip, shared device helpers: select_common_dev.h.
-// Bound: latency / LDS (no HBM roofline); batches keep all CUs busy with independent images.
+// Bound: one ordered chain of LDS and memory round trips per image; batches keep all CUs busy with independent images.
+// It is not free of memory traffic: 467 KB fetched and 129 KB written per EuRoC image in a 6144-image launch, 379 KB
+// of the fetched bytes by the tail's scattered windows, map entries and extra-sample rows and 110 KB by the candidate
+// records (profiles/select_traffic.txt, priced per source by tools/lab/select_traffic.sh), against 125 KB algorithmic.
+// The chain's memory round trips, as built: set-up -- the first 5120 candidate records in two waves of ten 12-byte
+// loads per lane (branch-free, packed five at a time), then the key scatter; per chunk -- its keys, requested one chunk
+// ahead; tail (refine_emit, one lane per keypoint) -- the kept record, 21 pixel dwords, ray + Jacobian together, the
+// rows of each extra sample (its constants requested one trip ahead).  What is the same for every keypoint of an image
+// (ImageParams, the camera's map pointers, border / reach / point count of the pattern) is loaded at kernel start,
+// before the first store, as scalar loads nothing waits for (describe_image_params, describe_setup_dev.h).
 #include <mutex>
 #include "describe_setup_dev.h"
 #include <type_traits>
@@ -22,10 +31,12 @@
 namespace okvfe {
 namespace {
 
-// ---- K4 of both lazy-occupancy kernels: sub-pixel refinement and emission of kept keypoint i (one lane each) ----
+// ---- K4 of the three lazy-occupancy kernels: sub-pixel refinement and emission of kept keypoint i (one lane each);
+// dp = the image's parameters, loaded once at kernel start ----
 __device__ __forceinline__ void refine_emit(const int32_t* __restrict__ scores, const ScoreLayout& layout, int w, int h,
                                             int img, const uint8_t* __restrict__ images, const DescribeSetup& setup,
-                                            okvfe_keypoint* __restrict__ out, int i, size_t slot) {
+                                            const DescribeImageParams& dp, okvfe_keypoint* __restrict__ out, int i,
+                                            size_t slot) {
   okvfe_keypoint kp = out[i];  // pixel position and exact score, left there by the acceptance
   const int u = (int)kp.x, v = (int)kp.y;
   int32_t patch[9];
@@ -45,10 +56,10 @@ __device__ __forceinline__ void refine_emit(const int32_t* __restrict__ scores, 
   kp.y = (float)v + ddy;
   kp.response = (float)kp.class_id;
   kp.class_id = -1;
-  out[i] = kp;
+  OKVFE_TAIL_STORE(out[i] = kp);
   // detection and description in one call: the extractor's per-keypoint preparation right here
   // (describe_setup_dev.h) instead of a launch of its own
-  if (setup.pat) describe_setup_one(setup, w, h, img, slot, kp);
+  if (setup.pat) describe_setup_one(setup, dp, w, h, img, slot, kp);
 }
 
 // ---- lazy-occupancy selection: no grid, one workgroup of 4 waves per image ----------------------
@@ -176,7 +187,10 @@ __global__ __launch_bounds__(kLazyThreads) __attribute__((amdgpu_waves_per_eu(OK
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int lane = tid & 63;
   const int img = blockIdx.x;
-  int n = cand_count[img];
+  // the tail's per-image parameters: uniform addresses, requested before the kernel's first store (scalar loads)
+  const DescribeImageParams dp = setup.pat ? describe_image_params(setup, img) : DescribeImageParams{};
+  const int cimg = (kSelectOff & 8) ? 0 : img;  // (lab: whose candidate list this image reads)
+  int n = cand_count[cimg];
   // overflowed candidate list: WHICH maxima were dropped depends on the order of the atomics, so
   // the image keeps no keypoints at all (deterministic) and okvfe_check_capacity reports it
   n = n > cand_cap ? 0 : n;
@@ -190,6 +204,40 @@ __global__ __launch_bounds__(kLazyThreads) __attribute__((amdgpu_waves_per_eu(OK
   int n_surv = 0, n_rounds = 0;
 #endif
   if (n > 0) {  // block-uniform
+    // SORTS: the first 5120 candidate records are read ONCE and STAY in registers as {score, y << 16 | x} for both bucket passes:
+    // in a batch every pass over the records is 53 KB per image from HBM (81 MB per 1536 images: 16 us)
+    const Candidate* crec = cand + (size_t)cimg * cand_cap;
+    int32_t scv0[SORTS ? kFuseFirst : 1];
+    uint32_t pyx0[SORTS ? kFuseFirst : 1];
+    // One 12-byte load per record, in four groups of five: a group is packed to {score, y << 16 | x} as it lands,
+    // with the next group's loads already in flight (twenty whole records in flight need 60 registers and spill;
+    // three loads per record -- x and y as 16-bit values -- tripled the load instructions of the set-up).
+    constexpr int kGroup = 5;
+    auto request = [&](int g, Candidate (&c)[kGroup]) {
+#pragma unroll
+      for (int k = 0; k < kGroup; ++k) {
+        // (a lane past the list reads the last record instead of branching round its load: a load inside a branch is
+        // waited for inside it, and the twenty loads of a lane became twenty serial round trips)
+        c[k] = crec[min(tid + (g * kGroup + k) * kLazyThreads, n - 1)];
+      }
+    };
+    auto pack = [&](int g, const Candidate (&c)[kGroup]) {
+#pragma unroll
+      for (int k = 0; k < kGroup; ++k) {
+        const bool in = tid + (g * kGroup + k) * kLazyThreads < n;
+        pyx0[g * kGroup + k] = in ? ((uint32_t)c[k].y << 16) | ((uint32_t)c[k].x & 0xFFFFu) : 0u;
+        scv0[g * kGroup + k] = in ? c[k].score : INT_MIN;
+        // (pins the packing here, before the next group's loads: left to itself the compiler requests all twenty
+        // records first and keeps the 60 registers they need in scratch)
+        asm volatile("" : "+v"(pyx0[g * kGroup + k]), "+v"(scv0[g * kGroup + k]) : : "memory");
+      }
+    };
+    static_assert(kFuseFirst == 4 * kGroup, "four groups");
+    Candidate ca[kGroup], cb[kGroup];
+    if constexpr (SORTS) {  // (the first two groups travel while the tables are set up)
+      request(0, ca);
+      request(1, cb);
+    }
     // weight(|dx|, |dy|) at [|dy| << 5 | |dx|], zero outside the 31 x 31 stamp
     for (int i = tid; i < 32 * 32; i += kLazyThreads) {
       const int dx = i & 31, dy = i >> 5;
@@ -207,30 +255,13 @@ __global__ __launch_bounds__(kLazyThreads) __attribute__((amdgpu_waves_per_eu(OK
     if constexpr (SORTS) {  // bucket counts: in the survivor buffer, which is idle until the first chunk
       for (int i = tid; i <= kFuseBins; i += kLazyThreads) reinterpret_cast<uint32_t*>(surv)[i] = 0u;
     }
-    // SORTS: the first 5120 candidate records are are read ONCE and STAY in registers as {score, y << 16 | x} for both bucket passes:
-    // in a batch every pass over the records is 53 KB per image from HBM (81 MB per 1536 images: 16 us)
-    const Candidate* crec = cand + (size_t)img * cand_cap;
-    int32_t scv0[SORTS ? kFuseFirst : 1];
-    uint32_t pyx0[SORTS ? kFuseFirst : 1];
     if constexpr (SORTS) {
-      // (x and y are read as 16-bit values, not with the record: twenty whole 12-byte records in flight need 60
-      // registers, and four of them spilled to scratch)
-      typedef unsigned short ushort2_t __attribute__((ext_vector_type(2)));
-#pragma unroll
-      for (int u = 0; u < kFuseFirst; ++u) {
-        const int i = tid + u * kLazyThreads;
-        if (i < n) {
-          const unsigned short* c16 = reinterpret_cast<const unsigned short*>(crec + i);
-          ushort2_t yx;
-          yx.x = c16[0];
-          yx.y = c16[2];
-          pyx0[u] = __builtin_bit_cast(uint32_t, yx);
-          scv0[u] = crec[i].score;
-        } else {
-          pyx0[u] = 0u;
-          scv0[u] = INT_MIN;
-        }
-      }
+      pack(0, ca);
+      request(2, ca);
+      pack(1, cb);
+      request(3, cb);
+      pack(2, ca);
+      pack(3, cb);
     }
     const float scaling = (float)(15.0 / (double)radius);
     float max_score = 1.0f;  // the highest score of the image (SORTS: known after the bucket pass)
@@ -728,11 +759,16 @@ __global__ __launch_bounds__(kLazyThreads) __attribute__((amdgpu_waves_per_eu(OK
 #ifdef OKVFE_LAB
       t_pb = __builtin_amdgcn_s_memrealtime();
 #endif
+#if defined(OKVFE_LAB) && defined(OKVFE_SELECT_OFF)
+      const bool keys_live = !(kSelectOff & 4) || g_select_off_flag == 0;
+#else
+      constexpr bool keys_live = true;
+#endif
 #pragma unroll
       for (int u = 0; u < kFuseFirst; ++u) {
         if (tid + u * kLazyThreads < n) {
           const uint32_t p = atomicAdd(&hist[fuse_bin(scv0[u])], 1u);
-          keys[p] = ((uint64_t)(uint32_t)(0x7FFFFFFF - scv0[u]) << 32) | pyx0[u];  // = make_key
+          if (keys_live) keys[p] = ((uint64_t)(uint32_t)(0x7FFFFFFF - scv0[u]) << 32) | pyx0[u];  // = make_key
         }
       }
       for (int base = tid + kFuseFirst * kLazyThreads; base < n; base += kFuseUnroll * kLazyThreads) {  // (more than 5120)
@@ -746,7 +782,7 @@ __global__ __launch_bounds__(kLazyThreads) __attribute__((amdgpu_waves_per_eu(OK
         for (int u = 0; u < kFuseUnroll; ++u) {
           if (base + u * kLazyThreads < n) {
             const uint32_t p = atomicAdd(&hist[fuse_bin(cv[u].score)], 1u);
-            keys[p] = make_key(cv[u]);
+            if (keys_live) keys[p] = make_key(cv[u]);
           }
         }
       }
@@ -1006,8 +1042,9 @@ __global__ __launch_bounds__(kLazyThreads) __attribute__((amdgpu_waves_per_eu(OK
 #ifdef OKVFE_LAB
   t_blocks = __builtin_amdgcn_s_memrealtime();
 #endif
-  for (int i = tid; i < kept; i += kLazyThreads)
-    refine_emit(scores, layout, w, h, img, images, setup, out, i, (size_t)img * kp_cap + i);
+  if (!(kSelectOff & 1))
+    for (int i = tid; i < kept; i += kLazyThreads)
+      refine_emit(scores, layout, w, h, img, images, setup, dp, out, i, (size_t)img * kp_cap + i);
   if (tid == 0) kp_count[img] = kept;
 #ifdef OKVFE_LAB
   __syncthreads();
@@ -1079,6 +1116,8 @@ __global__ __launch_bounds__(kLazyThreads) __attribute__((amdgpu_waves_per_eu(6,
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int lane = tid & 63;
   const int img = blockIdx.x;
+  // the tail's per-image parameters: uniform addresses, requested before the kernel's first store (scalar loads)
+  const DescribeImageParams dp = setup.pat ? describe_image_params(setup, img) : DescribeImageParams{};
   int n = cand_count[img];
   // overflowed candidate list: WHICH maxima were dropped depends on the order of the atomics, so
   // the image keeps no keypoints at all (deterministic) and okvfe_check_capacity reports it
@@ -1298,7 +1337,7 @@ __global__ __launch_bounds__(kLazyThreads) __attribute__((amdgpu_waves_per_eu(6,
   // ---- K4: sub-pixel refinement and keypoint emission (all four waves)
   __syncthreads();
   for (int i = tid; i < kept; i += kLazyThreads)
-    refine_emit(scores, layout, w, h, img, images, setup, out, i, (size_t)img * kp_cap + i);
+    refine_emit(scores, layout, w, h, img, images, setup, dp, out, i, (size_t)img * kp_cap + i);
   if (tid == 0) kp_count[img] = kept;
 }
 
@@ -1391,6 +1430,14 @@ bool launch_select(const int32_t* score, ScoreLayout layout, int w, int h, int n
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLazyMaxLds) != hipSuccess)
         (void)hipGetLastError();
     });
+#if defined(OKVFE_LAB) && defined(OKVFE_SELECT_OFF)
+    if (kSelectOff & 4) {  // from the second full batch on the key workspace holds these images' keys already
+      static int full_batches = 0;
+      static const int one = 1;
+      if (n_images >= 1024 && ++full_batches == 2)
+        (void)hipMemcpyToSymbolAsync(HIP_SYMBOL(g_select_off_flag), &one, sizeof(one), 0, hipMemcpyHostToDevice, stream);
+    }
+#endif
 #define OKVFE_LAZY_LAUNCH(SORTS)                                                                                     \
   hipLaunchKernelGGL(select_lazy_kernel<SORTS>, dim3(n_images), dim3(kLazyThreads), lp.lds, stream, score, layout, w, \
                      h, cand, cand_cap, cand_count, sort_ws, ws_stride, radius, max_kpts, lut, lp.bins_x, lp.bins_y,  \
