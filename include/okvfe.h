@@ -671,6 +671,55 @@ okvfe_status okvfe_match_motion_stereo_blocks_device(okvfe_ctx* ctx, int32_t cam
                                                      const okvfe_pose* T_WC0,
                                                      const okvfe_pose* T_WC1,
                                                      okvfe_motion_match* matches_dev, void* stream);
+/* The same for n_pairs (older frame, current frame, camera) triples in ONE launch, and -- with `claim` -- the part of
+ * matchMotionStereo's insertion loop that depends on frame data alone, so that the sweep of a current multiframe over
+ * its older keyframes (Frontend.cpp:1773-1775), for a whole batch of current frames, is queued without the host
+ * waiting for anything.
+ *
+ * Matching = Frontend.cpp:1789-1905.  Pair p matches older block idx0[p] of blocks0_dev (frame 0) against current
+ * block idx1[p] of blocks1_dev (frame 1), both arrays contiguous with the stride okvfe_gather_block_bytes, with the
+ * camera of slot cam_ids[p] (okvfe_set_camera; f0 = 0.5 (fu + fv) of the slot, :1786).  Row (p, k0) of matches_dev
+ * [n_pairs][K], K = okvfe_device_outputs.max_keypoints, holds the bytes okvfe_match_motion_stereo_blocks_device writes
+ * for that pair given row p of skip0_dev [n_pairs][K] (pair-major) and row idx1[p] of matched1_dev [n_blocks1][K]
+ * (indexed by the CURRENT block); either array may be NULL.  Rows at or past the older block's count are untouched.
+ * The same older block may appear in several pairs.  idx0 / idx1 NULL = the identity (pair p uses block p).
+ *
+ * Claims = Frontend.cpp:1915-1958 restricted to frame data.  Row (p, k0) is a candidate iff k0 < count0, k1 >= 0 and
+ * accepted != 0 (a skipped k0 has k1 == -1, so the re-checks at :1923-1933 add nothing).  Candidates are visited in
+ * ascending k0 (:1916); a candidate is claimed iff its k1 is free: matched1_out is NULL or
+ * matched1_out[idx1[p] K + k1] == 0 when the claim kernel starts, and no candidate with a smaller k0 of this pair has
+ * the same k1 (:1935-1938) -- for each free k1 the candidate with the smallest k0 wins.  n_claimed[p] counts the
+ * winners (the pair's share of retCtr, :1957); matched1_out gets 1 at the winners' k1 (:1954) and is otherwise
+ * unchanged.  Pairs are resolved in parallel, so a call with claim != NULL must not name a current block twice
+ * (OKVFE_ERR_INVALID_ARGUMENT, the block and both pairs named); without claim repeats are allowed: one frozen
+ * matched1 against many older frames.  With claim, K above 12288 is OKVFE_ERR_UNSUPPORTED (the per-pair owner table of
+ * 4 K bytes stays within 48 KB of LDS); matching alone has no such limit.
+ *
+ * What stays with the caller: skip0 stands for the estimator-state tests of :1814-1841.  An earlier step of a sweep
+ * can initialise a landmark that a keypoint of a later older frame carries; the quality comparison at :1943
+ * (lm.quality < acos(cos_quality)) and setLandmark / addLandmark / addObservation (:1940-1956) need estimator state
+ * and a libm acos.  A caller that needs that coupling refreshes its skip0 rows between the calls, on the device or the
+ * host; with skip0 fixed up front the sweep equals the reference whenever no such landmark exists.  A landmark observed
+ * by two keypoints of one older image is not modelled.  runRansac2d2d (:1964-1969, before initialisation only) and the
+ * choice and order of the older frames (:1742-1767) stay with the caller as well.
+ *
+ * An index outside [0, n_blocks*), a NULL required pointer, a negative count, a camera slot out of range or without
+ * intrinsics (the pair and the slot named): OKVFE_ERR_INVALID_ARGUMENT before anything is launched.  n_pairs == 0 is OK
+ * and launches nothing.  One record per pair (256 bytes) goes through the pinned parameter ring; nothing synchronises
+ * the host. */
+typedef struct okvfe_motion_claim_device { /* every member device memory; the struct pointer may be NULL */
+  uint8_t* claimed;      /* n_pairs x K: 1 = row (p, k0) is inserted by :1915-1958, 0 = not; rows >= count0 untouched */
+  int32_t* n_claimed;    /* n_pairs: the pair's contribution to retCtr (:1957); written, not accumulated */
+  uint8_t* matched1_out; /* n_blocks1 x K or NULL: byte k1 of the pair's CURRENT block becomes 1 where claimed;
+                          * may be matched1_dev itself (the in-place sweep) */
+} okvfe_motion_claim_device;
+okvfe_status okvfe_match_motion_stereo_blocks_batch_device(
+    okvfe_ctx* ctx, const void* blocks0_dev, int32_t n_blocks0, const void* blocks1_dev, int32_t n_blocks1,
+    int32_t n_pairs, const int32_t* idx0 /* HOST n_pairs or NULL = p */, const int32_t* idx1 /* HOST or NULL = p */,
+    const int32_t* cam_ids /* HOST n_pairs */, const okvfe_pose* T_WC0 /* HOST n_pairs */,
+    const okvfe_pose* T_WC1 /* HOST n_pairs */, const uint8_t* skip0_dev /* n_pairs x K, pair-major, or NULL */,
+    const uint8_t* matched1_dev /* n_blocks1 x K, indexed by CURRENT block, or NULL */,
+    okvfe_motion_match* matches_dev /* n_pairs x K */, const okvfe_motion_claim_device* claim, void* stream);
 /* Matches two gathered blocks (device), as okvfe_match_stereo_batch_device. */
 okvfe_status okvfe_match_stereo_blocks_device(okvfe_ctx* ctx, const void* block0_dev,
                                               const void* block1_dev, const okvfe_pose* T_WC0,

@@ -117,6 +117,7 @@ EXPORTS = [
     "okvfe_landmark_table_check_device", "okvfe_match_to_map_table_blocks_device",
     "okvfe_match_to_map_table_uninitialised_blocks_device",
     "okvfe_ransac3d2d_consensus_blocks_device", "okvfe_remove_outliers_blocks_device",
+    "okvfe_match_motion_stereo_blocks_batch_device",
 ]
 
 STAGES = ["harris", "nms", "sort", "select", "map", "describe", "compact", "match"]
@@ -152,6 +153,13 @@ class RansacResultDevice(C.Structure):
                 ("accepted", C.c_void_p), ("hyp_inliers", C.c_void_p), ("state", C.c_void_p),
                 ("distance", C.c_void_p), ("landmark_out", C.c_void_p)]
 
+
+class MotionClaimDevice(C.Structure):
+    """okvfe_motion_claim_device: device pointers; matched1_out is optional (None)."""
+    _fields_ = [("claimed", C.c_void_p), ("n_claimed", C.c_void_p), ("matched1_out", C.c_void_p)]
+
+
+MOTION_CLAIM_MAX_KEYPOINTS = 12288  # K above it: claims are OKVFE_ERR_UNSUPPORTED
 
 RANSAC_MAX_HYPOTHESES = 64  # OKVFE_RANSAC_MAX_HYPOTHESES
 RANSAC_THRESHOLD = 16.0     # Frontend.cpp:2235
@@ -201,6 +209,9 @@ def lib():
             V, V, V, C.c_int32, C.c_int32, V, V, V, V, V, C.c_int32, C.c_double, C.c_int32, V, V]
         L.okvfe_remove_outliers_blocks_device.restype = C.c_int32
         L.okvfe_remove_outliers_blocks_device.argtypes = [V, V, V, C.c_int32, V, V, C.c_double, V, V, V, V]
+        L.okvfe_match_motion_stereo_blocks_batch_device.restype = C.c_int32
+        L.okvfe_match_motion_stereo_blocks_batch_device.argtypes = [
+            V, V, C.c_int32, V, C.c_int32, C.c_int32, V, V, V, V, V, V, V, V, V, V]
         _LIB = L
     return _LIB
 
@@ -991,6 +1002,34 @@ class Frontend:
         self._check(lib().okvfe_match_motion_stereo_blocks_device(
             self._h, int(cam), _p(block0_ptr), _p(block1_ptr), _p(skip0_ptr), _p(matched1_ptr),
             C.byref(P0), C.byref(P1), _p(matches_ptr), _s(stream)))
+
+    def match_motion_stereo_blocks_batch_device(self, blocks0_ptr, n_blocks0, blocks1_ptr, n_blocks1, idx0, idx1,
+                                                cam_ids, poses_T_WC0, poses_T_WC1, skip0_ptr, matched1_ptr,
+                                                matches_ptr, claim=None, stream=None):
+        """matchMotionStereo for len(cam_ids) (older block idx0[p], current block idx1[p], camera slot cam_ids[p])
+        pairs in one launch.  idx0 / idx1: host int sequences or None (= pair p uses block p); poses: host sequences of
+        (C, r), one per pair; skip0_ptr: device n_pairs x K (pair-major) or None; matched1_ptr: device n_blocks1 x K
+        (by current block) or None; matches_ptr: device n_pairs x K MOTION_MATCH_DTYPE.  claim: None, or a dict of
+        device pointers {"claimed": n_pairs x K uint8, "n_claimed": n_pairs int32, "matched1_out": n_blocks1 x K uint8
+        or None (may be matched1_ptr)} -- the frame-data part of the insertion loop (Frontend.cpp:1915-1958)."""
+        cams = np.ascontiguousarray(cam_ids, dtype=np.int32)
+        n = len(cams)
+        if len(poses_T_WC0) != n or len(poses_T_WC1) != n:
+            raise ValueError("poses: one (C, r) per pair")
+        i0 = None if idx0 is None else np.ascontiguousarray(idx0, dtype=np.int32)
+        i1 = None if idx1 is None else np.ascontiguousarray(idx1, dtype=np.int32)
+        if (i0 is not None and len(i0) != n) or (i1 is not None and len(i1) != n):
+            raise ValueError("idx0 / idx1: one block index per pair")
+        P0 = (Pose * max(n, 1))(*[make_pose(*T) for T in poses_T_WC0])
+        P1 = (Pose * max(n, 1))(*[make_pose(*T) for T in poses_T_WC1])
+        cd = None
+        if claim is not None:
+            cd = MotionClaimDevice(int(claim["claimed"] or 0) or None, int(claim["n_claimed"] or 0) or None,
+                                   int(claim.get("matched1_out") or 0) or None)
+        self._check(lib().okvfe_match_motion_stereo_blocks_batch_device(
+            self._h, _p(blocks0_ptr), int(n_blocks0), _p(blocks1_ptr), int(n_blocks1), n,
+            _p(i0) if n else None, _p(i1) if n else None, _p(cams) if n else None, P0, P1, _p(skip0_ptr),
+            _p(matched1_ptr), _p(matches_ptr), C.byref(cd) if cd is not None else None, _s(stream)))
 
     def match_stereo_blocks_device(self, block0_ptr, block1_ptr, T0, T1, f0, f1, matches_ptr,
                                    stream=None):

@@ -436,6 +436,101 @@ okvfe_status okvfe_match_motion_stereo_blocks_device(okvfe_ctx* ctx, int32_t cam
   return ring_release(ctx, &ctx->cls_ring, cls_slot, s);
 }
 
+okvfe_status okvfe_match_motion_stereo_blocks_batch_device(
+    okvfe_ctx* ctx, const void* blocks0_dev, int32_t n_blocks0, const void* blocks1_dev, int32_t n_blocks1,
+    int32_t n_pairs, const int32_t* idx0, const int32_t* idx1, const int32_t* cam_ids, const okvfe_pose* T_WC0,
+    const okvfe_pose* T_WC1, const uint8_t* skip0_dev, const uint8_t* matched1_dev, okvfe_motion_match* matches_dev,
+    const okvfe_motion_claim_device* claim, void* stream) {
+  static const char* const fn = "okvfe_match_motion_stereo_blocks_batch_device";
+  if (!ctx) return OKVFE_ERR_INVALID_ARGUMENT;
+  if (n_pairs < 0 || n_blocks0 < 0 || n_blocks1 < 0)
+    return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "%s: negative count (n_blocks0 %d, n_blocks1 %d, n_pairs %d)", fn,
+                n_blocks0, n_blocks1, n_pairs);
+  if (n_pairs == 0) return OKVFE_OK;
+  if (!blocks0_dev || !blocks1_dev || !cam_ids || !T_WC0 || !T_WC1 || !matches_dev)
+    return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "%s: NULL %s", fn,
+                !blocks0_dev ? "blocks0_dev" : !blocks1_dev ? "blocks1_dev" : !cam_ids ? "cam_ids"
+                : !T_WC0 ? "T_WC0" : !T_WC1 ? "T_WC1" : "matches_dev");
+  if (claim && (!claim->claimed || !claim->n_claimed))
+    return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "%s: NULL claim->%s", fn, !claim->claimed ? "claimed" : "n_claimed");
+  // every record is built and checked before anything is queued
+  std::vector<MotionPairRecord> recs((size_t)n_pairs);
+  std::vector<int> slots;                                   // distinct camera slots of the call ...
+  std::vector<int> slot_of((size_t)n_pairs);                // ... and each pair's position among them
+  std::vector<int32_t> user(claim ? (size_t)n_blocks1 : 0, -1);  // with claims: the pair that names a current block
+  bool rt8 = false;
+  for (int p = 0; p < n_pairs; ++p) {
+    const int i0 = idx0 ? idx0[p] : p, i1 = idx1 ? idx1[p] : p, cam = cam_ids[p];
+    if (i0 < 0 || i0 >= n_blocks0)
+      return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "%s: pair %d: older block %d outside [0, %d)", fn, p, i0, n_blocks0);
+    if (i1 < 0 || i1 >= n_blocks1)
+      return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "%s: pair %d: current block %d outside [0, %d)", fn, p, i1, n_blocks1);
+    if (cam < 0 || cam >= (int)ctx->h_cams.size())
+      return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "%s: pair %d: camera slot %d outside [0, %d)", fn, p, cam,
+                  (int)ctx->h_cams.size());
+    const DeviceCamera& dc = ctx->h_cams[cam];
+    if (!(dc.fu > 0.0))
+      return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "%s: pair %d: camera slot %d has no intrinsics (okvfe_set_camera)", fn,
+                  p, cam);
+    if (claim) {
+      if (user[i1] >= 0)
+        return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT,
+                    "%s: current block %d is named by pairs %d and %d: with claims a call resolves a current block once",
+                    fn, i1, user[i1], p);
+      user[i1] = p;
+    }
+    rt8 = rt8 || dc.distortion == OKVFE_DIST_RADTAN8;
+    okvfe_stereo_pair sp{};
+    sp.T_WC0 = T_WC0[p]; sp.T_WC1 = T_WC1[p];
+    sp.f0 = sp.f1 = 0.5 * (dc.fu + dc.fv);  // sigma = size0 / f0 * 0.125 (Frontend.cpp:1834)
+    recs[p].pair = to_pair_params(sp);
+    recs[p].cam = cam; recs[p].idx0 = i0; recs[p].idx1 = i1; recs[p].pad = 0;
+    size_t j = 0;
+    while (j < slots.size() && slots[j] != cam) ++j;
+    if (j == slots.size()) slots.push_back(cam);
+    slot_of[p] = (int)j;
+  }
+  if (claim && ctx->kp_cap > kMotionClaimMaxKeypoints)
+    return fail(ctx, OKVFE_ERR_UNSUPPORTED, "%s: claims need max_keypoints <= %d (this context: %d)", fn,
+                kMotionClaimMaxKeypoints, ctx->kp_cap);
+  HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
+  hipStream_t s = pick_stream(ctx, stream);
+  const BlockLayout L = block_layout(ctx->kp_cap);
+  const int offs[6] = {(int)L.o_count, (int)L.o_kps, (int)L.o_desc, (int)L.o_bp, (int)L.o_bpv, (int)L.total};
+  okvfe_status st;
+  int cls_slot = -1;
+  if (ctx->n_layers > 1) {  // one size-class table per distinct camera slot
+    std::vector<double> tables(slots.size() * kClassTableDoubles);
+    for (size_t j = 0; j < slots.size(); ++j) {
+      const DeviceCamera& dc = ctx->h_cams[slots[j]];
+      const double f = 0.5 * (dc.fu + dc.fv);
+      fill_class_table(tables.data() + j * kClassTableDoubles, f, f, true);
+    }
+    void* d_tab = nullptr;
+    if ((st = ring_upload(ctx, &ctx->cls_ring, tables.data(), tables.size() * sizeof(double), s, &d_tab, &cls_slot)) !=
+        OKVFE_OK)
+      return st;
+    for (int p = 0; p < n_pairs; ++p)
+      recs[p].pair.cls = static_cast<const double*>(d_tab) + (size_t)slot_of[p] * kClassTableDoubles;
+  }
+  void* d_recs = nullptr;
+  int slot = -1;
+  if ((st = ring_upload(ctx, &ctx->pair_ring, recs.data(), recs.size() * sizeof(MotionPairRecord), s, &d_recs, &slot)) !=
+      OKVFE_OK)
+    return st;
+  launch_match_motion_pairs(static_cast<const MotionPairRecord*>(d_recs), n_pairs, ctx->d_cams, ctx->w, ctx->h, offs,
+                            static_cast<const uint8_t*>(blocks0_dev), static_cast<const uint8_t*>(blocks1_dev),
+                            skip0_dev, matched1_dev, ctx->kp_cap, ctx->cfg.match_threshold, matches_dev, s, rt8);
+  if (claim)  // behind the match kernel on the stream: matched1_out may be matched1_dev
+    launch_motion_claim(static_cast<const MotionPairRecord*>(d_recs), n_pairs, offs,
+                        static_cast<const uint8_t*>(blocks0_dev), ctx->kp_cap, matches_dev, claim->claimed,
+                        claim->n_claimed, claim->matched1_out, s);
+  HIP_TRY(ctx, hipGetLastError());
+  ctx->last_stream = s;
+  if ((st = ring_release(ctx, &ctx->pair_ring, slot, s)) != OKVFE_OK) return st;
+  return ring_release(ctx, &ctx->cls_ring, cls_slot, s);
+}
+
 okvfe_status okvfe_match_stereo_blocks_device(okvfe_ctx* ctx, const void* block0_dev, const void* block1_dev,
                                               const okvfe_pose* T_WC0, const okvfe_pose* T_WC1, double f0,
                                               double f1, okvfe_stereo_match* matches_dev, void* stream) {

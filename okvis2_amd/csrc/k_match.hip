@@ -1493,6 +1493,73 @@ __global__ __launch_bounds__(64 * kStereoSegs) void match_motion_blocks_kernel(
   match_motion_rows<kRT8>(pair, *camera, w, h, I0, I1, threshold, out);
 }
 
+// ... on many (older block, current block, camera slot) pairs in one launch: grid (rows, pairs), the pair's record
+// (MotionPairRecord: poses, slot, the two block indices) read from the parameter ring.  skip0 is pair-major, matched1
+// is indexed by the pair's CURRENT block.  A work-group past the older block's count leaves on match_motion_rows'
+// first test, which depends on blockIdx only: uniform, ahead of its barrier.
+template <bool kRT8>
+__global__ __launch_bounds__(64 * kStereoSegs) void match_motion_pairs_kernel(
+    const MotionPairRecord* __restrict__ recs, const DeviceCamera* __restrict__ cams, int w, int h,
+    BlockOffsets L, const uint8_t* __restrict__ blocks0, const uint8_t* __restrict__ blocks1,
+    const uint8_t* __restrict__ skip0, const uint8_t* __restrict__ matched1, int kp_cap, int threshold,
+    okvfe_motion_match* __restrict__ out) {
+  const MotionPairRecord& R = recs[blockIdx.y];
+  const uint8_t* b0 = blocks0 + (size_t)R.idx0 * L.total;
+  const uint8_t* b1 = blocks1 + (size_t)R.idx1 * L.total;
+  MotionView I0, I1;
+  I0.desc = b0 + L.o_desc; I0.kps = reinterpret_cast<const okvfe_keypoint*>(b0 + L.o_kps);
+  I0.bp = reinterpret_cast<const double*>(b0 + L.o_bp); I0.bpv = b0 + L.o_bpv;
+  I0.flag = skip0 ? skip0 + (size_t)blockIdx.y * kp_cap : nullptr;
+  I0.n = *reinterpret_cast<const int32_t*>(b0 + L.o_count);
+  I1.desc = b1 + L.o_desc; I1.kps = reinterpret_cast<const okvfe_keypoint*>(b1 + L.o_kps);
+  I1.bp = reinterpret_cast<const double*>(b1 + L.o_bp); I1.bpv = b1 + L.o_bpv;
+  I1.flag = matched1 ? matched1 + (size_t)R.idx1 * kp_cap : nullptr;
+  I1.n = *reinterpret_cast<const int32_t*>(b1 + L.o_count);
+  match_motion_rows<kRT8>(R.pair, cams[R.cam], w, h, I0, I1, threshold, out + (size_t)blockIdx.y * kp_cap);
+}
+
+// The frame-data part of matchMotionStereo's insertion loop (Frontend.cpp:1915-1958) on the rows the kernel above
+// wrote: one work-group per pair.  Row k0 is a candidate iff k0 < count0, k1 >= 0 and accepted; visited in ascending
+// k0 a candidate is inserted iff its k1 carries no landmark yet (:1935-1938), i.e. iff it is the smallest k0 among
+// the candidates of a free k1.  owner[k1] (dynamic LDS, 4 * kp_cap bytes): -1 = taken when the kernel starts, else
+// the smallest candidate k0 (INT_MAX: none).  Every read of matched1_out happens before the second barrier and every
+// write after it, so matched1_out may be the array the match kernel of the same call read.  The winners' k1 are
+// distinct: plain byte stores, no global atomics, nothing to zero beforehand.
+__global__ __launch_bounds__(256) void motion_claim_kernel(
+    const MotionPairRecord* __restrict__ recs, BlockOffsets L, const uint8_t* __restrict__ blocks0, int kp_cap,
+    const okvfe_motion_match* __restrict__ matches, uint8_t* __restrict__ claimed, int32_t* __restrict__ n_claimed,
+    uint8_t* matched1_out) {
+  extern __shared__ int32_t claim_owner[];
+  __shared__ int wave_claims[4];
+  const int p = blockIdx.x, tid = threadIdx.x;
+  const MotionPairRecord& R = recs[p];
+  const int count0 = min(max(*reinterpret_cast<const int32_t*>(blocks0 + (size_t)R.idx0 * L.total + L.o_count), 0), kp_cap);
+  uint8_t* m1 = matched1_out ? matched1_out + (size_t)R.idx1 * kp_cap : nullptr;
+  const okvfe_motion_match* rows = matches + (size_t)p * kp_cap;
+  for (int k1 = tid; k1 < kp_cap; k1 += 256) claim_owner[k1] = (m1 && m1[k1]) ? -1 : INT_MAX;
+  __syncthreads();
+  for (int k0 = tid; k0 < count0; k0 += 256) {
+    const int k1 = rows[k0].k1;
+    if (k1 >= 0 && k1 < kp_cap && rows[k0].accepted != 0) atomicMin(&claim_owner[k1], k0);
+  }
+  __syncthreads();
+  int mine = 0;  // winners seen by this wave (the same in all its lanes)
+  for (int base = 0; base < count0; base += 256) {  // uniform bounds: the ballot sees whole waves
+    const int k0 = base + tid;
+    bool win = false;
+    if (k0 < count0) {
+      const int k1 = rows[k0].k1;
+      win = k1 >= 0 && k1 < kp_cap && rows[k0].accepted != 0 && claim_owner[k1] == k0;
+      claimed[(size_t)p * kp_cap + k0] = win ? 1 : 0;
+      if (win && m1) m1[k1] = 1;
+    }
+    mine += __popcll(__ballot(win));
+  }
+  if ((tid & 63) == 0) wave_claims[tid >> 6] = mine;
+  __syncthreads();
+  if (tid == 0) n_claimed[p] = wave_claims[0] + wave_claims[1] + wave_claims[2] + wave_claims[3];
+}
+
 
 // ---- DBoW2 database query, L1 scoring (TemplatedDatabase::queryL1 behind Frontend.cpp:756-766) ----
 // One thread per database entry: merge-join of the entry's BowVector with the query's (both in
@@ -1540,6 +1607,31 @@ void launch_match_motion_blocks(const PairParams& pair, const DeviceCamera* came
   const BlockOffsets L{offs[0], offs[1], offs[2], offs[3], offs[4], offs[5]};
   hipLaunchKernelGGL(rt8 ? match_motion_blocks_kernel<true> : match_motion_blocks_kernel<false>, dim3((kp_cap + 63) / 64), dim3(64, kStereoSegs), 0,
                      stream, pair, camera, w, h, L, block0, block1, skip0, matched1, threshold, out);
+}
+
+void launch_match_motion_pairs(const MotionPairRecord* recs, int n_pairs, const DeviceCamera* cams, int w, int h,
+                               const int offs[6], const uint8_t* blocks0, const uint8_t* blocks1,
+                               const uint8_t* skip0, const uint8_t* matched1, int kp_cap, int threshold,
+                               okvfe_motion_match* out, hipStream_t stream, bool rt8) {
+  if (n_pairs <= 0 || kp_cap <= 0) return;
+  const BlockOffsets L{offs[0], offs[1], offs[2], offs[3], offs[4], offs[5]};
+  constexpr int kMaxGridY = 65535;
+  for (int first = 0; first < n_pairs; first += kMaxGridY) {
+    const int n = std::min(kMaxGridY, n_pairs - first);
+    hipLaunchKernelGGL(rt8 ? match_motion_pairs_kernel<true> : match_motion_pairs_kernel<false>,
+                       dim3((kp_cap + 63) / 64, n), dim3(64, kStereoSegs), 0, stream, recs + first, cams, w, h, L,
+                       blocks0, blocks1, skip0 ? skip0 + (size_t)first * kp_cap : nullptr, matched1, kp_cap, threshold,
+                       out + (size_t)first * kp_cap);
+  }
+}
+
+void launch_motion_claim(const MotionPairRecord* recs, int n_pairs, const int offs[6], const uint8_t* blocks0,
+                         int kp_cap, const okvfe_motion_match* matches, uint8_t* claimed, int32_t* n_claimed,
+                         uint8_t* matched1_out, hipStream_t stream) {
+  if (n_pairs <= 0 || kp_cap <= 0) return;
+  const BlockOffsets L{offs[0], offs[1], offs[2], offs[3], offs[4], offs[5]};
+  hipLaunchKernelGGL(motion_claim_kernel, dim3(n_pairs), dim3(256), (size_t)kp_cap * sizeof(int32_t), stream, recs, L,
+                     blocks0, kp_cap, matches, claimed, n_claimed, matched1_out);
 }
 
 void launch_pack_blocks(const int offs[6], int first, int n, int kp_cap, const int32_t* counts,

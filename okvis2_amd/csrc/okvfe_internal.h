@@ -165,6 +165,17 @@ struct PairParams {  // one stereo pair on device
   const double* cls;
 };
 constexpr int kSizeClasses = 8;
+// okvfe_match_motion_stereo_blocks_batch_device: one pair's record in the parameter block (host-filled, one upload per call)
+struct MotionPairRecord {
+  PairParams pair;  // poses, f0 = f1 = 0.5 (fu + fv) of the slot, cls = the slot's size-class table or null
+  int32_t cam;      // camera slot
+  int32_t idx0;     // older block (frame 0) in blocks0
+  int32_t idx1;     // current block (frame 1) in blocks1; also the row of matched1 / matched1_out
+  int32_t pad;
+};
+static_assert(sizeof(MotionPairRecord) == 256, "PairParams (240 bytes) and four int32");
+// (the owner table of motion_claim_kernel, 4 bytes per keypoint slot, within 48 KB of LDS)
+constexpr int kMotionClaimMaxKeypoints = 12288;
 
 // okvfe_match_to_map_table_blocks_device: one frame's record in the parameter block (host-filled, one upload per call)
 struct MapFrameParams {
@@ -442,6 +453,15 @@ void launch_match_motion_blocks(const PairParams& pair, const DeviceCamera* came
                                 const int offs[6], const uint8_t* block0, const uint8_t* block1,
                                 const uint8_t* skip0, const uint8_t* matched1, int kp_cap,
                                 int threshold, okvfe_motion_match* out, hipStream_t stream, bool rt8 = false);
+// n_pairs (older block, current block, slot) pairs in one launch; skip0 [n_pairs][kp_cap], matched1 [n_blocks1][kp_cap]
+void launch_match_motion_pairs(const MotionPairRecord* recs, int n_pairs, const DeviceCamera* cams, int w, int h,
+                               const int offs[6], const uint8_t* blocks0, const uint8_t* blocks1,
+                               const uint8_t* skip0, const uint8_t* matched1, int kp_cap, int threshold,
+                               okvfe_motion_match* out, hipStream_t stream, bool rt8);
+// ... and the frame-data part of the insertion loop on its rows (kp_cap <= kMotionClaimMaxKeypoints)
+void launch_motion_claim(const MotionPairRecord* recs, int n_pairs, const int offs[6], const uint8_t* blocks0,
+                         int kp_cap, const okvfe_motion_match* matches, uint8_t* claimed, int32_t* n_claimed,
+                         uint8_t* matched1_out, hipStream_t stream);
 void launch_match_stereo_blocks(const PairParams& pair, const int offs[6], const uint8_t* blocks0,
                                 const uint8_t* blocks1, int n_frames, int kp_cap, int threshold,
                                 okvfe_stereo_match* out, hipStream_t stream);

@@ -499,6 +499,57 @@ class HipFrontend {
         contexts_[cameraIndex]->get(), &table.get(), blocksDev, nFrames, cams.data(), T_WC.data(), maxError, landmarkDev,
         landmarkOutDev, keptDev, stream));
   }
+  // Frontend::matchMotionStereo's matcher (Frontend.cpp:1789-1905) for idx0.size() (older block, current block) pairs
+  // of camera `cameraIndex` in one launch, and -- with `claim` -- the frame-data part of its insertion loop
+  // (:1915-1958; okvfe.h, okvfe_match_motion_stereo_blocks_batch_device).  blocks0Dev / blocks1Dev: device arrays of
+  // nBlocks0 / nBlocks1 gather blocks; pair p matches older block idx0[p] against current block idx1[p] with the poses
+  // T_WC0[p], T_WC1[p]; skip0Dev: device pairs x K (pair-major) or null; matched1Dev: device nBlocks1 x K (by current
+  // block) or null; matchesDev: device pairs x K.  With claim a current block may appear once.  Nothing synchronises
+  // the host.
+  void matchMotionStereoBlocks(size_t cameraIndex, const void* blocks0Dev, int nBlocks0, const void* blocks1Dev,
+                               int nBlocks1, const std::vector<int32_t>& idx0, const std::vector<int32_t>& idx1,
+                               const std::vector<okvfe_pose>& T_WC0, const std::vector<okvfe_pose>& T_WC1,
+                               const uint8_t* skip0Dev, const uint8_t* matched1Dev, okvfe_motion_match* matchesDev,
+                               const okvfe_motion_claim_device* claim = nullptr, void* stream = nullptr) {
+    if (cameraIndex >= cameras_.size())
+      throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "Camera index exceeds number of cameras.");
+    const size_t n = idx0.size();
+    if (idx1.size() != n || T_WC0.size() != n || T_WC1.size() != n)
+      throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "matchMotionStereoBlocks: two block indices and two poses per pair");
+    std::lock_guard<std::mutex> lock(mutexes_[cameraIndex]);
+    if (!extractors_[cameraIndex].isCameraAware()) extractors_[cameraIndex].setCamera(cameras_[cameraIndex]);
+    const std::vector<int32_t> cams(n + 1, 0);  // slot 0 of the camera's own context
+    contexts_[cameraIndex]->check(okvfe_match_motion_stereo_blocks_batch_device(
+        contexts_[cameraIndex]->get(), blocks0Dev, nBlocks0, blocks1Dev, nBlocks1, int32_t(n), idx0.data(), idx1.data(),
+        cams.data(), T_WC0.data(), T_WC1.data(), skip0Dev, matched1Dev, matchesDev, claim, stream));
+  }
+  // One older frame of a sweep: its pairs (as above) and where their results go (device; claimedDev pairs x K,
+  // nClaimedDev pairs int32)
+  struct MotionSweepStep {
+    std::vector<int32_t> idx0, idx1;
+    std::vector<okvfe_pose> T_WC0, T_WC1;
+    const uint8_t* skip0Dev = nullptr;
+    okvfe_motion_match* matchesDev = nullptr;
+    uint8_t* claimedDev = nullptr;
+    int32_t* nClaimedDev = nullptr;
+  };
+  // The loop over the older frames (Frontend.cpp:1773): one matchMotionStereoBlocks call with claims per step, queued
+  // back to back on `stream`, matched1Dev (device nBlocks1 x K) read by each step's matcher and updated in place by its
+  // claims, so that step j + 1 matches only the current keypoints steps 0 .. j left free (:1792-1796).  Returns without
+  // synchronising; the estimator-side half of the insertion loop stays with the caller (okvfe.h).
+  void matchMotionStereoSweep(size_t cameraIndex, const void* blocks0Dev, int nBlocks0, const void* blocks1Dev,
+                              int nBlocks1, const std::vector<MotionSweepStep>& steps, uint8_t* matched1Dev,
+                              void* stream = nullptr) {
+    if (!matched1Dev) throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "matchMotionStereoSweep: matched1Dev is required");
+    for (const MotionSweepStep& st : steps) {
+      okvfe_motion_claim_device claim{};
+      claim.claimed = st.claimedDev;
+      claim.n_claimed = st.nClaimedDev;
+      claim.matched1_out = matched1Dev;
+      matchMotionStereoBlocks(cameraIndex, blocks0Dev, nBlocks0, blocks1Dev, nBlocks1, st.idx0, st.idx1, st.T_WC0,
+                              st.T_WC1, st.skip0Dev, matched1Dev, st.matchesDev, &claim, stream);
+    }
+  }
   // Frontend::matchToMapByThread on an already pooled 3-D landmark set (Frontend.cpp:1552-1589)
   MapMatches matchToMapPooled(size_t cameraIndex, const FrameData& frame, const std::vector<uint8_t>& use,
                               const std::vector<double>& projections, const std::vector<int32_t>& descBegin,
