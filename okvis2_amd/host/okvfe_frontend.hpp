@@ -282,6 +282,10 @@ class HipFrontend {
   // the k0 x k1 loop of Frontend::matchStereo for one camera pair (Frontend.cpp:2016-2076)
   std::vector<okvfe_stereo_match> matchStereo(size_t im0, const FrameData& f0, const okvfe_pose& T_WC0,
                                               size_t im1, const FrameData& f1, const okvfe_pose& T_WC1) {
+    checkCamera(im0);
+    checkCamera(im1);
+    checkFrame(f0, kDescriptors | kBackProjections, "matchStereo: f0");
+    checkFrame(f1, kDescriptors | kBackProjections, "matchStereo: f1");
     std::lock_guard<std::mutex> lock(mutexes_[im0]);
     std::vector<okvfe_stereo_match> out(f0.keypoints.size());
     const double fa = 0.5 * (cameras_[im0].base.fu + cameras_[im0].base.fv);
@@ -308,8 +312,11 @@ class HipFrontend {
                                                     const okvfe_pose& T_WC1,
                                                     const std::vector<uint8_t>& skip0 = {},
                                                     const std::vector<uint8_t>& matched1 = {}) {
-    if (cameraIndex >= cameras_.size())
-      throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "Camera index exceeds number of cameras.");
+    checkCamera(cameraIndex);
+    checkFrame(f0, kDescriptors | kBackProjections, "matchMotionStereo: f0");
+    checkFrame(f1, kDescriptors | kBackProjections, "matchMotionStereo: f1");
+    checkPerKeypoint(skip0.size(), f0, "matchMotionStereo: skip0");
+    checkPerKeypoint(matched1.size(), f1, "matchMotionStereo: matched1");
     std::lock_guard<std::mutex> lock(mutexes_[cameraIndex]);
     std::vector<okvfe_motion_match> out(f0.keypoints.size());
     const std::vector<double> b0 = flat(f0.backProjections), b1 = flat(f1.backProjections);
@@ -330,8 +337,9 @@ class HipFrontend {
   MapMatches matchToMap(size_t cameraIndex, const FrameData& frame, const okvfe_landmark_table& table,
                         const okvfe_pose& T_WC1, double reprojectionThreshold, bool exclusive,
                         const std::vector<uint8_t>& use = {}, okvfe_landmark_pool* poolOut = nullptr) {
-    if (cameraIndex >= cameras_.size())
-      throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "Camera index exceeds number of cameras.");
+    checkCamera(cameraIndex);
+    checkFrame(frame, kDescriptors, "matchToMap: frame");
+    checkPerKeypoint(use.size(), frame, "matchToMap: use");
     std::lock_guard<std::mutex> lock(mutexes_[cameraIndex]);
     if (!extractors_[cameraIndex].isCameraAware()) extractors_[cameraIndex].setCamera(cameras_[cameraIndex]);
     const size_t n = frame.keypoints.size();
@@ -554,6 +562,12 @@ class HipFrontend {
   MapMatches matchToMapPooled(size_t cameraIndex, const FrameData& frame, const std::vector<uint8_t>& use,
                               const std::vector<double>& projections, const std::vector<int32_t>& descBegin,
                               const std::vector<uint8_t>& pool, double reprojectionThreshold) {
+    checkCamera(cameraIndex);
+    checkFrame(frame, kDescriptors, "matchToMapPooled: frame");
+    checkPerKeypoint(use.size(), frame, "matchToMapPooled: use");
+    const size_t rows = checkDescBegin(descBegin, "matchToMapPooled");
+    checkLength(projections.size(), 2 * (descBegin.size() - 1), "matchToMapPooled: projections: 2 per landmark");
+    checkLength(pool.size(), size_t(OKVFE_DESC_BYTES) * rows, "matchToMapPooled: pool: 48 bytes per row of descBegin");
     std::lock_guard<std::mutex> lock(mutexes_[cameraIndex]);
     const size_t n = frame.keypoints.size();
     MapMatches m{std::vector<int32_t>(n, -1), std::vector<int32_t>(n, 0)};
@@ -573,12 +587,25 @@ class HipFrontend {
   };
   // Frontend::matchToMapByThreadUnitialised (Frontend.cpp:1616-1719): landmarks without a 3-D
   // position yet; pool row d carries its observing unit ray e0_W[d] and camera centre r0_W[d].
+  // A keypoint takes part iff use[k] (empty = every keypoint) AND frame.backProjectionsValid[k]: the
+  // reference sets its use[k] only where getBackProjection(im, k, ...) succeeds (Frontend.cpp:1622-1634),
+  // as the device-resident form does.  The other half of those lines ("already matched", :1628-1632)
+  // needs the exclusive flag and stays in the caller's use.
   UninitialisedMatches matchToMapUninitialised(size_t cameraIndex, const FrameData& frame,
                                                const std::vector<uint8_t>& use,
                                                const std::vector<int32_t>& previousLandmark,
                                                const std::vector<int32_t>& descBegin,
                                                const std::vector<uint8_t>& pool, const std::vector<double>& e0_W,
                                                const std::vector<double>& r0_W, const okvfe_pose& T_WC1) {
+    checkCamera(cameraIndex);
+    checkFrame(frame, kDescriptors | kBackProjections, "matchToMapUninitialised: frame");
+    // empty = "every keypoint" / "no keypoint carries a landmark yet", like the sibling wrappers
+    checkPerKeypoint(use.size(), frame, "matchToMapUninitialised: use");
+    checkPerKeypoint(previousLandmark.size(), frame, "matchToMapUninitialised: previousLandmark");
+    const size_t rows = checkDescBegin(descBegin, "matchToMapUninitialised");
+    checkLength(pool.size(), size_t(OKVFE_DESC_BYTES) * rows, "matchToMapUninitialised: pool: 48 bytes per row of descBegin");
+    checkLength(e0_W.size(), 3 * rows, "matchToMapUninitialised: e0_W: 3 per row of descBegin");
+    checkLength(r0_W.size(), 3 * rows, "matchToMapUninitialised: r0_W: 3 per row of descBegin");
     std::lock_guard<std::mutex> lock(mutexes_[cameraIndex]);
     const size_t n = frame.keypoints.size();
     UninitialisedMatches u;
@@ -587,15 +614,11 @@ class HipFrontend {
     u.hpSet.assign(n, 0);
     const std::vector<double> bp = flat(frame.backProjections);
     const double focal = 0.5 * (cameras_[cameraIndex].base.fu + cameras_[cameraIndex].base.fv);
-    // empty = "every keypoint" / "no keypoint carries a landmark yet", like the sibling wrappers
-    if (!use.empty() && use.size() != n) throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "use: one entry per keypoint");
-    if (!previousLandmark.empty() && previousLandmark.size() != n)
-      throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "previousLandmark: one entry per keypoint");
-    if (descBegin.empty()) throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "descBegin needs n_landmarks + 1 entries");
-    const std::vector<uint8_t> all(n, 1);
+    std::vector<uint8_t> take(n);  // Frontend.cpp:1622-1634
+    for (size_t k = 0; k < n; ++k) take[k] = (use.empty() || use[k]) && frame.backProjectionsValid[k] ? 1 : 0;
     const std::vector<int32_t> none(n, -1);
     contexts_[cameraIndex]->check(okvfe_match_to_map_uninitialised(
-        contexts_[cameraIndex]->get(), frame.descriptors.data.data(), bp.data(), use.empty() ? all.data() : use.data(),
+        contexts_[cameraIndex]->get(), frame.descriptors.data.data(), bp.data(), take.data(),
         previousLandmark.empty() ? none.data() : previousLandmark.data(), int32_t(n), descBegin.data(),
         int32_t(descBegin.size()) - 1, pool.data(),
         e0_W.data(), r0_W.data(), &T_WC1, focal, u.matches.landmark.data(), u.matches.distance.data(), hp.data(),
@@ -613,8 +636,13 @@ class HipFrontend {
   // camera of the current frame (Frontend.cpp:330-355)
   PlaceMatches verifyRecognisedPlace(size_t cameraIndex, const std::vector<uint8_t>& landmarkDescriptors,
                                      const std::vector<int32_t>& descBegin, const FrameData& frame) {
+    checkCamera(cameraIndex);
+    checkFrame(frame, kDescriptors, "verifyRecognisedPlace: frame");
+    const size_t rows = checkDescBegin(descBegin, "verifyRecognisedPlace");
+    checkLength(landmarkDescriptors.size(), size_t(OKVFE_DESC_BYTES) * rows,
+                "verifyRecognisedPlace: landmarkDescriptors: 48 bytes per row of descBegin");
     std::lock_guard<std::mutex> lock(mutexes_[cameraIndex]);
-    const size_t nl = descBegin.empty() ? 0 : descBegin.size() - 1;
+    const size_t nl = descBegin.size() - 1;
     PlaceMatches p{std::vector<int32_t>(nl, 0), std::vector<uint32_t>(nl, 0)};
     contexts_[cameraIndex]->check(okvfe_verify_place_match(
         contexts_[cameraIndex]->get(), landmarkDescriptors.data(), descBegin.data(), int32_t(nl),
@@ -663,6 +691,39 @@ class HipFrontend {
   }
 
  private:
+  // What the host-buffer matchers check before anything reaches the library (they hand it plain pointers and the
+  // frame's keypoint count): every failure throws OKVFE_ERR_INVALID_ARGUMENT.
+  enum FrameMembers { kDescriptors = 1, kBackProjections = 2 };
+  void checkCamera(size_t cameraIndex) const {
+    if (cameraIndex >= cameras_.size())
+      throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "Camera index exceeds number of cameras.");
+  }
+  static void checkLength(size_t got, size_t want, const std::string& what) {
+    if (got != want)
+      throw Exception(OKVFE_ERR_INVALID_ARGUMENT,
+                      what + " (" + std::to_string(got) + " given, " + std::to_string(want) + " needed)");
+  }
+  // A FrameData is well-formed when descriptors.data holds 48 bytes per keypoint and backProjections /
+  // backProjectionsValid one entry per keypoint; a method asks for the members it reads.
+  static void checkFrame(const FrameData& f, int members, const std::string& what) {
+    const size_t n = f.keypoints.size();
+    if (members & kDescriptors)
+      checkLength(f.descriptors.data.size(), size_t(OKVFE_DESC_BYTES) * n, what + ": descriptors.data: 48 bytes per keypoint");
+    if (members & kBackProjections) {
+      checkLength(f.backProjections.size(), n, what + ": backProjections: one per keypoint");
+      checkLength(f.backProjectionsValid.size(), n, what + ": backProjectionsValid: one per keypoint");
+    }
+  }
+  // skip0 / matched1 / use / previousLandmark: empty, or one entry per keypoint of their frame
+  static void checkPerKeypoint(size_t size, const FrameData& f, const std::string& what) {
+    if (size != 0) checkLength(size, f.keypoints.size(), what + ": empty or one entry per keypoint");
+  }
+  // descBegin: n_landmarks + 1 entries, the last one the number of pool rows -> that number
+  static size_t checkDescBegin(const std::vector<int32_t>& descBegin, const std::string& what) {
+    if (descBegin.empty() || descBegin.back() < 0)
+      throw Exception(OKVFE_ERR_INVALID_ARGUMENT, what + ": descBegin needs n_landmarks + 1 entries");
+    return size_t(descBegin.back());
+  }
   static std::vector<double> flat(const std::vector<std::array<double, 3>>& v) {
     std::vector<double> b(v.size() * 3 + 3);
     for (size_t k = 0; k < v.size(); ++k)
