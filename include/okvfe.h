@@ -357,7 +357,8 @@ int32_t okvfe_scale_index(float keypoint_size);
 /* NMS candidate capacity check of the last batch (synchronises; one small copy): an image whose
  * score map had more maxima than the context's candidate capacity (okvfe_config.max_candidates)
  * keeps NO keypoints -- which maxima an overflowing list drops would depend on the order of the
- * atomics -- and makes this call fail with OKVFE_ERR_CAPACITY (*first_overflowed = its index, -1
+ * atomics; in a scale space (octaves > 0) the list of ANY layer empties the whole image, on the
+ * device (detect_counts, counts, gather blocks) as on the host -- and makes this call fail with OKVFE_ERR_CAPACITY (*first_overflowed = its index, -1
  * if none; may be NULL).  Device-resident pipelines (batch detect -> match / gather) call this
  * once per batch or once per sequence, as their budget allows. */
 okvfe_status okvfe_check_capacity(okvfe_ctx* ctx, int32_t n_images, int32_t* first_overflowed);

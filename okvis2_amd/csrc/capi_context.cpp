@@ -455,7 +455,10 @@ okvfe_status create_impl(const okvfe_config* cfg, bool child, okvfe_ctx** out) {
   ctx->n_layers = n_layers;
   // row capacity per image: every layer of a scale space may deliver max_keypoints
   ctx->kp_cap = cfg->max_keypoints * n_layers;
-  const int worst = (cfg->width / 2 + 1) * (cfg->height - 4);
+  // worst case: the raster scan keeps every second pixel of a row at most, but the fused score + NMS kernel appends BOTH
+  // pixels of a tied pair and nms_fixup_kernel removes one afterwards -- the list must hold every pixel the scan visits
+  // (an egg-crate pattern sampled down to a period of 4 px gave twice (w / 2 + 1)(h - 4) records and a false overflow)
+  const int worst = (cfg->width - 4) * (cfg->height - 4);
   ctx->cand_cap = cfg->max_candidates > 0 ? std::min(cfg->max_candidates, worst) : worst;
   ctx->cand_cap = (std::max(ctx->cand_cap, 64) + 1) & ~1;  // even: the array doubles as 8-byte records
   ctx->ws_stride = 1;

@@ -300,15 +300,19 @@ void scale_layer_keypoints(okvfe_ctx* ctx, int l, int n_images, hipStream_t s) {
 void merge_layers(okvfe_ctx* ctx, int n_images, hipStream_t s) {
   const okvfe_keypoint* kps[8];
   const int32_t* counts[8];
+  const int32_t* cand_counts[8];
+  int cand_cap[8];
   float scale[8];
   for (int l = 0; l < ctx->n_layers; ++l) {
     kps[l] = ctx->layers[l]->d_kps_det;
     counts[l] = ctx->layers[l]->d_det_count;
+    cand_counts[l] = ctx->layers[l]->d_cand_count;
+    cand_cap[l] = ctx->layers[l]->cand_cap;
     int sn, sd;
     layer_scale(l, &sn, &sd);
     scale[l] = (float)sn / (float)sd;
   }
-  launch_merge_layers(kps, counts, scale, ctx->n_layers, ctx->cfg.max_keypoints, n_images, ctx->d_kps_det, ctx->kp_cap,
+  launch_merge_layers(kps, counts, cand_counts, cand_cap, scale, ctx->n_layers, ctx->cfg.max_keypoints, n_images, ctx->d_kps_det, ctx->kp_cap,
                       ctx->d_det_count, s);
 }
 

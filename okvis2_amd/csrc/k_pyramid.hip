@@ -127,16 +127,21 @@ __global__ __launch_bounds__(256) void scale_filter_kernel(
 struct MergeLayers {
   const okvfe_keypoint* kps[8];   // per layer [n_images][layer_cap]
   const int32_t* counts[8];       // per layer [n_images]
+  const int32_t* cand_counts[8];  // per layer [n_images]: its NMS candidate count ...
+  int cand_cap[8];                // ... and capacity
   float scale[8];
   int n_layers, layer_cap;
 };
-// layers in ascending order -> out[img][0 .. sum), image coordinates X = s (x + 1/2) - 1/2
+// layers in ascending order -> out[img][0 .. sum), image coordinates X = s (x + 1/2) - 1/2.  An image whose candidate
+// list overflowed in ANY layer keeps no keypoints (okvfe_check_capacity): the selection zeroes only the overflowed layer.
 __global__ __launch_bounds__(256) void merge_layers_kernel(MergeLayers m, okvfe_keypoint* __restrict__ out,
                                                            int out_cap, int32_t* __restrict__ out_count) {
   const int img = blockIdx.x;
+  bool overflowed = false;
+  for (int l = 0; l < m.n_layers; ++l) overflowed = overflowed || m.cand_counts[l][img] > m.cand_cap[l];
   int off = 0;
   for (int l = 0; l < m.n_layers; ++l) {
-    const int n = m.counts[l][img];
+    const int n = overflowed ? 0 : m.counts[l][img];
     const okvfe_keypoint* src = m.kps[l] + (size_t)img * m.layer_cap;
     const float s = m.scale[l];
     for (int i = threadIdx.x; i < n; i += 256) {
@@ -178,14 +183,17 @@ void launch_scale_filter(Candidate* cand, int cand_cap, int32_t* cand_count, int
   hipLaunchKernelGGL(scale_filter_kernel, dim3(n_images), dim3(256), 0, stream, cand, cand_cap, cand_count,
                      below, lb, wb, hb, rn_b, rd_b, above, la, wa, ha, rn_a, rd_a);
 }
-void launch_merge_layers(const okvfe_keypoint* const* kps, const int32_t* const* counts, const float* scale,
-                         int n_layers, int layer_cap, int n_images, okvfe_keypoint* out, int out_cap,
-                         int32_t* out_count, hipStream_t stream) {
+void launch_merge_layers(const okvfe_keypoint* const* kps, const int32_t* const* counts,
+                         const int32_t* const* cand_counts, const int* cand_cap, const float* scale, int n_layers,
+                         int layer_cap, int n_images, okvfe_keypoint* out, int out_cap, int32_t* out_count,
+                         hipStream_t stream) {
   if (n_images <= 0) return;
   MergeLayers m{};
   for (int l = 0; l < n_layers; ++l) {
     m.kps[l] = kps[l];
     m.counts[l] = counts[l];
+    m.cand_counts[l] = cand_counts[l];
+    m.cand_cap[l] = cand_cap[l];
     m.scale[l] = scale[l];
   }
   m.n_layers = n_layers;

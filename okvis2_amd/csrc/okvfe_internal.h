@@ -525,8 +525,9 @@ void launch_scale_filter(Candidate* cand, int cand_cap, int32_t* cand_count, int
                          const int32_t* below, ScoreLayout lb, int wb, int hb, int rn_b, int rd_b,
                          const int32_t* above, ScoreLayout la, int wa, int ha, int rn_a, int rd_a,
                          hipStream_t stream);
-void launch_merge_layers(const okvfe_keypoint* const* kps, const int32_t* const* counts, const float* scale,
-                         int n_layers, int layer_cap, int n_images, okvfe_keypoint* out, int out_cap,
+void launch_merge_layers(const okvfe_keypoint* const* kps, const int32_t* const* counts,
+                         const int32_t* const* cand_counts, const int* cand_cap, const float* scale, int n_layers,
+                         int layer_cap, int n_images, okvfe_keypoint* out, int out_cap,
                          int32_t* out_count, hipStream_t stream);
 void launch_hamming_argmin(const uint8_t* A, int nA, const uint8_t* B, int nB, uint32_t thr,
                            int32_t* best_j, uint32_t* best_d, hipStream_t stream);

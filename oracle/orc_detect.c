@@ -185,6 +185,12 @@ void orc_scale_refine(double rb, int have_b, int32_t sb, int32_t s, double ra, i
   *score = (float)u;
 }
 
+/* orc_scale_refine over n (sb, s, sa) triples with both neighbours present (tests enumerate every triple) */
+void orc_scale_refine_many(double rb, double ra, double lo, const int32_t* sb, const int32_t* s, const int32_t* sa,
+                           int n, float* rel_scale, float* score) {
+  for (int i = 0; i < n; ++i) orc_scale_refine(rb, 1, sb[i], s[i], ra, 1, sa[i], lo, &rel_scale[i], &score[i]);
+}
+
 void orc_score_map(int score_type, const uint8_t* img, int w, int h, int stride, int32_t* score) {
   if (score_type == 1 || score_type == 2)
     orc_agast_score(img, w, h, stride, score);

@@ -201,6 +201,54 @@ def twothirdsample(img):
     return out
 
 
+def fast58_score(img: np.ndarray) -> np.ndarray:
+    """orc_fast58_score: the virtual layer below c0 of the BRISK scale space"""
+    img = np.ascontiguousarray(img, dtype=np.uint8)
+    h, w = img.shape
+    out = np.empty((h, w), dtype=np.int32)
+    lib().orc_fast58_score(_p(img), w, h, w, _p(out))
+    return out
+
+
+def layer_scale(layer):
+    """orc_layer_scale: (numerator, denominator) of the scale of a scale-space layer"""
+    n, d = C.c_int(), C.c_int()
+    lib().orc_layer_scale(int(layer), C.byref(n), C.byref(d))
+    return n.value, d.value
+
+
+def scale_neighbour_ok(other, x, y, s, rn, rd) -> bool:
+    other = np.ascontiguousarray(other, dtype=np.int32)
+    ho, wo = other.shape
+    return bool(lib().orc_scale_neighbour_ok(_p(other), wo, ho, int(x), int(y), int(s), int(rn), int(rd)))
+
+
+def scale_neighbour_max(other, x, y, rn, rd) -> int:
+    other = np.ascontiguousarray(other, dtype=np.int32)
+    ho, wo = other.shape
+    f = lib().orc_scale_neighbour_max
+    f.restype = C.c_int32
+    return int(f(_p(other), wo, ho, int(x), int(y), int(rn), int(rd)))
+
+
+def scale_refine(rb, sb, s, ra, sa, lo, have_b=True, have_a=True):
+    """orc_scale_refine -> (relative scale, refined score), both float32"""
+    rel, sc = C.c_float(), C.c_float()
+    lib().orc_scale_refine(C.c_double(rb), int(have_b), int(sb), int(s), C.c_double(ra), int(have_a), int(sa),
+                           C.c_double(lo), C.byref(rel), C.byref(sc))
+    return np.float32(rel.value), np.float32(sc.value)
+
+
+def scale_refine_many(rb, ra, lo, sb, s, sa):
+    """orc_scale_refine for arrays of triples (both neighbours present) -> (relative scales, refined scores), float32"""
+    sb, s, sa = (np.ascontiguousarray(v, dtype=np.int32) for v in (sb, s, sa))
+    rel = np.empty(len(s), dtype=np.float32)
+    sc = np.empty(len(s), dtype=np.float32)
+    lib().orc_scale_refine_many(C.c_double(rb), C.c_double(ra), C.c_double(lo), _p(sb), _p(s), _p(sa), len(s),
+                                _p(rel), _p(sc))
+    return rel, sc
+
+
 def integral(img):
     img = np.ascontiguousarray(img, dtype=np.uint8)
     h, w = img.shape
