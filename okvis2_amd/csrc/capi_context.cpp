@@ -465,9 +465,7 @@ okvfe_status create_impl(const okvfe_config* cfg, bool child, okvfe_ctx** out) {
   while (ctx->ws_stride < ctx->cand_cap) ctx->ws_stride <<= 1;
   ctx->mode_default = cfg->rotation_invariant ? kGradient : kUpright;
   if (cfg->uniformity_radius > 0.0f) {
-    const float scaling = (float)(15.0 / (double)cfg->uniformity_radius);
-    ctx->occ_rows = (int)((float)(ctx->h - 1) * scaling + 16.0f) + 17;
-    ctx->occ_cols = (int)((float)(ctx->w - 1) * scaling + 16.0f) + 17;
+    occupancy_grid_dims(ctx->w, ctx->h, cfg->uniformity_radius, &ctx->occ_rows, &ctx->occ_cols);
   } else {
     ctx->occ_rows = ctx->occ_cols = 1;
   }

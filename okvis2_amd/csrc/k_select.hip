@@ -13,11 +13,13 @@
 // launch_select picks the form; sorts: k_sort.hip, grid fall-backs: k_select_grid.hip, BRISK scale
 // refinement: k_brisk_refine.hip, shared device helpers: select_common_dev.h.
 // Bound: one ordered chain of LDS and memory round trips per image; batches keep all CUs busy with independent images.
-// It is not free of memory traffic: 467 KB fetched and 129 KB written per EuRoC image in a 6144-image launch, 379 KB
-// of the fetched bytes by the tail's scattered windows, map entries and extra-sample rows and 110 KB by the candidate
-// records (profiles/select_traffic.txt, priced per source by tools/lab/select_traffic.sh), against 125 KB algorithmic.
+// It is not free of memory traffic: 458 KB fetched and 89 KB written per EuRoC image in a 6144-image launch
+// (profiles/select_keys_traffic.txt), about 380 KB of the fetched bytes by the tail's scattered windows, map entries and
+// extra-sample rows and 110 KB by the candidate records (profiles/select_traffic.txt, priced per source by
+// tools/lab/select_traffic.sh), against 125 KB algorithmic.
 // The chain's memory round trips, as built: set-up -- the first 5120 candidate records in two waves of ten 12-byte
-// loads per lane (branch-free, packed five at a time), then the key scatter; per chunk -- its keys, requested one chunk
+// loads per lane (branch-free, packed five at a time), then the key scatter (one write cursor per CHUNK, so a wave's
+// stores form a few contiguous runs; keys are unordered inside a chunk); per chunk -- its keys, requested one chunk
 // ahead; tail (refine_emit, one lane per keypoint) -- the kept record, 21 pixel dwords, ray + Jacobian together, the
 // rows of each extra sample (its constants requested one trip ahead).  What is the same for every keypoint of an image
 // (ImageParams, the camera's map pointers, border / reach / point count of the pattern) is loaded at kernel start,
@@ -36,9 +38,9 @@ namespace {
 __device__ __forceinline__ void refine_emit(const int32_t* __restrict__ scores, const ScoreLayout& layout, int w, int h,
                                             int img, const uint8_t* __restrict__ images, const DescribeSetup& setup,
                                             const DescribeImageParams& dp, okvfe_keypoint* __restrict__ out, int i,
-                                            size_t slot) {
-  okvfe_keypoint kp = out[i];  // pixel position and exact score, left there by the acceptance
-  const int u = (int)kp.x, v = (int)kp.y;
+                                            size_t slot, int u, int v, int32_t score) {
+  // (u, v, score): pixel position and exact score, which the caller has read back from the record the acceptance left in
+  // out[i] -- three values, not the record's seven words, stay live across the nine scores
   int32_t patch[9];
   if (images) {  // map-free call: the nine scores from the pixels (block-uniform)
     harris_scores_3x3(images + (size_t)img * w * h, w, h, u, v, patch);
@@ -52,9 +54,13 @@ __device__ __forceinline__ void refine_emit(const int32_t* __restrict__ scores, 
   }
   float ddx, ddy;
   subpixel2d(patch, &ddx, &ddy);
+  okvfe_keypoint kp;
   kp.x = (float)u + ddx;
   kp.y = (float)v + ddy;
-  kp.response = (float)kp.class_id;
+  kp.size = 12.0f;
+  kp.angle = -1.0f;
+  kp.response = (float)score;
+  kp.octave = 0;
   kp.class_id = -1;
   OKVFE_TAIL_STORE(out[i] = kp);
   // detection and description in one call: the extractor's per-keypoint preparation right here
@@ -99,8 +105,8 @@ __device__ __forceinline__ void refine_emit(const int32_t* __restrict__ scores, 
 //
 // Ordering (round 4, select_lazy_kernel<true>, the default): the kernel takes the UNSORTED candidate
 // records and orders only what the greedy pass consumes -- log buckets of the score, chunks of whole
-// buckets scattered into bucket order, chunk prefilter in any order, survivors rank-sorted in LDS,
-// oversized chunks split by key range (see the SORTS branch below).  select_lazy_kernel<false> reads
+// buckets, keys scattered chunk by chunk (unordered inside a chunk), chunk prefilter in any order, survivors
+// rank-sorted in LDS, oversized chunks split by key range (see the SORTS branch below).  select_lazy_kernel<false> reads
 // keys sorted by launch_sort (lab knob OKVFE_SELECT_PRESORTED).
 //
 // K4 runs in the tail: 2-D sub-pixel fit of the kept keypoints, from the score map or -- map-free calls
@@ -148,6 +154,11 @@ constexpr int kFuseBins = 496;
 constexpr int kFuseUnroll = 8;  // candidate records in flight per thread in the scatter pass
 constexpr int kFuseFirst = 20;   // scores per thread requested before the tables are set up (5120 candidates)
 constexpr int kFuseSched = 40;  // chunk ends kept in LDS; what lies beyond them is ONE last chunk (split by key range)
+// the scatter's tables: chunk of every bucket (bytes, in the survivor buffer behind the bucket counts) and one write
+// cursor per chunk (in the partial sums, idle until the first window)
+constexpr int kFuseChunkOfAt = 2048;
+static_assert((kFuseBins + 1) * 4 <= kFuseChunkOfAt && kFuseChunkOfAt + kFuseBins <= kLazyBlockMax * 8, "chunk map in the survivor buffer");
+static_assert(kFuseSched + 1 <= 4 * 64, "cursors in the partial sums (and chunk numbers in a byte)");
 __device__ __forceinline__ int fuse_bin(int32_t score) {
   if (score <= 0) return kFuseBins - 1;
   const uint32_t s = (uint32_t)score;
@@ -168,7 +179,7 @@ __global__ __launch_bounds__(kLazyThreads) __attribute__((amdgpu_waves_per_eu(OK
   __shared__ int s_kept;
   __shared__ int s_spill;       // points that did not fit their bin (HBM list)
   __shared__ int s_surv[2][4];  // survivor counts per wave, double-buffered by block parity
-  // SORTS: ends of the chunks in the bucket-ordered key array, their number, the highest score, and the
+  // SORTS: ends of the chunks in the chunk-ordered key array, their number, the highest score, and the
   // scratch of the key-range split of an oversized chunk
   __shared__ uint32_t s_sched[kFuseSched + 2];
   __shared__ int s_nsched, s_max, s_cnt;
@@ -648,12 +659,18 @@ __global__ __launch_bounds__(kLazyThreads) __attribute__((amdgpu_waves_per_eu(OK
       // order is never used: a candidate that fails against the points accepted from HIGHER scores fails
       // whatever its rank among its peers.  So: (A) count the candidates into log buckets of the score,
       // (B) cut the bucket sequence into CHUNKS of about 64, 128, ... 1024 candidates (whole buckets), (C)
-      // scatter the keys into bucket order (HBM workspace, unordered inside a bucket); then per chunk:
+      // scatter the keys into chunk order (HBM workspace; UNORDERED INSIDE A CHUNK: only chunk membership is ever
+      // read.  One write cursor per chunk, found through a bucket -> chunk byte table: the lanes of a store
+      // instruction that share a chunk take consecutive positions, so a wave's 64 stores form at most as many
+      // contiguous runs as the image has chunks, about eight -- a cursor per BUCKET sent them to dozens of lines, each
+      // 8-byte store a partial line of its own: 75 KB written per image for 36 KB of keys); then per chunk:
       // prefilter its keys in any order against the points accepted from the earlier chunks, rank-sort
       // the SURVIVORS (a hundred or so) in LDS, and run the ordered windows over them.  A chunk larger
       // than the buffer (a bucket of a thousand equal scores) is split by key range: histogram of the key
       // over the bucket's own [min, max], narrowed until a prefix of it fits.
       uint32_t* hist = reinterpret_cast<uint32_t*>(surv);  // [kFuseBins + 1], until the first chunk is worked on
+      uint8_t* chunk_of = reinterpret_cast<uint8_t*>(surv) + kFuseChunkOfAt;  // [kFuseBins], likewise
+      uint32_t* cursor = reinterpret_cast<uint32_t*>(part);                   // [kFuseSched + 1], until the first window
       __syncthreads();
 #ifdef OKVFE_LAB
       t_p0 = __builtin_amdgcn_s_memrealtime();
@@ -743,14 +760,22 @@ __global__ __launch_bounds__(kLazyThreads) __attribute__((amdgpu_waves_per_eu(OK
             }
             e = (int)hist[x_last + 1];
           }
-          if (lane == 0) s_sched[k] = (uint32_t)e;
+          for (int idx = b + lane; idx <= x_last; idx += 64) chunk_of[idx] = (uint8_t)k;
+          if (lane == 0) {
+            s_sched[k] = (uint32_t)e;
+            cursor[k] = (uint32_t)pos;
+          }
           ++k;
           pos = e;
           b = x_last + 1;
           target = min(2u * target, (uint32_t)round_cap);
         }
         if (pos < n) {  // what the table cannot hold: one last chunk
-          if (lane == 0) s_sched[k] = (uint32_t)n;
+          for (int idx = b + lane; idx < kFuseBins; idx += 64) chunk_of[idx] = (uint8_t)k;
+          if (lane == 0) {
+            s_sched[k] = (uint32_t)n;
+            cursor[k] = (uint32_t)pos;
+          }
           ++k;
         }
         if (lane == 0) s_nsched = k;
@@ -767,7 +792,7 @@ __global__ __launch_bounds__(kLazyThreads) __attribute__((amdgpu_waves_per_eu(OK
 #pragma unroll
       for (int u = 0; u < kFuseFirst; ++u) {
         if (tid + u * kLazyThreads < n) {
-          const uint32_t p = atomicAdd(&hist[fuse_bin(scv0[u])], 1u);
+          const uint32_t p = atomicAdd(&cursor[chunk_of[fuse_bin(scv0[u])]], 1u);
           if (keys_live) keys[p] = ((uint64_t)(uint32_t)(0x7FFFFFFF - scv0[u]) << 32) | pyx0[u];  // = make_key
         }
       }
@@ -781,7 +806,7 @@ __global__ __launch_bounds__(kLazyThreads) __attribute__((amdgpu_waves_per_eu(OK
 #pragma unroll
         for (int u = 0; u < kFuseUnroll; ++u) {
           if (base + u * kLazyThreads < n) {
-            const uint32_t p = atomicAdd(&hist[fuse_bin(cv[u].score)], 1u);
+            const uint32_t p = atomicAdd(&cursor[chunk_of[fuse_bin(cv[u].score)]], 1u);
             if (keys_live) keys[p] = make_key(cv[u]);
           }
         }
@@ -1043,8 +1068,11 @@ __global__ __launch_bounds__(kLazyThreads) __attribute__((amdgpu_waves_per_eu(OK
   t_blocks = __builtin_amdgcn_s_memrealtime();
 #endif
   if (!(kSelectOff & 1))
-    for (int i = tid; i < kept; i += kLazyThreads)
-      refine_emit(scores, layout, w, h, img, images, setup, dp, out, i, (size_t)img * kp_cap + i);
+    for (int i = tid; i < kept; i += kLazyThreads) {
+      const okvfe_keypoint kp = out[i];
+      refine_emit(scores, layout, w, h, img, images, setup, dp, out, i, (size_t)img * kp_cap + i, (int)kp.x, (int)kp.y,
+                  kp.class_id);
+    }
   if (tid == 0) kp_count[img] = kept;
 #ifdef OKVFE_LAB
   __syncthreads();
@@ -1336,8 +1364,11 @@ __global__ __launch_bounds__(kLazyThreads) __attribute__((amdgpu_waves_per_eu(6,
   }
   // ---- K4: sub-pixel refinement and keypoint emission (all four waves)
   __syncthreads();
-  for (int i = tid; i < kept; i += kLazyThreads)
-    refine_emit(scores, layout, w, h, img, images, setup, dp, out, i, (size_t)img * kp_cap + i);
+  for (int i = tid; i < kept; i += kLazyThreads) {
+    const okvfe_keypoint kp = out[i];
+    refine_emit(scores, layout, w, h, img, images, setup, dp, out, i, (size_t)img * kp_cap + i, (int)kp.x, (int)kp.y,
+                kp.class_id);
+  }
   if (tid == 0) kp_count[img] = kept;
 }
 
@@ -1456,6 +1487,29 @@ bool launch_select(const int32_t* score, ScoreLayout layout, int w, int h, int n
 }
 
 #ifdef OKVFE_LAB
+// lab build only: which selection kernel launch_select runs for a w x h context at a uniformity radius, a keypoint cap
+// and a row capacity, with the grid and the workspace a context would give it.  out[3] = {select_lazy_kernel serves
+// it, select_list_kernel does, the dynamic LDS of the one that does (0: the grid kernels)}.
+extern "C" void okvfe_lab_select_plan(int32_t w, int32_t h, float radius, int32_t max_kpts, int32_t kp_cap, int32_t* out) {
+  int rows = 1, cols = 1;
+  if (radius > 0.0f) occupancy_grid_dims(w, h, radius, &rows, &cols);
+  static const uint8_t some_workspace = 0;  // (the plan only tests the pointer against null)
+  const LazyPlan lp = lazy_plan(radius, max_kpts, kp_cap, &some_workspace, ((size_t)rows * cols + 255) / 256 * 256, rows, cols);
+  out[0] = lp.array;
+  out[1] = lp.list;
+  out[2] = (int32_t)(lp.array ? lp.lds : (lp.list ? lp.lds_list : 0));
+}
+// lab build only, on the GPU: workgroups of select_lazy_kernel<true> per CU at `lds_dyn` bytes of dynamic LDS, as the
+// runtime counts them (EuRoC: 26 560 B, six); -1 on error
+extern "C" int32_t okvfe_lab_select_occupancy(int32_t lds_dyn) {
+  int n = -1;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(select_lazy_kernel<true>), kLazyThreads,
+                                                   (size_t)lds_dyn) != hipSuccess) {
+    (void)hipGetLastError();
+    return -1;
+  }
+  return n;
+}
 extern "C" int okvfe_lab_lazy_prof(unsigned long long out[16], int reset) {
   if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_lazy_prof), 16 * sizeof(unsigned long long)) != hipSuccess) return 1;
   if (reset) {

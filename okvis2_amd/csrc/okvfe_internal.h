@@ -333,6 +333,13 @@ struct DescribeSetup {  // pat == nullptr: not requested
   int extra_box = 0;
 };
 constexpr int kAwareMaxExtra = 6;  // ints that fit the descriptor slot behind M (16 B) and the patch geometry (8 B)
+// cells of the occupancy grid of a w x h image at a uniformity radius (> 0): 15 cells per radius, a stamp's reach of
+// border (what a context allocates and hands to launch_select as occ_rows x occ_cols)
+inline void occupancy_grid_dims(int w, int h, float radius, int* rows, int* cols) {
+  const float scaling = (float)(15.0 / (double)radius);
+  *rows = (int)((float)(h - 1) * scaling + 16.0f) + 17;
+  *cols = (int)((float)(w - 1) * scaling + 16.0f) + 17;
+}
 // true: launch_select orders the candidates itself for this configuration (array-bin lazy selection): the
 // caller launches no sort before it
 bool select_sorts_candidates(float radius, int max_kpts, int kp_cap, const uint8_t* occupancy, size_t occ_image_bytes,
