@@ -989,6 +989,104 @@ okvfe_status okvfe_remove_outliers_blocks_device(
     const int32_t* cam_ids /* HOST, n_frames */, const okvfe_pose* T_WC /* HOST, n_frames */, double max_error,
     const int32_t* landmark_dev, int32_t* landmark_out_dev, int32_t* kept_dev, void* stream);
 
+/* ---- loop closure: verifyRecognisedPlace up to the point where ceres takes over --------------
+ * Frontend::verifyRecognisedPlace (Frontend.cpp:270-556) for one candidate old frame against a batch of multiframes,
+ * from the old frame's landmark set to the verdict of :389.  The chain, all on one stream and without a host
+ * synchronisation:
+ *   okvfe_place_landmark_set                  host, once per old frame: the landmark set of :289-327
+ *   okvfe_verify_place_blocks_device          the descriptor matching of :330-346 (k_min / dist_min per block and row)
+ *   okvfe_place_claims_blocks_device          :347-351, :359, :380: the `matches` map, the counts and the gate
+ *   okvfe_place_consensus_blocks_device       :372-397: the consensus over the caller's pose hypotheses and the verdict
+ * Landmarks of a set are rows 0 .. L - 1 in ascending landmark id: the rows and the order of the okvfe_map_device
+ * (desc_begin, pool) that okvfe_verify_place_blocks_device is given.  Multiframe m owns gather blocks m n_cams + c, as
+ * in okvfe_ransac3d2d_consensus_blocks_device, so the rows of k_min_dev / dist_min_dev of block b start at b L.
+ * Several candidate old frames are several chains on one stream; the verdicts are downloaded once and the caller takes
+ * the oldest verified candidate.
+ *
+ * What stays with the caller: the walk over the DBoW results and its non-maximum suppression with the estimator's
+ * predicates (:771-819); the sampler and opengv's gp3p; opengv's adaptive stop, which only ever shortens the
+ * hypothesis list; the ceres refinement (:399-527); the Hessian H (:529-551), which is evaluated at the refined pose
+ * through ReprojectionError; attemptLoopClosure and everything after it.  PARITY UNPINNED: opengv's winner rule, as for
+ * okvfe_ransac3d2d_consensus_blocks_device. */
+
+/* The landmark set of the old frame (Frontend.cpp:289-327).  Host helper, no context.  The old frame's keypoints of all
+ * n_cams cameras, camera-major and ascending (n_kps[c] of camera c): landmark_ids (0 = none, :293; the use_cnn filter of
+ * :305-317 is the caller's, which passes 0), landmarks (x 4, getLandmark's Vector4d), initialised (x 1 byte),
+ * descriptors (x 48).  An observation is skipped iff its id is 0, or it is not initialised, or landmark.norm() < 1.0e-12
+ * (:301; a NaN norm stays in).  norm() is the square root of the four-term sum of squares, taken in the `order` of
+ * okvfe_set_fp64_reduction: 1 = (x0 x0 + x1 x1) + (x2 x2 + x3 x3), 0 = left to right.  A vectorised Eigen build may
+ * take a third order (packets of two: (x0 x0 + x2 x2) + (x1 x1 + x3 x3)); the choice matters only to the last ulp of a
+ * norm at 1e-12.  The first passing observation of a landmark supplies its Vector4d (:323), every passing observation
+ * appends its descriptor (:320-322).
+ * Outputs, landmarks in ascending id: ids_out (cap_landmarks), hp_out (cap_landmarks x 4), desc_begin_out
+ * (cap_landmarks + 1), pool_out (cap_rows x 48, the rows of a landmark in (camera, keypoint) order).  *n_landmarks and
+ * *n_rows receive the totals even when they exceed the capacities (then OKVFE_ERR_CAPACITY and nothing else is
+ * written). */
+okvfe_status okvfe_place_landmark_set(int32_t n_cams, const int32_t* n_kps /* n_cams */, const uint64_t* landmark_ids,
+                                      const double* landmarks, const uint8_t* initialised, const uint8_t* descriptors,
+                                      int32_t order, uint64_t* ids_out, double* hp_out, int32_t* desc_begin_out,
+                                      int32_t cap_landmarks, uint8_t* pool_out, int32_t cap_rows, int32_t* n_landmarks,
+                                      int32_t* n_rows);
+
+typedef struct okvfe_place_set_device {
+  int32_t n_landmarks; /* L */
+  const double* hp;    /* device, L x 4: okvfe_place_landmark_set's hp_out */
+} okvfe_place_set_device;
+typedef struct okvfe_place_claims_device {
+  int32_t* n_matches;         /* device, per multiframe: the reference's ctr */
+  int32_t* n_points;          /* device, per multiframe: points.size() */
+  int32_t* n_correspondences; /* device, per multiframe: adapter.getNumberCorrespondences() */
+  uint8_t* gate;              /* device, per multiframe */
+  int32_t* match_landmark;    /* device, blocks x K */
+} okvfe_place_claims_device;
+/* The claims of verifyRecognisedPlace (Frontend.cpp:347-351) and its two count gates (:359, :380) for n_multiframes
+ * multiframes of n_cams gather blocks.  k_min_dev / dist_min_dev: what okvfe_verify_place_blocks_device wrote for these
+ * blocks and this set's (desc_begin, pool), blocks x L.  A hit of row l in block b is dist_min < the context's
+ * match_threshold (the value the matcher writes when nothing is below it); a hit whose k_min is outside [0, count) of
+ * its block is ignored and not counted (the matcher cannot produce one).
+ * Per multiframe: n_matches = the number of hits (ctr, :348); n_points = the number of rows with a hit in at least one
+ * camera (:349); match_landmark[b K + k] = the largest hitting row l with k_min == k, or -1 (:350 is std::map
+ * assignment with the landmarks in ascending order: the last writer keeps the keypoint, the loser stays in ctr and in
+ * points); rows at or past the block's count are untouched.  n_correspondences = the number of claimed keypoints whose
+ * landmark passes fabs(hp[3]) >= 1.0e-8 or is a NaN (LoopclosureNoncentralAbsoluteAdapter.cpp:126), written whatever
+ * the gate says.  gate = 0 if n_matches < min_inliers || n_points < 8 (:359), else 1 if n_correspondences < 7 (:380: eight
+ * above and seven here, as written), else 2: the multiframe goes on to RANSAC.
+ * One work-group per multiframe, one camera at a time; the claims of a camera are one int per keypoint in LDS, resolved
+ * with atomicMax (order-independent, hence deterministic).  The keypoints are not tiled: a context whose max_keypoints
+ * exceeds 12288 is refused with OKVFE_ERR_UNSUPPORTED before anything is launched.  Nothing synchronises the host; no
+ * workspace.  A NULL or negative argument: OKVFE_ERR_INVALID_ARGUMENT before any device work; n_multiframes == 0 is OK
+ * and launches nothing. */
+okvfe_status okvfe_place_claims_blocks_device(okvfe_ctx* ctx, const okvfe_place_set_device* set, const void* blocks_dev,
+                                              int32_t n_multiframes, int32_t n_cams, const int32_t* k_min_dev,
+                                              const uint32_t* dist_min_dev, int32_t min_inliers,
+                                              const okvfe_place_claims_device* result, void* stream);
+/* The consensus of verifyRecognisedPlace (Frontend.cpp:372-397): okvfe_ransac3d2d_consensus_blocks_device's kernel
+ * under another policy.  cam_ids, T_SC, hypotheses_dev, hyp_valid_dev, n_hyp (the reference: 50, :383), threshold (16,
+ * :382), the distance (FrameAbsolutePoseSacProblem.hpp:135-167, which accepts both adapters: :97-101), the winner rule
+ * and the order of the sums are those of that call.  match_landmark_dev: blocks x K rows of the set, as the claims call
+ * writes them.
+ * Correspondences (LoopclosureNoncentralAbsoluteAdapter.cpp:69-154), camera-major with keypoints ascending: keypoint
+ * k < count with l = match_landmark[k] in [0, L), unless fabs(hp[4 l + 3]) < 1.0e-8 (:126; a NaN stays in).  Point,
+ * bearing with the (1, 0, 0) fall-back, normalize() and sigma exactly as in FrameNoncentralAbsoluteAdapter; there is no
+ * test on the number of observations.
+ * verdict_dev (u8 per multiframe): 0 if gate_dev is given and gate_dev[m] == 0 (:359); else 1 if the kernel's own count
+ * of correspondences is below 7 (:380); else the hypotheses are scored, the winner picked, and the verdict is 2 if
+ * n_inliers < min_inliers || double(n_inliers) / double(n_correspondences) < 0.7 (:389), else 3: verified.  A ratio of
+ * exactly 0.7 passes here (runRansac3d2d asks for > 0.7: 14 of 20 is verified here and rejected there).
+ * result: n_correspondences is the kernel's own count under every verdict; accepted = (verdict == 3).  For verdicts 0
+ * and 1 nothing is scored: best_hypothesis -1, n_inliers 0, hyp_inliers -1.  The optional state, distance and
+ * landmark_out mean what they mean in the 3d2d call (:393-397 are the states 2); landmark_out may be
+ * match_landmark_dev itself and holds -1 where the multiframe is verified and the state is 1.
+ * Nothing synchronises the host; no workspace; 112 bytes per camera go through the pinned parameter ring.  A NULL or
+ * negative argument: OKVFE_ERR_INVALID_ARGUMENT before anything is launched; n_multiframes == 0 is OK and launches
+ * nothing. */
+okvfe_status okvfe_place_consensus_blocks_device(
+    okvfe_ctx* ctx, const okvfe_place_set_device* set, const void* blocks_dev, int32_t n_multiframes, int32_t n_cams,
+    const int32_t* cam_ids /* HOST, n_cams */, const okvfe_pose* T_SC /* HOST, n_cams */,
+    const int32_t* match_landmark_dev, const uint8_t* gate_dev /* or NULL */, const double* hypotheses_dev,
+    const uint8_t* hyp_valid_dev /* or NULL */, int32_t n_hyp, double threshold, int32_t min_inliers,
+    const okvfe_ransac_result_device* result, uint8_t* verdict_dev, void* stream);
+
 /* ---- keyframe decision: keypoint coverage masks and their IoU ---------------- */
 /* Frontend::doWeNeedANewKeyframe (Frontend.cpp:1058-1167), the step between the map matchers and matchStereo whose
  * answer is *asKeyframe.  Per camera image of size w x h (the context's) the reference keeps two zeroed u8 masks of

@@ -118,6 +118,7 @@ EXPORTS = [
     "okvfe_match_to_map_table_uninitialised_blocks_device",
     "okvfe_ransac3d2d_consensus_blocks_device", "okvfe_remove_outliers_blocks_device",
     "okvfe_match_motion_stereo_blocks_batch_device",
+    "okvfe_place_landmark_set", "okvfe_place_claims_blocks_device", "okvfe_place_consensus_blocks_device",
 ]
 
 STAGES = ["harris", "nms", "sort", "select", "map", "describe", "compact", "match"]
@@ -154,6 +155,17 @@ class RansacResultDevice(C.Structure):
                 ("distance", C.c_void_p), ("landmark_out", C.c_void_p)]
 
 
+class PlaceSetDevice(C.Structure):
+    """okvfe_place_set_device: the old frame's landmark set, hp a device pointer (L x 4 doubles)."""
+    _fields_ = [("n_landmarks", C.c_int32), ("hp", C.c_void_p)]
+
+
+class PlaceClaimsDevice(C.Structure):
+    """okvfe_place_claims_device: device pointers, all required."""
+    _fields_ = [("n_matches", C.c_void_p), ("n_points", C.c_void_p), ("n_correspondences", C.c_void_p),
+                ("gate", C.c_void_p), ("match_landmark", C.c_void_p)]
+
+
 class MotionClaimDevice(C.Structure):
     """okvfe_motion_claim_device: device pointers; matched1_out is optional (None)."""
     _fields_ = [("claimed", C.c_void_p), ("n_claimed", C.c_void_p), ("matched1_out", C.c_void_p)]
@@ -164,6 +176,8 @@ MOTION_CLAIM_MAX_KEYPOINTS = 12288  # K above it: claims are OKVFE_ERR_UNSUPPORT
 RANSAC_MAX_HYPOTHESES = 64  # OKVFE_RANSAC_MAX_HYPOTHESES
 RANSAC_THRESHOLD = 16.0     # Frontend.cpp:2235
 REMOVE_OUTLIERS_MAX_ERROR = 4.0  # Frontend.cpp:2185
+PLACE_CLAIMS_MAX_KEYPOINTS = 12288  # K above it: okvfe_place_claims_blocks_device is OKVFE_ERR_UNSUPPORTED
+PLACE_VERDICTS = ("gate", "too_few_correspondences", "rejected", "verified")  # okvfe_place_consensus_blocks_device
 
 
 class OkvfeError(RuntimeError):
@@ -212,6 +226,13 @@ def lib():
         L.okvfe_match_motion_stereo_blocks_batch_device.restype = C.c_int32
         L.okvfe_match_motion_stereo_blocks_batch_device.argtypes = [
             V, V, C.c_int32, V, C.c_int32, C.c_int32, V, V, V, V, V, V, V, V, V, V]
+        L.okvfe_place_landmark_set.restype = C.c_int32
+        L.okvfe_place_landmark_set.argtypes = [C.c_int32, V, V, V, V, V, C.c_int32, V, V, V, C.c_int32, V, C.c_int32, V, V]
+        L.okvfe_place_claims_blocks_device.restype = C.c_int32
+        L.okvfe_place_claims_blocks_device.argtypes = [V, V, V, C.c_int32, C.c_int32, V, V, C.c_int32, V, V]
+        L.okvfe_place_consensus_blocks_device.restype = C.c_int32
+        L.okvfe_place_consensus_blocks_device.argtypes = [
+            V, V, V, C.c_int32, C.c_int32, V, V, V, V, V, V, C.c_int32, C.c_double, C.c_int32, V, V, V]
         _LIB = L
     return _LIB
 
@@ -342,6 +363,31 @@ def bow_vector(word_ids, word_weight, weighting=0, normalise_l1=True):
     if st != OK:
         raise OkvfeError(st, "okvfe_bow_vector")
     return ids[:n.value].copy(), vals[:n.value].copy()
+
+
+def place_landmark_set(n_kps, landmark_ids, landmarks, initialised, descriptors, eigen_tree=True):
+    """okvfe_place_landmark_set: the landmark set of an old frame (Frontend.cpp:289-327) from its keypoints of all
+    cameras, camera-major (n_kps per camera).  -> dict(ids [L] u64, hp [L, 4], desc_begin [L + 1] i32, pool [rows, 48])
+    in ascending landmark id.  Host helper."""
+    nk = np.ascontiguousarray(n_kps, dtype=np.int32)
+    ids = np.ascontiguousarray(landmark_ids, dtype=np.uint64)
+    hp = np.ascontiguousarray(landmarks, dtype=np.float64).reshape(-1, 4)
+    ini = np.ascontiguousarray(initialised, dtype=np.uint8)
+    desc = np.ascontiguousarray(descriptors, dtype=np.uint8).reshape(-1, 48)
+    n = int(nk.sum())
+    if not (len(ids) == len(hp) == len(ini) == len(desc) == n):
+        raise ValueError("one id, landmark, flag and descriptor per keypoint")
+    cap_l = cap_r = n
+    out = dict(ids=np.zeros(cap_l, np.uint64), hp=np.zeros((cap_l, 4)), desc_begin=np.zeros(cap_l + 1, np.int32),
+               pool=np.zeros((cap_r, 48), np.uint8))
+    nl, nr = C.c_int32(0), C.c_int32(0)
+    st = lib().okvfe_place_landmark_set(len(nk), _p(nk), _p(ids), _p(hp), _p(ini), _p(desc), 1 if eigen_tree else 0,
+                                        _p(out["ids"]), _p(out["hp"]), _p(out["desc_begin"]), cap_l, _p(out["pool"]),
+                                        cap_r, C.byref(nl), C.byref(nr))
+    if st != 0:
+        raise OkvfeError(st, "okvfe_place_landmark_set")
+    L, R = nl.value, nr.value
+    return dict(ids=out["ids"][:L], hp=out["hp"][:L], desc_begin=out["desc_begin"][:L + 1], pool=out["pool"][:R])
 
 
 def keyframe_decision(current, others=None, overlap_threshold=KEYFRAME_OVERLAP_THRESHOLD):
@@ -931,6 +977,44 @@ class Frontend:
         self._check(lib().okvfe_remove_outliers_blocks_device(
             self._h, C.byref(table), _p(blocks_ptr), n, _p(cams) if n else _p(np.zeros(1, np.int32)), P,
             C.c_double(max_error), _p(landmark_ptr), _p(landmark_out_ptr), _p(kept_ptr), _s(stream)))
+
+    # -- loop closure: verifyRecognisedPlace after its descriptor matching ---------------------
+    place_landmark_set = staticmethod(place_landmark_set)
+
+    @staticmethod
+    def make_place_set_device(n_landmarks, hp_ptr) -> PlaceSetDevice:
+        return PlaceSetDevice(int(n_landmarks), int(hp_ptr) if hp_ptr else None)
+
+    @staticmethod
+    def make_place_claims_device(n_matches_ptr, n_points_ptr, n_correspondences_ptr, gate_ptr,
+                                 match_landmark_ptr) -> PlaceClaimsDevice:
+        return PlaceClaimsDevice(*[int(p) if p else None for p in (
+            n_matches_ptr, n_points_ptr, n_correspondences_ptr, gate_ptr, match_landmark_ptr)])
+
+    def place_claims_blocks_device(self, place_set: PlaceSetDevice, blocks_ptr, n_multiframes, n_cams, k_min_ptr,
+                                   dist_min_ptr, min_inliers, result: PlaceClaimsDevice, stream=None):
+        """The claims and count gates of verifyRecognisedPlace (Frontend.cpp:347-351, 359, 380) for n_multiframes
+        multiframes of n_cams gather blocks, from the rows okvfe_verify_place_blocks_device wrote (blocks x L)."""
+        self._check(lib().okvfe_place_claims_blocks_device(
+            self._h, C.byref(place_set) if place_set is not None else None, _p(blocks_ptr), int(n_multiframes),
+            int(n_cams), _p(k_min_ptr), _p(dist_min_ptr), int(min_inliers),
+            C.byref(result) if result is not None else None, _s(stream)))
+
+    def place_consensus_blocks_device(self, place_set: PlaceSetDevice, blocks_ptr, n_multiframes, cam_ids, poses_T_SC,
+                                      match_landmark_ptr, gate_ptr, hypotheses_ptr, hyp_valid_ptr, n_hyp, min_inliers,
+                                      result: RansacResultDevice, verdict_ptr, threshold=RANSAC_THRESHOLD, stream=None):
+        """The consensus and verdict of verifyRecognisedPlace (Frontend.cpp:372-397).  verdict_ptr: device bytes per
+        multiframe, an index into PLACE_VERDICTS; the other arguments as ransac3d2d_consensus_blocks_device."""
+        cams = np.ascontiguousarray(cam_ids, dtype=np.int32)
+        n_cams = len(cams)
+        if len(poses_T_SC) != n_cams:
+            raise ValueError("cam_ids and poses_T_SC: one per camera")
+        P = (Pose * max(n_cams, 1))(*[make_pose(*T) for T in poses_T_SC])
+        self._check(lib().okvfe_place_consensus_blocks_device(
+            self._h, C.byref(place_set) if place_set is not None else None, _p(blocks_ptr), int(n_multiframes), n_cams,
+            _p(cams) if n_cams else _p(np.zeros(1, np.int32)), P, _p(match_landmark_ptr), _p(gate_ptr),
+            _p(hypotheses_ptr), _p(hyp_valid_ptr), int(n_hyp), C.c_double(threshold), int(min_inliers),
+            C.byref(result) if result is not None else None, _p(verdict_ptr), _s(stream)))
 
     @staticmethod
     def _test_ransac_chunk_records() -> int:

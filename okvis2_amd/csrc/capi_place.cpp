@@ -1,0 +1,91 @@
+// capi_place.cpp -- Frontend::verifyRecognisedPlace behind the C ABI, around the descriptor matching that
+// okvfe_verify_place_blocks_device does: the old frame's landmark set (Frontend.cpp:289-327, on the host) and the
+// claims with their two count gates (:347-351, :359, :380) on device-resident batches.  The consensus that follows is
+// okvfe_place_consensus_blocks_device (capi_ransac.cpp).
+#include <algorithm>
+#include <cmath>
+#include <map>
+
+#include "okvfe_ctx.h"
+
+using namespace okvfe;
+
+extern "C" {
+
+okvfe_status okvfe_place_landmark_set(int32_t n_cams, const int32_t* n_kps, const uint64_t* landmark_ids,
+                                      const double* landmarks, const uint8_t* initialised, const uint8_t* descriptors,
+                                      int32_t order, uint64_t* ids_out, double* hp_out, int32_t* desc_begin_out,
+                                      int32_t cap_landmarks, uint8_t* pool_out, int32_t cap_rows, int32_t* n_landmarks,
+                                      int32_t* n_rows) {
+  if (n_cams < 0 || (n_cams > 0 && !n_kps) || (order != 0 && order != 1) || cap_landmarks < 0 || cap_rows < 0 ||
+      !desc_begin_out || !n_landmarks || !n_rows || (cap_landmarks > 0 && (!ids_out || !hp_out)) ||
+      (cap_rows > 0 && !pool_out))
+    return OKVFE_ERR_INVALID_ARGUMENT;
+  int64_t total = 0;
+  for (int c = 0; c < n_cams; ++c) {
+    if (n_kps[c] < 0) return OKVFE_ERR_INVALID_ARGUMENT;
+    total += n_kps[c];
+  }
+  if (total > INT32_MAX || (total > 0 && (!landmark_ids || !landmarks || !initialised || !descriptors)))
+    return OKVFE_ERR_INVALID_ARGUMENT;
+  // cameras ascending, keypoints ascending: per landmark the keypoints that pass, the first of them supplies hp (:319-324)
+  std::map<uint64_t, std::vector<int32_t>> set;
+  int64_t rows = 0;
+  for (int64_t i = 0; i < total; ++i) {
+    if (landmark_ids[i] == 0) continue;  // :293
+    if (!initialised[i]) continue;       // :300
+    const double* x = landmarks + 4 * i;
+    const double q0 = x[0] * x[0], q1 = x[1] * x[1], q2 = x[2] * x[2], q3 = x[3] * x[3];
+    const double norm = std::sqrt(order ? (q0 + q1) + (q2 + q3) : ((q0 + q1) + q2) + q3);
+    if (norm < 1.0e-12) continue;        // :301 (a NaN stays in)
+    set[landmark_ids[i]].push_back((int32_t)i);
+    ++rows;
+  }
+  *n_landmarks = (int32_t)set.size();
+  *n_rows = (int32_t)rows;
+  if ((int64_t)set.size() > cap_landmarks || rows > cap_rows) return OKVFE_ERR_CAPACITY;
+  int32_t l = 0, row = 0;
+  for (const auto& lm : set) {  // ascending id (:330)
+    ids_out[l] = lm.first;
+    std::copy_n(landmarks + 4 * (int64_t)lm.second.front(), 4, hp_out + 4 * (int64_t)l);
+    desc_begin_out[l] = row;
+    for (int32_t i : lm.second) {
+      std::copy_n(descriptors + 48 * (int64_t)i, 48, pool_out + 48 * (int64_t)row);
+      ++row;
+    }
+    ++l;
+  }
+  desc_begin_out[l] = row;
+  return OKVFE_OK;
+}
+
+okvfe_status okvfe_place_claims_blocks_device(okvfe_ctx* ctx, const okvfe_place_set_device* set, const void* blocks_dev,
+                                              int32_t n_multiframes, int32_t n_cams, const int32_t* k_min_dev,
+                                              const uint32_t* dist_min_dev, int32_t min_inliers,
+                                              const okvfe_place_claims_device* result, void* stream) {
+  if (!ctx) return OKVFE_ERR_INVALID_ARGUMENT;
+  if (!set || set->n_landmarks < 0 || (set->n_landmarks > 0 && (!set->hp || !k_min_dev || !dist_min_dev)) || !blocks_dev ||
+      n_multiframes < 0 || n_cams < 1 || min_inliers < 0 || !result || !result->n_matches || !result->n_points ||
+      !result->n_correspondences || !result->gate || !result->match_landmark)
+    return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_place_claims_blocks_device: bad argument");
+  if (ctx->kp_cap > kPlaceClaimsMaxKeypoints)
+    return fail(ctx, OKVFE_ERR_UNSUPPORTED, "okvfe_place_claims_blocks_device: claims need max_keypoints <= %d (this context: %d)",
+                kPlaceClaimsMaxKeypoints, ctx->kp_cap);
+  if ((int64_t)n_multiframes * n_cams >= (int64_t)1 << 30)
+    return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_place_claims_blocks_device: too many blocks");
+  if (n_multiframes == 0) return OKVFE_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
+  hipStream_t s = pick_stream(ctx, stream);
+  const BlockLayout L = block_layout(ctx->kp_cap);
+  const int offs[6] = {(int)L.o_count, (int)L.o_kps, (int)L.o_desc, (int)L.o_bp, (int)L.o_bpv, (int)L.total};
+  {
+    StageTimer t(ctx, OKVFE_STAGE_MAP, s);
+    launch_place_claims(set->hp, set->n_landmarks, offs, static_cast<const uint8_t*>(blocks_dev), n_multiframes, n_cams,
+                        ctx->kp_cap, k_min_dev, dist_min_dev, (uint32_t)ctx->cfg.match_threshold, min_inliers, *result, s);
+  }
+  HIP_TRY(ctx, hipGetLastError());
+  ctx->last_stream = s;
+  return OKVFE_OK;
+}
+
+}  // extern "C"

@@ -108,6 +108,57 @@ okvfe_status okvfe_remove_outliers_blocks_device(okvfe_ctx* ctx, const okvfe_lan
   return rel;
 }
 
+// The consensus of Frontend::verifyRecognisedPlace (Frontend.cpp:372-397): the kernel above under its kPlace policy, fed
+// with the claims of okvfe_place_claims_blocks_device (capi_place.cpp).
+okvfe_status okvfe_place_consensus_blocks_device(
+    okvfe_ctx* ctx, const okvfe_place_set_device* set, const void* blocks_dev, int32_t n_multiframes, int32_t n_cams,
+    const int32_t* cam_ids, const okvfe_pose* T_SC, const int32_t* match_landmark_dev, const uint8_t* gate_dev,
+    const double* hypotheses_dev, const uint8_t* hyp_valid_dev, int32_t n_hyp, double threshold, int32_t min_inliers,
+    const okvfe_ransac_result_device* result, uint8_t* verdict_dev, void* stream) {
+  if (!ctx) return OKVFE_ERR_INVALID_ARGUMENT;
+  if (!set || set->n_landmarks < 0 || (set->n_landmarks > 0 && !set->hp) || !blocks_dev || n_multiframes < 0 ||
+      n_cams < 1 || n_cams > (int)ctx->h_cams.size() || !cam_ids || !T_SC || !match_landmark_dev || !hypotheses_dev ||
+      n_hyp < 1 || n_hyp > OKVFE_RANSAC_MAX_HYPOTHESES || !(threshold >= 0.0) || min_inliers < 0 || !result ||
+      !result->n_correspondences || !result->best_hypothesis || !result->n_inliers || !result->accepted || !verdict_dev)
+    return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_place_consensus_blocks_device: bad argument");
+  if ((int64_t)n_cams * ctx->kp_cap >= (int64_t)1 << 30)
+    return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_place_consensus_blocks_device: too many keypoints per multiframe");
+  std::vector<RansacCamParams> cp((size_t)n_cams);
+  for (int c = 0; c < n_cams; ++c) {
+    const DeviceCamera* dc = slot_camera(ctx, cam_ids[c]);
+    if (!dc)
+      return fail(ctx, OKVFE_ERR_NOT_READY,
+                  "okvfe_place_consensus_blocks_device: frame %d: camera slot %d has no intrinsics (okvfe_set_camera)", c,
+                  cam_ids[c]);
+    cp[(size_t)c] = RansacCamParams{};
+    std::memcpy(cp[(size_t)c].C, T_SC[c].C, sizeof(cp[(size_t)c].C));
+    std::memcpy(cp[(size_t)c].r, T_SC[c].r, sizeof(cp[(size_t)c].r));
+    cp[(size_t)c].fu = dc->fu;
+    cp[(size_t)c].cam = cam_ids[c];
+  }
+  if (n_multiframes == 0) return OKVFE_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
+  hipStream_t s = pick_stream(ctx, stream);
+  const BlockLayout L = block_layout(ctx->kp_cap);
+  const int offs[6] = {(int)L.o_count, (int)L.o_kps, (int)L.o_desc, (int)L.o_bp, (int)L.o_bpv, (int)L.total};
+  void* d_cp = nullptr;
+  int slot = -1;
+  okvfe_status st = ring_upload(ctx, &ctx->pair_ring, cp.data(), cp.size() * sizeof(RansacCamParams), s, &d_cp, &slot);
+  if (st != OKVFE_OK) return st;
+  hipError_t e = hipSuccess;
+  {
+    StageTimer t(ctx, OKVFE_STAGE_MAP, s);
+    launch_place_consensus(set->hp, set->n_landmarks, offs, static_cast<const uint8_t*>(blocks_dev), n_multiframes, n_cams,
+                           ctx->kp_cap, static_cast<const RansacCamParams*>(d_cp), match_landmark_dev, gate_dev,
+                           hypotheses_dev, hyp_valid_dev, n_hyp, threshold, min_inliers, *result, verdict_dev, s);
+    e = hipGetLastError();
+  }
+  const okvfe_status rel = ring_release(ctx, &ctx->pair_ring, slot, s);  // on every path: the slot has a reader or not
+  HIP_TRY(ctx, e);
+  ctx->last_stream = s;
+  return rel;
+}
+
 // Test hook, deliberately not in include/okvfe.h: the number of correspondences the consensus kernel scores at a time,
 // so that the tests straddle it whatever it is.
 int32_t okvfe_test_ransac_chunk_records(void) { return ransac_chunk_records(); }

@@ -2,6 +2,10 @@
 // batch of multiframes: the correspondences of FrameNoncentralAbsoluteAdapter (FrameNoncentralAbsoluteAdapter.cpp:
 // 50-148), the distance of every correspondence to every pose hypothesis (FrameAbsolutePoseSacProblem.hpp:135-167),
 // the winner, the acceptance rule and the outlier removal.  The minimal solver and the sampler stay with the caller.
+// The same kernel under the policy kPlace is the consensus of Frontend::verifyRecognisedPlace (Frontend.cpp:372-397)
+// over the correspondences of LoopclosureNoncentralAbsoluteAdapter (LoopclosureNoncentralAbsoluteAdapter.cpp:69-154):
+// the rows are those of the old frame's landmark set, there is no test on observations, seven correspondences are the
+// floor (:380) and the verdict is :389.
 //   ransac_consensus_kernel   one work-group per multiframe.  The correspondences are compacted, in the adapter's
 //                             order, into an LDS ring of 64-byte records and scored kRansacChunk at a time: a lane
 //                             keeps one record (and its camera's extrinsics) in registers and walks the inverted
@@ -70,15 +74,21 @@ struct RansacArgs {
   uint8_t* state;
   double* distance;
   int32_t* landmark_out;
+  // kPlace only (at the end: the members above keep their offsets)
+  const uint8_t* gate;  // per multiframe or NULL: 0 = Frontend.cpp:359 returned false
+  uint8_t* verdict;
+  int min_inliers;
 };
 
 // FrameNoncentralAbsoluteAdapter.cpp:101-145 for keypoint k (< count) of one block that carries table row l: false =
-// no correspondence.  A row outside the table is no correspondence either.
-template <bool kTree>
+// no correspondence.  A row outside the table is no correspondence either.  kPlace: the same lines of
+// LoopclosureNoncentralAbsoluteAdapter.cpp (:112-150), which has no test on the observations.
+template <bool kTree, bool kPlace>
 __device__ __forceinline__ bool make_correspondence(const RansacArgs& A, const uint8_t* blk, int c, int k, int l,
                                                     Corr& R) {
   if (l < 0 || l >= A.n_landmarks) return false;                 // :105
-  if (A.obs_begin[l + 1] - A.obs_begin[l] < 1) return false;     // :109, without the observation of this frame
+  if constexpr (!kPlace)
+    if (A.obs_begin[l + 1] - A.obs_begin[l] < 1) return false;   // :109, without the observation of this frame
   const double* hp = A.hp_W + 4 * (size_t)l;
   const double w = hp[3];
   if (fabs(w) < 1.0e-8) return false;                            // :116 (a NaN stays in)
@@ -130,7 +140,7 @@ __device__ __forceinline__ double ransac_distance(const double* inv, const doubl
   return sum3m<kTree>(e[0] * e[0], e[1] * e[1], e[2] * e[2]) / sigma;
 }
 
-template <bool kTree>
+template <bool kTree, bool kPlace>
 __global__ __launch_bounds__(kRansacThreads) void ransac_consensus_kernel(RansacArgs A) {
   __shared__ Corr s_rec[kRansacRing];               // 32 KiB
   __shared__ double s_inv[OKVFE_RANSAC_MAX_HYPOTHESES][12];  // 6 KiB
@@ -141,6 +151,9 @@ __global__ __launch_bounds__(kRansacThreads) void ransac_consensus_kernel(Ransac
   const int m = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int K = A.kp_cap, slots = A.n_cams * K;
   const size_t frame0 = (size_t)m * (size_t)A.n_cams;
+  // kPlace: the caller's gate 0 (Frontend.cpp:359 returned false before the adapter existed): nothing is scored
+  const bool gated = kPlace && A.gate && A.gate[m] == 0;
+  constexpr int kMinCorr = kPlace ? 7 : 10;  // Frontend.cpp:380 : Frontend.cpp:2226
 
   if (tid < A.n_hyp) {
     const size_t h = (size_t)m * (size_t)A.n_hyp + (size_t)tid;
@@ -174,7 +187,7 @@ __global__ __launch_bounds__(kRansacThreads) void ransac_consensus_kernel(Ransac
       const uint8_t* blk = A.blocks + (frame0 + c) * A.block_bytes;
       int count = *reinterpret_cast<const int32_t*>(blk + A.o_count);
       count = count < 0 ? 0 : (count > K ? K : count);
-      if (k < count) take = make_correspondence<kTree>(A, blk, c, k, A.landmark[(frame0 + c) * K + k], R);
+      if (k < count) take = make_correspondence<kTree, kPlace>(A, blk, c, k, A.landmark[(frame0 + c) * K + k], R);
     }
     const unsigned long long bal = __ballot(take);
     if (lane == 0) s_wave[wave] = (int)__popcll(bal);
@@ -187,12 +200,12 @@ __global__ __launch_bounds__(kRansacThreads) void ransac_consensus_kernel(Ransac
     if (take) s_rec[pos & (kRansacRing - 1)] = R;
     __syncthreads();
     if (head - tail >= kRansacChunk) {
-      score(tail, kRansacChunk);
+      if (!gated) score(tail, kRansacChunk);
       tail += kRansacChunk;
     }
   }
   const int n_corr = head;
-  const bool scored = n_corr >= 10;  // Frontend.cpp:2226
+  const bool scored = !gated && n_corr >= kMinCorr;
   if (scored && head > tail) score(tail, head - tail);
   __syncthreads();
 
@@ -205,7 +218,15 @@ __global__ __launch_bounds__(kRansacThreads) void ransac_consensus_kernel(Ransac
           most = s_cnt[h];
           best = h;
         }
-    const int acc = most >= 10 && (double)most / (double)n_corr > 0.7;  // Frontend.cpp:2243
+    int acc;
+    if constexpr (kPlace) {
+      // Frontend.cpp:389: a ratio of exactly 0.7 passes here (and not at :2243)
+      const int v = gated ? 0 : !scored ? 1 : (most < A.min_inliers || (double)most / (double)n_corr < 0.7) ? 2 : 3;
+      A.verdict[m] = (uint8_t)v;
+      acc = v == 3;
+    } else {
+      acc = most >= 10 && (double)most / (double)n_corr > 0.7;  // Frontend.cpp:2243
+    }
     A.n_corr[m] = n_corr;
     A.best[m] = best;
     A.n_inl[m] = most;
@@ -220,7 +241,7 @@ __global__ __launch_bounds__(kRansacThreads) void ransac_consensus_kernel(Ransac
 
   // the final sweep: every keypoint below its block's count against the winner
   const int best = s_best;
-  const bool remove = s_accepted && A.remove_outliers;  // Frontend.cpp:2245-2260
+  const bool remove = s_accepted && A.remove_outliers;  // Frontend.cpp:2245-2260 (kPlace: the inlier flags of :393-397)
   for (int s = tid; s < slots; s += kRansacThreads) {
     const int c = s / K, k = s - c * K;
     const uint8_t* blk = A.blocks + (frame0 + c) * A.block_bytes;
@@ -231,7 +252,7 @@ __global__ __launch_bounds__(kRansacThreads) void ransac_consensus_kernel(Ransac
     const int l = A.landmark[row];
     Corr R;
     int st = 0;
-    if (make_correspondence<kTree>(A, blk, c, k, l, R)) {
+    if (make_correspondence<kTree, kPlace>(A, blk, c, k, l, R)) {
       st = 1;
       if (best >= 0) {
         const RansacCamParams P = A.cams[c];
@@ -247,12 +268,11 @@ __global__ __launch_bounds__(kRansacThreads) void ransac_consensus_kernel(Ransac
 
 }  // namespace
 
-void launch_ransac_consensus(const double* hp_W, const int32_t* obs_begin, int n_landmarks, const int offs[6],
-                             const uint8_t* blocks, int n_multiframes, int n_cams, int kp_cap,
-                             const RansacCamParams* cams, const int32_t* landmark, const double* hypotheses,
-                             const uint8_t* hyp_valid, int n_hyp, double threshold, int remove_outliers,
-                             const okvfe_ransac_result_device& out, hipStream_t stream) {
-  if (n_multiframes <= 0) return;
+namespace {
+RansacArgs ransac_args(const double* hp_W, const int32_t* obs_begin, int n_landmarks, const int offs[6],
+                       const uint8_t* blocks, int n_cams, int kp_cap, const RansacCamParams* cams, const int32_t* landmark,
+                       const double* hypotheses, const uint8_t* hyp_valid, int n_hyp, double threshold, int remove_outliers,
+                       const okvfe_ransac_result_device& out) {
   RansacArgs A;
   A.hp_W = hp_W; A.obs_begin = obs_begin; A.n_landmarks = n_landmarks;
   A.blocks = blocks; A.o_count = offs[0]; A.o_kps = offs[1]; A.o_bp = offs[3]; A.o_bpv = offs[4];
@@ -261,9 +281,36 @@ void launch_ransac_consensus(const double* hp_W, const int32_t* obs_begin, int n
   A.threshold = threshold; A.remove_outliers = remove_outliers;
   A.n_corr = out.n_correspondences; A.best = out.best_hypothesis; A.n_inl = out.n_inliers; A.accepted = out.accepted;
   A.hyp_inliers = out.hyp_inliers; A.state = out.state; A.distance = out.distance; A.landmark_out = out.landmark_out;
+  A.gate = nullptr; A.verdict = nullptr; A.min_inliers = 0;
+  return A;
+}
+}  // namespace
+
+void launch_ransac_consensus(const double* hp_W, const int32_t* obs_begin, int n_landmarks, const int offs[6],
+                             const uint8_t* blocks, int n_multiframes, int n_cams, int kp_cap,
+                             const RansacCamParams* cams, const int32_t* landmark, const double* hypotheses,
+                             const uint8_t* hyp_valid, int n_hyp, double threshold, int remove_outliers,
+                             const okvfe_ransac_result_device& out, hipStream_t stream) {
+  if (n_multiframes <= 0) return;
+  const RansacArgs A = ransac_args(hp_W, obs_begin, n_landmarks, offs, blocks, n_cams, kp_cap, cams, landmark, hypotheses,
+                                   hyp_valid, n_hyp, threshold, remove_outliers, out);
   const bool ltr = g_fp64_ltr_ransac[current_device_slot()].load() != 0;
-  hipLaunchKernelGGL(ltr ? ransac_consensus_kernel<false> : ransac_consensus_kernel<true>, dim3(n_multiframes),
-                     dim3(kRansacThreads), 0, stream, A);
+  auto* kernel = ltr ? ransac_consensus_kernel<false, false> : ransac_consensus_kernel<true, false>;
+  hipLaunchKernelGGL(kernel, dim3(n_multiframes), dim3(kRansacThreads), 0, stream, A);
+}
+
+void launch_place_consensus(const double* hp, int n_landmarks, const int offs[6], const uint8_t* blocks, int n_multiframes,
+                            int n_cams, int kp_cap, const RansacCamParams* cams, const int32_t* match_landmark,
+                            const uint8_t* gate, const double* hypotheses, const uint8_t* hyp_valid, int n_hyp,
+                            double threshold, int min_inliers, const okvfe_ransac_result_device& out, uint8_t* verdict,
+                            hipStream_t stream) {
+  if (n_multiframes <= 0) return;
+  RansacArgs A = ransac_args(hp, nullptr, n_landmarks, offs, blocks, n_cams, kp_cap, cams, match_landmark, hypotheses,
+                             hyp_valid, n_hyp, threshold, 1, out);
+  A.gate = gate; A.verdict = verdict; A.min_inliers = min_inliers;
+  const bool ltr = g_fp64_ltr_ransac[current_device_slot()].load() != 0;
+  auto* kernel = ltr ? ransac_consensus_kernel<false, true> : ransac_consensus_kernel<true, true>;
+  hipLaunchKernelGGL(kernel, dim3(n_multiframes), dim3(kRansacThreads), 0, stream, A);
 }
 
 int ransac_chunk_records() { return kRansacChunk; }

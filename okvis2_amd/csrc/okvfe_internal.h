@@ -525,6 +525,17 @@ void launch_ransac_consensus(const double* hp_W, const int32_t* obs_begin, int n
                              const uint8_t* hyp_valid, int n_hyp, double threshold, int remove_outliers,
                              const okvfe_ransac_result_device& out, hipStream_t stream);
 int ransac_chunk_records();  // correspondences the consensus kernel scores at a time
+// verifyRecognisedPlace after the descriptor matching (Frontend.cpp:347-397): the claims (k_place.hip) and the consensus
+// over LoopclosureNoncentralAbsoluteAdapter's correspondences (k_ransac.hip, the kPlace policy of the kernel above)
+constexpr int kPlaceClaimsMaxKeypoints = 12288;  // one int per keypoint in LDS
+void launch_place_claims(const double* hp, int n_landmarks, const int offs[6], const uint8_t* blocks, int n_multiframes,
+                         int n_cams, int kp_cap, const int32_t* k_min, const uint32_t* dist_min, uint32_t threshold,
+                         int min_inliers, const okvfe_place_claims_device& out, hipStream_t stream);
+void launch_place_consensus(const double* hp, int n_landmarks, const int offs[6], const uint8_t* blocks, int n_multiframes,
+                            int n_cams, int kp_cap, const RansacCamParams* cams, const int32_t* match_landmark,
+                            const uint8_t* gate, const double* hypotheses, const uint8_t* hyp_valid, int n_hyp,
+                            double threshold, int min_inliers, const okvfe_ransac_result_device& out, uint8_t* verdict,
+                            hipStream_t stream);
 // scale space (k_pyramid.hip)
 void launch_halfsample(const uint8_t* src, int w, int h, int n_images, uint8_t* dst, hipStream_t stream);
 void launch_twothird(const uint8_t* src, int w, int h, int n_images, uint8_t* dst, hipStream_t stream);

@@ -405,6 +405,143 @@ class HipFrontend {
     c.check(okvfe_landmark_table_check_device(c.get(), &v, nullptr));
     return out;
   }
+  // Loop closure: Frontend::verifyRecognisedPlace (Frontend.cpp:270-397) up to the point where ceres takes over.  The
+  // landmark set of an old frame on the host, a device copy of it, the descriptor matching with the claims and count
+  // gates, and the consensus with the verdict.  What stays with the caller: the walk over the DBoW results and its
+  // non-maximum suppression (:771-819), the sampler and gp3p, opengv's adaptive stop, the ceres refinement (:399-527),
+  // the Hessian H (:529-551), attemptLoopClosure and everything after it.
+  struct PlaceLandmarkSet {
+    std::vector<uint64_t> ids;       // ascending
+    std::vector<double> hp;          // x 4
+    std::vector<int32_t> descBegin;  // ids.size() + 1
+    std::vector<uint8_t> pool;       // descBegin.back() x 48
+  };
+  // The landmark set of an old frame (Frontend.cpp:289-327): oldFrame one FrameData per camera (keypoints' landmarkIds
+  // and descriptors are read; the use_cnn filter of :305-317 is the caller's, which passes id 0); landmarks /
+  // initialised: per camera, per keypoint, what getLandmark returns.  eigenTree: the order of norm()'s sum, as
+  // okvfe_set_fp64_reduction.
+  static PlaceLandmarkSet placeLandmarkSet(const std::vector<FrameData>& oldFrame,
+                                           const std::vector<std::vector<std::array<double, 4>>>& landmarks,
+                                           const std::vector<std::vector<uint8_t>>& initialised, bool eigenTree = true) {
+    if (landmarks.size() != oldFrame.size() || initialised.size() != oldFrame.size())
+      throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "placeLandmarkSet: landmarks and initialised: one vector per camera");
+    std::vector<int32_t> nKps;
+    std::vector<uint64_t> ids;
+    std::vector<double> hp;
+    std::vector<uint8_t> init, desc;
+    for (size_t im = 0; im < oldFrame.size(); ++im) {
+      const FrameData& f = oldFrame[im];
+      const size_t n = f.keypoints.size();
+      if (f.landmarkIds.size() != n || landmarks[im].size() != n || initialised[im].size() != n ||
+          f.descriptors.data.size() != n * size_t(OKVFE_DESC_BYTES))
+        throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "placeLandmarkSet: one id, landmark, flag and descriptor per keypoint");
+      nKps.push_back(int32_t(n));
+      ids.insert(ids.end(), f.landmarkIds.begin(), f.landmarkIds.end());
+      for (const auto& l : landmarks[im]) hp.insert(hp.end(), l.begin(), l.end());
+      init.insert(init.end(), initialised[im].begin(), initialised[im].end());
+      desc.insert(desc.end(), f.descriptors.data.begin(), f.descriptors.data.end());
+    }
+    const size_t total = ids.size();
+    PlaceLandmarkSet out;
+    out.ids.resize(total + 1);
+    out.hp.resize(4 * total + 4);
+    out.descBegin.resize(total + 1);
+    out.pool.resize(size_t(OKVFE_DESC_BYTES) * total + 1);
+    int32_t nl = 0, nr = 0;
+    const okvfe_status st = okvfe_place_landmark_set(
+        int32_t(nKps.size()), nKps.data(), ids.data(), hp.data(), init.data(), desc.data(), eigenTree ? 1 : 0,
+        out.ids.data(), out.hp.data(), out.descBegin.data(), int32_t(total), out.pool.data(), int32_t(total), &nl, &nr);
+    if (st != OKVFE_OK) throw Exception(st, "okvfe_place_landmark_set");
+    out.ids.resize(size_t(nl));
+    out.hp.resize(4 * size_t(nl));
+    out.descBegin.resize(size_t(nl) + 1);
+    out.pool.resize(size_t(OKVFE_DESC_BYTES) * size_t(nr));
+    return out;
+  }
+  // A landmark set in device memory: uploaded once per candidate old frame.  Owns its device copies.
+  class DevicePlaceSet {
+   public:
+    DevicePlaceSet() = default;
+    DevicePlaceSet(const DevicePlaceSet&) = delete;
+    DevicePlaceSet& operator=(const DevicePlaceSet&) = delete;
+    ~DevicePlaceSet() {
+      for (void* p : allocs_) okvfe_device_free(p);
+    }
+    const okvfe_place_set_device& get() const { return view_; }
+    const okvfe_map_device& map() const { return map_; }  // (desc_begin, pool) for okvfe_verify_place_blocks_device
+
+   private:
+    friend class HipFrontend;
+    okvfe_place_set_device view_{};
+    okvfe_map_device map_{};
+    std::vector<void*> allocs_;
+  };
+  // Copies `set` to the device with asynchronous copies on `stream`: `set` stays valid and unchanged until it has drained.
+  std::shared_ptr<DevicePlaceSet> uploadPlaceSet(size_t cameraIndex, const PlaceLandmarkSet& set, void* stream = nullptr) {
+    if (cameraIndex >= cameras_.size())
+      throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "Camera index exceeds number of cameras.");
+    const size_t nl = set.ids.size();
+    if (set.hp.size() != 4 * nl || set.descBegin.size() != nl + 1 || set.descBegin.back() < 0 ||
+        set.pool.size() != size_t(OKVFE_DESC_BYTES) * size_t(set.descBegin.back()))
+      throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "uploadPlaceSet: bad set");
+    std::lock_guard<std::mutex> lock(mutexes_[cameraIndex]);
+    Context& c = *contexts_[cameraIndex];
+    auto out = std::make_shared<DevicePlaceSet>();
+    auto up = [&](const void* src, size_t bytes) -> const void* {
+      void* d = nullptr;
+      c.check(okvfe_device_alloc(device_, bytes ? bytes : 1, &d));
+      out->allocs_.push_back(d);
+      if (bytes) c.check(okvfe_copy_to_device(d, src, bytes, stream));
+      return d;
+    };
+    out->view_.n_landmarks = int32_t(nl);
+    out->view_.hp = static_cast<const double*>(up(set.hp.data(), nl * 32));
+    out->map_.n_landmarks = int32_t(nl);
+    out->map_.desc_begin = static_cast<const int32_t*>(up(set.descBegin.data(), (nl + 1) * 4));
+    out->map_.pool = static_cast<const uint8_t*>(up(set.pool.data(), set.pool.size()));
+    return out;
+  }
+  // Frontend.cpp:330-355, 359, 380 for nMultiframes frames of camera `cameraIndex` (a context of this class holds ONE
+  // camera, so a multiframe is one gather block here; a rig whose cameras share a context calls the C entry points
+  // itself): okvfe_verify_place_blocks_device into kMinDev / distMinDev (device, nMultiframes x L), then
+  // okvfe_place_claims_blocks_device into `result`.  Nothing synchronises the host.
+  void verifyPlaceClaimsBlocks(size_t cameraIndex, const DevicePlaceSet& set, const void* blocksDev, int nMultiframes,
+                               int32_t* kMinDev, uint32_t* distMinDev, int minInliers,
+                               const okvfe_place_claims_device& result, void* stream = nullptr) {
+    if (cameraIndex >= cameras_.size())
+      throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "Camera index exceeds number of cameras.");
+    if (nMultiframes < 0) throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "verifyPlaceClaimsBlocks: nMultiframes");
+    if (nMultiframes == 0) return;
+    std::lock_guard<std::mutex> lock(mutexes_[cameraIndex]);
+    Context& c = *contexts_[cameraIndex];
+    c.check(okvfe_verify_place_blocks_device(c.get(), blocksDev, nMultiframes, &set.map(), kMinDev, distMinDev, stream));
+    c.check(okvfe_place_claims_blocks_device(c.get(), &set.get(), blocksDev, nMultiframes, 1, kMinDev, distMinDev,
+                                             minInliers, &result, stream));
+  }
+  // Frontend.cpp:372-397 for the same frames: matchLandmarkDev / gateDev as verifyPlaceClaimsBlocks wrote them (gateDev
+  // may be null), hypotheses / hypValid / nHyp and their upload as in ransac3d2dBlocks; verdictDev: device bytes, 3 =
+  // verified.  result.landmark_out may be matchLandmarkDev.  Nothing else synchronises the host.
+  void verifyPlaceConsensusBlocks(size_t cameraIndex, const DevicePlaceSet& set, const void* blocksDev, int nMultiframes,
+                                  const okvfe_pose& T_SC, const int32_t* matchLandmarkDev, const uint8_t* gateDev,
+                                  const std::vector<double>& hypotheses, const std::vector<uint8_t>& hypValid, int nHyp,
+                                  int minInliers, const okvfe_ransac_result_device& result, uint8_t* verdictDev,
+                                  double threshold = 16.0, void* stream = nullptr) {
+    if (cameraIndex >= cameras_.size())
+      throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "Camera index exceeds number of cameras.");
+    if (nMultiframes < 0 || nHyp < 1 || hypotheses.size() != size_t(nMultiframes) * size_t(nHyp) * 12 ||
+        (!hypValid.empty() && hypValid.size() != size_t(nMultiframes) * size_t(nHyp)))
+      throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "verifyPlaceConsensusBlocks: nHyp hypotheses (and flags) per multiframe");
+    std::lock_guard<std::mutex> lock(mutexes_[cameraIndex]);
+    if (!extractors_[cameraIndex].isCameraAware()) extractors_[cameraIndex].setCamera(cameras_[cameraIndex]);
+    Context& c = *contexts_[cameraIndex];
+    const size_t hypBytes = hypotheses.size() * sizeof(double);
+    uint8_t* d = uploadHypotheses(cameraIndex, hypotheses, hypValid, stream);
+    const int32_t cam = 0;  // slot 0 of the camera's own context
+    c.check(okvfe_place_consensus_blocks_device(
+        c.get(), &set.get(), blocksDev, nMultiframes, 1, &cam, &T_SC, matchLandmarkDev, gateDev,
+        reinterpret_cast<const double*>(d), hypValid.empty() ? nullptr : d + hypBytes, nHyp, threshold, minInliers, &result,
+        verdictDev, stream));
+  }
   // matchToMap (above) for nFrames frames that live in device memory as gather blocks, against an uploaded table: one
   // call per frame batch, nothing synchronises the host.  T_WC1: one pose per frame; useDev: device nFrames x K flags
   // or null; outputs device nFrames x K (K = the context's row capacity); poolOut and its members may be null.  All
@@ -469,22 +606,8 @@ class HipFrontend {
     std::lock_guard<std::mutex> lock(mutexes_[cameraIndex]);
     if (!extractors_[cameraIndex].isCameraAware()) extractors_[cameraIndex].setCamera(cameras_[cameraIndex]);
     Context& c = *contexts_[cameraIndex];
-    HypothesisScratch& hs = hyp_scratch_[cameraIndex];
-    const size_t hypBytes = hypotheses.size() * sizeof(double), bytes = hypBytes + hypValid.size();
-    if (bytes > hs.bytes) {
-      if (hs.d) {
-        c.check(okvfe_stream_synchronize(nullptr));
-        if (stream) c.check(okvfe_stream_synchronize(stream));
-        okvfe_device_free(hs.d);
-        hs.d = nullptr;
-        hs.bytes = 0;
-      }
-      c.check(okvfe_device_alloc(device_, bytes, &hs.d));
-      hs.bytes = bytes;
-    }
-    uint8_t* d = static_cast<uint8_t*>(hs.d);
-    if (hypBytes) c.check(okvfe_copy_to_device(d, hypotheses.data(), hypBytes, stream));
-    if (!hypValid.empty()) c.check(okvfe_copy_to_device(d + hypBytes, hypValid.data(), hypValid.size(), stream));
+    const size_t hypBytes = hypotheses.size() * sizeof(double);
+    uint8_t* d = uploadHypotheses(cameraIndex, hypotheses, hypValid, stream);
     const int32_t cam = 0;  // slot 0 of the camera's own context
     c.check(okvfe_ransac3d2d_consensus_blocks_device(
         c.get(), &table.get(), blocksDev, nMultiframes, 1, &cam, &T_SC, landmarkDev, reinterpret_cast<const double*>(d),
@@ -747,6 +870,28 @@ class HipFrontend {
     }
   };
   std::vector<HypothesisScratch> hyp_scratch_;  // per camera
+  // hypotheses, then the flags, into the camera's scratch buffer with asynchronous copies on `stream` (mutex held)
+  uint8_t* uploadHypotheses(size_t cameraIndex, const std::vector<double>& hypotheses, const std::vector<uint8_t>& hypValid,
+                            void* stream) {
+    Context& c = *contexts_[cameraIndex];
+    HypothesisScratch& hs = hyp_scratch_[cameraIndex];
+    const size_t hypBytes = hypotheses.size() * sizeof(double), bytes = hypBytes + hypValid.size();
+    if (bytes > hs.bytes) {
+      if (hs.d) {
+        c.check(okvfe_stream_synchronize(nullptr));
+        if (stream) c.check(okvfe_stream_synchronize(stream));
+        okvfe_device_free(hs.d);
+        hs.d = nullptr;
+        hs.bytes = 0;
+      }
+      c.check(okvfe_device_alloc(device_, bytes, &hs.d));
+      hs.bytes = bytes;
+    }
+    uint8_t* d = static_cast<uint8_t*>(hs.d);
+    if (hypBytes) c.check(okvfe_copy_to_device(d, hypotheses.data(), hypBytes, stream));
+    if (!hypValid.empty()) c.check(okvfe_copy_to_device(d + hypBytes, hypValid.data(), hypValid.size(), stream));
+    return d;
+  }
   int device_ = 0;
 };
 
