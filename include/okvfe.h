@@ -1087,6 +1087,130 @@ okvfe_status okvfe_place_consensus_blocks_device(
     const uint8_t* hyp_valid_dev /* or NULL */, int32_t n_hyp, double threshold, int32_t min_inliers,
     const okvfe_ransac_result_device* result, uint8_t* verdict_dev, void* stream);
 
+/* ---- place recognition: the DBoW2 query and database on device-resident batches ----------------
+ * What decides which old frames verifyRecognisedPlace is run against.  The reference runs
+ * dBow_->database.query(features, dBoWResult, -1) on every frame once it is initialised (Frontend.cpp:660-672,
+ * :752-766), again per component for multi-session relocalisation (:677-685), and database.add(features) at keyframes
+ * (:896-898).  Here the vocabulary and the database stay in device memory, and one chain on one stream takes a batch of
+ * multiframes from their gather blocks to the few candidate entries per multiframe that the reference's walk over the
+ * sorted results would consider -- without a host synchronisation:
+ *   okvfe_vocabulary_check                  host, once per upload: the tree is a tree
+ *   okvfe_bow_vectors_blocks_device         features -> words -> BowVector per multiframe (:660-672 and DBoW2's transform)
+ *   okvfe_place_query_blocks_device         the L1 scores against every entry, :761-765, :780-799 and :802
+ *   okvfe_bow_database_add_blocks_device    :896-898 for the keyframes of the batch
+ *   okvfe_bow_database_check_device         the one call of the group that synchronises: did an add run out of room
+ * The B = 1 host seams okvfe_fbrisk_transform / okvfe_bow_vector / okvfe_bow_query_l1 above compute the same numbers
+ * from host arrays; the descent and the score are one piece of device code under both.
+ * Multiframe m owns gather blocks m n_cams + c.  Entry ids are positions in the database; the caller keeps the poseIds
+ * (:898).  All queries of one call see the database as it is at the call: the reference, which goes frame by frame,
+ * lets frame t see the keyframe added at t - 1.  Batch granularity is the caller's choice; the entries of the last
+ * few frames are excluded by the estimator's predicates (:808-819) anyway.
+ * What stays with the caller: poseIds; estimator.isPlaceRecognitionFrame per entry (it arrives as suppressible_dev);
+ * the attempts / attempts0 limits and the estimator predicates of :801-819, walked over at most a few dozen candidates
+ * per multiframe after ONE download of the candidate rows; verifyRecognisedPlace itself is the group above.
+ * PARITY UNPINNED: DBoW2 is not in the reference tree (an external dependency of it); transform, addWeight, normalize
+ * and queryL1 are restated from DBoW2's published source, as the B = 1 calls and the oracle restate them.
+ * okvfe_set_fp64_reduction does NOT apply to anything here: DBoW2's sums are plain loops, and their order -- repeated
+ * addition of a word's weight, the L1 norm in ascending word order, the score over the common words in ascending word
+ * order -- is part of the contract. */
+typedef struct okvfe_vocabulary_device {
+  int32_t n_nodes, n_words;
+  int32_t weighting;               /* 0 TF_IDF, 1 TF, 2 IDF, 3 BINARY, as in okvfe_bow_vector */
+  int32_t normalise_l1;            /* as in okvfe_bow_vector */
+  const uint8_t* node_descriptors; /* n_nodes x 48 (the root's row is unused) */
+  const int32_t* child_begin;      /* n_nodes + 1 */
+  const int32_t* child_index;      /* child_begin[n_nodes] */
+  const int32_t* node_word;        /* n_nodes: word id of a leaf, < 0 for an inner node */
+  const double* word_weight;       /* n_words */
+} okvfe_vocabulary_device;
+/* Host-only, no context: the struct filled with HOST pointers.  OKVFE_ERR_INVALID_ARGUMENT (okvfe_last_error(NULL) names
+ * the first offence) unless n_nodes >= 1, n_words >= 1, weighting in 0..3, child_begin[0] == 0, child_begin monotone,
+ * every child in (parent, n_nodes), every node but the root the child of exactly one node and reachable from the root,
+ * node_word in [0, n_words) for every leaf and < 0 for every inner node.  Called once per upload (okvfe_device_alloc /
+ * okvfe_copy_to_device); the device calls trust the vocabulary, as the table calls trust a checked landmark table. */
+okvfe_status okvfe_vocabulary_check(const okvfe_vocabulary_device* vocabulary_host);
+
+typedef struct okvfe_bow_vectors_device {
+  int32_t* n_words;           /* device, per multiframe: the number of distinct words */
+  int32_t* ids;               /* device, M x stride: ascending word ids */
+  double* values;             /* device, M x stride */
+  int32_t stride;
+  int32_t n_vocabulary_words; /* n_words of the vocabulary the vectors come from, or 0 if unknown (the query then never
+                                 uses its dense table); the vectors call does not read it */
+} okvfe_bow_vectors_device;
+/* BowVectors of n_multiframes multiframes of n_cams gather blocks.  The features of multiframe m are the descriptors of
+ * camera 0's keypoints k < count, then camera 1's, and so on (:663-672).  Per feature the descent of
+ * okvfe_fbrisk_transform; per multiframe the vector of okvfe_bow_vector: words with !(weight > 0) are skipped; TF_IDF /
+ * TF add the weight once per occurrence by repeated addition (BowVector::addWeight), IDF / BINARY keep it once; words
+ * ascending; with normalise_l1 the values are divided by their L1 norm, summed sequentially in ascending word order
+ * (one lane per work-group: a dependent chain of at most a few thousand FP64 additions, accepted because the order is
+ * the contract), unless the norm is not > 0; otherwise TF_IDF / TF divide by the number of distinct words.
+ * vectors->stride must be at least min(n_cams max_keypoints, n_words), so nothing is ever truncated; rows past
+ * n_words[m] are untouched.  word_ids_dev: NULL, or device blocks x max_keypoints: the word id of every feature (those
+ * of skipped words too), untouched at or past a block's count.
+ * One work-group per multiframe sorts the multiframe's word ids in LDS and run-length encodes them, for any n_words.
+ * The node descriptors sit in LDS when n_nodes <= 1024 and they fit beside the sort keys (the shipped 9^3 vocabulary
+ * does up to 4096 features per multiframe).  A context with n_cams max_keypoints > 8192 is refused with
+ * OKVFE_ERR_UNSUPPORTED before anything is launched.  Nothing synchronises the host; no workspace.  A NULL or negative
+ * argument: OKVFE_ERR_INVALID_ARGUMENT before any device work; n_multiframes == 0 is OK and launches nothing. */
+okvfe_status okvfe_bow_vectors_blocks_device(okvfe_ctx* ctx, const okvfe_vocabulary_device* vocabulary,
+                                             const void* blocks_dev, int32_t n_multiframes, int32_t n_cams,
+                                             const okvfe_bow_vectors_device* vectors, int32_t* word_ids_dev,
+                                             void* stream);
+
+typedef struct okvfe_bow_database_device {
+  int32_t* begin;      /* device, cap_entries + 1; begin[0] = 0 is the caller's (okvfe_device_fill) */
+  int32_t* ids;        /* device, cap_words */
+  double* values;      /* device, cap_words */
+  int32_t cap_entries, cap_words;
+  int32_t n_entries;   /* HOST: grows with every okvfe_bow_database_add_blocks_device */
+  int32_t* overflow;   /* device, one int32, zeroed by the caller: entries stored empty for want of room */
+} okvfe_bow_database_device;
+/* begin / ids / values are the arrays okvfe_bow_query_l1 takes: entry e owns [begin[e], begin[e + 1]), ascending word
+ * ids, so a database built on the host uploads as it is. */
+typedef struct okvfe_place_candidates_device {
+  int32_t* n_listed;     /* device, per multiframe: dBoWResult.size() */
+  int32_t* n_candidates; /* device, per multiframe: the true count, even above cap */
+  int32_t* entry;        /* device, M x cap */
+  double* score;         /* device, M x cap */
+  int32_t cap;
+} okvfe_place_candidates_device;
+/* database.query and the estimator-free part of the walk over its results, for n_multiframes query vectors (rows of
+ * `vectors`) against the db->n_entries entries the database holds at the call.
+ * Score of entry e for query m = okvfe_bow_query_l1's: over the common words in ascending word order
+ * t = |q - d|; t = t - |q|; t = t - |d|; value = value + t; score = -value / 2; -1 and "not listed" when there is no
+ * common word (an empty entry is never listed).  scores_dev: NULL, or device M x n_entries doubles receiving them all.
+ * The listed entries of a query in ascending entry id are the reference's sorted dBoWResult (:761-765).  Listed position
+ * f with score p is a candidate iff
+ *   NOT (suppressible[id_f] AND any of the listed neighbours f-1, f-2, f+1, f+2 that exist has Score > p)   (:780-799)
+ *   AND p > min_score                                                               (:802, strict; the reference: 0.4)
+ * with the comparisons written exactly like that: equal scores do not suppress, a NaN neither suppresses nor passes.
+ * suppressible_dev: device, n_entries bytes (estimator.isPlaceRecognitionFrame of the entry's frame), or NULL = all
+ * ones, which is the component walk of :700-719.  result: n_listed, the true n_candidates, and the first `cap`
+ * candidates in ascending entry id with their scores; rows past the count are untouched.
+ * One work-group per multiframe, no workspace: the query vector is staged in LDS (vocabularies up to 4096 words as a
+ * dense word -> position table, larger ones as the sorted vector, of which up to 4096 words are staged and longer
+ * vectors read from memory); every work-group walks all entries.  Nothing synchronises the host.  A NULL or negative
+ * argument, or cap < 0: OKVFE_ERR_INVALID_ARGUMENT before any device work; n_multiframes == 0 is OK. */
+okvfe_status okvfe_place_query_blocks_device(okvfe_ctx* ctx, const okvfe_bow_database_device* database,
+                                             const okvfe_bow_vectors_device* vectors, int32_t n_multiframes,
+                                             double min_score, const uint8_t* suppressible_dev, double* scores_dev,
+                                             const okvfe_place_candidates_device* result, void* stream);
+/* database.add (:896-898) for n_add multiframes of the batch: entry n_entries + i becomes a copy of the vector of
+ * multiframe add_index[i] (HOST array, strictly ascending, each in [0, n_multiframes): the keyframe decision is host
+ * arithmetic; the indices travel through the pinned parameter ring).  begin is extended on the device, because the word
+ * counts never visit the host; database->n_entries (host) grows by n_add.
+ * n_entries + n_add > cap_entries: OKVFE_ERR_CAPACITY before anything is launched, nothing changed.  Not enough room in
+ * ids / values is only known on the device: that entry and all later ones of the call are stored empty
+ * (begin[e + 1] = begin[e]) and *overflow is incremented once per such entry.  An empty vector is a legal entry.  A
+ * query queued after an add on the same stream sees the new entries.  Nothing synchronises the host. */
+okvfe_status okvfe_bow_database_add_blocks_device(okvfe_ctx* ctx, okvfe_bow_database_device* database,
+                                                  const okvfe_bow_vectors_device* vectors, int32_t n_multiframes,
+                                                  const int32_t* add_index /* HOST, n_add */, int32_t n_add,
+                                                  void* stream);
+/* Waits for the stream and returns OKVFE_ERR_CAPACITY if *overflow != 0 (the message has the count), else OKVFE_OK. */
+okvfe_status okvfe_bow_database_check_device(okvfe_ctx* ctx, const okvfe_bow_database_device* database, void* stream);
+
 /* ---- keyframe decision: keypoint coverage masks and their IoU ---------------- */
 /* Frontend::doWeNeedANewKeyframe (Frontend.cpp:1058-1167), the step between the map matchers and matchStereo whose
  * answer is *asKeyframe.  Per camera image of size w x h (the context's) the reference keeps two zeroed u8 masks of

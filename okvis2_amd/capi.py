@@ -119,6 +119,8 @@ EXPORTS = [
     "okvfe_ransac3d2d_consensus_blocks_device", "okvfe_remove_outliers_blocks_device",
     "okvfe_match_motion_stereo_blocks_batch_device",
     "okvfe_place_landmark_set", "okvfe_place_claims_blocks_device", "okvfe_place_consensus_blocks_device",
+    "okvfe_vocabulary_check", "okvfe_bow_vectors_blocks_device", "okvfe_place_query_blocks_device",
+    "okvfe_bow_database_add_blocks_device", "okvfe_bow_database_check_device",
 ]
 
 STAGES = ["harris", "nms", "sort", "select", "map", "describe", "compact", "match"]
@@ -166,6 +168,31 @@ class PlaceClaimsDevice(C.Structure):
                 ("gate", C.c_void_p), ("match_landmark", C.c_void_p)]
 
 
+class VocabularyDevice(C.Structure):
+    """okvfe_vocabulary_device: the DBoW2 vocabulary tree; device pointers (host pointers for okvfe_vocabulary_check)."""
+    _fields_ = [("n_nodes", C.c_int32), ("n_words", C.c_int32), ("weighting", C.c_int32), ("normalise_l1", C.c_int32),
+                ("node_descriptors", C.c_void_p), ("child_begin", C.c_void_p), ("child_index", C.c_void_p),
+                ("node_word", C.c_void_p), ("word_weight", C.c_void_p)]
+
+
+class BowVectorsDevice(C.Structure):
+    """okvfe_bow_vectors_device: BowVectors of a batch, device rows M x stride."""
+    _fields_ = [("n_words", C.c_void_p), ("ids", C.c_void_p), ("values", C.c_void_p), ("stride", C.c_int32),
+                ("n_vocabulary_words", C.c_int32)]
+
+
+class BowDatabaseDevice(C.Structure):
+    """okvfe_bow_database_device: device arrays in okvfe_bow_query_l1's layout; n_entries is a HOST field."""
+    _fields_ = [("begin", C.c_void_p), ("ids", C.c_void_p), ("values", C.c_void_p), ("cap_entries", C.c_int32),
+                ("cap_words", C.c_int32), ("n_entries", C.c_int32), ("overflow", C.c_void_p)]
+
+
+class PlaceCandidatesDevice(C.Structure):
+    """okvfe_place_candidates_device: device pointers; entry / score are M x cap rows."""
+    _fields_ = [("n_listed", C.c_void_p), ("n_candidates", C.c_void_p), ("entry", C.c_void_p), ("score", C.c_void_p),
+                ("cap", C.c_int32)]
+
+
 class MotionClaimDevice(C.Structure):
     """okvfe_motion_claim_device: device pointers; matched1_out is optional (None)."""
     _fields_ = [("claimed", C.c_void_p), ("n_claimed", C.c_void_p), ("matched1_out", C.c_void_p)]
@@ -177,6 +204,8 @@ RANSAC_MAX_HYPOTHESES = 64  # OKVFE_RANSAC_MAX_HYPOTHESES
 RANSAC_THRESHOLD = 16.0     # Frontend.cpp:2235
 REMOVE_OUTLIERS_MAX_ERROR = 4.0  # Frontend.cpp:2185
 PLACE_CLAIMS_MAX_KEYPOINTS = 12288  # K above it: okvfe_place_claims_blocks_device is OKVFE_ERR_UNSUPPORTED
+BOW_MAX_FEATURES = 8192  # n_cams x K above it: okvfe_bow_vectors_blocks_device is OKVFE_ERR_UNSUPPORTED
+PLACE_MIN_SCORE = 0.4    # Frontend.cpp:802
 PLACE_VERDICTS = ("gate", "too_few_correspondences", "rejected", "verified")  # okvfe_place_consensus_blocks_device
 
 
@@ -233,6 +262,16 @@ def lib():
         L.okvfe_place_consensus_blocks_device.restype = C.c_int32
         L.okvfe_place_consensus_blocks_device.argtypes = [
             V, V, V, C.c_int32, C.c_int32, V, V, V, V, V, V, C.c_int32, C.c_double, C.c_int32, V, V, V]
+        L.okvfe_vocabulary_check.restype = C.c_int32
+        L.okvfe_vocabulary_check.argtypes = [V]
+        L.okvfe_bow_vectors_blocks_device.restype = C.c_int32
+        L.okvfe_bow_vectors_blocks_device.argtypes = [V, V, V, C.c_int32, C.c_int32, V, V, V]
+        L.okvfe_place_query_blocks_device.restype = C.c_int32
+        L.okvfe_place_query_blocks_device.argtypes = [V, V, V, C.c_int32, C.c_double, V, V, V, V]
+        L.okvfe_bow_database_add_blocks_device.restype = C.c_int32
+        L.okvfe_bow_database_add_blocks_device.argtypes = [V, V, V, C.c_int32, V, C.c_int32, V]
+        L.okvfe_bow_database_check_device.restype = C.c_int32
+        L.okvfe_bow_database_check_device.argtypes = [V, V, V]
         _LIB = L
     return _LIB
 
@@ -363,6 +402,23 @@ def bow_vector(word_ids, word_weight, weighting=0, normalise_l1=True):
     if st != OK:
         raise OkvfeError(st, "okvfe_bow_vector")
     return ids[:n.value].copy(), vals[:n.value].copy()
+
+
+def vocabulary_check(node_desc, child_begin, child_index, node_word, word_weight, weighting=0, normalise_l1=True):
+    """okvfe_vocabulary_check on host arrays: raises OkvfeError (the first offence named) unless the tree is a tree whose
+    leaves carry words in range.  Host helper; call it once before the vocabulary is uploaded."""
+    nd = np.ascontiguousarray(node_desc, dtype=np.uint8).reshape(-1, DESC_BYTES)
+    cb = np.ascontiguousarray(child_begin, dtype=np.int32)
+    ci = np.ascontiguousarray(child_index, dtype=np.int32)
+    nw = np.ascontiguousarray(node_word, dtype=np.int32)
+    ww = np.ascontiguousarray(word_weight, dtype=np.float64)
+    if len(cb) != len(nd) + 1 or len(nw) != len(nd) or (len(cb) and cb[-1] > len(ci)):
+        raise ValueError("vocabulary arrays: n_nodes descriptors and words, n_nodes + 1 child_begin, child_begin[-1] children")
+    v = VocabularyDevice(len(nd), len(ww), int(weighting), int(bool(normalise_l1)), _p(nd), _p(cb),
+                         _p(ci) if len(ci) else None, _p(nw), _p(ww))
+    st = lib().okvfe_vocabulary_check(C.byref(v))
+    if st != OK:
+        raise OkvfeError(st, lib().okvfe_last_error(None).decode())
 
 
 def place_landmark_set(n_kps, landmark_ids, landmarks, initialised, descriptors, eigen_tree=True):
@@ -1015,6 +1071,41 @@ class Frontend:
             _p(cams) if n_cams else _p(np.zeros(1, np.int32)), P, _p(match_landmark_ptr), _p(gate_ptr),
             _p(hypotheses_ptr), _p(hyp_valid_ptr), int(n_hyp), C.c_double(threshold), int(min_inliers),
             C.byref(result) if result is not None else None, _p(verdict_ptr), _s(stream)))
+
+    # -- place recognition: the DBoW2 query and database on device-resident batches -----------
+    def bow_vectors_blocks_device(self, vocabulary: VocabularyDevice, blocks_ptr, n_multiframes, n_cams,
+                                  vectors: BowVectorsDevice, word_ids_ptr=None, stream=None):
+        """BowVectors of n_multiframes multiframes of n_cams gather blocks (Frontend.cpp:660-672 + DBoW2's transform) into
+        the device rows of `vectors`; word_ids_ptr: None or device blocks x K int32."""
+        self._check(lib().okvfe_bow_vectors_blocks_device(
+            self._h, C.byref(vocabulary) if vocabulary is not None else None, _p(blocks_ptr), int(n_multiframes),
+            int(n_cams), C.byref(vectors) if vectors is not None else None, _p(word_ids_ptr), _s(stream)))
+
+    def place_query_blocks_device(self, database: BowDatabaseDevice, vectors: BowVectorsDevice, n_multiframes,
+                                  result: PlaceCandidatesDevice, min_score=PLACE_MIN_SCORE, suppressible_ptr=None,
+                                  scores_ptr=None, stream=None):
+        """database.query and the estimator-free part of the walk (Frontend.cpp:761-802): per multiframe n_listed, the
+        true n_candidates and the first result.cap candidates.  suppressible_ptr: None (all ones) or device n_entries
+        bytes; scores_ptr: None or device M x n_entries doubles."""
+        self._check(lib().okvfe_place_query_blocks_device(
+            self._h, C.byref(database) if database is not None else None,
+            C.byref(vectors) if vectors is not None else None, int(n_multiframes), C.c_double(min_score),
+            _p(suppressible_ptr), _p(scores_ptr), C.byref(result) if result is not None else None, _s(stream)))
+
+    def bow_database_add_blocks_device(self, database: BowDatabaseDevice, vectors: BowVectorsDevice, n_multiframes,
+                                       add_index, stream=None):
+        """database.add (Frontend.cpp:896-898) for the multiframes add_index (host ints, strictly ascending):
+        database.n_entries (host) grows by len(add_index)."""
+        idx = np.ascontiguousarray(add_index, dtype=np.int32).reshape(-1)
+        self._check(lib().okvfe_bow_database_add_blocks_device(
+            self._h, C.byref(database) if database is not None else None,
+            C.byref(vectors) if vectors is not None else None, int(n_multiframes), _p(idx) if len(idx) else None,
+            len(idx), _s(stream)))
+
+    def bow_database_check_device(self, database: BowDatabaseDevice, stream=None):
+        """Waits for the stream; raises OkvfeError(ERR_CAPACITY) if an add stored entries empty for want of room."""
+        self._check(lib().okvfe_bow_database_check_device(
+            self._h, C.byref(database) if database is not None else None, _s(stream)))
 
     @staticmethod
     def _test_ransac_chunk_records() -> int:

@@ -25,30 +25,10 @@
 #include <algorithm>
 
 #include "okvfe_internal.h"
+#include "bow_dev.h"
 
 namespace okvfe {
 namespace {
-
-struct Desc12 {
-  uint32_t w[12];
-};
-
-__device__ __forceinline__ Desc12 load_desc(const uint8_t* p) {
-  Desc12 d;
-  const uint4* q = reinterpret_cast<const uint4*>(p);
-  const uint4 a = q[0], b = q[1], c = q[2];
-  d.w[0] = a.x; d.w[1] = a.y; d.w[2] = a.z; d.w[3] = a.w;
-  d.w[4] = b.x; d.w[5] = b.y; d.w[6] = b.z; d.w[7] = b.w;
-  d.w[8] = c.x; d.w[9] = c.y; d.w[10] = c.z; d.w[11] = c.w;
-  return d;
-}
-
-__device__ __forceinline__ int hamming(const Desc12& a, const uint32_t* __restrict__ b) {
-  int c = 0;
-#pragma unroll
-  for (int i = 0; i < 12; ++i) c += __popc(a.w[i] ^ b[i]);
-  return c;
-}
 
 // Order of every 3-term FP64 sum (okvfe_set_fp64_reduction; oracle/orc_match.c states the reasoning):
 // 1 = Eigen's unrolled non-vectorised redux x0 + (x1 + x2) (default), 0 = left to right.
@@ -598,10 +578,7 @@ __global__ __launch_bounds__(256) void verify_place_kernel(
 }
 
 // ---- DBoW2 vocabulary descent with the FBrisk trait (oracle: orc_voc_transform) ----------------
-// Lane = one feature; the node descriptors (819 x 48 B for the shipped 9^3 vocabulary) sit in LDS
-// when they fit.  At every level the child with the smallest Hamming distance wins, the first on
-// ties.
-constexpr int kVocLdsNodes = 1024;
+// Lane = one feature; the descent itself is voc_descend (bow_dev.h).
 __global__ __launch_bounds__(256) void voc_transform_kernel(
     const uint8_t* __restrict__ desc, int n, const uint8_t* __restrict__ node_desc, int n_nodes,
     const int32_t* __restrict__ child_begin, const int32_t* __restrict__ child_index,
@@ -616,23 +593,7 @@ __global__ __launch_bounds__(256) void voc_transform_kernel(
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const Desc12 a = load_desc(desc + (size_t)i * OKVFE_DESC_BYTES);
-  int node = 0;
-  while (true) {
-    const int c0 = child_begin[node], c1 = child_begin[node + 1];
-    if (c1 <= c0) break;
-    int best = -1, best_d = 0x7FFFFFFF;
-    for (int c = c0; c < c1; ++c) {
-      const int id = child_index[c];
-      const uint32_t* row = in_lds ? reinterpret_cast<const uint32_t*>(lds_nodes + 3 * id)
-                                   : reinterpret_cast<const uint32_t*>(node_desc + (size_t)id * OKVFE_DESC_BYTES);
-      const int d = hamming(a, row);
-      if (d < best_d) {
-        best_d = d;
-        best = id;
-      }
-    }
-    node = best;
-  }
+  const int node = voc_descend(a, lds_nodes, in_lds, node_desc, child_begin, child_index);
   word_out[i] = word[node];
   node_out[i] = node;
 }
@@ -1562,9 +1523,7 @@ __global__ __launch_bounds__(256) void motion_claim_kernel(
 
 
 // ---- DBoW2 database query, L1 scoring (TemplatedDatabase::queryL1 behind Frontend.cpp:756-766) ----
-// One thread per database entry: merge-join of the entry's BowVector with the query's (both in
-// ascending word order), value += |q - d| - |q| - |d| over the common words in that order -- the
-// order in which the reference's inverted-file walk reaches this entry -- then score = -value / 2.
+// One thread per database entry: bow_l1_merge (bow_dev.h) of the entry's BowVector with the query's.
 // A few hundred words per vector, a few thousand entries: latency-bound, one small launch.
 __global__ __launch_bounds__(256) void bow_query_l1_kernel(const int32_t* __restrict__ db_begin,
                                                            const int32_t* __restrict__ db_ids,
@@ -1574,29 +1533,7 @@ __global__ __launch_bounds__(256) void bow_query_l1_kernel(const int32_t* __rest
                                                            double* __restrict__ scores) {
   const int e = blockIdx.x * 256 + threadIdx.x;
   if (e >= n_entries) return;
-  int i = db_begin[e];
-  const int i_end = db_begin[e + 1];
-  int j = 0;
-  double value = 0.0;
-  bool any = false;
-  while (i < i_end && j < n_q) {
-    const int a = db_ids[i], b = q_ids[j];
-    if (a == b) {
-      const double d = db_values[i], q = q_values[j];
-      double t = fabs(q - d);
-      t = t - fabs(q);
-      t = t - fabs(d);
-      value = value + t;
-      any = true;
-      ++i;
-      ++j;
-    } else if (a < b) {
-      ++i;
-    } else {
-      ++j;
-    }
-  }
-  scores[e] = any ? -value / 2.0 : -1.0;
+  scores[e] = bow_l1_merge(db_ids, db_values, db_begin[e], db_begin[e + 1], q_ids, q_values, n_q);
 }
 }  // namespace
 

@@ -576,4 +576,53 @@ void circle_half_widths(int r, uint8_t* hw);
 void launch_keyframe_coverage(const CoverageArgs& args, int n_frames, size_t lds_bytes, okvfe_coverage* out,
                               hipStream_t stream);
 
+// place recognition on device-resident batches (k_bow.hip): one work-group per multiframe
+constexpr int kBowMaxFeatures = 8192;            // n_cams x max_keypoints: the sort keys of a multiframe, padded to a power of two
+constexpr size_t kBowLdsBudget = 61 * 1024;      // dynamic LDS of bow_vectors_kernel; its static LDS is below 2.2 KB
+constexpr int kBowDenseWords = 4096;             // vocabularies up to here: the query is a dense word -> position table
+constexpr int kBowQueryLdsWords = 4096;          // query words staged in LDS (12 bytes each); longer vectors are read from memory
+struct BowVectorsArgs {
+  const uint8_t* node_desc;
+  const int32_t *child_begin, *child_index, *node_word;
+  const double* word_weight;
+  int n_nodes, n_words, weighting, normalise_l1, nodes_in_lds;
+  const uint8_t* blocks;
+  int o_count, o_desc;
+  size_t block_bytes;
+  int kp_cap, n_cams;
+  int32_t* n_out;
+  int32_t* ids;
+  double* values;
+  int stride;
+  int32_t* word_ids;  // or null
+};
+struct PlaceQueryArgs {
+  const int32_t *db_begin, *db_ids;
+  const double* db_values;
+  int n_entries;
+  const int32_t *q_n, *q_ids;
+  const double* q_values;
+  int stride, n_vocab, lds_values;
+  double min_score;
+  const uint8_t* suppressible;  // or null
+  double* scores;               // or null
+  int32_t *n_listed, *n_candidates, *entry;
+  double* score;
+  int cap;
+};
+struct BowDbAddArgs {
+  const int32_t* add_index;  // device, n_add
+  const int32_t *q_n, *q_ids;
+  const double* q_values;
+  int stride;
+  int32_t *begin, *ids;
+  double* values;
+  int n_entries, cap_words;
+  int32_t* overflow;
+};
+size_t bow_vectors_lds_bytes(int n_nodes, int keys_cap, bool* nodes_in_lds);
+void launch_bow_vectors(const BowVectorsArgs& args, int n_multiframes, size_t lds_bytes, hipStream_t stream);
+void launch_place_query(const PlaceQueryArgs& args, int n_multiframes, bool dense, size_t lds_bytes, hipStream_t stream);
+void launch_bow_db_add(const BowDbAddArgs& args, int n_add, hipStream_t stream);
+
 }  // namespace okvfe

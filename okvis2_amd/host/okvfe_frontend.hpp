@@ -542,6 +542,203 @@ class HipFrontend {
         reinterpret_cast<const double*>(d), hypValid.empty() ? nullptr : d + hypBytes, nHyp, threshold, minInliers, &result,
         verdictDev, stream));
   }
+  // Place recognition: dBow_->database.query / add (Frontend.cpp:660-672, :752-766, :896-898) with the vocabulary and the
+  // database in device memory, and the estimator-free part of the walk over the results (:771-802).  A context of this
+  // class holds ONE camera, so a multiframe is one gather block here (a rig whose cameras share a context calls the C
+  // entry points itself).  What stays with the caller: poseIds, isPlaceRecognitionFrame per entry (suppressibleDev), the
+  // attempts limits and the estimator predicates of :801-819.
+  struct Vocabulary {
+    std::vector<uint8_t> nodeDescriptors;  // n_nodes x 48
+    std::vector<int32_t> childBegin;       // n_nodes + 1
+    std::vector<int32_t> childIndex;
+    std::vector<int32_t> nodeWord;         // n_nodes
+    std::vector<double> wordWeight;        // n_words
+    int weighting = 0;                     // 0 TF_IDF, 1 TF, 2 IDF, 3 BINARY
+    bool normaliseL1 = true;
+  };
+  // Device memory that a holder below owns (okvfe_device_alloc / okvfe_device_free).
+  class DeviceArrays {
+   public:
+    DeviceArrays() = default;
+    DeviceArrays(const DeviceArrays&) = delete;
+    DeviceArrays& operator=(const DeviceArrays&) = delete;
+    ~DeviceArrays() {
+      for (void* p : allocs_) okvfe_device_free(p);
+    }
+
+   protected:
+    friend class HipFrontend;
+    std::vector<void*> allocs_;
+  };
+  class DeviceVocabulary : public DeviceArrays {
+   public:
+    const okvfe_vocabulary_device& get() const { return view_; }
+
+   private:
+    friend class HipFrontend;
+    okvfe_vocabulary_device view_{};
+  };
+  class DeviceBowVectors : public DeviceArrays {
+   public:
+    const okvfe_bow_vectors_device& get() const { return view_; }
+    int multiframes() const { return multiframes_; }
+
+   private:
+    friend class HipFrontend;
+    okvfe_bow_vectors_device view_{};
+    int multiframes_ = 0;
+  };
+  class DevicePlaceDatabase : public DeviceArrays {
+   public:
+    const okvfe_bow_database_device& get() const { return view_; }
+    int entries() const { return view_.n_entries; }
+
+   private:
+    friend class HipFrontend;
+    okvfe_bow_database_device view_{};
+  };
+  // Runs okvfe_vocabulary_check on the host arrays (throws, the first offence named, if the tree is no tree), then copies
+  // them to the device with asynchronous copies on `stream`: `v` stays valid and unchanged until it has drained.
+  std::shared_ptr<DeviceVocabulary> uploadVocabulary(size_t cameraIndex, const Vocabulary& v, void* stream = nullptr) {
+    if (cameraIndex >= cameras_.size())
+      throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "Camera index exceeds number of cameras.");
+    const size_t nn = v.nodeWord.size();
+    if (nn < 1 || v.nodeDescriptors.size() != nn * size_t(OKVFE_DESC_BYTES) || v.childBegin.size() != nn + 1 ||
+        v.wordWeight.empty() || v.childBegin.back() < 0 || v.childIndex.size() < size_t(v.childBegin.back()))
+      throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "uploadVocabulary: bad vocabulary");
+    okvfe_vocabulary_device h{};
+    h.n_nodes = int32_t(nn);
+    h.n_words = int32_t(v.wordWeight.size());
+    h.weighting = v.weighting;
+    h.normalise_l1 = v.normaliseL1 ? 1 : 0;
+    h.node_descriptors = v.nodeDescriptors.data();
+    h.child_begin = v.childBegin.data();
+    h.child_index = v.childIndex.data();
+    h.node_word = v.nodeWord.data();
+    h.word_weight = v.wordWeight.data();
+    const okvfe_status st = okvfe_vocabulary_check(&h);
+    if (st != OKVFE_OK) throw Exception(st, okvfe_last_error(nullptr));
+    std::lock_guard<std::mutex> lock(mutexes_[cameraIndex]);
+    Context& c = *contexts_[cameraIndex];
+    auto out = std::make_shared<DeviceVocabulary>();
+    auto up = [&](const void* src, size_t bytes) -> const void* {
+      void* d = nullptr;
+      c.check(okvfe_device_alloc(device_, bytes ? bytes : 1, &d));
+      out->allocs_.push_back(d);
+      if (bytes) c.check(okvfe_copy_to_device(d, src, bytes, stream));
+      return d;
+    };
+    out->view_ = h;
+    out->view_.node_descriptors = static_cast<const uint8_t*>(up(v.nodeDescriptors.data(), v.nodeDescriptors.size()));
+    out->view_.child_begin = static_cast<const int32_t*>(up(v.childBegin.data(), (nn + 1) * 4));
+    out->view_.child_index = static_cast<const int32_t*>(up(v.childIndex.data(), size_t(v.childBegin.back()) * 4));
+    out->view_.node_word = static_cast<const int32_t*>(up(v.nodeWord.data(), nn * 4));
+    out->view_.word_weight = static_cast<const double*>(up(v.wordWeight.data(), v.wordWeight.size() * 8));
+    return out;
+  }
+  // Rows for the BowVectors of nMultiframes multiframes of `vocabulary`'s words: the stride is the smallest the vectors
+  // call accepts for this context, min(max keypoints, n_words).
+  std::shared_ptr<DeviceBowVectors> allocBowVectors(size_t cameraIndex, const DeviceVocabulary& vocabulary, int nMultiframes) {
+    if (cameraIndex >= cameras_.size())
+      throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "Camera index exceeds number of cameras.");
+    if (nMultiframes < 1) throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "allocBowVectors: nMultiframes");
+    std::lock_guard<std::mutex> lock(mutexes_[cameraIndex]);
+    Context& c = *contexts_[cameraIndex];
+    okvfe_device_outputs o{};
+    c.check(okvfe_get_device_outputs(c.get(), &o));
+    auto out = std::make_shared<DeviceBowVectors>();
+    const size_t stride = size_t(std::max(1, std::min(o.max_keypoints, vocabulary.get().n_words)));
+    auto alloc = [&](size_t bytes) -> void* {
+      void* d = nullptr;
+      c.check(okvfe_device_alloc(device_, bytes, &d));
+      out->allocs_.push_back(d);
+      return d;
+    };
+    out->view_.n_words = static_cast<int32_t*>(alloc(size_t(nMultiframes) * 4));
+    out->view_.ids = static_cast<int32_t*>(alloc(size_t(nMultiframes) * stride * 4));
+    out->view_.values = static_cast<double*>(alloc(size_t(nMultiframes) * stride * 8));
+    out->view_.stride = int32_t(stride);
+    out->view_.n_vocabulary_words = vocabulary.get().n_words;
+    out->multiframes_ = nMultiframes;
+    return out;
+  }
+  // An empty database of up to capEntries entries and capWords words in all (begin and the overflow counter zeroed on
+  // `stream`).
+  std::shared_ptr<DevicePlaceDatabase> createPlaceDatabase(size_t cameraIndex, int capEntries, int capWords,
+                                                           void* stream = nullptr) {
+    if (cameraIndex >= cameras_.size())
+      throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "Camera index exceeds number of cameras.");
+    if (capEntries < 0 || capWords < 0) throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "createPlaceDatabase: capacities");
+    std::lock_guard<std::mutex> lock(mutexes_[cameraIndex]);
+    Context& c = *contexts_[cameraIndex];
+    auto out = std::make_shared<DevicePlaceDatabase>();
+    auto alloc = [&](size_t bytes, bool zero) -> void* {
+      void* d = nullptr;
+      c.check(okvfe_device_alloc(device_, bytes ? bytes : 1, &d));
+      out->allocs_.push_back(d);
+      if (zero) c.check(okvfe_device_fill(d, 0, bytes, stream));
+      return d;
+    };
+    out->view_.begin = static_cast<int32_t*>(alloc((size_t(capEntries) + 1) * 4, true));
+    out->view_.ids = static_cast<int32_t*>(alloc(size_t(capWords) * 4, false));
+    out->view_.values = static_cast<double*>(alloc(size_t(capWords) * 8, false));
+    out->view_.overflow = static_cast<int32_t*>(alloc(4, true));
+    out->view_.cap_entries = capEntries;
+    out->view_.cap_words = capWords;
+    out->view_.n_entries = 0;
+    return out;
+  }
+  // :660-672 and DBoW2's transform for nMultiframes gather blocks into `vectors`.  wordIdsDev: null, or device
+  // nMultiframes x K: the word of every feature.  Nothing synchronises the host.
+  void bowVectorsBlocks(size_t cameraIndex, const DeviceVocabulary& vocabulary, const void* blocksDev, int nMultiframes,
+                        const DeviceBowVectors& vectors, int32_t* wordIdsDev = nullptr, void* stream = nullptr) {
+    if (cameraIndex >= cameras_.size())
+      throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "Camera index exceeds number of cameras.");
+    if (nMultiframes < 0 || nMultiframes > vectors.multiframes())
+      throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "bowVectorsBlocks: nMultiframes exceeds the rows of the vectors");
+    std::lock_guard<std::mutex> lock(mutexes_[cameraIndex]);
+    Context& c = *contexts_[cameraIndex];
+    c.check(okvfe_bow_vectors_blocks_device(c.get(), &vocabulary.get(), blocksDev, nMultiframes, 1, &vectors.get(),
+                                            wordIdsDev, stream));
+  }
+  // database.query with :761-765, :780-799 and :802 for the first nMultiframes rows of `vectors`: per multiframe the
+  // number of listed entries, the true number of candidates and the first result.cap candidates in ascending entry id.
+  // suppressibleDev: device bytes per entry (isPlaceRecognitionFrame) or null = all ones; scoresDev: null, or device
+  // nMultiframes x entries() doubles.  Nothing synchronises the host.
+  void placeQueryBlocks(size_t cameraIndex, const DevicePlaceDatabase& database, const DeviceBowVectors& vectors,
+                        int nMultiframes, const okvfe_place_candidates_device& result, double minScore = 0.4,
+                        const uint8_t* suppressibleDev = nullptr, double* scoresDev = nullptr, void* stream = nullptr) {
+    if (cameraIndex >= cameras_.size())
+      throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "Camera index exceeds number of cameras.");
+    if (nMultiframes < 0 || nMultiframes > vectors.multiframes())
+      throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "placeQueryBlocks: nMultiframes exceeds the rows of the vectors");
+    std::lock_guard<std::mutex> lock(mutexes_[cameraIndex]);
+    Context& c = *contexts_[cameraIndex];
+    c.check(okvfe_place_query_blocks_device(c.get(), &database.get(), &vectors.get(), nMultiframes, minScore,
+                                            suppressibleDev, scoresDev, &result, stream));
+  }
+  // database.add (:896-898): the vectors of the multiframes addIndex (strictly ascending) become the next entries.
+  // Throws OKVFE_ERR_CAPACITY, nothing changed, if the entries do not fit; words that do not fit are only known on the
+  // device (placeDatabaseCheck).  Nothing synchronises the host.
+  void placeDatabaseAdd(size_t cameraIndex, DevicePlaceDatabase& database, const DeviceBowVectors& vectors, int nMultiframes,
+                        const std::vector<int32_t>& addIndex, void* stream = nullptr) {
+    if (cameraIndex >= cameras_.size())
+      throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "Camera index exceeds number of cameras.");
+    if (nMultiframes < 0 || nMultiframes > vectors.multiframes())
+      throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "placeDatabaseAdd: nMultiframes exceeds the rows of the vectors");
+    std::lock_guard<std::mutex> lock(mutexes_[cameraIndex]);
+    Context& c = *contexts_[cameraIndex];
+    c.check(okvfe_bow_database_add_blocks_device(c.get(), &database.view_, &vectors.get(), nMultiframes, addIndex.data(),
+                                                 int32_t(addIndex.size()), stream));
+  }
+  // Waits for `stream`; throws OKVFE_ERR_CAPACITY if an add stored entries empty for want of room in ids / values.
+  void placeDatabaseCheck(size_t cameraIndex, const DevicePlaceDatabase& database, void* stream = nullptr) {
+    if (cameraIndex >= cameras_.size())
+      throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "Camera index exceeds number of cameras.");
+    std::lock_guard<std::mutex> lock(mutexes_[cameraIndex]);
+    Context& c = *contexts_[cameraIndex];
+    c.check(okvfe_bow_database_check_device(c.get(), &database.get(), stream));
+  }
   // matchToMap (above) for nFrames frames that live in device memory as gather blocks, against an uploaded table: one
   // call per frame batch, nothing synchronises the host.  T_WC1: one pose per frame; useDev: device nFrames x K flags
   // or null; outputs device nFrames x K (K = the context's row capacity); poolOut and its members may be null.  All
