@@ -989,6 +989,87 @@ okvfe_status okvfe_remove_outliers_blocks_device(
     const int32_t* cam_ids /* HOST, n_frames */, const okvfe_pose* T_WC /* HOST, n_frames */, double max_error,
     const int32_t* landmark_dev, int32_t* landmark_out_dev, int32_t* kept_dev, void* stream);
 
+/* ---- matchStereo's landmark bookkeeping, chained over the camera pairs of a rig ----------------
+ * Frontend::matchStereo after its k0 x k1 loop (Frontend.cpp:2076-2141) for n_multiframes multiframes of n_cams cameras,
+ * over n_pairs ordered camera pairs per multiframe, in ONE launch that synchronises nothing.  The matching (:2016-2075)
+ * does not read the landmark ids, so all pairs of a rig are matched first (okvfe_match_stereo_blocks_batch_device, one
+ * call per pair, pointed at slice p of matches_dev) and this call then resolves the whole chain per multiframe: ids
+ * written for pair (0,1) are read by pair (0,2) (":2081 may change!!"), and rows of one pair that matched the same k1 see
+ * each other's writes.
+ *
+ * table: only hp_W and n_landmarks (= L) are read; one table for the whole batch.  initialised_dev: L bytes, byte l =
+ * isLandmarkInitialised of table row l (required when L > 0).
+ * blocks_dev, block_stride_m, block_stride_c: the gather block of (multiframe m, camera c) is block
+ * m block_stride_m + c block_stride_c; (n_cams, 1) is the multiframe-major layout of the RANSAC call, (1, n_multiframes)
+ * the camera-major layout of the stereo matcher and the cross-camera gather.  The rows of every per-keypoint array of
+ * (m, c) -- landmark_dev, landmark_out -- start at that block index x K.  Two (m, c) on one block, or a negative stride:
+ * OKVFE_ERR_INVALID_ARGUMENT.
+ * pairs: HOST, n_pairs x 2 camera indices (c0, c1) in the order the reference visits them: im0 ascending, im1 > im0,
+ * overlapping pairs only (:1990-2000).  n_pairs in 1 .. OKVFE_STEREO_MAX_PAIRS; c0 == c1 or an index outside the rig:
+ * OKVFE_ERR_INVALID_ARGUMENT, the pair named.  cam_ids: HOST, n_cams camera slots (without intrinsics:
+ * OKVFE_ERR_NOT_READY, camera and slot named).  T_WC: HOST, n_multiframes x n_cams poses, T_WS T_SC as the caller's
+ * Transformation class computes it (:2004-2005); they travel through the pinned parameter ring (96 bytes each).
+ * matches_dev: n_pairs x n_multiframes x K okvfe_stereo_match; row (p, m, k0) is what
+ * okvfe_match_stereo_blocks_batch_device wrote for pair p of multiframe m.
+ * landmark_dev: int32, K per block: TABLE rows, -1 = none, any value outside [-1, L) is read as none (and leaves as -1):
+ * the device form of multiFrame->landmarkId, e.g. what the map matchers and the motion sweep left.
+ * as_keyframe_dev: n_multiframes bytes, or NULL for all 1 (:2103).
+ *
+ * Per multiframe exactly the sequential loop: pairs in list order, k0 ascending within a pair.  State: id[c][k] (from
+ * landmark_dev) and a per-multiframe view v -> (point, initialised), for v < L starting as (hp_W[v],
+ * initialised_dev[v] != 0).  Row (p, k0), k0 < count(c0):
+ *  1. k1 = row.k1; k1 < 0 or k1 >= count(c1): action 0, lm -1, done ("distances < briskMatchingThreshold_" is k1 >= 0).
+ *  2. id0 = id[c0][k0], id1 = id[c1][k1], as they are at this moment.
+ *  3. both set (:2085-2092): lm = id0; if !initialised(id0) && row.initialisable: point(id0) = row.hp_W,
+ *     initialised(id0) = true, action |= OKVFE_STEREO_REINIT.
+ *  4. only id1 (:2093-2096): lm = id1, add0.   5. only id0 (:2098-2101): lm = id0, add1.
+ *  6. neither (:2102-2114): not a keyframe: action 0, lm -1, done.  Else a landmark with id L + p K + k0,
+ *     point = row.hp_W, initialised = (row.initialisable != 0); action |= OKVFE_STEREO_CREATE; add0 and add1.  New ids
+ *     are not dense: the id names the creating row, whose hp_W is the record.  addLandmark hands out ascending ids in
+ *     creation order, so the caller maps creating rows in ascending (p, k0) onto real LandmarkIds.
+ *  7. add0 (:2115-2127): hp_C = T_WC0^-1 point(lm) in the expression order of okvfe_remove_outliers_blocks_device,
+ *     projectHomogeneous (head negated when hp_C[3] < 0), the project of slot cam_ids[c0]; iff Successful and
+ *     sqrt(dx dx + dy dy) < 4.0 (dx, dy = double(keypoint) - projection): id[c0][k0] = lm, action |= OKVFE_STEREO_OBS0.
+ *     A NaN norm adds nothing (removeOutliers KEEPS on NaN; this loop does not).
+ *  8. add1 (:2128-2140): the same with c1, k1, T_WC1: id[c1][k1] = lm, action |= OKVFE_STEREO_OBS1.
+ * The point read in 7 / 8 is the view's at that moment: re-set by an earlier row of any earlier or the same pair, or the
+ * creating row's own hp_W.  No input is exempt: several k0 on one k1, a landmark carried by two keypoints of one image, a
+ * row whose id0 landmark another k1 carries -- all equal the loop.
+ *
+ * result (device pointers): action u8 and lm int32, n_pairs x n_multiframes x K, each may be NULL; lm = the landmark the
+ * row acted on (-1 for rows without a match or dropped at 6).  landmark_out int32, shaped as landmark_dev and allowed to
+ * BE landmark_dev: id after the last pair.  A value >= L names a landmark created here, which is not in the table: the
+ * other device calls (RANSAC, removeOutliers, the matchers' `previous`) treat such rows as "no landmark".  counts int32,
+ * n_multiframes x 4, written (not accumulated): {rows with a match (past step 1), created, re-initialised, observations
+ * added}.  landmark_out and counts are required.  Rows at or past a block's count are untouched in every output.
+ *
+ * What stays with the caller: hasOverlap and the pair list; T_WS; addLandmark / setLandmark / addObservation /
+ * setLandmarkId themselves, replayed from action / lm without any geometry; the refreshed points reach the table at the
+ * next upload.  Both orders of okvfe_set_fp64_reduction apply.
+ * Limits: one work-group holds the rig's ids and its tables in 65280 bytes of LDS:
+ * 4 (n_cams K + P2(n_cams K) + 3 K + P2(2 K)) bytes, P2(x) = the smallest power of two above x; beyond that
+ * OKVFE_ERR_UNSUPPORTED (the need and the limit named).  L + n_pairs K must stay below 2^31.  A NULL required pointer or
+ * a negative count: OKVFE_ERR_INVALID_ARGUMENT before anything is launched; n_multiframes == 0 is OK and launches
+ * nothing. */
+#define OKVFE_STEREO_MAX_PAIRS 16
+#define OKVFE_STEREO_REINIT 1
+#define OKVFE_STEREO_CREATE 2
+#define OKVFE_STEREO_OBS0 4
+#define OKVFE_STEREO_OBS1 8
+typedef struct okvfe_stereo_insert_device {
+  uint8_t* action;       /* optional */
+  int32_t* lm;           /* optional */
+  int32_t* landmark_out; /* may be landmark_dev */
+  int32_t* counts;       /* n_multiframes x 4 */
+} okvfe_stereo_insert_device;
+okvfe_status okvfe_stereo_insert_blocks_device(
+    okvfe_ctx* ctx, const okvfe_landmark_table_device* table, const uint8_t* initialised_dev, const void* blocks_dev,
+    int32_t block_stride_m, int32_t block_stride_c, int32_t n_multiframes, int32_t n_cams,
+    const int32_t* pairs /* HOST, n_pairs x 2 */, int32_t n_pairs, const int32_t* cam_ids /* HOST, n_cams */,
+    const okvfe_pose* T_WC /* HOST, n_multiframes x n_cams */, const okvfe_stereo_match* matches_dev,
+    const int32_t* landmark_dev, const uint8_t* as_keyframe_dev /* or NULL */,
+    const okvfe_stereo_insert_device* result, void* stream);
+
 /* ---- loop closure: verifyRecognisedPlace up to the point where ceres takes over --------------
  * Frontend::verifyRecognisedPlace (Frontend.cpp:270-556) for one candidate old frame against a batch of multiframes,
  * from the old frame's landmark set to the verdict of :389.  The chain, all on one stream and without a host

@@ -121,6 +121,7 @@ EXPORTS = [
     "okvfe_place_landmark_set", "okvfe_place_claims_blocks_device", "okvfe_place_consensus_blocks_device",
     "okvfe_vocabulary_check", "okvfe_bow_vectors_blocks_device", "okvfe_place_query_blocks_device",
     "okvfe_bow_database_add_blocks_device", "okvfe_bow_database_check_device",
+    "okvfe_stereo_insert_blocks_device",
 ]
 
 STAGES = ["harris", "nms", "sort", "select", "map", "describe", "compact", "match"]
@@ -148,6 +149,15 @@ class LandmarkTableDevice(C.Structure):
 class LandmarkPoolDevice(C.Structure):
     """okvfe_landmark_pool_device: per-frame pooling results, device arrays n_frames x L (any member may be None)."""
     _fields_ = LandmarkPool._fields_
+
+
+class StereoInsertDevice(C.Structure):
+    """okvfe_stereo_insert_device: device pointers; action and lm are optional (None)."""
+    _fields_ = [("action", C.c_void_p), ("lm", C.c_void_p), ("landmark_out", C.c_void_p), ("counts", C.c_void_p)]
+
+
+STEREO_MAX_PAIRS = 16
+STEREO_REINIT, STEREO_CREATE, STEREO_OBS0, STEREO_OBS1 = 1, 2, 4, 8
 
 
 class RansacResultDevice(C.Structure):
@@ -250,6 +260,9 @@ def lib():
         L.okvfe_ransac3d2d_consensus_blocks_device.restype = C.c_int32
         L.okvfe_ransac3d2d_consensus_blocks_device.argtypes = [
             V, V, V, C.c_int32, C.c_int32, V, V, V, V, V, C.c_int32, C.c_double, C.c_int32, V, V]
+        L.okvfe_stereo_insert_blocks_device.restype = C.c_int32
+        L.okvfe_stereo_insert_blocks_device.argtypes = [
+            V, V, V, V, C.c_int32, C.c_int32, C.c_int32, C.c_int32, V, C.c_int32, V, V, V, V, V, V, V]
         L.okvfe_remove_outliers_blocks_device.restype = C.c_int32
         L.okvfe_remove_outliers_blocks_device.argtypes = [V, V, V, C.c_int32, V, V, C.c_double, V, V, V, V]
         L.okvfe_match_motion_stereo_blocks_batch_device.restype = C.c_int32
@@ -1033,6 +1046,31 @@ class Frontend:
         self._check(lib().okvfe_remove_outliers_blocks_device(
             self._h, C.byref(table), _p(blocks_ptr), n, _p(cams) if n else _p(np.zeros(1, np.int32)), P,
             C.c_double(max_error), _p(landmark_ptr), _p(landmark_out_ptr), _p(kept_ptr), _s(stream)))
+
+    # -- matchStereo's landmark bookkeeping, chained over the pairs of a rig ---------------------
+    @staticmethod
+    def make_stereo_insert_device(action_ptr, lm_ptr, landmark_out_ptr, counts_ptr) -> StereoInsertDevice:
+        return StereoInsertDevice(*[int(p) if p else None for p in (action_ptr, lm_ptr, landmark_out_ptr, counts_ptr)])
+
+    def stereo_insert_blocks_device(self, table: LandmarkTableDevice, initialised_ptr, blocks_ptr, block_stride_m,
+                                    block_stride_c, n_multiframes, pairs, cam_ids, poses_T_WC, matches_ptr, landmark_ptr,
+                                    as_keyframe_ptr, result: StereoInsertDevice, stream=None):
+        """Frontend.cpp:2076-2141 for n_multiframes multiframes of len(cam_ids) cameras over the ordered camera `pairs`
+        (host, n_pairs x 2).  poses_T_WC: host sequence of n_multiframes x n_cams (C, r), multiframe-major; matches_ptr:
+        device n_pairs x n_multiframes x K rows of the stereo matcher; landmark_ptr: device int32, K per block;
+        as_keyframe_ptr: device bytes or None; result.landmark_out may be landmark_ptr."""
+        n = int(n_multiframes)
+        cams = np.ascontiguousarray(cam_ids, dtype=np.int32)
+        n_cams = len(cams)
+        pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        if len(poses_T_WC) != n * n_cams:
+            raise ValueError("poses_T_WC: one per (multiframe, camera)")
+        P = (Pose * max(n * n_cams, 1))(*[make_pose(*T) for T in poses_T_WC])
+        self._check(lib().okvfe_stereo_insert_blocks_device(
+            self._h, C.byref(table) if table is not None else None, _p(initialised_ptr), _p(blocks_ptr),
+            int(block_stride_m), int(block_stride_c), n, n_cams, _p(pr) if len(pr) else _p(np.zeros(2, np.int32)),
+            len(pr), _p(cams) if n_cams else _p(np.zeros(1, np.int32)), P, _p(matches_ptr), _p(landmark_ptr),
+            _p(as_keyframe_ptr), C.byref(result) if result is not None else None, _s(stream)))
 
     # -- loop closure: verifyRecognisedPlace after its descriptor matching ---------------------
     place_landmark_set = staticmethod(place_landmark_set)

@@ -12,7 +12,10 @@
 //                              descriptors, and the count of 3-D landmarks stays on the device;
 //   pack_uninit_frames_kernel   the landmarks a frame's first pass left with status 2 (not 3-D yet), packed in
 //                              table order for the second pass (okvfe_match_to_map_table_uninitialised_blocks_device);
-//   check_landmark_table_kernel   the structural checks of a device-resident table.
+//   check_landmark_table_kernel   the structural checks of a device-resident table;
+//   stereo_insert_kernel       (stereo_insert_dev.h, included below) matchStereo's landmark bookkeeping
+//                              (Frontend.cpp:2076-2141) chained over the camera pairs of a rig, one work-group per
+//                              multiframe, on this file's projection chain.
 // FP64, 3-term sums in the order of okvfe_set_fp64_reduction, no FMA; acos / cos through atan_fixed.h resp. host-computed constants.
 #include "camera_dev.h"
 #include "okvfe_internal.h"
@@ -42,7 +45,7 @@ __device__ __forceinline__ void normalize3m(const double v[3], double out[3]) {
 }
 
 // hp_C = T_WC^-1 * hp_W as the reference's Transformation::inverse() * hp evaluates it.  The ONE copy of this expression
-// order: prepare_landmark and remove_outliers_frames_kernel compile it.
+// order: prepare_landmark, remove_outliers_frames_kernel and stereo_insert_kernel (stereo_insert_dev.h) compile it.
 __device__ __forceinline__ void pose_inverse_times(const okvfe_pose& T1, const double hp[4], double hp_C[4]) {
   double cr[3], hh[3];
   for (int i = 0; i < 3; ++i) {
@@ -422,7 +425,24 @@ __global__ __launch_bounds__(1024) void compact_landmarks_kernel(
   }
 }
 
+// matchStereo's landmark bookkeeping (okvfe_stereo_insert_blocks_device): stereo_insert_kernel, on the projection chain above
+#include "stereo_insert_dev.h"
+
 }  // namespace
+
+size_t stereo_insert_lds_bytes(int n_cams, int kp_cap, int* ov_log2, int* kh_log2) {
+  int a = 1, b = 1;
+  while (((int64_t)1 << a) <= (int64_t)n_cams * kp_cap) ++a;  // more slots than entries: a probe always ends
+  while (((int64_t)1 << b) <= (int64_t)2 * kp_cap) ++b;
+  if (ov_log2) *ov_log2 = a;
+  if (kh_log2) *kh_log2 = b;
+  return sizeof(int32_t) * ((size_t)n_cams * kp_cap + ((size_t)1 << a) + 3 * (size_t)kp_cap + ((size_t)1 << b));
+}
+void launch_stereo_insert(const StereoInsertArgs& args, size_t lds_bytes, hipStream_t stream, bool rt8) {
+  if (args.n_multiframes <= 0 || args.kp_cap <= 0) return;
+  hipLaunchKernelGGL(rt8 ? stereo_insert_kernel<true> : stereo_insert_kernel<false>, dim3(args.n_multiframes), dim3(256),
+                     lds_bytes, stream, args);
+}
 
 void launch_prepare_landmarks(const double* hp_W, const double* quality, const int32_t* obs_begin,
                               int n_landmarks, const int32_t* obs_pose, const double* obs_bp,

@@ -209,6 +209,28 @@ struct RansacCamParams {
   int32_t pad;
 };
 static_assert(sizeof(RansacCamParams) == 112, "112 bytes per camera");
+// okvfe_stereo_insert_blocks_device: the kernel's arguments, passed by value.  cam_slots (n_cams int32) and poses
+// (n_multiframes x n_cams, T_WC) lie in the parameter block of the call; every other pointer is the caller's device memory.
+constexpr int kStereoInsertMaxCams = 32;          // every camera of OKVFE_STEREO_MAX_PAIRS pairs
+constexpr size_t kStereoInsertMaxLds = 64 * 1024 - 256;  // dynamic LDS of one work-group (ids, overlay, the pair's tables) beside its static words
+struct StereoInsertArgs {
+  const double* hp_W;
+  const uint8_t* initialised;
+  const uint8_t* blocks;
+  const DeviceCamera* cameras;
+  const int32_t* cam_slots;
+  const okvfe_pose* poses;
+  const okvfe_stereo_match* matches;
+  const int32_t* landmark;
+  const uint8_t* as_keyframe;
+  uint8_t* action;
+  int32_t* lm;
+  int32_t* landmark_out;
+  int32_t* counts;
+  size_t block_bytes;
+  int32_t n_landmarks, n_multiframes, n_cams, n_pairs, kp_cap, w, h, o_count, o_kps, stride_m, stride_c, ov_log2, kh_log2;
+  int8_t pair_c0[OKVFE_STEREO_MAX_PAIRS], pair_c1[OKVFE_STEREO_MAX_PAIRS];
+};
 
 // Layout of a context's int32 score map in HBM.
 //   dense   (strips <= 1): pixel (x, y) at y * pitch + x, pitch == w;
@@ -518,6 +540,10 @@ void launch_remove_outliers_frames(const double* hp_W, int n_landmarks, const Ma
                                    const DeviceCamera* cameras, int w, int h, const int offs[6], const uint8_t* blocks,
                                    int kp_cap, double max_error, const int32_t* landmark, int32_t* landmark_out,
                                    int32_t* kept, hipStream_t stream, bool rt8);
+// matchStereo's landmark bookkeeping for a batch of multiframes (k_map.hip, stereo_insert_kernel); the LDS one work-group
+// needs, and the sizes (log2) of its two open-addressed tables
+size_t stereo_insert_lds_bytes(int n_cams, int kp_cap, int* ov_log2, int* kh_log2);
+void launch_stereo_insert(const StereoInsertArgs& args, size_t lds_bytes, hipStream_t stream, bool rt8);
 // the consensus step of runRansac3d2d for a batch of multiframes (k_ransac.hip)
 void launch_ransac_consensus(const double* hp_W, const int32_t* obs_begin, int n_landmarks, const int offs[6],
                              const uint8_t* blocks, int n_multiframes, int n_cams, int kp_cap,

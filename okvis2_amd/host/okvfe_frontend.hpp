@@ -17,6 +17,7 @@
 
 #include <array>
 #include <cstdint>
+#include <cstring>
 #include <memory>
 #include <mutex>
 #include <stdexcept>
@@ -218,7 +219,7 @@ class HipFrontend {
       : HipFrontend(extendCameras(cameras), p, device) {}
   HipFrontend(const std::vector<okvfe_camera_ext>& cameras, const FrontendParameters& p, int device = 0)
       : cameras_(cameras), mutexes_(cameras.size()), bp_scratch_(cameras.size()), hyp_scratch_(cameras.size()),
-        device_(device) {
+        params_(p), device_(device) {
     if (cameras.empty()) throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "no cameras");
     for (size_t i = 0; i < cameras.size(); ++i) {
       okvfe_config cfg{};
@@ -827,6 +828,84 @@ class HipFrontend {
         contexts_[cameraIndex]->get(), &table.get(), blocksDev, nFrames, cams.data(), T_WC.data(), maxError, landmarkDev,
         landmarkOutDev, keptDev, stream));
   }
+  // Frontend::matchStereo (Frontend.cpp:1982-2150) for nMultiframes multiframes of the whole rig that live in device
+  // memory as gather blocks; which line is whose:
+  //   :1988, :2004-2005   T_WS and T_WC = T_WS * T_SC: the caller's (T_WC, nMultiframes x numCameras(), multiframe-major)
+  //   :1990-2000          the loop over im0 < im1 and hasOverlap: the caller's `pairs`, (c0, c1) in that order
+  //   :2010-2015          keypoint counts and f0 / f1: from the blocks and the cameras of this object
+  //   :2016-2075          the k0 x k1 loop: okvfe_match_stereo_blocks_batch_device, one call per pair (matchStereoRig)
+  //   :2076-2141          the landmark bookkeeping: okvfe_stereo_insert_blocks_device (matchStereoInsertBlocks), chained
+  //                       over the pairs: ids written for pair (0,1) are read by pair (0,2), rows on one k1 see each other
+  //   estimator.addLandmark / setLandmark / addObservation, multiFrame->setLandmarkId: the caller's, replayed from
+  //                       result.action / result.lm (okvfe.h) without any geometry
+  // The rig shares ONE context (every camera a slot of it; all cameras of one image size and the row capacity K of the
+  // per-camera contexts), created at the first call.  The block of (multiframe m, camera c) is block
+  // m * blockStrideM + c * blockStrideC of blocksDev; landmarkDev / result.landmark_out: K rows per block, table rows,
+  // -1 = none; initialisedDev: one byte per table row; asKeyframeDev: nMultiframes bytes or null (all keyframes).
+  // Nothing synchronises the host.
+  void matchStereoInsertBlocks(const DeviceLandmarkTable& table, const uint8_t* initialisedDev, const void* blocksDev,
+                               int blockStrideM, int blockStrideC, int nMultiframes,
+                               const std::vector<std::array<int32_t, 2>>& pairs, const std::vector<okvfe_pose>& T_WC,
+                               const okvfe_stereo_match* matchesDev, const int32_t* landmarkDev,
+                               const uint8_t* asKeyframeDev, const okvfe_stereo_insert_device& result,
+                               void* stream = nullptr) {
+    if (nMultiframes < 0 || T_WC.size() != size_t(nMultiframes) * cameras_.size())
+      throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "matchStereoInsertBlocks: one pose per (multiframe, camera)");
+    Context& c = rigContext();
+    std::lock_guard<std::mutex> lock(rigMutex_);
+    std::vector<int32_t> cams(cameras_.size());
+    for (size_t i = 0; i < cams.size(); ++i) cams[i] = int32_t(i);
+    const okvfe_pose none{};
+    c.check(okvfe_stereo_insert_blocks_device(
+        c.get(), &table.get(), initialisedDev, blocksDev, blockStrideM, blockStrideC, nMultiframes, int32_t(cams.size()),
+        pairs.empty() ? nullptr : pairs[0].data(), int32_t(pairs.size()), cams.data(), T_WC.empty() ? &none : T_WC.data(),
+        matchesDev, landmarkDev, asKeyframeDev, &result, stream));
+  }
+  // The whole of matchStereo on one stream: for every pair the matcher (matchesDev: device pairs x nMultiframes x K,
+  // slice p written by pair p), then matchStereoInsertBlocks.  The matcher takes one pose pair per launch, so
+  // consecutive multiframes share a launch only when their blocks are consecutive (blockStrideM == 1) and their poses
+  // equal byte for byte; otherwise a multiframe costs one launch per pair.
+  void matchStereoRig(const DeviceLandmarkTable& table, const uint8_t* initialisedDev, const void* blocksDev,
+                      int blockStrideM, int blockStrideC, int nMultiframes,
+                      const std::vector<std::array<int32_t, 2>>& pairs, const std::vector<okvfe_pose>& T_WC,
+                      okvfe_stereo_match* matchesDev, const int32_t* landmarkDev, const uint8_t* asKeyframeDev,
+                      const okvfe_stereo_insert_device& result, void* stream = nullptr) {
+    const size_t nc = cameras_.size();
+    if (nMultiframes < 0 || T_WC.size() != size_t(nMultiframes) * nc || blockStrideM < 0 || blockStrideC < 0)
+      throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "matchStereoRig: one pose per (multiframe, camera)");
+    Context& c = rigContext();
+    {
+      std::lock_guard<std::mutex> lock(rigMutex_);
+      const size_t K = size_t(c.maxKeypoints()), bb = okvfe_gather_block_bytes(c.get());
+      const uint8_t* blocks = static_cast<const uint8_t*>(blocksDev);
+      for (size_t p = 0; p < pairs.size(); ++p) {
+        const int32_t c0 = pairs[p][0], c1 = pairs[p][1];
+        if (c0 < 0 || size_t(c0) >= nc || c1 < 0 || size_t(c1) >= nc)
+          throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "matchStereoRig: pair " + std::to_string(p) + " names a camera outside the rig");
+        const double f0 = 0.5 * (cameras_[size_t(c0)].base.fu + cameras_[size_t(c0)].base.fv);
+        const double f1 = 0.5 * (cameras_[size_t(c1)].base.fu + cameras_[size_t(c1)].base.fv);
+        for (int m = 0; m < nMultiframes;) {
+          const okvfe_pose& T0 = T_WC[size_t(m) * nc + size_t(c0)];
+          const okvfe_pose& T1 = T_WC[size_t(m) * nc + size_t(c1)];
+          int n = 1;
+          while (blockStrideM == 1 && m + n < nMultiframes &&
+                 std::memcmp(&T0, &T_WC[size_t(m + n) * nc + size_t(c0)], sizeof(okvfe_pose)) == 0 &&
+                 std::memcmp(&T1, &T_WC[size_t(m + n) * nc + size_t(c1)], sizeof(okvfe_pose)) == 0)
+            ++n;
+          c.check(okvfe_match_stereo_blocks_batch_device(
+              c.get(), blocks + (size_t(m) * size_t(blockStrideM) + size_t(c0) * size_t(blockStrideC)) * bb,
+              blocks + (size_t(m) * size_t(blockStrideM) + size_t(c1) * size_t(blockStrideC)) * bb, n, &T0, &T1, f0, f1,
+              matchesDev + (p * size_t(nMultiframes) + size_t(m)) * K, stream));
+          m += n;
+        }
+      }
+    }
+    matchStereoInsertBlocks(table, initialisedDev, blocksDev, blockStrideM, blockStrideC, nMultiframes, pairs, T_WC,
+                            matchesDev, landmarkDev, asKeyframeDev, result, stream);
+  }
+  // Row capacity and block size of the rig's shared context (creates it)
+  int rigMaxKeypoints() { return rigContext().maxKeypoints(); }
+  size_t rigBlockBytes() { return okvfe_gather_block_bytes(rigContext().get()); }
   // Frontend::matchMotionStereo's matcher (Frontend.cpp:1789-1905) for idx0.size() (older block, current block) pairs
   // of camera `cameraIndex` in one launch, and -- with `claim` -- the frame-data part of its insertion loop
   // (:1915-1958; okvfe.h, okvfe_match_motion_stereo_blocks_batch_device).  blocks0Dev / blocks1Dev: device arrays of
@@ -1089,6 +1168,37 @@ class HipFrontend {
     if (!hypValid.empty()) c.check(okvfe_copy_to_device(d + hypBytes, hypValid.data(), hypValid.size(), stream));
     return d;
   }
+  // the context matchStereoInsertBlocks / matchStereoRig run on: every camera of the rig in a slot of its own
+  Context& rigContext() {
+    std::lock_guard<std::mutex> lock(rigMutex_);
+    if (!rigContext_) {
+      for (const okvfe_camera_ext& cam : cameras_)
+        if (cam.base.width != cameras_[0].base.width || cam.base.height != cameras_[0].base.height)
+          throw Exception(OKVFE_ERR_UNSUPPORTED, "the rig's shared context needs cameras of one image size");
+      okvfe_config cfg{};
+      cfg.abi_version = OKVFE_ABI_VERSION;
+      cfg.device = device_;
+      cfg.width = cameras_[0].base.width;
+      cfg.height = cameras_[0].base.height;
+      cfg.max_batch = 1;
+      cfg.num_cameras = int32_t(cameras_.size());
+      cfg.uniformity_radius = params_.detection_threshold;
+      cfg.octaves = params_.octaves;
+      cfg.absolute_threshold = params_.absolute_threshold;
+      cfg.max_keypoints = params_.max_num_keypoints;
+      cfg.rotation_invariant = params_.rotation_invariance;
+      cfg.scale_invariant = params_.scale_invariance;
+      cfg.match_threshold = params_.matching_threshold;
+      cfg.box_scale = params_.box_scale;
+      auto ctx = std::make_shared<Context>(cfg);
+      for (size_t i = 0; i < cameras_.size(); ++i) ctx->check(okvfe_set_camera_ext(ctx->get(), int32_t(i), &cameras_[i]));
+      rigContext_ = ctx;
+    }
+    return *rigContext_;
+  }
+  FrontendParameters params_;
+  std::shared_ptr<Context> rigContext_;
+  std::mutex rigMutex_;
   int device_ = 0;
 };
 
