@@ -147,23 +147,20 @@ okvfe_status okvfe_bow_database_add_blocks_device(okvfe_ctx* ctx, okvfe_bow_data
   if (n_add == 0) return OKVFE_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
   hipStream_t s = pick_stream(ctx, stream);
-  void* d_idx = nullptr;
-  int slot = -1;
-  okvfe_status st = ring_upload(ctx, &ctx->pair_ring, add_index, (size_t)n_add * sizeof(int32_t), s, &d_idx, &slot);
+  RingSlot index(ctx, &ctx->pair_ring, s);
+  okvfe_status st = index.upload(add_index, (size_t)n_add * sizeof(int32_t));
   if (st != OKVFE_OK) return st;
   BowDbAddArgs A{};
-  A.add_index = static_cast<const int32_t*>(d_idx);
+  A.add_index = index.as<int32_t>();
   A.q_n = vectors->n_words; A.q_ids = vectors->ids; A.q_values = vectors->values; A.stride = vectors->stride;
   A.begin = db->begin; A.ids = db->ids; A.values = db->values; A.n_entries = db->n_entries; A.cap_words = db->cap_words;
   A.overflow = db->overflow;
-  hipError_t e = hipSuccess;
   {
     StageTimer t(ctx, OKVFE_STAGE_MAP, s);
     launch_bow_db_add(A, n_add, s);
-    e = hipGetLastError();
   }
-  const okvfe_status rel = ring_release(ctx, &ctx->pair_ring, slot, s);  // on every path: the slot has a reader or not
-  HIP_TRY(ctx, e);
+  HIP_TRY(ctx, hipGetLastError());
+  const okvfe_status rel = index.release();
   db->n_entries += n_add;
   ctx->last_stream = s;
   return rel;

@@ -167,6 +167,37 @@ void ring_destroy(okvfe_ctx::ParamRing* r) {
   if (r->d) (void)hipFree(r->d);
 }
 
+okvfe_status stream_workspace(okvfe_ctx* ctx, std::vector<okvfe_ctx::StreamWorkspace>* list, hipStream_t s, size_t bytes,
+                              uint8_t** out) {
+  okvfe_ctx::StreamWorkspace* ws = nullptr;
+  for (auto& m : *list)
+    if (m.stream == s) ws = &m;
+  if (!ws) {
+    // an application that creates a stream per frame would otherwise leave a buffer behind per handle
+    constexpr size_t kMaxStreams = 8;
+    if (list->size() >= kMaxStreams) {
+      const okvfe_ctx::StreamWorkspace old = list->front();
+      list->erase(list->begin());
+      HIP_TRY(ctx, hipDeviceSynchronize());
+      if (old.d) HIP_TRY(ctx, hipFree(old.d));
+    }
+    list->push_back(okvfe_ctx::StreamWorkspace{s, nullptr, 0});
+    ws = &list->back();
+  }
+  bytes = std::max<size_t>(bytes, 256);
+  if (bytes > ws->bytes) {
+    if (ws->d) HIP_TRY(ctx, hipFree(ws->d));
+    ws->d = nullptr;
+    ws->bytes = 0;
+    void* q = nullptr;
+    HIP_TRY(ctx, hipMalloc(&q, bytes));
+    ws->d = static_cast<uint8_t*>(q);
+    ws->bytes = bytes;
+  }
+  *out = ws->d;
+  return OKVFE_OK;
+}
+
 DeviceCamera to_device_camera(const okvfe_camera_ext& ce) {
   const okvfe_camera& c = ce.base;
   DeviceCamera d{};
@@ -627,10 +658,9 @@ void okvfe_destroy(okvfe_ctx* ctx) {
   for (uint8_t* p : ctx->d_layer_img)
     if (p) (void)hipFree(p);
   if (ctx->d_virtual) (void)hipFree(ctx->d_virtual);
-  for (auto& m : ctx->map_perm)
-    if (m.d) (void)hipFree(m.d);
-  for (auto& m : ctx->map_table_ws)
-    if (m.d) (void)hipFree(m.d);
+  for (auto* list : {&ctx->map_perm, &ctx->map_table_ws})
+    for (auto& m : *list)
+      if (m.d) (void)hipFree(m.d);
   for (void* p : ctx->allocs) (void)hipFree(p);
   for (float* p : ctx->cam_rays)
     if (p) (void)hipFree(p);

@@ -6,6 +6,19 @@
 
 using namespace okvfe;
 
+namespace {
+// the second pass's record of one frame: the pose NOW and the two gate constants of its focal length
+PairParams uninit_pair_params(const okvfe_pose& T_WC1, double focal_length) {
+  PairParams pp{};
+  std::memcpy(pp.C1, T_WC1.C, sizeof(pp.C1));
+  std::memcpy(pp.r1, T_WC1.r, sizeof(pp.r1));
+  const double sigma = 1.0 / focal_length;  // Frontend.cpp:1636
+  pp.cos26 = std::cos(2.6 * sigma);
+  pp.cos6 = std::cos(6.0 * sigma);
+  return pp;
+}
+}  // namespace
+
 extern "C" {
 
 okvfe_status okvfe_match_to_map(okvfe_ctx* ctx, const uint8_t* desc, const okvfe_keypoint* kps, const uint8_t* use,
@@ -64,7 +77,7 @@ okvfe_status okvfe_match_to_map_landmarks(okvfe_ctx* ctx, int32_t cam, const okv
       (T->n_landmarks > 0 && (!T->hp_W || !T->quality)) ||
       (T->n_observations > 0 && (!T->obs_pose || !T->obs_desc || !T->obs_backproj || !T->poses)))
     return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_match_to_map_landmarks: bad argument");
-  if (cam < 0 || cam >= (int)ctx->h_cams.size() || !(ctx->h_cams[cam].fu > 0.0))
+  if (!slot_camera(ctx, cam))
     return fail(ctx, OKVFE_ERR_NOT_READY, "okvfe_match_to_map_landmarks: camera slot %d has no intrinsics (okvfe_set_camera)", cam);
   const int nl = T->n_landmarks, no = T->n_observations;
   for (int l = 0; l < nl; ++l)
@@ -182,12 +195,7 @@ okvfe_status okvfe_match_to_map_uninitialised(okvfe_ctx* ctx, const uint8_t* des
   okvfe_status st = ensure_scratch(ctx, off);
   if (st != OKVFE_OK) return st;
   uint8_t* base = static_cast<uint8_t*>(ctx->scratch);
-  PairParams pp{};
-  std::memcpy(pp.C1, T_WC1->C, sizeof(pp.C1));
-  std::memcpy(pp.r1, T_WC1->r, sizeof(pp.r1));
-  const double sigma = 1.0 / focal_length;  // Frontend.cpp:1636
-  pp.cos26 = std::cos(2.6 * sigma);
-  pp.cos6 = std::cos(6.0 * sigma);
+  const PairParams pp = uninit_pair_params(*T_WC1, focal_length);
   auto up = [&](size_t o, const void* src, size_t bytes) -> hipError_t {
     return bytes ? hipMemcpyAsync(base + o, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
   };
@@ -428,40 +436,15 @@ okvfe_status okvfe_match_to_map_blocks_device(okvfe_ctx* ctx, const void* blocks
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
   hipStream_t s = pick_stream(ctx, stream);
   const BlockLayout L = block_layout(ctx->kp_cap);
-  const int offs[6] = {(int)L.o_count, (int)L.o_kps, (int)L.o_desc, (int)L.o_bp, (int)L.o_bpv, (int)L.total};
-  // workspace of the region order: one per stream, grown on demand (growing frees the old buffer, which
-  // synchronises the device once)
-  okvfe_ctx::MapPerm* mp = nullptr;
-  for (auto& m : ctx->map_perm)
-    if (m.stream == s) mp = &m;
-  if (!mp) {
-    // at most eight streams keep a workspace: an application that creates a stream per frame would otherwise leave one
-    // behind per handle; the oldest entry is recycled (its stream is drained first: a launch may still read it)
-    constexpr size_t kMaxPermStreams = 8;
-    if (ctx->map_perm.size() >= kMaxPermStreams) {
-      okvfe_ctx::MapPerm old = ctx->map_perm.front();
-      ctx->map_perm.erase(ctx->map_perm.begin());
-      HIP_TRY(ctx, hipDeviceSynchronize());
-      if (old.d) HIP_TRY(ctx, hipFree(old.d));
-    }
-    ctx->map_perm.push_back(okvfe_ctx::MapPerm{s, nullptr, 0});
-    mp = &ctx->map_perm.back();
-  }
-  if ((size_t)n_frames > mp->frames) {
-    if (mp->d) HIP_TRY(ctx, hipFree(mp->d));
-    mp->d = nullptr;
-    mp->frames = 0;
-    void* q = nullptr;
-    HIP_TRY(ctx, hipMalloc(&q, (size_t)n_frames * ctx->kp_cap * sizeof(int32_t)));
-    mp->d = static_cast<int32_t*>(q);
-    mp->frames = (size_t)n_frames;
-  }
+  uint8_t* perm = nullptr;  // workspace of the region order
+  if ((st = stream_workspace(ctx, &ctx->map_perm, s, (size_t)n_frames * ctx->kp_cap * sizeof(int32_t), &perm)) != OKVFE_OK)
+    return st;
   {
     StageTimer t(ctx, OKVFE_STAGE_MAP, s);
-    launch_match_to_map_blocks(offs, static_cast<const uint8_t*>(blocks_dev), n_frames, ctx->kp_cap, use_dev,
+    launch_match_to_map_blocks(L, static_cast<const uint8_t*>(blocks_dev), n_frames, ctx->kp_cap, use_dev,
                                map->projections, (size_t)map->n_landmarks * 2, map->desc_begin, map->n_landmarks,
                                map->pool, reprojection_threshold * reprojection_threshold, ctx->cfg.match_threshold,
-                               best_landmark_dev, best_dist_dev, mp->d, s);
+                               best_landmark_dev, best_dist_dev, reinterpret_cast<int32_t*>(perm), s);
   }
   HIP_TRY(ctx, hipGetLastError());
   ctx->last_stream = s;
@@ -483,69 +466,31 @@ okvfe_status okvfe_match_to_map_uninitialised_blocks_device(okvfe_ctx* ctx, cons
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
   hipStream_t s = pick_stream(ctx, stream);
   const BlockLayout L = block_layout(ctx->kp_cap);
-  const int offs[6] = {(int)L.o_count, (int)L.o_kps, (int)L.o_desc, (int)L.o_bp, (int)L.o_bpv, (int)L.total};
   // one pose record per frame, through the pinned parameter ring (one asynchronous copy, no host sync)
   std::vector<PairParams> pp((size_t)n_frames);
-  const double sigma = 1.0 / focal_length;  // Frontend.cpp:1636
-  const double c26 = std::cos(2.6 * sigma), c6 = std::cos(6.0 * sigma);
-  for (int f = 0; f < n_frames; ++f) {
-    pp[(size_t)f] = PairParams{};
-    std::memcpy(pp[(size_t)f].C1, T_WC1[f].C, sizeof(pp[(size_t)f].C1));
-    std::memcpy(pp[(size_t)f].r1, T_WC1[f].r, sizeof(pp[(size_t)f].r1));
-    pp[(size_t)f].cos26 = c26;
-    pp[(size_t)f].cos6 = c6;
-  }
-  void* d_pairs = nullptr;
-  int slot = -1;
-  st = ring_upload(ctx, &ctx->pair_ring, pp.data(), pp.size() * sizeof(PairParams), s, &d_pairs, &slot);
-  if (st != OKVFE_OK) return st;
-  hipError_t e = hipMemsetAsync(already_matched_dev, 0, (size_t)n_frames * sizeof(int32_t), s);
-  if (e == hipSuccess) {
+  for (int f = 0; f < n_frames; ++f) pp[(size_t)f] = uninit_pair_params(T_WC1[f], focal_length);
+  RingSlot pairs(ctx, &ctx->pair_ring, s);
+  if ((st = pairs.upload(pp.data(), pp.size() * sizeof(PairParams))) != OKVFE_OK) return st;
+  HIP_TRY(ctx, hipMemsetAsync(already_matched_dev, 0, (size_t)n_frames * sizeof(int32_t), s));
+  {
     StageTimer t(ctx, OKVFE_STAGE_MAP, s);
-    launch_match_to_map_uninit_blocks(static_cast<const PairParams*>(d_pairs), offs,
+    launch_match_to_map_uninit_blocks(pairs.as<PairParams>(), L,
                                       static_cast<const uint8_t*>(blocks_dev), n_frames, ctx->kp_cap, use_dev,
                                       previous_landmark_dev, map->desc_begin, map->n_landmarks, map->pool, map->e0_W,
                                       map->r0_W, ctx->cfg.match_threshold, best_landmark_dev, best_dist_dev, hps_W_dev,
                                       hp_set_dev, already_matched_dev, s);
-    e = hipGetLastError();
   }
-  const okvfe_status rel = ring_release(ctx, &ctx->pair_ring, slot, s);  // on every path: the slot has a reader or not
-  HIP_TRY(ctx, e);
+  HIP_TRY(ctx, hipGetLastError());
+  const okvfe_status rel = pairs.release();
   ctx->last_stream = s;
   return rel;
 }
 
 // ---- matchToMap from a device-resident landmark table, a batch of frames -----------------------
 namespace {
-// the per-stream workspace of the two entry points below, at least `bytes` large (growing frees the old buffer, which
-// synchronises the device once; at most eight streams keep one, as for MapPerm above)
+// the workspace of stream s for the table passes and the table check: the context's map_table_ws list
 okvfe_status map_table_workspace(okvfe_ctx* ctx, hipStream_t s, size_t bytes, uint8_t** out) {
-  okvfe_ctx::MapTableWs* ws = nullptr;
-  for (auto& m : ctx->map_table_ws)
-    if (m.stream == s) ws = &m;
-  if (!ws) {
-    constexpr size_t kMaxStreams = 8;
-    if (ctx->map_table_ws.size() >= kMaxStreams) {
-      okvfe_ctx::MapTableWs old = ctx->map_table_ws.front();
-      ctx->map_table_ws.erase(ctx->map_table_ws.begin());
-      HIP_TRY(ctx, hipDeviceSynchronize());  // a launch may still read it
-      if (old.d) HIP_TRY(ctx, hipFree(old.d));
-    }
-    ctx->map_table_ws.push_back(okvfe_ctx::MapTableWs{s, nullptr, 0});
-    ws = &ctx->map_table_ws.back();
-  }
-  bytes = std::max<size_t>(bytes, 256);
-  if (bytes > ws->bytes) {
-    if (ws->d) HIP_TRY(ctx, hipFree(ws->d));
-    ws->d = nullptr;
-    ws->bytes = 0;
-    void* q = nullptr;
-    HIP_TRY(ctx, hipMalloc(&q, bytes));
-    ws->d = static_cast<uint8_t*>(q);
-    ws->bytes = bytes;
-  }
-  *out = ws->d;
-  return OKVFE_OK;
+  return stream_workspace(ctx, &ctx->map_table_ws, s, bytes, out);
 }
 
 bool table_pointers_ok(const okvfe_landmark_table_device* T) {
@@ -590,17 +535,17 @@ okvfe_status okvfe_match_to_map_table_blocks_device(okvfe_ctx* ctx, const okvfe_
     return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_match_to_map_table_blocks_device: bad argument");
   bool rt8 = false;  // the 8-coefficient form of the projection only when a slot this call uses holds that model
   for (int f = 0; f < n_frames; ++f) {
-    const int cam = cam_ids[f];
-    if (cam < 0 || cam >= (int)ctx->h_cams.size() || !(ctx->h_cams[cam].fu > 0.0))
+    const DeviceCamera* dc = slot_camera(ctx, cam_ids[f]);
+    if (!dc)
       return fail(ctx, OKVFE_ERR_NOT_READY,
-                  "okvfe_match_to_map_table_blocks_device: frame %d: camera slot %d has no intrinsics (okvfe_set_camera)", f, cam);
-    rt8 = rt8 || ctx->h_cams[cam].distortion == OKVFE_DIST_RADTAN8;
+                  "okvfe_match_to_map_table_blocks_device: frame %d: camera slot %d has no intrinsics (okvfe_set_camera)", f,
+                  cam_ids[f]);
+    rt8 = rt8 || dc->distortion == OKVFE_DIST_RADTAN8;
   }
   if (n_frames == 0) return OKVFE_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
   hipStream_t s = pick_stream(ctx, stream);
   const BlockLayout L = block_layout(ctx->kp_cap);
-  const int offs[6] = {(int)L.o_count, (int)L.o_kps, (int)L.o_desc, (int)L.o_bp, (int)L.o_bpv, (int)L.total};
   const size_t nl = (size_t)T->n_landmarks, K = (size_t)ctx->kp_cap;
   // workspace per frame: the packed records, the keypoint order and the count of 3-D landmarks; a call that would need
   // more than the limit runs its frames in slices, one after another on the same stream
@@ -621,37 +566,33 @@ okvfe_status okvfe_match_to_map_table_blocks_device(okvfe_ctx* ctx, const okvfe_
     fp[(size_t)f].cos10 = std::cos(10.0 / (dc.fu + dc.fv));  // the SUM, as at Frontend.cpp:1213-1215
     fp[(size_t)f].cam = cam_ids[f];
   }
-  void* d_fp = nullptr;
-  int slot = -1;
-  st = ring_upload(ctx, &ctx->pair_ring, fp.data(), fp.size() * sizeof(MapFrameParams), s, &d_fp, &slot);
-  if (st != OKVFE_OK) return st;
-  hipError_t e = hipSuccess;
+  RingSlot frames(ctx, &ctx->pair_ring, s);
+  if ((st = frames.upload(fp.data(), fp.size() * sizeof(MapFrameParams))) != OKVFE_OK) return st;
   {
     StageTimer t(ctx, OKVFE_STAGE_MAP, s);
     MapPacked* packed = reinterpret_cast<MapPacked*>(ws);
     int32_t* perm = reinterpret_cast<int32_t*>(ws + o_perm);
     int32_t* counts = reinterpret_cast<int32_t*>(ws + o_cnt);
-    for (int f0 = 0; f0 < n_frames && e == hipSuccess; f0 += slice) {
+    for (int f0 = 0; f0 < n_frames; f0 += slice) {
       const int nf = std::min(slice, n_frames - f0);
       const size_t row = (size_t)f0 * nl;  // first row of the slice in the caller's frame-major pool arrays
       auto at = [&](auto* p, size_t per_row) { return p ? p + row * per_row : p; };
       launch_prepare_landmarks_frames(
           T->hp_W, T->quality, T->obs_begin, T->n_landmarks, T->obs_pose, T->obs_backproj, T->poses,
-          static_cast<const MapFrameParams*>(d_fp) + f0, nf, ctx->d_cams, ctx->w, ctx->h, reprojection_threshold,
+          frames.as<MapFrameParams>() + f0, nf, ctx->d_cams, ctx->w, ctx->h, reprojection_threshold,
           exclusive ? 1 : 0, std::cos(0.6), at(pool_out ? pool_out->status : nullptr, 1),
           at(pool_out ? pool_out->n_desc : nullptr, 1), at(pool_out ? pool_out->obs_rows : nullptr, 3),
           at(pool_out ? pool_out->projection : nullptr, 2), at(pool_out ? pool_out->e_W : nullptr, 6),
           at(pool_out ? pool_out->r_W : nullptr, 6), packed, counts, s, rt8);
-      launch_match_to_map_table_blocks(offs, static_cast<const uint8_t*>(blocks_dev) + (size_t)f0 * L.total, nf,
+      launch_match_to_map_table_blocks(L, static_cast<const uint8_t*>(blocks_dev) + (size_t)f0 * L.total, nf,
                                        ctx->kp_cap, use_dev ? use_dev + (size_t)f0 * K : nullptr, packed, counts,
                                        T->n_landmarks, T->obs_desc, reprojection_threshold * reprojection_threshold,
                                        ctx->cfg.match_threshold, best_landmark_dev + (size_t)f0 * K,
                                        best_dist_dev + (size_t)f0 * K, perm, s);
-      e = hipGetLastError();
+      HIP_TRY(ctx, hipGetLastError());
     }
   }
-  const okvfe_status rel = ring_release(ctx, &ctx->pair_ring, slot, s);  // on every path: the slot has a reader or not
-  HIP_TRY(ctx, e);
+  const okvfe_status rel = frames.release();
   ctx->last_stream = s;
   return rel;
 }
@@ -666,18 +607,15 @@ okvfe_status okvfe_match_to_map_table_uninitialised_blocks_device(
       !best_dist_dev || !hps_W_dev || !hp_set_dev || !already_matched_dev ||
       (T->n_landmarks > 0 && (!T->obs_desc || !pool->status || !pool->n_desc || !pool->obs_rows || !pool->e_W || !pool->r_W)))
     return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_match_to_map_table_uninitialised_blocks_device: bad argument");
-  for (int f = 0; f < n_frames; ++f) {
-    const int cam = cam_ids[f];
-    if (cam < 0 || cam >= (int)ctx->h_cams.size() || !(ctx->h_cams[cam].fu > 0.0))
+  for (int f = 0; f < n_frames; ++f)
+    if (!slot_camera(ctx, cam_ids[f]))
       return fail(ctx, OKVFE_ERR_NOT_READY,
                   "okvfe_match_to_map_table_uninitialised_blocks_device: frame %d: camera slot %d has no intrinsics (okvfe_set_camera)",
-                  f, cam);
-  }
+                  f, cam_ids[f]);
   if (n_frames == 0) return OKVFE_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
   hipStream_t s = pick_stream(ctx, stream);
   const BlockLayout L = block_layout(ctx->kp_cap);
-  const int offs[6] = {(int)L.o_count, (int)L.o_kps, (int)L.o_desc, (int)L.o_bp, (int)L.o_bpv, (int)L.total};
   const size_t nl = (size_t)T->n_landmarks, K = (size_t)ctx->kp_cap;
   // workspace per frame: one packed record per landmark and the count of the status-2 set; slices as in the first pass
   const size_t per_frame = nl * sizeof(MapUninitPacked) + sizeof(int32_t);
@@ -692,40 +630,32 @@ okvfe_status okvfe_match_to_map_table_uninitialised_blocks_device(
   std::vector<PairParams> pp((size_t)n_frames);
   for (int f = 0; f < n_frames; ++f) {
     const DeviceCamera& dc = ctx->h_cams[cam_ids[f]];
-    const double sigma = 1.0 / (0.5 * (dc.fu + dc.fv));  // Frontend.cpp:1636
-    pp[(size_t)f] = PairParams{};
-    std::memcpy(pp[(size_t)f].C1, T_WC1[f].C, sizeof(pp[(size_t)f].C1));
-    std::memcpy(pp[(size_t)f].r1, T_WC1[f].r, sizeof(pp[(size_t)f].r1));
-    pp[(size_t)f].cos26 = std::cos(2.6 * sigma);
-    pp[(size_t)f].cos6 = std::cos(6.0 * sigma);
+    pp[(size_t)f] = uninit_pair_params(T_WC1[f], 0.5 * (dc.fu + dc.fv));
   }
-  void* d_pairs = nullptr;
-  int slot = -1;
-  st = ring_upload(ctx, &ctx->pair_ring, pp.data(), pp.size() * sizeof(PairParams), s, &d_pairs, &slot);
-  if (st != OKVFE_OK) return st;
-  hipError_t e = hipMemsetAsync(already_matched_dev, 0, (size_t)n_frames * sizeof(int32_t), s);
-  if (e == hipSuccess) {
+  RingSlot pairs(ctx, &ctx->pair_ring, s);
+  if ((st = pairs.upload(pp.data(), pp.size() * sizeof(PairParams))) != OKVFE_OK) return st;
+  HIP_TRY(ctx, hipMemsetAsync(already_matched_dev, 0, (size_t)n_frames * sizeof(int32_t), s));
+  {
     StageTimer t(ctx, OKVFE_STAGE_MAP, s);
     MapUninitPacked* packed = reinterpret_cast<MapUninitPacked*>(ws);
     int32_t* counts = reinterpret_cast<int32_t*>(ws + o_cnt);
-    for (int f0 = 0; f0 < n_frames && e == hipSuccess; f0 += slice) {
+    for (int f0 = 0; f0 < n_frames; f0 += slice) {
       const int nf = std::min(slice, n_frames - f0);
       const size_t row = (size_t)f0 * nl;  // first row of the slice in the caller's frame-major pool arrays
       auto at = [&](auto* p, size_t per_row) { return p ? p + row * per_row : p; };
       launch_pack_uninit_frames(at(pool->status, 1), at(pool->n_desc, 1), at(pool->obs_rows, 3), T->n_landmarks, nf,
                                 packed, counts, s);
       launch_match_to_map_table_uninit_blocks(
-          static_cast<const PairParams*>(d_pairs) + f0, offs, static_cast<const uint8_t*>(blocks_dev) + (size_t)f0 * L.total,
+          pairs.as<PairParams>() + f0, L, static_cast<const uint8_t*>(blocks_dev) + (size_t)f0 * L.total,
           nf, ctx->kp_cap, use_dev ? use_dev + (size_t)f0 * K : nullptr,
           previous_landmark_dev ? previous_landmark_dev + (size_t)f0 * K : nullptr, exclusive ? 1 : 0, packed, counts,
           T->n_landmarks, T->obs_desc, at(pool->e_W, 6), at(pool->r_W, 6), ctx->cfg.match_threshold,
           best_landmark_dev + (size_t)f0 * K, best_dist_dev + (size_t)f0 * K, hps_W_dev + 4 * (size_t)f0 * K,
           hp_set_dev + (size_t)f0 * K, already_matched_dev + f0, s);
-      e = hipGetLastError();
+      HIP_TRY(ctx, hipGetLastError());  // (an early return leaves the slot to ~RingSlot)
     }
   }
-  const okvfe_status rel = ring_release(ctx, &ctx->pair_ring, slot, s);  // on every path: the slot has a reader or not
-  HIP_TRY(ctx, e);
+  const okvfe_status rel = pairs.release();  // ring_release() behind the last launch of the last slice
   ctx->last_stream = s;
   return rel;
 }
@@ -750,10 +680,9 @@ okvfe_status okvfe_verify_place_blocks_device(okvfe_ctx* ctx, const void* blocks
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
   hipStream_t s = pick_stream(ctx, stream);
   const BlockLayout L = block_layout(ctx->kp_cap);
-  const int offs[6] = {(int)L.o_count, (int)L.o_kps, (int)L.o_desc, (int)L.o_bp, (int)L.o_bpv, (int)L.total};
   {
     StageTimer t(ctx, OKVFE_STAGE_MAP, s);
-    launch_verify_place_blocks(map->pool, map->desc_begin, map->n_landmarks, offs,
+    launch_verify_place_blocks(map->pool, map->desc_begin, map->n_landmarks, L,
                                static_cast<const uint8_t*>(blocks_dev), n_frames, ctx->kp_cap,
                                (uint32_t)ctx->cfg.match_threshold, k_min_dev, dist_min_dev, s);
   }

@@ -38,7 +38,7 @@ okvfe_status okvfe_match_stereo_batch_device(okvfe_ctx* ctx, const okvfe_stereo_
   }
   hipStream_t s = piped ? pick_stream_raw(ctx, stream) : pick_stream(ctx, stream);
   okvfe_status st;
-  int cls_slot = -1;
+  RingSlot cls(ctx, &ctx->cls_ring, s), prm(ctx, &ctx->pair_ring, s);
   if (ctx->n_layers > 1) {
     // one table per distinct (f0, f1); usually one for the whole call
     std::vector<double> tables;
@@ -55,17 +55,10 @@ okvfe_status okvfe_match_stereo_batch_device(okvfe_ctx* ctx, const okvfe_stereo_
       }
       which[i] = j;
     }
-    void* d_tab = nullptr;
-    if ((st = ring_upload(ctx, &ctx->cls_ring, tables.data(), tables.size() * sizeof(double), s, &d_tab,
-                          &cls_slot)) != OKVFE_OK)
-      return st;
-    for (int i = 0; i < n_pairs; ++i)
-      pp[i].cls = static_cast<const double*>(d_tab) + (size_t)which[i] * kClassTableDoubles;
+    if ((st = cls.upload(tables.data(), tables.size() * sizeof(double))) != OKVFE_OK) return st;
+    for (int i = 0; i < n_pairs; ++i) pp[i].cls = cls.as<double>() + (size_t)which[i] * kClassTableDoubles;
   }
-  void* d_pairs = nullptr;
-  int slot = -1;
-  st = ring_upload(ctx, &ctx->pair_ring, pp.data(), (size_t)n_pairs * sizeof(PairParams), s, &d_pairs, &slot);
-  if (st != OKVFE_OK) return st;
+  if ((st = prm.upload(pp.data(), (size_t)n_pairs * sizeof(PairParams))) != OKVFE_OK) return st;
   if (piped) {
     HIP_TRY(ctx, hipEventRecord(ctx->lane_fork, s));  // behind the pair upload
     for (int l = 0; l < ctx->lanes_used; ++l) {
@@ -74,14 +67,14 @@ okvfe_status okvfe_match_stereo_batch_device(okvfe_ctx* ctx, const okvfe_stereo_
       HIP_TRY(ctx, hipStreamWaitEvent(ls, ctx->lane_fork, 0));
       if (n > 0) {
         StageTimer t(ctx, OKVFE_STAGE_MATCH, ls);
-        launch_match_stereo(static_cast<const PairParams*>(d_pairs) + first, n, ctx->d_kps, ctx->d_desc, ctx->d_bp,
+        launch_match_stereo(prm.as<PairParams>() + first, n, ctx->d_kps, ctx->d_desc, ctx->d_bp,
                             ctx->d_bpv, ctx->d_count, ctx->kp_cap, ctx->cfg.match_threshold,
                             matches_dev + (size_t)first * ctx->kp_cap, ls);
       }
       HIP_TRY(ctx, hipEventRecord(ctx->lane_done[l], ls));
       HIP_TRY(ctx, hipStreamWaitEvent(ctx->join_stream, ctx->lane_done[l], 0));
     }
-    if ((st = ring_release(ctx, &ctx->pair_ring, slot, ctx->join_stream)) != OKVFE_OK) return st;
+    if ((st = prm.release(ctx->join_stream)) != OKVFE_OK) return st;
     HIP_TRY(ctx, hipEventRecord(ctx->join_done, ctx->join_stream));
     HIP_TRY(ctx, hipGetLastError());
     ctx->last_stream = s;
@@ -89,11 +82,11 @@ okvfe_status okvfe_match_stereo_batch_device(okvfe_ctx* ctx, const okvfe_stereo_
   }
   {
     StageTimer t(ctx, OKVFE_STAGE_MATCH, s);
-    launch_match_stereo(static_cast<const PairParams*>(d_pairs), n_pairs, ctx->d_kps, ctx->d_desc, ctx->d_bp,
+    launch_match_stereo(prm.as<PairParams>(), n_pairs, ctx->d_kps, ctx->d_desc, ctx->d_bp,
                         ctx->d_bpv, ctx->d_count, ctx->kp_cap, ctx->cfg.match_threshold, matches_dev, s);
   }
-  if ((st = ring_release(ctx, &ctx->pair_ring, slot, s)) != OKVFE_OK) return st;
-  if ((st = ring_release(ctx, &ctx->cls_ring, cls_slot, s)) != OKVFE_OK) return st;
+  if ((st = prm.release()) != OKVFE_OK) return st;
+  if ((st = cls.release()) != OKVFE_OK) return st;
   HIP_TRY(ctx, hipGetLastError());
   ctx->last_stream = s;
   return OKVFE_OK;
@@ -355,8 +348,7 @@ okvfe_status okvfe_pack_gather_blocks_device(okvfe_ctx* ctx, int32_t first_index
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
   hipStream_t s = pick_stream(ctx, stream);
   const BlockLayout L = block_layout(ctx->kp_cap);
-  const int offs[6] = {(int)L.o_count, (int)L.o_kps, (int)L.o_desc, (int)L.o_bp, (int)L.o_bpv, (int)L.total};
-  launch_pack_blocks(offs, first_index, n, ctx->kp_cap, ctx->d_count, ctx->d_kps, ctx->d_desc, ctx->d_bp,
+  launch_pack_blocks(L, first_index, n, ctx->kp_cap, ctx->d_count, ctx->d_kps, ctx->d_desc, ctx->d_bp,
                      ctx->d_bpv, static_cast<uint8_t*>(blocks_dev), s);
   HIP_TRY(ctx, hipGetLastError());
   ctx->last_stream = s;
@@ -377,26 +369,24 @@ okvfe_status okvfe_match_stereo_blocks_batch_device(okvfe_ctx* ctx, const void* 
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
   hipStream_t s = pick_stream(ctx, stream);
   const BlockLayout L = block_layout(ctx->kp_cap);
-  const int offs[6] = {(int)L.o_count, (int)L.o_kps, (int)L.o_desc, (int)L.o_bp, (int)L.o_bpv, (int)L.total};
   okvfe_stereo_pair sp{};
   sp.T_WC0 = *T_WC0; sp.T_WC1 = *T_WC1; sp.f0 = f0; sp.f1 = f1;
   PairParams pp = to_pair_params(sp);
-  int cls_slot = -1;
+  RingSlot cls(ctx, &ctx->cls_ring, s);
   if (ctx->n_layers > 1) {
     double table[kClassTableDoubles];
     fill_class_table(table, f0, f1, false);
-    void* d_tab = nullptr;
-    okvfe_status st = ring_upload(ctx, &ctx->cls_ring, table, sizeof(table), s, &d_tab, &cls_slot);
+    okvfe_status st = cls.upload(table, sizeof(table));
     if (st != OKVFE_OK) return st;
-    pp.cls = static_cast<const double*>(d_tab);
+    pp.cls = cls.as<double>();
   }
   // the pair record travels by value as a kernel argument: nothing to keep alive
-  launch_match_stereo_blocks(pp, offs, static_cast<const uint8_t*>(blocks0_dev),
+  launch_match_stereo_blocks(pp, L, static_cast<const uint8_t*>(blocks0_dev),
                              static_cast<const uint8_t*>(blocks1_dev), n_frames, ctx->kp_cap,
                              ctx->cfg.match_threshold, matches_dev, s);
   HIP_TRY(ctx, hipGetLastError());
   ctx->last_stream = s;
-  return ring_release(ctx, &ctx->cls_ring, cls_slot, s);
+  return cls.release();
 }
 okvfe_status okvfe_match_motion_stereo_blocks_device(okvfe_ctx* ctx, int32_t cam, const void* block0_dev,
                                                      const void* block1_dev, const uint8_t* skip0_dev,
@@ -407,33 +397,31 @@ okvfe_status okvfe_match_motion_stereo_blocks_device(okvfe_ctx* ctx, int32_t cam
   if (!block0_dev || !block1_dev || !T_WC0 || !T_WC1 || !matches_dev || cam < 0 ||
       cam >= (int)ctx->h_cams.size())
     return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_match_motion_stereo_blocks_device: bad argument");
-  const DeviceCamera& dc = ctx->h_cams[cam];
-  if (!(dc.fu > 0.0))
+  if (!slot_camera(ctx, cam))
     return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "camera slot %d has no intrinsics (okvfe_set_camera)", cam);
+  const DeviceCamera& dc = ctx->h_cams[cam];
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
   hipStream_t s = pick_stream(ctx, stream);
   const BlockLayout L = block_layout(ctx->kp_cap);
-  const int offs[6] = {(int)L.o_count, (int)L.o_kps, (int)L.o_desc, (int)L.o_bp, (int)L.o_bpv, (int)L.total};
   okvfe_stereo_pair sp{};
   sp.T_WC0 = *T_WC0; sp.T_WC1 = *T_WC1;
   sp.f0 = sp.f1 = 0.5 * (dc.fu + dc.fv);  // sigma = size0 / f0 * 0.125 (Frontend.cpp:1834)
   PairParams pp = to_pair_params(sp);
-  int cls_slot = -1;
+  RingSlot cls(ctx, &ctx->cls_ring, s);
   if (ctx->n_layers > 1) {
     double table[kClassTableDoubles];
     fill_class_table(table, sp.f0, sp.f1, true);
-    void* d_tab = nullptr;
-    okvfe_status st = ring_upload(ctx, &ctx->cls_ring, table, sizeof(table), s, &d_tab, &cls_slot);
+    okvfe_status st = cls.upload(table, sizeof(table));
     if (st != OKVFE_OK) return st;
-    pp.cls = static_cast<const double*>(d_tab);
+    pp.cls = cls.as<double>();
   }
-  launch_match_motion_blocks(pp, ctx->d_cams + cam, ctx->w, ctx->h, offs,
+  launch_match_motion_blocks(pp, ctx->d_cams + cam, ctx->w, ctx->h, L,
                              static_cast<const uint8_t*>(block0_dev), static_cast<const uint8_t*>(block1_dev),
                              skip0_dev, matched1_dev, ctx->kp_cap, ctx->cfg.match_threshold, matches_dev, s,
                              dc.distortion == OKVFE_DIST_RADTAN8);
   HIP_TRY(ctx, hipGetLastError());
   ctx->last_stream = s;
-  return ring_release(ctx, &ctx->cls_ring, cls_slot, s);
+  return cls.release();
 }
 
 okvfe_status okvfe_match_motion_stereo_blocks_batch_device(
@@ -468,10 +456,10 @@ okvfe_status okvfe_match_motion_stereo_blocks_batch_device(
     if (cam < 0 || cam >= (int)ctx->h_cams.size())
       return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "%s: pair %d: camera slot %d outside [0, %d)", fn, p, cam,
                   (int)ctx->h_cams.size());
-    const DeviceCamera& dc = ctx->h_cams[cam];
-    if (!(dc.fu > 0.0))
+    if (!slot_camera(ctx, cam))
       return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "%s: pair %d: camera slot %d has no intrinsics (okvfe_set_camera)", fn,
                   p, cam);
+    const DeviceCamera& dc = ctx->h_cams[cam];
     if (claim) {
       if (user[i1] >= 0)
         return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT,
@@ -496,9 +484,8 @@ okvfe_status okvfe_match_motion_stereo_blocks_batch_device(
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
   hipStream_t s = pick_stream(ctx, stream);
   const BlockLayout L = block_layout(ctx->kp_cap);
-  const int offs[6] = {(int)L.o_count, (int)L.o_kps, (int)L.o_desc, (int)L.o_bp, (int)L.o_bpv, (int)L.total};
   okvfe_status st;
-  int cls_slot = -1;
+  RingSlot cls(ctx, &ctx->cls_ring, s), rec(ctx, &ctx->pair_ring, s);
   if (ctx->n_layers > 1) {  // one size-class table per distinct camera slot
     std::vector<double> tables(slots.size() * kClassTableDoubles);
     for (size_t j = 0; j < slots.size(); ++j) {
@@ -506,29 +493,21 @@ okvfe_status okvfe_match_motion_stereo_blocks_batch_device(
       const double f = 0.5 * (dc.fu + dc.fv);
       fill_class_table(tables.data() + j * kClassTableDoubles, f, f, true);
     }
-    void* d_tab = nullptr;
-    if ((st = ring_upload(ctx, &ctx->cls_ring, tables.data(), tables.size() * sizeof(double), s, &d_tab, &cls_slot)) !=
-        OKVFE_OK)
-      return st;
-    for (int p = 0; p < n_pairs; ++p)
-      recs[p].pair.cls = static_cast<const double*>(d_tab) + (size_t)slot_of[p] * kClassTableDoubles;
+    if ((st = cls.upload(tables.data(), tables.size() * sizeof(double))) != OKVFE_OK) return st;
+    for (int p = 0; p < n_pairs; ++p) recs[p].pair.cls = cls.as<double>() + (size_t)slot_of[p] * kClassTableDoubles;
   }
-  void* d_recs = nullptr;
-  int slot = -1;
-  if ((st = ring_upload(ctx, &ctx->pair_ring, recs.data(), recs.size() * sizeof(MotionPairRecord), s, &d_recs, &slot)) !=
-      OKVFE_OK)
-    return st;
-  launch_match_motion_pairs(static_cast<const MotionPairRecord*>(d_recs), n_pairs, ctx->d_cams, ctx->w, ctx->h, offs,
+  if ((st = rec.upload(recs.data(), recs.size() * sizeof(MotionPairRecord))) != OKVFE_OK) return st;
+  launch_match_motion_pairs(rec.as<MotionPairRecord>(), n_pairs, ctx->d_cams, ctx->w, ctx->h, L,
                             static_cast<const uint8_t*>(blocks0_dev), static_cast<const uint8_t*>(blocks1_dev),
                             skip0_dev, matched1_dev, ctx->kp_cap, ctx->cfg.match_threshold, matches_dev, s, rt8);
   if (claim)  // behind the match kernel on the stream: matched1_out may be matched1_dev
-    launch_motion_claim(static_cast<const MotionPairRecord*>(d_recs), n_pairs, offs,
+    launch_motion_claim(rec.as<MotionPairRecord>(), n_pairs, L,
                         static_cast<const uint8_t*>(blocks0_dev), ctx->kp_cap, matches_dev, claim->claimed,
                         claim->n_claimed, claim->matched1_out, s);
   HIP_TRY(ctx, hipGetLastError());
   ctx->last_stream = s;
-  if ((st = ring_release(ctx, &ctx->pair_ring, slot, s)) != OKVFE_OK) return st;
-  return ring_release(ctx, &ctx->cls_ring, cls_slot, s);
+  if ((st = rec.release()) != OKVFE_OK) return st;
+  return cls.release();
 }
 
 okvfe_status okvfe_match_stereo_blocks_device(okvfe_ctx* ctx, const void* block0_dev, const void* block1_dev,

@@ -77,10 +77,9 @@ okvfe_status okvfe_place_claims_blocks_device(okvfe_ctx* ctx, const okvfe_place_
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
   hipStream_t s = pick_stream(ctx, stream);
   const BlockLayout L = block_layout(ctx->kp_cap);
-  const int offs[6] = {(int)L.o_count, (int)L.o_kps, (int)L.o_desc, (int)L.o_bp, (int)L.o_bpv, (int)L.total};
   {
     StageTimer t(ctx, OKVFE_STAGE_MAP, s);
-    launch_place_claims(set->hp, set->n_landmarks, offs, static_cast<const uint8_t*>(blocks_dev), n_multiframes, n_cams,
+    launch_place_claims(set->hp, set->n_landmarks, L, static_cast<const uint8_t*>(blocks_dev), n_multiframes, n_cams,
                         ctx->kp_cap, k_min_dev, dist_min_dev, (uint32_t)ctx->cfg.match_threshold, min_inliers, *result, s);
   }
   HIP_TRY(ctx, hipGetLastError());

@@ -5,9 +5,22 @@
 using namespace okvfe;
 
 namespace {
-const DeviceCamera* slot_camera(okvfe_ctx* ctx, int cam) {
-  if (cam < 0 || cam >= (int)ctx->h_cams.size() || !(ctx->h_cams[cam].fu > 0.0)) return nullptr;
-  return &ctx->h_cams[cam];
+// the rig of a consensus call: one record per camera, its pose in the sensor frame and its slot
+okvfe_status rig_params(okvfe_ctx* ctx, const char* who, int n_cams, const int32_t* cam_ids, const okvfe_pose* T_SC,
+                        std::vector<RansacCamParams>* cp) {
+  cp->assign((size_t)n_cams, RansacCamParams{});
+  for (int c = 0; c < n_cams; ++c) {
+    const DeviceCamera* dc = slot_camera(ctx, cam_ids[c]);
+    if (!dc)
+      return fail(ctx, OKVFE_ERR_NOT_READY, "%s: frame %d: camera slot %d has no intrinsics (okvfe_set_camera)", who, c,
+                  cam_ids[c]);
+    RansacCamParams& p = (*cp)[(size_t)c];
+    std::memcpy(p.C, T_SC[c].C, sizeof(p.C));
+    std::memcpy(p.r, T_SC[c].r, sizeof(p.r));
+    p.fu = dc->fu;
+    p.cam = cam_ids[c];
+  }
+  return OKVFE_OK;
 }
 }  // namespace
 
@@ -26,39 +39,24 @@ okvfe_status okvfe_ransac3d2d_consensus_blocks_device(
     return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_ransac3d2d_consensus_blocks_device: bad argument");
   if ((int64_t)n_cams * ctx->kp_cap >= (int64_t)1 << 30)
     return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_ransac3d2d_consensus_blocks_device: too many keypoints per multiframe");
-  std::vector<RansacCamParams> cp((size_t)n_cams);
-  for (int c = 0; c < n_cams; ++c) {
-    const DeviceCamera* dc = slot_camera(ctx, cam_ids[c]);
-    if (!dc)
-      return fail(ctx, OKVFE_ERR_NOT_READY,
-                  "okvfe_ransac3d2d_consensus_blocks_device: frame %d: camera slot %d has no intrinsics (okvfe_set_camera)",
-                  c, cam_ids[c]);
-    cp[(size_t)c] = RansacCamParams{};
-    std::memcpy(cp[(size_t)c].C, T_SC[c].C, sizeof(cp[(size_t)c].C));
-    std::memcpy(cp[(size_t)c].r, T_SC[c].r, sizeof(cp[(size_t)c].r));
-    cp[(size_t)c].fu = dc->fu;
-    cp[(size_t)c].cam = cam_ids[c];
-  }
+  std::vector<RansacCamParams> cp;
+  okvfe_status st = rig_params(ctx, "okvfe_ransac3d2d_consensus_blocks_device", n_cams, cam_ids, T_SC, &cp);
+  if (st != OKVFE_OK) return st;
   if (n_multiframes == 0) return OKVFE_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
   hipStream_t s = pick_stream(ctx, stream);
   const BlockLayout L = block_layout(ctx->kp_cap);
-  const int offs[6] = {(int)L.o_count, (int)L.o_kps, (int)L.o_desc, (int)L.o_bp, (int)L.o_bpv, (int)L.total};
   // the rig: one record per camera through the pinned parameter ring (one asynchronous copy, no host sync)
-  void* d_cp = nullptr;
-  int slot = -1;
-  okvfe_status st = ring_upload(ctx, &ctx->pair_ring, cp.data(), cp.size() * sizeof(RansacCamParams), s, &d_cp, &slot);
-  if (st != OKVFE_OK) return st;
-  hipError_t e = hipSuccess;
+  RingSlot rig(ctx, &ctx->pair_ring, s);
+  if ((st = rig.upload(cp.data(), cp.size() * sizeof(RansacCamParams))) != OKVFE_OK) return st;
   {
     StageTimer t(ctx, OKVFE_STAGE_MAP, s);
-    launch_ransac_consensus(T->hp_W, T->obs_begin, T->n_landmarks, offs, static_cast<const uint8_t*>(blocks_dev),
-                            n_multiframes, n_cams, ctx->kp_cap, static_cast<const RansacCamParams*>(d_cp), landmark_dev,
+    launch_ransac_consensus(T->hp_W, T->obs_begin, T->n_landmarks, L, static_cast<const uint8_t*>(blocks_dev),
+                            n_multiframes, n_cams, ctx->kp_cap, rig.as<RansacCamParams>(), landmark_dev,
                             hypotheses_dev, hyp_valid_dev, n_hyp, threshold, remove_outliers ? 1 : 0, *result, s);
-    e = hipGetLastError();
   }
-  const okvfe_status rel = ring_release(ctx, &ctx->pair_ring, slot, s);  // on every path: the slot has a reader or not
-  HIP_TRY(ctx, e);
+  HIP_TRY(ctx, hipGetLastError());
+  const okvfe_status rel = rig.release();
   ctx->last_stream = s;
   return rel;
 }
@@ -88,22 +86,19 @@ okvfe_status okvfe_remove_outliers_blocks_device(okvfe_ctx* ctx, const okvfe_lan
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
   hipStream_t s = pick_stream(ctx, stream);
   const BlockLayout L = block_layout(ctx->kp_cap);
-  const int offs[6] = {(int)L.o_count, (int)L.o_kps, (int)L.o_desc, (int)L.o_bp, (int)L.o_bpv, (int)L.total};
   // pose and camera slot: one record per frame through the pinned parameter ring (one asynchronous copy, no host sync)
-  void* d_fp = nullptr;
-  int slot = -1;
-  okvfe_status st = ring_upload(ctx, &ctx->pair_ring, fp.data(), fp.size() * sizeof(MapFrameParams), s, &d_fp, &slot);
+  RingSlot frames(ctx, &ctx->pair_ring, s);
+  okvfe_status st = frames.upload(fp.data(), fp.size() * sizeof(MapFrameParams));
   if (st != OKVFE_OK) return st;
-  hipError_t e = hipMemsetAsync(kept_dev, 0, (size_t)n_frames * sizeof(int32_t), s);
-  if (e == hipSuccess) {
+  HIP_TRY(ctx, hipMemsetAsync(kept_dev, 0, (size_t)n_frames * sizeof(int32_t), s));
+  {
     StageTimer t(ctx, OKVFE_STAGE_MAP, s);
-    launch_remove_outliers_frames(T->hp_W, T->n_landmarks, static_cast<const MapFrameParams*>(d_fp), n_frames, ctx->d_cams,
-                                  ctx->w, ctx->h, offs, static_cast<const uint8_t*>(blocks_dev), ctx->kp_cap, max_error,
+    launch_remove_outliers_frames(T->hp_W, T->n_landmarks, frames.as<MapFrameParams>(), n_frames, ctx->d_cams,
+                                  ctx->w, ctx->h, L, static_cast<const uint8_t*>(blocks_dev), ctx->kp_cap, max_error,
                                   landmark_dev, landmark_out_dev, kept_dev, s, rt8);
-    e = hipGetLastError();
   }
-  const okvfe_status rel = ring_release(ctx, &ctx->pair_ring, slot, s);  // on every path: the slot has a reader or not
-  HIP_TRY(ctx, e);
+  HIP_TRY(ctx, hipGetLastError());
+  const okvfe_status rel = frames.release();
   ctx->last_stream = s;
   return rel;
 }
@@ -123,38 +118,23 @@ okvfe_status okvfe_place_consensus_blocks_device(
     return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_place_consensus_blocks_device: bad argument");
   if ((int64_t)n_cams * ctx->kp_cap >= (int64_t)1 << 30)
     return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_place_consensus_blocks_device: too many keypoints per multiframe");
-  std::vector<RansacCamParams> cp((size_t)n_cams);
-  for (int c = 0; c < n_cams; ++c) {
-    const DeviceCamera* dc = slot_camera(ctx, cam_ids[c]);
-    if (!dc)
-      return fail(ctx, OKVFE_ERR_NOT_READY,
-                  "okvfe_place_consensus_blocks_device: frame %d: camera slot %d has no intrinsics (okvfe_set_camera)", c,
-                  cam_ids[c]);
-    cp[(size_t)c] = RansacCamParams{};
-    std::memcpy(cp[(size_t)c].C, T_SC[c].C, sizeof(cp[(size_t)c].C));
-    std::memcpy(cp[(size_t)c].r, T_SC[c].r, sizeof(cp[(size_t)c].r));
-    cp[(size_t)c].fu = dc->fu;
-    cp[(size_t)c].cam = cam_ids[c];
-  }
+  std::vector<RansacCamParams> cp;
+  okvfe_status st = rig_params(ctx, "okvfe_place_consensus_blocks_device", n_cams, cam_ids, T_SC, &cp);
+  if (st != OKVFE_OK) return st;
   if (n_multiframes == 0) return OKVFE_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
   hipStream_t s = pick_stream(ctx, stream);
   const BlockLayout L = block_layout(ctx->kp_cap);
-  const int offs[6] = {(int)L.o_count, (int)L.o_kps, (int)L.o_desc, (int)L.o_bp, (int)L.o_bpv, (int)L.total};
-  void* d_cp = nullptr;
-  int slot = -1;
-  okvfe_status st = ring_upload(ctx, &ctx->pair_ring, cp.data(), cp.size() * sizeof(RansacCamParams), s, &d_cp, &slot);
-  if (st != OKVFE_OK) return st;
-  hipError_t e = hipSuccess;
+  RingSlot rig(ctx, &ctx->pair_ring, s);
+  if ((st = rig.upload(cp.data(), cp.size() * sizeof(RansacCamParams))) != OKVFE_OK) return st;
   {
     StageTimer t(ctx, OKVFE_STAGE_MAP, s);
-    launch_place_consensus(set->hp, set->n_landmarks, offs, static_cast<const uint8_t*>(blocks_dev), n_multiframes, n_cams,
-                           ctx->kp_cap, static_cast<const RansacCamParams*>(d_cp), match_landmark_dev, gate_dev,
+    launch_place_consensus(set->hp, set->n_landmarks, L, static_cast<const uint8_t*>(blocks_dev), n_multiframes, n_cams,
+                           ctx->kp_cap, rig.as<RansacCamParams>(), match_landmark_dev, gate_dev,
                            hypotheses_dev, hyp_valid_dev, n_hyp, threshold, min_inliers, *result, verdict_dev, s);
-    e = hipGetLastError();
   }
-  const okvfe_status rel = ring_release(ctx, &ctx->pair_ring, slot, s);  // on every path: the slot has a reader or not
-  HIP_TRY(ctx, e);
+  HIP_TRY(ctx, hipGetLastError());
+  const okvfe_status rel = rig.release();
   ctx->last_stream = s;
   return rel;
 }

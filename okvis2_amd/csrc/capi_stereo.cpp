@@ -31,11 +31,11 @@ okvfe_status okvfe_stereo_insert_blocks_device(
   }
   bool rt8 = false;
   for (int c = 0; c < n_cams; ++c) {
-    const int slot = cam_ids[c];
-    if (slot < 0 || slot >= (int)ctx->h_cams.size() || !(ctx->h_cams[slot].fu > 0.0))
+    const DeviceCamera* dc = slot_camera(ctx, cam_ids[c]);
+    if (!dc)
       return fail(ctx, OKVFE_ERR_NOT_READY, "%s: camera %d: camera slot %d has no intrinsics (okvfe_set_camera)", kName, c,
-                  slot);
-    rt8 = rt8 || ctx->h_cams[slot].distortion == OKVFE_DIST_RADTAN8;
+                  cam_ids[c]);
+    rt8 = rt8 || dc->distortion == OKVFE_DIST_RADTAN8;
   }
   if ((int64_t)T->n_landmarks + (int64_t)n_pairs * K > (int64_t)INT32_MAX)
     return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "%s: %d table rows + %d x %d created ids do not fit an int32", kName,
@@ -70,16 +70,15 @@ okvfe_status okvfe_stereo_insert_blocks_device(
   std::vector<uint8_t> block(slots_bytes + poses_bytes, 0);
   std::memcpy(block.data(), cam_ids, (size_t)n_cams * sizeof(int32_t));
   std::memcpy(block.data() + slots_bytes, T_WC, poses_bytes);
-  void* d_block = nullptr;
-  int slot = -1;
-  okvfe_status st = ring_upload(ctx, &ctx->pair_ring, block.data(), block.size(), s, &d_block, &slot);
+  RingSlot params(ctx, &ctx->pair_ring, s);
+  okvfe_status st = params.upload(block.data(), block.size());
   if (st != OKVFE_OK) return st;
   A.hp_W = T->hp_W;
   A.initialised = initialised_dev;
   A.blocks = static_cast<const uint8_t*>(blocks_dev);
   A.cameras = ctx->d_cams;
-  A.cam_slots = static_cast<const int32_t*>(d_block);
-  A.poses = reinterpret_cast<const okvfe_pose*>(static_cast<const uint8_t*>(d_block) + slots_bytes);
+  A.cam_slots = params.as<int32_t>();
+  A.poses = reinterpret_cast<const okvfe_pose*>(params.as<uint8_t>() + slots_bytes);
   A.matches = matches_dev;
   A.landmark = landmark_dev;
   A.as_keyframe = as_keyframe_dev;
@@ -101,14 +100,12 @@ okvfe_status okvfe_stereo_insert_blocks_device(
   A.stride_c = block_stride_c;
   A.ov_log2 = ov_log2;
   A.kh_log2 = kh_log2;
-  hipError_t e = hipSuccess;
   {
     StageTimer t(ctx, OKVFE_STAGE_MATCH, s);
     launch_stereo_insert(A, lds, s, rt8);
-    e = hipGetLastError();
   }
-  const okvfe_status rel = ring_release(ctx, &ctx->pair_ring, slot, s);  // on every path: the slot has a reader or not
-  HIP_TRY(ctx, e);
+  HIP_TRY(ctx, hipGetLastError());
+  const okvfe_status rel = params.release();
   ctx->last_stream = s;
   return rel;
 }

@@ -485,7 +485,7 @@ void launch_pack_uninit_frames(const int32_t* status, const int32_t* n_desc, con
                      n_landmarks, packed, counts);
 }
 void launch_remove_outliers_frames(const double* hp_W, int n_landmarks, const MapFrameParams* frames, int n_frames,
-                                   const DeviceCamera* cameras, int w, int h, const int offs[6], const uint8_t* blocks,
+                                   const DeviceCamera* cameras, int w, int h, const BlockLayout& L, const uint8_t* blocks,
                                    int kp_cap, double max_error, const int32_t* landmark, int32_t* landmark_out,
                                    int32_t* kept, hipStream_t stream, bool rt8) {
   if (kp_cap <= 0) return;
@@ -494,7 +494,7 @@ void launch_remove_outliers_frames(const double* hp_W, int n_landmarks, const Ma
     const size_t row = (size_t)f0 * (size_t)kp_cap;
     hipLaunchKernelGGL(rt8 ? remove_outliers_frames_kernel<true> : remove_outliers_frames_kernel<false>,
                        dim3((kp_cap + 127) / 128, nf), dim3(128), 0, stream, hp_W, n_landmarks, frames + f0, cameras, w, h,
-                       blocks + (size_t)f0 * (size_t)offs[5], offs[0], offs[1], (size_t)offs[5], kp_cap, max_error,
+                       blocks + (size_t)f0 * L.total, (int)L.o_count, (int)L.o_kps, L.total, kp_cap, max_error,
                        landmark + row, landmark_out + row, kept + f0);
   }
 }

@@ -1535,58 +1535,61 @@ __global__ __launch_bounds__(256) void bow_query_l1_kernel(const int32_t* __rest
   if (e >= n_entries) return;
   scores[e] = bow_l1_merge(db_ids, db_values, db_begin[e], db_begin[e + 1], q_ids, q_values, n_q);
 }
+
+// the kernels' views of a gather block's layout (okvfe_internal.h, BlockLayout)
+BlockOffsets block_offsets(const BlockLayout& L) {
+  return {(int)L.o_count, (int)L.o_kps, (int)L.o_desc, (int)L.o_bp, (int)L.o_bpv, (int)L.total};
+}
+MapBatch map_batch(const uint8_t* blocks, const BlockLayout& L, int kp_cap, size_t frame_stride) {
+  return {blocks, (int)L.o_kps, (int)L.o_desc, (int)L.o_bp, (int)L.total, kp_cap, frame_stride, nullptr};
+}
 }  // namespace
 
 void launch_match_motion_blocks(const PairParams& pair, const DeviceCamera* camera, int w, int h,
-                                const int offs[6], const uint8_t* block0, const uint8_t* block1,
+                                const BlockLayout& L, const uint8_t* block0, const uint8_t* block1,
                                 const uint8_t* skip0, const uint8_t* matched1, int kp_cap,
                                 int threshold, okvfe_motion_match* out, hipStream_t stream, bool rt8) {
-  const BlockOffsets L{offs[0], offs[1], offs[2], offs[3], offs[4], offs[5]};
   hipLaunchKernelGGL(rt8 ? match_motion_blocks_kernel<true> : match_motion_blocks_kernel<false>, dim3((kp_cap + 63) / 64), dim3(64, kStereoSegs), 0,
-                     stream, pair, camera, w, h, L, block0, block1, skip0, matched1, threshold, out);
+                     stream, pair, camera, w, h, block_offsets(L), block0, block1, skip0, matched1, threshold, out);
 }
 
 void launch_match_motion_pairs(const MotionPairRecord* recs, int n_pairs, const DeviceCamera* cams, int w, int h,
-                               const int offs[6], const uint8_t* blocks0, const uint8_t* blocks1,
+                               const BlockLayout& L, const uint8_t* blocks0, const uint8_t* blocks1,
                                const uint8_t* skip0, const uint8_t* matched1, int kp_cap, int threshold,
                                okvfe_motion_match* out, hipStream_t stream, bool rt8) {
   if (n_pairs <= 0 || kp_cap <= 0) return;
-  const BlockOffsets L{offs[0], offs[1], offs[2], offs[3], offs[4], offs[5]};
   constexpr int kMaxGridY = 65535;
   for (int first = 0; first < n_pairs; first += kMaxGridY) {
     const int n = std::min(kMaxGridY, n_pairs - first);
     hipLaunchKernelGGL(rt8 ? match_motion_pairs_kernel<true> : match_motion_pairs_kernel<false>,
-                       dim3((kp_cap + 63) / 64, n), dim3(64, kStereoSegs), 0, stream, recs + first, cams, w, h, L,
-                       blocks0, blocks1, skip0 ? skip0 + (size_t)first * kp_cap : nullptr, matched1, kp_cap, threshold,
-                       out + (size_t)first * kp_cap);
+                       dim3((kp_cap + 63) / 64, n), dim3(64, kStereoSegs), 0, stream, recs + first, cams, w, h,
+                       block_offsets(L), blocks0, blocks1, skip0 ? skip0 + (size_t)first * kp_cap : nullptr, matched1,
+                       kp_cap, threshold, out + (size_t)first * kp_cap);
   }
 }
 
-void launch_motion_claim(const MotionPairRecord* recs, int n_pairs, const int offs[6], const uint8_t* blocks0,
+void launch_motion_claim(const MotionPairRecord* recs, int n_pairs, const BlockLayout& L, const uint8_t* blocks0,
                          int kp_cap, const okvfe_motion_match* matches, uint8_t* claimed, int32_t* n_claimed,
                          uint8_t* matched1_out, hipStream_t stream) {
   if (n_pairs <= 0 || kp_cap <= 0) return;
-  const BlockOffsets L{offs[0], offs[1], offs[2], offs[3], offs[4], offs[5]};
-  hipLaunchKernelGGL(motion_claim_kernel, dim3(n_pairs), dim3(256), (size_t)kp_cap * sizeof(int32_t), stream, recs, L,
-                     blocks0, kp_cap, matches, claimed, n_claimed, matched1_out);
+  hipLaunchKernelGGL(motion_claim_kernel, dim3(n_pairs), dim3(256), (size_t)kp_cap * sizeof(int32_t), stream, recs,
+                     block_offsets(L), blocks0, kp_cap, matches, claimed, n_claimed, matched1_out);
 }
 
-void launch_pack_blocks(const int offs[6], int first, int n, int kp_cap, const int32_t* counts,
+void launch_pack_blocks(const BlockLayout& L, int first, int n, int kp_cap, const int32_t* counts,
                         const okvfe_keypoint* kps, const uint8_t* desc, const double* bp,
                         const uint8_t* bpv, uint8_t* blocks, hipStream_t stream) {
   if (n <= 0) return;
-  const BlockOffsets L{offs[0], offs[1], offs[2], offs[3], offs[4], offs[5]};
-  hipLaunchKernelGGL(pack_blocks_kernel, dim3(n), dim3(256), 0, stream, L, first, kp_cap, counts, kps,
-                     desc, bp, bpv, blocks);
+  hipLaunchKernelGGL(pack_blocks_kernel, dim3(n), dim3(256), 0, stream, block_offsets(L), first, kp_cap, counts,
+                     kps, desc, bp, bpv, blocks);
 }
 
-void launch_match_stereo_blocks(const PairParams& pair, const int offs[6], const uint8_t* blocks0,
+void launch_match_stereo_blocks(const PairParams& pair, const BlockLayout& L, const uint8_t* blocks0,
                                 const uint8_t* blocks1, int n_frames, int kp_cap, int threshold,
                                 okvfe_stereo_match* out, hipStream_t stream) {
   if (n_frames <= 0) return;
-  const BlockOffsets L{offs[0], offs[1], offs[2], offs[3], offs[4], offs[5]};
   hipLaunchKernelGGL(match_stereo_blocks_kernel, dim3((kp_cap + 63) / 64, n_frames), dim3(64, kStereoSegs), 0,
-                     stream, pair, L, blocks0, blocks1, kp_cap, threshold, out);
+                     stream, pair, block_offsets(L), blocks0, blocks1, kp_cap, threshold, out);
 }
 
 void launch_match_to_map_uninit(const PairParams* pair, const uint8_t* desc_k, const double* bp,
@@ -1600,14 +1603,14 @@ void launch_match_to_map_uninit(const PairParams* pair, const uint8_t* desc_k, c
                      desc_k, bp, use, previous, n_k, desc_begin, n_lm, pool, e0_W, r0_W, threshold,
                      best_lm, best_d, hps_W, hp_set, ctr_total, MapBatch{});
 }
-void launch_match_to_map_uninit_blocks(const PairParams* pairs, const int offs[6], const uint8_t* blocks,
+void launch_match_to_map_uninit_blocks(const PairParams* pairs, const BlockLayout& L, const uint8_t* blocks,
                                        int n_frames, int kp_cap, const uint8_t* use, const int32_t* previous,
                                        const int32_t* desc_begin, int n_lm, const uint8_t* pool,
                                        const double* e0_W, const double* r0_W, int threshold, int32_t* best_lm,
                                        int32_t* best_d, double* hps_W, uint8_t* hp_set, int32_t* ctr_total,
                                        hipStream_t stream) {
   if (n_frames <= 0 || kp_cap <= 0) return;
-  const MapBatch mb{blocks, offs[1], offs[2], offs[3], offs[5], kp_cap, 0, nullptr};
+  const MapBatch mb = map_batch(blocks, L, kp_cap, 0);
   hipLaunchKernelGGL(match_to_map_uninit_kernel, dim3((kp_cap + 63) / 64, n_frames), dim3(64, kUninitSegs), 0,
                      stream, pairs, nullptr, nullptr, use, previous, 0, desc_begin, n_lm, pool, e0_W, r0_W,
                      threshold, best_lm, best_d, hps_W, hp_set, ctr_total, mb);
@@ -1634,13 +1637,13 @@ void launch_match_to_map(const uint8_t* desc_k, const okvfe_keypoint* kps, const
                      use, n_k, projections, desc_begin, n_lm, pool, thr_sq, threshold, best_lm,
                      best_d, MapBatch{});
 }
-void launch_match_to_map_blocks(const int offs[6], const uint8_t* blocks, int n_frames, int kp_cap,
+void launch_match_to_map_blocks(const BlockLayout& L, const uint8_t* blocks, int n_frames, int kp_cap,
                                 const uint8_t* use, const double* projections, size_t proj_stride,
                                 const int32_t* desc_begin, int n_lm, const uint8_t* pool, double thr_sq,
                                 int threshold, int32_t* best_lm, int32_t* best_d, int32_t* perm_ws,
                                 hipStream_t stream) {
   if (n_frames <= 0 || kp_cap <= 0) return;
-  MapBatch mb{blocks, offs[1], offs[2], offs[3], offs[5], kp_cap, proj_stride, nullptr};
+  MapBatch mb = map_batch(blocks, L, kp_cap, proj_stride);
   if (perm_ws) {  // [n_frames][kp_cap] workspace: order the frames' keypoints by image region first
     hipLaunchKernelGGL(keypoint_order_kernel, dim3(n_frames), dim3(256), 0, stream, mb, perm_ws);
     mb.perm = perm_ws;
@@ -1650,29 +1653,29 @@ void launch_match_to_map_blocks(const int offs[6], const uint8_t* blocks, int n_
                      best_d, mb);
 }
 
-void launch_match_to_map_table_blocks(const int offs[6], const uint8_t* blocks, int n_frames, int kp_cap,
+void launch_match_to_map_table_blocks(const BlockLayout& L, const uint8_t* blocks, int n_frames, int kp_cap,
                                       const uint8_t* use, const MapPacked* packed, const int32_t* counts,
                                       int n_landmarks, const uint8_t* obs_desc, double thr_sq, int threshold,
                                       int32_t* best_lm, int32_t* best_d, int32_t* perm_ws, hipStream_t stream) {
   if (n_frames <= 0 || kp_cap <= 0) return;
-  MapBatch mb{blocks, offs[1], offs[2], offs[3], offs[5], kp_cap, 0, nullptr};
+  MapBatch mb = map_batch(blocks, L, kp_cap, 0);
   hipLaunchKernelGGL(keypoint_order_kernel, dim3(n_frames), dim3(256), 0, stream, mb, perm_ws);
   mb.perm = perm_ws;
   hipLaunchKernelGGL(match_to_map_table_kernel, dim3((kp_cap + 63) / 64, n_frames), dim3(64, kMapSegs), 0, stream,
                      mb, use, packed, counts, n_landmarks, obs_desc, thr_sq, threshold, best_lm, best_d);
 }
 
-void launch_match_to_map_table_uninit_blocks(const PairParams* pairs, const int offs[6], const uint8_t* blocks,
+void launch_match_to_map_table_uninit_blocks(const PairParams* pairs, const BlockLayout& L, const uint8_t* blocks,
                                              int n_frames, int kp_cap, const uint8_t* use, const int32_t* previous,
                                              int exclusive, const MapUninitPacked* packed, const int32_t* counts,
                                              int n_landmarks, const uint8_t* obs_desc, const double* e_W,
                                              const double* r_W, int threshold, int32_t* best_lm, int32_t* best_d,
                                              double* hps_W, uint8_t* hp_set, int32_t* ctr_total, hipStream_t stream) {
   if (n_frames <= 0 || kp_cap <= 0) return;
-  MapBatch mb{blocks, offs[1], offs[2], offs[3], offs[5], kp_cap, 0, nullptr};
+  MapBatch mb = map_batch(blocks, L, kp_cap, 0);
   hipLaunchKernelGGL(match_to_map_table_uninit_kernel, dim3((kp_cap + 63) / 64, n_frames), dim3(64, kUninitSegs), 0,
-                     stream, pairs, mb, offs[4], use, previous, exclusive, packed, counts, n_landmarks, obs_desc, e_W,
-                     r_W, threshold, best_lm, best_d, hps_W, hp_set, ctr_total);
+                     stream, pairs, mb, (int)L.o_bpv, use, previous, exclusive, packed, counts, n_landmarks, obs_desc,
+                     e_W, r_W, threshold, best_lm, best_d, hps_W, hp_set, ctr_total);
 }
 
 void launch_match_stereo(const PairParams* pairs, int n_pairs, const okvfe_keypoint* kps,
@@ -1703,12 +1706,12 @@ void launch_verify_place(const uint8_t* pool, const int32_t* desc_begin, int n_l
   hipLaunchKernelGGL(verify_place_kernel, dim3(blocks), dim3(256), 0, stream, pool, desc_begin, n_landmarks,
                      frame_desc, K, threshold, k_min, dist_min, MapBatch{});
 }
-void launch_verify_place_blocks(const uint8_t* pool, const int32_t* desc_begin, int n_landmarks, const int offs[6],
+void launch_verify_place_blocks(const uint8_t* pool, const int32_t* desc_begin, int n_landmarks, const BlockLayout& L,
                                 const uint8_t* blocks, int n_frames, int kp_cap, uint32_t threshold,
                                 int32_t* k_min, uint32_t* dist_min, hipStream_t stream) {
   if (n_landmarks <= 0 || n_frames <= 0) return;
   const int blocks_x = std::min((n_landmarks + 3) / 4, 2048);
-  const MapBatch mb{blocks, offs[1], offs[2], offs[3], offs[5], kp_cap, 0, nullptr};
+  const MapBatch mb = map_batch(blocks, L, kp_cap, 0);
   hipLaunchKernelGGL(verify_place_kernel, dim3(blocks_x, n_frames), dim3(256), 0, stream, pool, desc_begin,
                      n_landmarks, nullptr, 0, threshold, k_min, dist_min, mb);
 }

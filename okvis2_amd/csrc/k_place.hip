@@ -113,12 +113,12 @@ __global__ __launch_bounds__(kPlaceThreads) void place_claims_kernel(PlaceArgs A
 
 }  // namespace
 
-void launch_place_claims(const double* hp, int n_landmarks, const int offs[6], const uint8_t* blocks, int n_multiframes,
+void launch_place_claims(const double* hp, int n_landmarks, const BlockLayout& L, const uint8_t* blocks, int n_multiframes,
                          int n_cams, int kp_cap, const int32_t* k_min, const uint32_t* dist_min, uint32_t threshold,
                          int min_inliers, const okvfe_place_claims_device& out, hipStream_t stream) {
   if (n_multiframes <= 0) return;
   PlaceArgs A;
-  A.hp = hp; A.n_landmarks = n_landmarks; A.blocks = blocks; A.o_count = offs[0]; A.block_bytes = (size_t)offs[5];
+  A.hp = hp; A.n_landmarks = n_landmarks; A.blocks = blocks; A.o_count = (int)L.o_count; A.block_bytes = L.total;
   A.kp_cap = kp_cap; A.n_cams = n_cams; A.k_min = k_min; A.dist_min = dist_min; A.threshold = threshold;
   A.min_inliers = min_inliers;
   A.n_matches = out.n_matches; A.n_points = out.n_points; A.n_corr = out.n_correspondences; A.gate = out.gate;

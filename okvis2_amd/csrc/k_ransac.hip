@@ -269,14 +269,14 @@ __global__ __launch_bounds__(kRansacThreads) void ransac_consensus_kernel(Ransac
 }  // namespace
 
 namespace {
-RansacArgs ransac_args(const double* hp_W, const int32_t* obs_begin, int n_landmarks, const int offs[6],
+RansacArgs ransac_args(const double* hp_W, const int32_t* obs_begin, int n_landmarks, const BlockLayout& L,
                        const uint8_t* blocks, int n_cams, int kp_cap, const RansacCamParams* cams, const int32_t* landmark,
                        const double* hypotheses, const uint8_t* hyp_valid, int n_hyp, double threshold, int remove_outliers,
                        const okvfe_ransac_result_device& out) {
   RansacArgs A;
   A.hp_W = hp_W; A.obs_begin = obs_begin; A.n_landmarks = n_landmarks;
-  A.blocks = blocks; A.o_count = offs[0]; A.o_kps = offs[1]; A.o_bp = offs[3]; A.o_bpv = offs[4];
-  A.block_bytes = (size_t)offs[5]; A.kp_cap = kp_cap; A.n_cams = n_cams; A.cams = cams;
+  A.blocks = blocks; A.o_count = (int)L.o_count; A.o_kps = (int)L.o_kps; A.o_bp = (int)L.o_bp; A.o_bpv = (int)L.o_bpv;
+  A.block_bytes = L.total; A.kp_cap = kp_cap; A.n_cams = n_cams; A.cams = cams;
   A.landmark = landmark; A.hyp = hypotheses; A.hyp_valid = hyp_valid; A.n_hyp = n_hyp;
   A.threshold = threshold; A.remove_outliers = remove_outliers;
   A.n_corr = out.n_correspondences; A.best = out.best_hypothesis; A.n_inl = out.n_inliers; A.accepted = out.accepted;
@@ -286,26 +286,26 @@ RansacArgs ransac_args(const double* hp_W, const int32_t* obs_begin, int n_landm
 }
 }  // namespace
 
-void launch_ransac_consensus(const double* hp_W, const int32_t* obs_begin, int n_landmarks, const int offs[6],
+void launch_ransac_consensus(const double* hp_W, const int32_t* obs_begin, int n_landmarks, const BlockLayout& L,
                              const uint8_t* blocks, int n_multiframes, int n_cams, int kp_cap,
                              const RansacCamParams* cams, const int32_t* landmark, const double* hypotheses,
                              const uint8_t* hyp_valid, int n_hyp, double threshold, int remove_outliers,
                              const okvfe_ransac_result_device& out, hipStream_t stream) {
   if (n_multiframes <= 0) return;
-  const RansacArgs A = ransac_args(hp_W, obs_begin, n_landmarks, offs, blocks, n_cams, kp_cap, cams, landmark, hypotheses,
+  const RansacArgs A = ransac_args(hp_W, obs_begin, n_landmarks, L, blocks, n_cams, kp_cap, cams, landmark, hypotheses,
                                    hyp_valid, n_hyp, threshold, remove_outliers, out);
   const bool ltr = g_fp64_ltr_ransac[current_device_slot()].load() != 0;
   auto* kernel = ltr ? ransac_consensus_kernel<false, false> : ransac_consensus_kernel<true, false>;
   hipLaunchKernelGGL(kernel, dim3(n_multiframes), dim3(kRansacThreads), 0, stream, A);
 }
 
-void launch_place_consensus(const double* hp, int n_landmarks, const int offs[6], const uint8_t* blocks, int n_multiframes,
+void launch_place_consensus(const double* hp, int n_landmarks, const BlockLayout& L, const uint8_t* blocks, int n_multiframes,
                             int n_cams, int kp_cap, const RansacCamParams* cams, const int32_t* match_landmark,
                             const uint8_t* gate, const double* hypotheses, const uint8_t* hyp_valid, int n_hyp,
                             double threshold, int min_inliers, const okvfe_ransac_result_device& out, uint8_t* verdict,
                             hipStream_t stream) {
   if (n_multiframes <= 0) return;
-  RansacArgs A = ransac_args(hp, nullptr, n_landmarks, offs, blocks, n_cams, kp_cap, cams, match_landmark, hypotheses,
+  RansacArgs A = ransac_args(hp, nullptr, n_landmarks, L, blocks, n_cams, kp_cap, cams, match_landmark, hypotheses,
                              hyp_valid, n_hyp, threshold, 1, out);
   A.gate = gate; A.verdict = verdict; A.min_inliers = min_inliers;
   const bool ltr = g_fp64_ltr_ransac[current_device_slot()].load() != 0;

@@ -53,22 +53,16 @@ struct okvfe_ctx {
   std::vector<void*> allocs;
   int32_t* d_scores = nullptr;
   int32_t* d_virtual = nullptr;   // scale-space parent, OKVFE_SCORE_BRISK_SCALESPACE: FAST 5-8 map of layer 0
-  // okvfe_match_to_map_blocks_device: keypoint order per frame [frames][kp_cap], ONE workspace PER STREAM the entry
-  // point was called on (calls on one stream are ordered; calls on different streams no longer share a buffer)
-  struct MapPerm {
-    hipStream_t stream = nullptr;
-    int32_t* d = nullptr;
-    size_t frames = 0;  // frames d holds
-  };
-  std::vector<MapPerm> map_perm;
-  // okvfe_match_to_map_table_blocks_device / okvfe_landmark_table_check_device: packed records, counts and keypoint
-  // order of a slice of frames, ONE workspace PER STREAM as above (grown on demand, never shrunk)
-  struct MapTableWs {
+  // A device buffer PER STREAM an entry point was called on (stream_workspace): calls on one stream are ordered, calls on
+  // different streams do not share a buffer.  map_perm: okvfe_match_to_map_blocks_device's keypoint order per frame
+  // [frames][kp_cap]; map_table_ws: okvfe_match_to_map_table_blocks_device / okvfe_landmark_table_check_device and the
+  // second pass, packed records, counts and keypoint order of a slice of frames
+  struct StreamWorkspace {
     hipStream_t stream = nullptr;
     uint8_t* d = nullptr;
     size_t bytes = 0;
   };
-  std::vector<MapTableWs> map_table_ws;
+  std::vector<StreamWorkspace> map_perm, map_table_ws;
   size_t map_table_ws_limit = (size_t)1 << 30;  // more than this per call: the frames go in slices
   ScoreLayout score_layout{0, 0};  // of d_scores: slotted where the fused score+NMS kernel applies
   ScoreLayout live_layout{0, 0};   // the layout the LAST score launch actually wrote (dense when the fused kernel refused the call)
@@ -253,6 +247,47 @@ okvfe_status ring_upload(okvfe_ctx* ctx, okvfe_ctx::ParamRing* r, const void* sr
                          bool* zeroed = nullptr);
 okvfe_status ring_release(okvfe_ctx* ctx, okvfe_ctx::ParamRing* r, int slot, hipStream_t s);
 void ring_destroy(okvfe_ctx::ParamRing* r);
+// One call's slot of pair_ring or cls_ring: filled by upload() on the call's stream and released behind the slot's last
+// reader by release(), at most once.  A call that returns early leaves the release to the destructor, which keeps the
+// error the call reports.
+class RingSlot {
+ public:
+  RingSlot(okvfe_ctx* ctx, okvfe_ctx::ParamRing* ring, hipStream_t s) : ctx_(ctx), ring_(ring), s_(s) {}
+  RingSlot(const RingSlot&) = delete;
+  RingSlot& operator=(const RingSlot&) = delete;
+  ~RingSlot() {
+    if (slot_ < 0) return;
+    std::string err = ctx_->err;
+    (void)release();
+    ctx_->err.swap(err);
+  }
+  okvfe_status upload(const void* src, size_t bytes) { return ring_upload(ctx_, ring_, src, bytes, s_, &d_, &slot_); }
+  template <typename T>
+  const T* as() const { return static_cast<const T*>(d_); }  // the device copy
+  okvfe_status release() { return release(s_); }
+  okvfe_status release(hipStream_t other) {  // the readers ran on another stream (pipelined lanes: the join stream)
+    const int slot = slot_;
+    slot_ = -1;
+    return ring_release(ctx_, ring_, slot, other);
+  }
+
+ private:
+  okvfe_ctx* ctx_;
+  okvfe_ctx::ParamRing* ring_;
+  hipStream_t s_;
+  void* d_ = nullptr;
+  int slot_ = -1;
+};
+// the workspace of stream s in `list`, at least max(bytes, 256) large and never shrunk.  At most eight streams keep one:
+// the oldest entry is evicted after a device synchronisation (a launch may still read it), and growing frees the old
+// buffer, which synchronises the device once
+okvfe_status stream_workspace(okvfe_ctx* ctx, std::vector<okvfe_ctx::StreamWorkspace>* list, hipStream_t s, size_t bytes,
+                              uint8_t** out);
+// the intrinsics of camera slot `cam`; null when there is no such slot or okvfe_set_camera has not filled it
+inline const DeviceCamera* slot_camera(const okvfe_ctx* ctx, int cam) {
+  if (cam < 0 || cam >= (int)ctx->h_cams.size() || !(ctx->h_cams[cam].fu > 0.0)) return nullptr;
+  return &ctx->h_cams[cam];
+}
 DeviceCamera to_device_camera(const okvfe_camera_ext& c);
 okvfe_camera_ext widen_camera(const okvfe_camera& c);  // d_ext = 0
 PairParams to_pair_params(const okvfe_stereo_pair& p);
@@ -297,12 +332,6 @@ struct StageTimer {
     if (idx >= 0) (void)hipEventRecord(ctx->prof_events[idx].b, s);
   }
 };
-
-// gather block = what travels between GPUs and what the device-resident matchers read
-struct BlockLayout {
-  size_t o_count, o_kps, o_desc, o_bp, o_bpv, total;
-};
-BlockLayout block_layout(int kp_cap);
 
 // okvfe_match_to_map_table_blocks_device: frames per slice when a frame needs `per_frame` bytes of workspace and a call
 // may hold `limit`: all of them if they fit, never fewer than one, never more than a launch's grid.y

@@ -460,38 +460,43 @@ void launch_match_to_map_uninit(const PairParams* pair, const uint8_t* desc_k, c
                                 const double* e0_W, const double* r0_W, int threshold,
                                 int32_t* best_lm, int32_t* best_d, double* hps_W, uint8_t* hp_set,
                                 int32_t* ctr_total, hipStream_t stream);
+// gather block = what travels between GPUs and what the device-resident matchers read: byte offsets of its parts
+struct BlockLayout {
+  size_t o_count, o_kps, o_desc, o_bp, o_bpv, total;
+};
+BlockLayout block_layout(int kp_cap);  // capi_context.cpp
 // device-resident batches of the map matchers (frame f reads gather block f; k_match.hip, MapBatch)
-void launch_match_to_map_blocks(const int offs[6], const uint8_t* blocks, int n_frames, int kp_cap,
+void launch_match_to_map_blocks(const BlockLayout& L, const uint8_t* blocks, int n_frames, int kp_cap,
                                 const uint8_t* use, const double* projections, size_t proj_stride,
                                 const int32_t* desc_begin, int n_lm, const uint8_t* pool, double thr_sq,
                                 int threshold, int32_t* best_lm, int32_t* best_d, int32_t* perm_ws,
                                 hipStream_t stream);
-void launch_match_to_map_uninit_blocks(const PairParams* pairs, const int offs[6], const uint8_t* blocks,
+void launch_match_to_map_uninit_blocks(const PairParams* pairs, const BlockLayout& L, const uint8_t* blocks,
                                        int n_frames, int kp_cap, const uint8_t* use, const int32_t* previous,
                                        const int32_t* desc_begin, int n_lm, const uint8_t* pool,
                                        const double* e0_W, const double* r0_W, int threshold, int32_t* best_lm,
                                        int32_t* best_d, double* hps_W, uint8_t* hp_set, int32_t* ctr_total,
                                        hipStream_t stream);
-void launch_verify_place_blocks(const uint8_t* pool, const int32_t* desc_begin, int n_landmarks, const int offs[6],
+void launch_verify_place_blocks(const uint8_t* pool, const int32_t* desc_begin, int n_landmarks, const BlockLayout& L,
                                 const uint8_t* blocks, int n_frames, int kp_cap, uint32_t threshold,
                                 int32_t* k_min, uint32_t* dist_min, hipStream_t stream);
-void launch_pack_blocks(const int offs[6], int first, int n, int kp_cap, const int32_t* counts,
+void launch_pack_blocks(const BlockLayout& L, int first, int n, int kp_cap, const int32_t* counts,
                         const okvfe_keypoint* kps, const uint8_t* desc, const double* bp,
                         const uint8_t* bpv, uint8_t* blocks, hipStream_t stream);
 void launch_match_motion_blocks(const PairParams& pair, const DeviceCamera* camera, int w, int h,
-                                const int offs[6], const uint8_t* block0, const uint8_t* block1,
+                                const BlockLayout& L, const uint8_t* block0, const uint8_t* block1,
                                 const uint8_t* skip0, const uint8_t* matched1, int kp_cap,
                                 int threshold, okvfe_motion_match* out, hipStream_t stream, bool rt8 = false);
 // n_pairs (older block, current block, slot) pairs in one launch; skip0 [n_pairs][kp_cap], matched1 [n_blocks1][kp_cap]
 void launch_match_motion_pairs(const MotionPairRecord* recs, int n_pairs, const DeviceCamera* cams, int w, int h,
-                               const int offs[6], const uint8_t* blocks0, const uint8_t* blocks1,
+                               const BlockLayout& L, const uint8_t* blocks0, const uint8_t* blocks1,
                                const uint8_t* skip0, const uint8_t* matched1, int kp_cap, int threshold,
                                okvfe_motion_match* out, hipStream_t stream, bool rt8);
 // ... and the frame-data part of the insertion loop on its rows (kp_cap <= kMotionClaimMaxKeypoints)
-void launch_motion_claim(const MotionPairRecord* recs, int n_pairs, const int offs[6], const uint8_t* blocks0,
+void launch_motion_claim(const MotionPairRecord* recs, int n_pairs, const BlockLayout& L, const uint8_t* blocks0,
                          int kp_cap, const okvfe_motion_match* matches, uint8_t* claimed, int32_t* n_claimed,
                          uint8_t* matched1_out, hipStream_t stream);
-void launch_match_stereo_blocks(const PairParams& pair, const int offs[6], const uint8_t* blocks0,
+void launch_match_stereo_blocks(const PairParams& pair, const BlockLayout& L, const uint8_t* blocks0,
                                 const uint8_t* blocks1, int n_frames, int kp_cap, int threshold,
                                 okvfe_stereo_match* out, hipStream_t stream);
 void launch_verify_place(const uint8_t* pool, const int32_t* desc_begin, int n_landmarks,
@@ -521,7 +526,7 @@ void launch_prepare_landmarks_frames(const double* hp_W, const double* quality, 
 void launch_check_landmark_table(const int32_t* obs_begin, int n_landmarks, const int32_t* obs_pose,
                                  int n_observations, int n_poses, uint32_t* bad, hipStream_t stream);
 // the matcher on the frames' packed records (k_match.hip, match_to_map_table_kernel)
-void launch_match_to_map_table_blocks(const int offs[6], const uint8_t* blocks, int n_frames, int kp_cap,
+void launch_match_to_map_table_blocks(const BlockLayout& L, const uint8_t* blocks, int n_frames, int kp_cap,
                                       const uint8_t* use, const MapPacked* packed, const int32_t* counts,
                                       int n_landmarks, const uint8_t* obs_desc, double thr_sq, int threshold,
                                       int32_t* best_lm, int32_t* best_d, int32_t* perm_ws, hipStream_t stream);
@@ -529,7 +534,7 @@ void launch_match_to_map_table_blocks(const int offs[6], const uint8_t* blocks, 
 // match_to_map_table_uninit_kernel)
 void launch_pack_uninit_frames(const int32_t* status, const int32_t* n_desc, const int32_t* obs_rows, int n_landmarks,
                                int n_frames, MapUninitPacked* packed, int32_t* counts, hipStream_t stream);
-void launch_match_to_map_table_uninit_blocks(const PairParams* pairs, const int offs[6], const uint8_t* blocks,
+void launch_match_to_map_table_uninit_blocks(const PairParams* pairs, const BlockLayout& L, const uint8_t* blocks,
                                              int n_frames, int kp_cap, const uint8_t* use, const int32_t* previous,
                                              int exclusive, const MapUninitPacked* packed, const int32_t* counts,
                                              int n_landmarks, const uint8_t* obs_desc, const double* e_W,
@@ -537,7 +542,7 @@ void launch_match_to_map_table_uninit_blocks(const PairParams* pairs, const int 
                                              double* hps_W, uint8_t* hp_set, int32_t* ctr_total, hipStream_t stream);
 // Frontend::removeOutliers for a batch of frames (k_map.hip, remove_outliers_frames_kernel); kept is zeroed by the caller
 void launch_remove_outliers_frames(const double* hp_W, int n_landmarks, const MapFrameParams* frames, int n_frames,
-                                   const DeviceCamera* cameras, int w, int h, const int offs[6], const uint8_t* blocks,
+                                   const DeviceCamera* cameras, int w, int h, const BlockLayout& L, const uint8_t* blocks,
                                    int kp_cap, double max_error, const int32_t* landmark, int32_t* landmark_out,
                                    int32_t* kept, hipStream_t stream, bool rt8);
 // matchStereo's landmark bookkeeping for a batch of multiframes (k_map.hip, stereo_insert_kernel); the LDS one work-group
@@ -545,7 +550,7 @@ void launch_remove_outliers_frames(const double* hp_W, int n_landmarks, const Ma
 size_t stereo_insert_lds_bytes(int n_cams, int kp_cap, int* ov_log2, int* kh_log2);
 void launch_stereo_insert(const StereoInsertArgs& args, size_t lds_bytes, hipStream_t stream, bool rt8);
 // the consensus step of runRansac3d2d for a batch of multiframes (k_ransac.hip)
-void launch_ransac_consensus(const double* hp_W, const int32_t* obs_begin, int n_landmarks, const int offs[6],
+void launch_ransac_consensus(const double* hp_W, const int32_t* obs_begin, int n_landmarks, const BlockLayout& L,
                              const uint8_t* blocks, int n_multiframes, int n_cams, int kp_cap,
                              const RansacCamParams* cams, const int32_t* landmark, const double* hypotheses,
                              const uint8_t* hyp_valid, int n_hyp, double threshold, int remove_outliers,
@@ -554,10 +559,10 @@ int ransac_chunk_records();  // correspondences the consensus kernel scores at a
 // verifyRecognisedPlace after the descriptor matching (Frontend.cpp:347-397): the claims (k_place.hip) and the consensus
 // over LoopclosureNoncentralAbsoluteAdapter's correspondences (k_ransac.hip, the kPlace policy of the kernel above)
 constexpr int kPlaceClaimsMaxKeypoints = 12288;  // one int per keypoint in LDS
-void launch_place_claims(const double* hp, int n_landmarks, const int offs[6], const uint8_t* blocks, int n_multiframes,
+void launch_place_claims(const double* hp, int n_landmarks, const BlockLayout& L, const uint8_t* blocks, int n_multiframes,
                          int n_cams, int kp_cap, const int32_t* k_min, const uint32_t* dist_min, uint32_t threshold,
                          int min_inliers, const okvfe_place_claims_device& out, hipStream_t stream);
-void launch_place_consensus(const double* hp, int n_landmarks, const int offs[6], const uint8_t* blocks, int n_multiframes,
+void launch_place_consensus(const double* hp, int n_landmarks, const BlockLayout& L, const uint8_t* blocks, int n_multiframes,
                             int n_cams, int kp_cap, const RansacCamParams* cams, const int32_t* match_landmark,
                             const uint8_t* gate, const double* hypotheses, const uint8_t* hyp_valid, int n_hyp,
                             double threshold, int min_inliers, const okvfe_ransac_result_device& out, uint8_t* verdict,

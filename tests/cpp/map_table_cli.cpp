@@ -13,37 +13,7 @@
 #include <vector>
 
 #include "../../okvis2_amd/host/okvfe_frontend.hpp"
-
-template <typename T>
-static void rd(FILE* f, T* p, size_t n) {
-  if (n && fread(p, sizeof(T), n, f) != n) {
-    fprintf(stderr, "short read\n");
-    exit(2);
-  }
-}
-template <typename T>
-static std::vector<T> rdv(FILE* f, size_t n) {
-  std::vector<T> v(n + 1);
-  rd(f, v.data(), n);
-  return v;
-}
-
-struct DeviceBuffer {
-  void* d = nullptr;
-  size_t bytes;
-  explicit DeviceBuffer(size_t n) : bytes(n ? n : 1) {
-    if (okvfe_device_alloc(0, bytes, &d) != OKVFE_OK || okvfe_device_fill(d, 0xF9, bytes, nullptr) != OKVFE_OK) exit(5);
-  }
-  ~DeviceBuffer() { okvfe_device_free(d); }
-  template <typename T>
-  std::vector<T> download(size_t n) const {
-    std::vector<T> v(n + 1);
-    if (n && okvfe_copy_to_host(v.data(), d, n * sizeof(T), nullptr) != OKVFE_OK) exit(6);
-    okvfe_stream_synchronize(nullptr);
-    v.resize(n);
-    return v;
-  }
-};
+#include "cli_io.hpp"
 
 int main(int argc, char** argv) {
   if (argc < 3) return 1;
@@ -74,7 +44,6 @@ int main(int argc, char** argv) {
   rd(f, fn, 2);
   const size_t nf = size_t(fn[0]), block_bytes = size_t(fn[1]), K = size_t(par[0]);
   std::vector<okvfe_pose> T_WC1 = rdv<okvfe_pose>(f, nf);
-  T_WC1.resize(nf);
   const std::vector<uint8_t> blocks = rdv<uint8_t>(f, nf * block_bytes), use = rdv<uint8_t>(f, nf * K);
   fclose(f);
   try {

@@ -16,44 +16,7 @@
 #include <vector>
 
 #include "../../okvis2_amd/host/okvfe_frontend.hpp"
-
-template <typename T>
-static void rd(FILE* f, T* p, size_t n) {
-  if (n && fread(p, sizeof(T), n, f) != n) {
-    fprintf(stderr, "short read\n");
-    exit(2);
-  }
-}
-template <typename T>
-static std::vector<T> rdv(FILE* f, size_t n) {
-  std::vector<T> v(n + 1);
-  rd(f, v.data(), n);
-  return v;
-}
-
-struct DeviceBuffer {
-  void* d = nullptr;
-  size_t bytes;
-  explicit DeviceBuffer(size_t n) : bytes(n ? n : 1) {
-    if (okvfe_device_alloc(0, bytes, &d) != OKVFE_OK || okvfe_device_fill(d, 0xF9, bytes, nullptr) != OKVFE_OK) exit(5);
-  }
-  ~DeviceBuffer() { okvfe_device_free(d); }
-  template <typename T>
-  T* as() const { return static_cast<T*>(d); }
-  template <typename T>
-  std::vector<T> download(size_t n) const {
-    std::vector<T> v(n + 1);
-    if (n && okvfe_copy_to_host(v.data(), d, n * sizeof(T), nullptr) != OKVFE_OK) exit(6);
-    okvfe_stream_synchronize(nullptr);
-    v.resize(n);
-    return v;
-  }
-};
-
-template <typename T>
-static void put(FILE* o, const std::vector<T>& v) {
-  fwrite(v.data(), sizeof(T), v.size(), o);
-}
+#include "cli_io.hpp"
 
 int main(int argc, char** argv) {
   if (argc < 3) return 1;
@@ -83,8 +46,6 @@ int main(int argc, char** argv) {
   rd(f, fn, 2);
   const size_t nf = size_t(fn[0]), block_bytes = size_t(fn[1]), K = size_t(par[0]);
   std::vector<okvfe_pose> T_first = rdv<okvfe_pose>(f, nf), T_second = rdv<okvfe_pose>(f, nf);
-  T_first.resize(nf);
-  T_second.resize(nf);
   const std::vector<uint8_t> blocks = rdv<uint8_t>(f, nf * block_bytes), use = rdv<uint8_t>(f, nf * K);
   const std::vector<int32_t> previous = rdv<int32_t>(f, nf * K);
   fclose(f);

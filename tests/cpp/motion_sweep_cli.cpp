@@ -15,37 +15,7 @@
 #include <vector>
 
 #include "../../okvis2_amd/host/okvfe_frontend.hpp"
-
-template <typename T>
-static std::vector<T> rdv(FILE* f, size_t n) {
-  std::vector<T> v(n + 1);
-  if (n && fread(v.data(), sizeof(T), n, f) != n) {
-    fprintf(stderr, "short read\n");
-    exit(2);
-  }
-  v.resize(n);
-  return v;
-}
-
-struct DeviceBuffer {
-  void* d = nullptr;
-  size_t bytes;
-  explicit DeviceBuffer(size_t n) : bytes(n ? n : 1) {
-    if (okvfe_device_alloc(0, bytes, &d) != OKVFE_OK || okvfe_device_fill(d, 0xF9, bytes, nullptr) != OKVFE_OK) exit(5);
-  }
-  DeviceBuffer(const DeviceBuffer&) = delete;
-  ~DeviceBuffer() { okvfe_device_free(d); }
-  template <typename T>
-  T* as() const { return static_cast<T*>(d); }
-  void upload(const void* src, size_t n) const {
-    if (n && okvfe_copy_to_device(d, src, n, nullptr) != OKVFE_OK) exit(5);
-  }
-  std::vector<uint8_t> download() const {
-    std::vector<uint8_t> v(bytes);
-    if (okvfe_copy_to_host(v.data(), d, bytes, nullptr) != OKVFE_OK || okvfe_stream_synchronize(nullptr) != OKVFE_OK) exit(6);
-    return v;
-  }
-};
+#include "cli_io.hpp"
 
 struct StepBuffers {  // one camera's share of one step
   std::vector<size_t> where;  // positions of its pairs in the request's step
@@ -90,9 +60,9 @@ int main(int argc, char** argv) {
     p.matching_threshold = par[1];
     okvfe::HipFrontend frontend(cams, p);
     DeviceBuffer d_blocks0(nb0 * block_bytes), d_blocks1(nb1 * block_bytes), d_matched1(nb1 * K);
-    d_blocks0.upload(blocks0.data(), blocks0.size());
-    d_blocks1.upload(blocks1.data(), blocks1.size());
-    d_matched1.upload(matched1.data(), matched1.size());
+    d_blocks0.upload(blocks0);
+    d_blocks1.upload(blocks1);
+    d_matched1.upload(matched1);
     const size_t nc = size_t(n_cams);
     std::vector<std::vector<StepBuffers>> buf(nc);
     for (auto& b : buf) b.resize(n_steps);
@@ -114,7 +84,7 @@ int main(int argc, char** argv) {
         b.matches.reset(new DeviceBuffer(n * K * sizeof(okvfe_motion_match)));
         b.claimed.reset(new DeviceBuffer(n * K));
         b.n_claimed.reset(new DeviceBuffer(n * 4));
-        b.skip0->upload(skip.data(), skip.size());
+        b.skip0->upload(skip);
         st.skip0Dev = b.skip0->as<uint8_t>();
         st.matchesDev = b.matches->as<okvfe_motion_match>();
         st.claimedDev = b.claimed->as<uint8_t>();
@@ -136,7 +106,9 @@ int main(int argc, char** argv) {
       for (int m = 0; m < n_cams; ++m) {
         const StepBuffers& b = buf[size_t(m)][j];
         if (b.where.empty()) continue;
-        const std::vector<uint8_t> r = b.matches->download(), c = b.claimed->download(), n = b.n_claimed->download();
+        const std::vector<uint8_t> r = b.matches->download<uint8_t>(b.matches->bytes),
+                                   c = b.claimed->download<uint8_t>(b.claimed->bytes),
+                                   n = b.n_claimed->download<uint8_t>(b.n_claimed->bytes);
         for (size_t i = 0; i < b.where.size(); ++i) {
           std::memcpy(rows.data() + b.where[i] * K * rec, r.data() + i * K * rec, K * rec);
           std::memcpy(claimed.data() + b.where[i] * K, c.data() + i * K, K);
@@ -147,7 +119,7 @@ int main(int argc, char** argv) {
       fwrite(claimed.data(), 1, claimed.size(), o);
       fwrite(ncl.data(), 1, ncl.size(), o);
     }
-    const std::vector<uint8_t> m1 = d_matched1.download();
+    const std::vector<uint8_t> m1 = d_matched1.download<uint8_t>(d_matched1.bytes);
     fwrite(m1.data(), 1, nb1 * K, o);
     // error behaviour: with claims a current block is named once per call, or the call throws before anything is launched
     int32_t threw = 0;

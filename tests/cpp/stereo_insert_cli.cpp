@@ -17,38 +17,7 @@
 #include <vector>
 
 #include "../../okvis2_amd/host/okvfe_frontend.hpp"
-
-template <typename T>
-static std::vector<T> rdv(FILE* f, size_t n) {
-  std::vector<T> v(n + 1);
-  if (n && fread(v.data(), sizeof(T), n, f) != n) {
-    fprintf(stderr, "short read\n");
-    exit(2);
-  }
-  v.resize(n);
-  return v;
-}
-
-struct DeviceBuffer {
-  void* d = nullptr;
-  size_t bytes;
-  explicit DeviceBuffer(size_t n) : bytes(n ? n : 1) {
-    if (okvfe_device_alloc(0, bytes, &d) != OKVFE_OK || okvfe_device_fill(d, 0xF9, bytes, nullptr) != OKVFE_OK) exit(5);
-  }
-  ~DeviceBuffer() { okvfe_device_free(d); }
-  template <typename T>
-  T* as() const { return static_cast<T*>(d); }
-  template <typename T>
-  void upload(const std::vector<T>& v) const {
-    if (!v.empty() && okvfe_copy_to_device(d, v.data(), v.size() * sizeof(T), nullptr) != OKVFE_OK) exit(5);
-  }
-  void put(FILE* o, size_t n) const {
-    std::vector<uint8_t> v(n + 1);
-    if (n && okvfe_copy_to_host(v.data(), d, n, nullptr) != OKVFE_OK) exit(6);
-    okvfe_stream_synchronize(nullptr);
-    fwrite(v.data(), 1, n, o);
-  }
-};
+#include "cli_io.hpp"
 
 int main(int argc, char** argv) {
   if (argc < 3) return 1;
@@ -118,11 +87,11 @@ int main(int argc, char** argv) {
     if (okvfe_stream_synchronize(stream) != OKVFE_OK) return 5;
     FILE* o = fopen(argv[2], "wb");
     if (!o) return 1;
-    d_action.put(o, rows);
-    d_lmrow.put(o, rows * 4);
-    d_out.put(o, nm * nc * K * 4);
-    d_counts.put(o, nm * 16);
-    if (mode != 0) d_matches.put(o, rows * sizeof(okvfe_stereo_match));
+    put(o, d_action.download<uint8_t>(rows));
+    put(o, d_lmrow.download<uint8_t>(rows * 4));
+    put(o, d_out.download<uint8_t>(nm * nc * K * 4));
+    put(o, d_counts.download<uint8_t>(nm * 16));
+    if (mode != 0) put(o, d_matches.download<uint8_t>(rows * sizeof(okvfe_stereo_match)));
     // error behaviour: one pose per (multiframe, camera), or the call throws before anything is launched
     int32_t threw = 0;
     T_WC.push_back(okvfe_pose{});

@@ -486,3 +486,53 @@ def test_sliced_batch_of_64_frames(oracle):
         hits += int((M.check_frame(oracle, m, ref, 20.0, frames[f], lm[f], bd[f], ("sliced", f)) >= 0).sum())
         M.check_pool({k: pool[k][f] for k in M.POOL_KEYS}, ref, ("sliced", f))
     assert hits > 300
+
+
+def test_ten_streams_recycle_the_table_workspace(oracle):
+    """Both passes on ten streams of ONE context, twice over, with 1..3 frames per call: the context keeps eight
+    per-stream workspaces, so later streams evict the oldest entries (the default stream's first), an evicted stream
+    gets a fresh buffer in the second round and a kept one has to grow.  Every stream's rows equal the default-stream
+    call's byte for byte; rows past n_frames keep their sentinels."""
+    import map_table_uninit_common as U
+    sc, _, poses = _small_case(oracle, 200, "mixed", 3)
+    poses = [poses[0], poses[1], poses[0]]
+    ref = M.reference(oracle, sc, poses[0], sc["cam"], False, 20.0)
+    frames = [U.frame(oracle, sc, ref, sc["cam"], 24, 16, seed, n3d=8) for seed in (1, 2, 3)]
+    cfg = dataclasses.replace(synth.euroc_config(), cams=[sc["cam"]])
+    fe = G.make_frontend(cfg)
+    keys = ("lm", "bd", "lm2", "bd2", "hp", "hs", "ctr") + tuple(M.POOL_KEYS)
+
+    def queue(nf, stream):
+        """both passes on the first nf frames of a three-frame batch -> (the tensors before the calls, the tensors)"""
+        T = U.prepare(fe, tab.n_landmarks, frames)
+        before = {k: T[k].cpu().numpy().copy() for k in keys}
+        fe.match_to_map_table_blocks_device(tab.desc, T["blocks"].data_ptr(), nf, [0] * nf, poses[:nf], 20.0, False,
+                                            T["use"].data_ptr(), U.pool_device(fe, T), T["lm"].data_ptr(),
+                                            T["bd"].data_ptr(), stream)
+        fe.match_to_map_table_uninitialised_blocks_device(
+            tab.desc, U.pool_device(fe, T, projection=False), T["blocks"].data_ptr(), nf, [0] * nf,
+            [U.second_pose(p) for p in poses[:nf]], False, T["use"].data_ptr(), T["prev"].data_ptr(), T["lm2"].data_ptr(),
+            T["bd2"].data_ptr(), T["hp"].data_ptr(), T["hs"].data_ptr(), T["ctr"].data_ptr(), stream)
+        return before, T
+
+    try:
+        fe.set_camera(0, sc["cam"])
+        tab = M.DeviceTable(fe, sc)
+        _, T = queue(3, None)
+        torch.cuda.synchronize()
+        want = {k: T[k].cpu().numpy() for k in keys}
+        assert (want["lm"] >= 0).sum() >= 8 and (want["lm2"] >= 0).sum() >= 8, "the scene exercises neither pass"
+        streams = [torch.cuda.Stream() for _ in range(10)]
+        pending = []
+        for rnd in range(2):
+            for i, st in enumerate(streams):
+                nf = 1 + (i + rnd) % 3
+                pending.append((rnd, i, nf) + queue(nf, st))
+        torch.cuda.synchronize()
+        for rnd, i, nf, before, T in pending:
+            for k in keys:
+                got = T[k].cpu().numpy()
+                assert got[:nf].tobytes() == want[k][:nf].tobytes(), (rnd, i, k, "rows of the call")
+                assert got[nf:].tobytes() == before[k][nf:].tobytes(), (rnd, i, k, "rows past n_frames")
+    finally:
+        fe.close()
