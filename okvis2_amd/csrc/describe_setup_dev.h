@@ -27,6 +27,18 @@ constexpr int kSelectOff = 0;
   } while (0)
 #endif
 
+// one pixel's entry of a camera's ray map (3 floats) and of its Jacobian map (2 x 3 floats, row-major); the maps are
+// device allocations of the library, so entry i of the Jacobian map is 8-byte aligned
+// (vector types, so that each is ONE load instruction by construction: 12 bytes, and 16 + 8 bytes; in the global
+// address space -- the map pointers come out of a table in memory, which leaves the compiler with flat loads)
+#define OKVFE_GLOBAL_AS __attribute__((address_space(1)))
+typedef float MapFloat3 __attribute__((ext_vector_type(3)));
+typedef float MapFloat4 __attribute__((ext_vector_type(4)));
+typedef float MapFloat2 __attribute__((ext_vector_type(2)));
+typedef MapFloat3 MapRay __attribute__((aligned(4)));
+typedef MapFloat4 MapJacobianLo __attribute__((aligned(8)));  // J00 J01 J02 J10
+typedef MapFloat2 MapJacobianHi __attribute__((aligned(8)));  // J11 J12
+
 // M = J * [e_x e_y] / fu on the tangent plane of the keypoint's ray, e_y along `dir`
 __device__ __forceinline__ bool camera_aware_matrix(const float* __restrict__ rays,
                                                     const float* __restrict__ jac, int w, float fu,
@@ -37,11 +49,16 @@ __device__ __forceinline__ bool camera_aware_matrix(const float* __restrict__ ra
     u = w / 2;
     v = w / 4;
   }
-  const float* r = rays + ((size_t)v * w + u) * 3;
-  const float* J = jac + ((size_t)v * w + u) * 6;
-  const float r0 = r[0], r1 = r[1], r2 = r[2];
+  // One element index, then the entry's 12 bytes of ray as one load and its 24 bytes of Jacobian as 16 + 8 (entries
+  // are 24 bytes apart: 8-byte aligned).  Every load of a lane is a cache line of its own here, so their count is the
+  // cost; written float by float, the compiler did merge the nine reads into these three, but as flat loads.
+  const size_t at = (size_t)v * w + u;
+  const MapRay ray = *(const OKVFE_GLOBAL_AS MapRay*)(rays + at * 3);
   // (requested with the ray, ahead of the tests below: behind them the Jacobian was a memory round trip of its own)
-  const float J0 = J[0], J1 = J[1], J2 = J[2], J3 = J[3], J4 = J[4], J5 = J[5];
+  const MapJacobianLo ja = *(const OKVFE_GLOBAL_AS MapJacobianLo*)(jac + at * 6);
+  const MapJacobianHi jb = *(const OKVFE_GLOBAL_AS MapJacobianHi*)(jac + at * 6 + 4);
+  const float r0 = ray.x, r1 = ray.y, r2 = ray.z;
+  const float J0 = ja.x, J1 = ja.y, J2 = ja.z, J3 = ja.w, J4 = jb.x, J5 = jb.y;
   if (r0 == 0.0f && r1 == 0.0f && r2 == 0.0f) return false;
   float ey0 = 0.f, ey1 = 0.f, ey2 = 0.f, n2 = 0.0f;
 #pragma unroll

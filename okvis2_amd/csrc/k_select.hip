@@ -14,14 +14,21 @@
 // refinement: k_brisk_refine.hip, shared device helpers: select_common_dev.h.
 // Bound: one ordered chain of LDS and memory round trips per image; batches keep all CUs busy with independent images.
 // It is not free of memory traffic: 458 KB fetched and 89 KB written per EuRoC image in a 6144-image launch
-// (profiles/select_keys_traffic.txt), about 380 KB of the fetched bytes by the tail's scattered windows, map entries and
-// extra-sample rows and 110 KB by the candidate records (profiles/select_traffic.txt, priced per source by
-// tools/lab/select_traffic.sh), against 125 KB algorithmic.
+// (profiles/select_keys_traffic.txt, before the tail's window became seven loads: profiles/select_tail_loads.txt),
+// about 380 KB of the fetched bytes by the tail's scattered windows, map entries and extra-sample rows and 110 KB by
+// the candidate records (profiles/select_traffic.txt, priced per source by tools/lab/select_traffic.sh), against 125 KB
+// algorithmic.
 // The chain's memory round trips, as built: set-up -- the first 5120 candidate records in two waves of ten 12-byte
 // loads per lane (branch-free, packed five at a time), then the key scatter (one write cursor per CHUNK, so a wave's
 // stores form a few contiguous runs; keys are unordered inside a chunk); per chunk -- its keys, requested one chunk
-// ahead; tail (refine_emit, one lane per keypoint) -- the kept record, 21 pixel dwords, ray + Jacobian together, the
-// rows of each extra sample (its constants requested one trip ahead).  What is the same for every keypoint of an image
+// ahead; tail (refine_emit, one lane per keypoint: every load instruction of a wave touches 64 lines, so the tail
+// costs what its COUNT of loads costs) -- the kept record (two loads), the 7 x 7 window as seven 12-byte loads from a
+// base clamped into the row with no branch between them, ray + Jacobian together as 12 + 16 + 8 bytes, the rows of
+// each extra sample, five 8-byte loads (its constants requested one trip ahead): five trips.  The first extra sample
+// of the built-in pattern sits at the keypoint and its box inside the window just read; taking it from those
+// registers was built and taken out again: 14 more live values across the sub-pixel fit put 96 bytes per lane into
+// scratch (LAB_NOTES, "Selection tail: fewer, wider loads", which also has the single keypoint record that was
+// measured and not kept).  What is the same for every keypoint of an image
 // (ImageParams, the camera's map pointers, border / reach / point count of the pattern) is loaded at kernel start,
 // before the first store, as scalar loads nothing waits for (describe_image_params, describe_setup_dev.h).
 #include <mutex>

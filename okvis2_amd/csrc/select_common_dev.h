@@ -28,23 +28,31 @@ __device__ __forceinline__ uint64_t make_key(const Candidate& c) {
 // A kernel of its own for this -- one thread per keypoint of the batch -- was measured and is slower (111 us:
 // it is all scattered line fetches, which hide behind other images' arithmetic in here).
 // xx | yy << 16 share a register (both < 2^14 after the binomial).
+// twelve bytes at a dword-aligned address as ONE load instruction (a vector type: the compiler takes a struct of three
+// words apart into three loads again, and sinks the ones a lane may not need behind a branch)
+typedef uint32_t Dwords3v __attribute__((ext_vector_type(3)));
+typedef Dwords3v Dwords3 __attribute__((aligned(4)));
 __device__ __forceinline__ void harris_scores_3x3(const uint8_t* __restrict__ im, int w, int h, int u, int v,
                                                   int32_t out[9]) {
-  // (requires w % 4 == 0 and a dword-aligned image, like the fused score kernel this stands in for)
-  // Pixels u - 3 .. u + 3 of rows v - 3 .. v + 3 as three aligned dwords per row (one keypoint per lane: every
-  // load instruction of the wave touches 64 different lines, so the count of loads is what this costs); the
-  // dword before the row / past its end is not read -- the pixel it would supply only feeds gradient products
-  // on the image rim, which are zero by definition.
+  // (requires w % 4 == 0, w >= 12 and a dword-aligned image, like the fused score kernel this stands in for)
+  // Pixels u - 3 .. u + 3 of rows v - 3 .. v + 3 from the three aligned dwords of each row that hold them (one
+  // keypoint per lane: every load instruction of the wave touches 64 different lines, so the count of loads is what
+  // this costs): ONE 12-byte load per row and no branch between the rows.  The run starts at the dword of pixel u - 3
+  // CLAMPED into the row, [0, w - 12], so no lane reads before the first image of a batch or behind its last; where the
+  // clamp moved it (by one dword, at the left and right rims) the dword that falls off the row is "whatever was
+  // loaded" -- the pixels it would supply only feed gradient products on the image rim, which are zero by definition.
   const int base = (u - 3) & ~3;  // -4 for u = 2
   const int sh = (u - 3) - base;  // 0..3
-  uint32_t q0[7], q1[7];          // pixels 0..3 and 4..6 of each row
+  const int cbase = base < 0 ? 0 : (base > w - 12 ? w - 12 : base);
+  const bool at_left = base < cbase, at_right = base > cbase;  // the row's dwords sit one place later / earlier
+  uint32_t q0[7], q1[7];                                      // pixels 0..3 and 4..6 of each row
 #pragma unroll
   for (int r = 0; r < 7; ++r) {
     const int y = v - 3 + r;
-    const uint32_t* row = reinterpret_cast<const uint32_t*>(im + (size_t)(y < 0 ? 0 : (y > h - 1 ? h - 1 : y)) * w);
-    const uint32_t d0 = base >= 0 ? row[base >> 2] : 0u;
-    const uint32_t d1 = row[(base >> 2) + 1];
-    const uint32_t d2 = base + 8 < w ? row[(base >> 2) + 2] : 0u;
+    const Dwords3 t = *reinterpret_cast<const Dwords3*>(im + (size_t)(y < 0 ? 0 : (y > h - 1 ? h - 1 : y)) * w + cbase);
+    const uint32_t d0 = at_right ? t.y : t.x;
+    const uint32_t d1 = at_left ? t.x : (at_right ? t.z : t.y);
+    const uint32_t d2 = at_left ? t.y : t.z;
     q0[r] = __builtin_amdgcn_alignbyte(d1, d0, (uint32_t)sh);
     q1[r] = __builtin_amdgcn_alignbyte(d2, d1, (uint32_t)sh);
   }
