@@ -701,8 +701,10 @@ okvfe_status okvfe_match_motion_stereo_blocks_device(okvfe_ctx* ctx, int32_t cam
  * (lm.quality < acos(cos_quality)) and setLandmark / addLandmark / addObservation (:1940-1956) need estimator state
  * and a libm acos.  A caller that needs that coupling refreshes its skip0 rows between the calls, on the device or the
  * host; with skip0 fixed up front the sweep equals the reference whenever no such landmark exists.  A landmark observed
- * by two keypoints of one older image is not modelled.  runRansac2d2d (:1964-1969, before initialisation only) and the
- * choice and order of the older frames (:1742-1767) stay with the caller as well.
+ * by two keypoints of one older image is not modelled.  The choice and order of the older frames (:1742-1767) stay
+ * with the caller as well.  The consensus of runRansac2d2d (:1964-1969, before initialisation only) is
+ * okvfe_ransac2d2d_consensus_blocks_device, queued after each step of the sweep; its sampler and minimal solvers are
+ * the caller's.
  *
  * An index outside [0, n_blocks*), a NULL required pointer, a negative count, a camera slot out of range or without
  * intrinsics (the pair and the slot named): OKVFE_ERR_INVALID_ARGUMENT before anything is launched.  n_pairs == 0 is OK
@@ -988,6 +990,108 @@ okvfe_status okvfe_remove_outliers_blocks_device(
     okvfe_ctx* ctx, const okvfe_landmark_table_device* table, const void* blocks_dev, int32_t n_frames,
     const int32_t* cam_ids /* HOST, n_frames */, const okvfe_pose* T_WC /* HOST, n_frames */, double max_error,
     const int32_t* landmark_dev, int32_t* landmark_out_dev, int32_t* kept_dev, void* stream);
+
+/* ---- before initialisation: the consensus of runRansac2d2d inside the motion-stereo sweep --------
+ * The consensus step of Frontend::runRansac2d2d (Frontend.cpp:2281-2394), which runs after every older frame of the
+ * matchMotionStereo sweep while the session is not initialised (:1961-1969) and whose rotationOnly decides whether it
+ * initialises at all (:644-648), for n_pairs (older multiframe, current multiframe) pairs of n_cams cameras in ONE
+ * launch.  Pair p relates older multiframe mf0[p] to current multiframe mf1[p]: the older one owns the gather blocks
+ * mf0[p] n_cams + c of blocks0_dev, the current one the blocks mf1[p] n_cams + c of blocks1_dev (the multiframe-major
+ * layout of okvfe_ransac3d2d_consensus_blocks_device; the two block pointers may be equal).  Frame 1 of opengv's model
+ * is the older one.  landmark0_dev / landmark1_dev: int32, K per block, block-indexed as in
+ * okvfe_stereo_insert_blocks_device; a value < 0 is "no landmark" (lmId == 0).  added_dev: n_landmarks bytes,
+ * byte l = estimator.isLandmarkAdded(l), an id >= n_landmarks is not added; NULL: every id >= 0 is added.  No landmark
+ * table: the adapter reads no 3-D point.  cam_ids: HOST, n_cams camera slots; fu comes from slot cam_ids[c] for both
+ * frames (FrameRelativeAdapter.cpp:78-129 reads fu2 from frame A's geometry at camIdB, the same camera here); a slot
+ * without intrinsics: OKVFE_ERR_NOT_READY.
+ *
+ * Correspondences per camera (FrameRelativeAdapter.cpp:137-165):
+ *   :139-152  over the CURRENT block's keypoints k < count, ascending: id < 0 skipped (:143), a not-added id skipped
+ *             (:147); the FIRST k of an id is kept (:151, std::map::insert does not overwrite).
+ *   :154-165  over the OLDER block's keypoints ascending: a keypoint with id >= 0 (:157) whose id is in that map (:160)
+ *             gives one correspondence (kA, kB), in older-keypoint order.  Two older keypoints on one landmark give two
+ *             correspondences to the same kB.  The older id is NOT tested for isLandmarkAdded.
+ * Bearings and sigmas (:168-193): sigma = ((sqrt2 s) s) / (fu fu), s = (0.8 double(size)) / 12.0, per side (:175-176,
+ * :186-187), written as in the 3d2d call.  b2 = the current block's stored back-projection, normalised, whatever its
+ * validity byte (:189-193: getBackProjection hands out the stored value, Frame.hpp:196-208).  b1 = (1, 0, 0) if EITHER
+ * validity byte is 0 (:178-179, and :190 overwrites bearingVectors1_, not 2_: the reference's slip, restated), else the
+ * older block's back-projection, normalised.  Normalisation is Eigen's: z = squaredNorm, divided by sqrt(z) iff z > 0.
+ *
+ * rot_hyp_dev: n_pairs x n_cams x n_hyp x 9 doubles, a row-major rotation M per hypothesis; rel_hyp_dev: ... x 12
+ * doubles, a row-major [R12 | t12] (opengv's model).  rot_valid_dev / rel_valid_dev: bytes of the same leading shape or
+ * NULL (all valid); 0 = a sample whose solver failed, skipped.  n_hyp in 1 .. OKVFE_RANSAC_MAX_HYPOTHESES (the
+ * reference: max_iterations_ 50, :2313, :2330); threshold: the reference's 9 (:2312, :2329).
+ * Distances, FP64 without FMA, 3- and 4-term sums in the order of okvfe_set_fp64_reduction:
+ *   rotation only (FrameRotationOnlySacProblem.hpp:126-144): f2u = M b2 (:131), f1u = M^T b1 (:134), e1 = f2u - b1
+ *     (:136), e2 = f1u - b2 (:137), d = (e1.e1 * 0.5) / s1 + (e2.e2 * 0.5) / s2 (:140-143).
+ *   relative pose (FrameRelativePoseSacProblem.hpp:130-160): Ri = R^T (:136), ti = (-Ri) t (:137),
+ *     p = triangulate2(b1, b2; R, t) (:143), rep1 = p / |p| (:147), rep2 = Ri p + ti * 1 in four-term rows (:146), then
+ *     / |rep2| (:148), e1 = rep1 - b1 (:153), e2 = rep2 - b2 (:154), d as above (:157-160).
+ *   triangulate2, with Eigen's 2 x 2 inverse: f2u = R b2; b0 = t . b1, b1' = t . f2u; A00 = b1 . b1, A10 = b1 . f2u,
+ *     A01 = -A10, A11 = -(f2u . f2u); det = A00 A11 - A10 A01, invdet = 1.0 / det; I00 = A11 invdet,
+ *     I10 = (-A10) invdet, I01 = (-A01) invdet, I11 = A00 invdet; l0 = I00 b0 + I01 b1', l1 = I10 b0 + I11 b1';
+ *     p = (l0 b1 + (t + l1 f2u)) / 2.
+ * An inlier is d < threshold; a NaN is an outlier (parallel bearings: det == 0, hence a NaN).
+ * Winners: per problem the valid hypothesis with the most inliers, more than 0, the first such in list order.
+ *
+ * Per camera, in order, the two success flags shared by the cameras of a pair as the reference's locals are (:2289-2290):
+ *   :2300      n < 10: skipped (branch 0), nothing is scored, added to the total or removed.
+ *   :2320,2337 the ratios are float(inliers) / float(n) in FLOAT32, compared with 0.8f.
+ *   :2341-2349 rot_ratio > rel_ratio || rot_ratio > 0.8f: branch 1; rotation_only_success iff rot_inliers > 10;
+ *              rotationOnly = true; total += rot_inliers.
+ *   :2350-2358 else branch 2; rel_pose_success iff rel_inliers > 10 && rel_ratio > 0.8f; total += rel_inliers.
+ *   :2361      neither flag set SO FAR (the earlier cameras' included): the camera is done.
+ *   :2365-2375 else removed = 1 and, with remove_outliers, every current keypoint kB with at least one correspondence
+ *              that is NOT an inlier of the taken branch's winner gets -1 in landmark1_out (without a winner every
+ *              correspondence is such a one).  All other rows below the current block's count copy landmark1_dev; rows
+ *              at or past the count are untouched.
+ *   :2387-2392 either flag set: total_inliers = the total, rotation_only as accumulated; else total_inliers = -1 and
+ *              rotation_only = 1.
+ * With landmark1_out a current multiframe may appear in at most one pair of a call (OKVFE_ERR_INVALID_ARGUMENT, the
+ * multiframe and both pairs named), and its rows must not be the OLDER rows of another pair of the same call: the
+ * reference visits the older frames one after another, so J older frames are J calls on one stream.
+ *
+ * NOT restated: the sampler; opengv's twopt_rotationOnly and the Stewenius five-point solver, which work on two and
+ * five correspondences and stay with the caller; opengv's adaptive stop (this call scores every hypothesis it is
+ * given); estimator.removeObservation beyond the id row; the LOG lines of :2378-2384; firstFrame and rotationOnly_tmp
+ * (:1971-1974) and :644, host lines over the result bytes.  PARITY UNPINNED: opengv's winner
+ * rule, as for okvfe_ransac3d2d_consensus_blocks_device.  PARITY UNPINNED: opengv::triangulation::triangulate2 and
+ * Eigen's 2 x 2 inverse are not in the reference tree; they are restated above from their published sources.
+ *
+ * Limits: one work-group keeps the id map of a current block in 4096 four-byte slots of LDS, and a probe ends at an
+ * empty slot: K = max_keypoints <= 4095, beyond that OKVFE_ERR_UNSUPPORTED.  8 bytes per pair and 8 per camera go through
+ * the pinned parameter ring; nothing synchronises the host; no workspace.  A NULL required pointer, a negative count or
+ * a multiframe index out of range: OKVFE_ERR_INVALID_ARGUMENT before anything is launched; n_pairs == 0 is OK and
+ * launches nothing. */
+typedef struct okvfe_ransac2d2d_result_device {
+  /* per (pair, camera), n_pairs x n_cams */
+  int32_t* n_correspondences;
+  int32_t* rot_best;  /* winner of the rotation-only problem, -1 = none */
+  int32_t* rot_inliers;
+  int32_t* rel_best;  /* winner of the relative-pose problem, -1 = none */
+  int32_t* rel_inliers;
+  uint8_t* branch;    /* 0 skipped (< 10 correspondences), 1 rotation-only taken (:2341), 2 relative pose taken (:2350) */
+  uint8_t* removed;   /* 1 = this camera reached :2365 (outliers kicked) */
+  /* per pair, n_pairs */
+  int32_t* total_inliers; /* the return value: the sum, or -1 (:2387-2392) */
+  uint8_t* rotation_only; /* the bool& of :2283 as it is on return (the "hack" at :2391 included) */
+  uint8_t* success;       /* bit 0 rotation_only_success, bit 1 rel_pose_success */
+  /* optional, NULL allowed */
+  int32_t* rot_hyp_inliers; /* n_pairs x n_cams x n_hyp; -1: skipped hypothesis / not scored */
+  int32_t* rel_hyp_inliers;
+  int32_t* match1;        /* n_pairs x n_cams x K, by OLDER keypoint: the current keypoint of its correspondence, -1 none */
+  uint8_t* state;         /* same shape: 0 no correspondence, 1 outlier of the taken branch's winner (or no winner, or the
+                           * camera was skipped), 2 inlier */
+  double* distance;       /* same shape: distance to the taken branch's winner; untouched without correspondence / winner */
+  int32_t* landmark1_out; /* current blocks x K, may be landmark1_dev itself */
+} okvfe_ransac2d2d_result_device;
+okvfe_status okvfe_ransac2d2d_consensus_blocks_device(
+    okvfe_ctx* ctx, const void* blocks0_dev, int32_t n_multiframes0, const void* blocks1_dev, int32_t n_multiframes1,
+    int32_t n_pairs, const int32_t* mf0 /* HOST, n_pairs */, const int32_t* mf1 /* HOST, n_pairs */, int32_t n_cams,
+    const int32_t* cam_ids /* HOST, n_cams */, const int32_t* landmark0_dev, const int32_t* landmark1_dev,
+    const uint8_t* added_dev /* n_landmarks bytes or NULL */, int32_t n_landmarks, const double* rot_hyp_dev,
+    const uint8_t* rot_valid_dev /* or NULL */, const double* rel_hyp_dev, const uint8_t* rel_valid_dev /* or NULL */,
+    int32_t n_hyp, double threshold, int32_t remove_outliers, const okvfe_ransac2d2d_result_device* result, void* stream);
 
 /* ---- matchStereo's landmark bookkeeping, chained over the camera pairs of a rig ----------------
  * Frontend::matchStereo after its k0 x k1 loop (Frontend.cpp:2076-2141) for n_multiframes multiframes of n_cams cameras,

@@ -122,6 +122,7 @@ EXPORTS = [
     "okvfe_vocabulary_check", "okvfe_bow_vectors_blocks_device", "okvfe_place_query_blocks_device",
     "okvfe_bow_database_add_blocks_device", "okvfe_bow_database_check_device",
     "okvfe_stereo_insert_blocks_device",
+    "okvfe_ransac2d2d_consensus_blocks_device",
 ]
 
 STAGES = ["harris", "nms", "sort", "select", "map", "describe", "compact", "match"]
@@ -165,6 +166,14 @@ class RansacResultDevice(C.Structure):
     _fields_ = [("n_correspondences", C.c_void_p), ("best_hypothesis", C.c_void_p), ("n_inliers", C.c_void_p),
                 ("accepted", C.c_void_p), ("hyp_inliers", C.c_void_p), ("state", C.c_void_p),
                 ("distance", C.c_void_p), ("landmark_out", C.c_void_p)]
+
+
+class Ransac2d2dResultDevice(C.Structure):
+    """okvfe_ransac2d2d_result_device: device pointers; the last six are optional (None)."""
+    _fields_ = [(n, C.c_void_p) for n in (
+        "n_correspondences", "rot_best", "rot_inliers", "rel_best", "rel_inliers", "branch", "removed",
+        "total_inliers", "rotation_only", "success",
+        "rot_hyp_inliers", "rel_hyp_inliers", "match1", "state", "distance", "landmark1_out")]
 
 
 class PlaceSetDevice(C.Structure):
@@ -213,6 +222,8 @@ MOTION_CLAIM_MAX_KEYPOINTS = 12288  # K above it: claims are OKVFE_ERR_UNSUPPORT
 RANSAC_MAX_HYPOTHESES = 64  # OKVFE_RANSAC_MAX_HYPOTHESES
 RANSAC_THRESHOLD = 16.0     # Frontend.cpp:2235
 REMOVE_OUTLIERS_MAX_ERROR = 4.0  # Frontend.cpp:2185
+RANSAC2D2D_THRESHOLD = 9.0  # Frontend.cpp:2312, 2329
+RANSAC2D2D_MAX_KEYPOINTS = 4095  # K above it: okvfe_ransac2d2d_consensus_blocks_device is OKVFE_ERR_UNSUPPORTED
 PLACE_CLAIMS_MAX_KEYPOINTS = 12288  # K above it: okvfe_place_claims_blocks_device is OKVFE_ERR_UNSUPPORTED
 BOW_MAX_FEATURES = 8192  # n_cams x K above it: okvfe_bow_vectors_blocks_device is OKVFE_ERR_UNSUPPORTED
 PLACE_MIN_SCORE = 0.4    # Frontend.cpp:802
@@ -260,6 +271,10 @@ def lib():
         L.okvfe_ransac3d2d_consensus_blocks_device.restype = C.c_int32
         L.okvfe_ransac3d2d_consensus_blocks_device.argtypes = [
             V, V, V, C.c_int32, C.c_int32, V, V, V, V, V, C.c_int32, C.c_double, C.c_int32, V, V]
+        L.okvfe_ransac2d2d_consensus_blocks_device.restype = C.c_int32
+        L.okvfe_ransac2d2d_consensus_blocks_device.argtypes = [
+            V, V, C.c_int32, V, C.c_int32, C.c_int32, V, V, C.c_int32, V, V, V, V, C.c_int32, V, V, V, V, C.c_int32,
+            C.c_double, C.c_int32, V, V]
         L.okvfe_stereo_insert_blocks_device.restype = C.c_int32
         L.okvfe_stereo_insert_blocks_device.argtypes = [
             V, V, V, V, C.c_int32, C.c_int32, C.c_int32, C.c_int32, V, C.c_int32, V, V, V, V, V, V, V]
@@ -1047,6 +1062,40 @@ class Frontend:
             self._h, C.byref(table), _p(blocks_ptr), n, _p(cams) if n else _p(np.zeros(1, np.int32)), P,
             C.c_double(max_error), _p(landmark_ptr), _p(landmark_out_ptr), _p(kept_ptr), _s(stream)))
 
+    # -- before initialisation: the consensus of runRansac2d2d inside the motion-stereo sweep ----
+    @staticmethod
+    def make_ransac2d2d_result_device(n_correspondences_ptr, rot_best_ptr, rot_inliers_ptr, rel_best_ptr,
+                                      rel_inliers_ptr, branch_ptr, removed_ptr, total_inliers_ptr, rotation_only_ptr,
+                                      success_ptr, rot_hyp_inliers_ptr=None, rel_hyp_inliers_ptr=None, match1_ptr=None,
+                                      state_ptr=None, distance_ptr=None,
+                                      landmark1_out_ptr=None) -> Ransac2d2dResultDevice:
+        return Ransac2d2dResultDevice(*[int(p) if p else None for p in (
+            n_correspondences_ptr, rot_best_ptr, rot_inliers_ptr, rel_best_ptr, rel_inliers_ptr, branch_ptr, removed_ptr,
+            total_inliers_ptr, rotation_only_ptr, success_ptr, rot_hyp_inliers_ptr, rel_hyp_inliers_ptr, match1_ptr,
+            state_ptr, distance_ptr, landmark1_out_ptr)])
+
+    def ransac2d2d_consensus_blocks_device(self, blocks0_ptr, n_multiframes0, blocks1_ptr, n_multiframes1, mf0, mf1,
+                                           cam_ids, landmark0_ptr, landmark1_ptr, added_ptr, n_landmarks, rot_hyp_ptr,
+                                           rot_valid_ptr, rel_hyp_ptr, rel_valid_ptr, n_hyp,
+                                           result: Ransac2d2dResultDevice, threshold=RANSAC2D2D_THRESHOLD,
+                                           remove_outliers=True, stream=None):
+        """The consensus step of runRansac2d2d for the pairs (older multiframe mf0[p], current multiframe mf1[p]) of
+        len(cam_ids) gather blocks each.  mf0 / mf1 / cam_ids: host sequences; rot_hyp_ptr / rel_hyp_ptr: device
+        n_pairs x n_cams x n_hyp x 9 / x 12 doubles; the valid pointers: device bytes or None; added_ptr: device
+        n_landmarks bytes or None."""
+        a0 = np.ascontiguousarray(mf0, dtype=np.int32).reshape(-1)
+        a1 = np.ascontiguousarray(mf1, dtype=np.int32).reshape(-1)
+        if len(a0) != len(a1):
+            raise ValueError("mf0 and mf1: one per pair")
+        cams = np.ascontiguousarray(cam_ids, dtype=np.int32)
+        one = np.zeros(1, np.int32)
+        self._check(lib().okvfe_ransac2d2d_consensus_blocks_device(
+            self._h, _p(blocks0_ptr), int(n_multiframes0), _p(blocks1_ptr), int(n_multiframes1), len(a0),
+            _p(a0) if len(a0) else _p(one), _p(a1) if len(a1) else _p(one), len(cams),
+            _p(cams) if len(cams) else _p(one), _p(landmark0_ptr), _p(landmark1_ptr), _p(added_ptr), int(n_landmarks),
+            _p(rot_hyp_ptr), _p(rot_valid_ptr), _p(rel_hyp_ptr), _p(rel_valid_ptr), int(n_hyp), C.c_double(threshold),
+            int(bool(remove_outliers)), C.byref(result) if result is not None else None, _s(stream)))
+
     # -- matchStereo's landmark bookkeeping, chained over the pairs of a rig ---------------------
     @staticmethod
     def make_stereo_insert_device(action_ptr, lm_ptr, landmark_out_ptr, counts_ptr) -> StereoInsertDevice:
@@ -1149,6 +1198,13 @@ class Frontend:
     def _test_ransac_chunk_records() -> int:
         """test hook (not part of include/okvfe.h): correspondences the consensus kernel scores at a time"""
         f = lib().okvfe_test_ransac_chunk_records
+        f.restype = C.c_int32
+        return int(f())
+
+    @staticmethod
+    def _test_ransac2d2d_chunk_records() -> int:
+        """test hook (not part of include/okvfe.h): correspondences the 2d2d consensus kernel scores at a time"""
+        f = lib().okvfe_test_ransac2d2d_chunk_records
         f.restype = C.c_int32
         return int(f())
 

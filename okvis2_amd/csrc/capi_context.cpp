@@ -366,7 +366,8 @@ okvfe_status okvfe_set_fp64_reduction(okvfe_ctx* ctx, int32_t order) {
     return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_set_fp64_reduction: order %d", order);
   if (hipSetDevice(ctx->cfg.device) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
     return fail(ctx, OKVFE_ERR_DEVICE, "okvfe_set_fp64_reduction: device %d", ctx->cfg.device);
-  if (!okvfe::set_fp64_tree_match(order) || !okvfe::set_fp64_tree_map(order) || !okvfe::set_fp64_tree_ransac(order))
+  if (!okvfe::set_fp64_tree_match(order) || !okvfe::set_fp64_tree_map(order) || !okvfe::set_fp64_tree_ransac(order) ||
+      !okvfe::set_fp64_tree_ransac2d2d(order))
     return fail(ctx, OKVFE_ERR_DEVICE, "okvfe_set_fp64_reduction: writing the device flag failed");
   return OKVFE_OK;
 }

@@ -1,0 +1,84 @@
+// capi_ransac2d2d.cpp -- the consensus step of Frontend::runRansac2d2d (Frontend.cpp:2281-2394) behind the C ABI: what the
+// motion-stereo sweep runs after every older frame while the session is not initialised, on device-resident batches.
+#include "okvfe_ctx.h"
+
+using namespace okvfe;
+
+extern "C" {
+
+okvfe_status okvfe_ransac2d2d_consensus_blocks_device(
+    okvfe_ctx* ctx, const void* blocks0_dev, int32_t n_multiframes0, const void* blocks1_dev, int32_t n_multiframes1,
+    int32_t n_pairs, const int32_t* mf0, const int32_t* mf1, int32_t n_cams, const int32_t* cam_ids,
+    const int32_t* landmark0_dev, const int32_t* landmark1_dev, const uint8_t* added_dev, int32_t n_landmarks,
+    const double* rot_hyp_dev, const uint8_t* rot_valid_dev, const double* rel_hyp_dev, const uint8_t* rel_valid_dev,
+    int32_t n_hyp, double threshold, int32_t remove_outliers, const okvfe_ransac2d2d_result_device* result, void* stream) {
+  const char* fn = "okvfe_ransac2d2d_consensus_blocks_device";
+  if (!ctx) return OKVFE_ERR_INVALID_ARGUMENT;
+  if (!blocks0_dev || !blocks1_dev || n_multiframes0 < 0 || n_multiframes1 < 0 || n_pairs < 0 ||
+      (n_pairs > 0 && (!mf0 || !mf1)) || n_cams < 1 || n_cams > (int)ctx->h_cams.size() || !cam_ids || !landmark0_dev ||
+      !landmark1_dev || n_landmarks < 0 || !rot_hyp_dev || !rel_hyp_dev || n_hyp < 1 ||
+      n_hyp > OKVFE_RANSAC_MAX_HYPOTHESES || !(threshold >= 0.0) || !result || !result->n_correspondences ||
+      !result->rot_best || !result->rot_inliers || !result->rel_best || !result->rel_inliers || !result->branch ||
+      !result->removed || !result->total_inliers || !result->rotation_only || !result->success)
+    return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "%s: bad argument", fn);
+  if (ctx->kp_cap > kRansac2dMaxKeypoints)
+    return fail(ctx, OKVFE_ERR_UNSUPPORTED, "%s: max_keypoints %d exceeds %d (the id map of a block: 4096 slots of LDS)", fn,
+                ctx->kp_cap, kRansac2dMaxKeypoints);
+  // the parameter block: fu per camera, then {mf0, mf1} per pair
+  std::vector<uint8_t> prm((size_t)n_cams * sizeof(double) + (size_t)n_pairs * 2 * sizeof(int32_t));
+  for (int c = 0; c < n_cams; ++c) {
+    const DeviceCamera* dc = slot_camera(ctx, cam_ids[c]);
+    if (!dc)
+      return fail(ctx, OKVFE_ERR_NOT_READY, "%s: frame %d: camera slot %d has no intrinsics (okvfe_set_camera)", fn, c,
+                  cam_ids[c]);
+    std::memcpy(prm.data() + (size_t)c * sizeof(double), &dc->fu, sizeof(double));
+  }
+  int32_t* pr = reinterpret_cast<int32_t*>(prm.data() + (size_t)n_cams * sizeof(double));
+  std::vector<int> user(result->landmark1_out ? (size_t)n_multiframes1 : 0, -1);
+  for (int p = 0; p < n_pairs; ++p) {
+    if (mf0[p] < 0 || mf0[p] >= n_multiframes0 || mf1[p] < 0 || mf1[p] >= n_multiframes1)
+      return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "%s: pair %d: multiframes (%d, %d) outside [0, %d) x [0, %d)", fn, p,
+                  mf0[p], mf1[p], n_multiframes0, n_multiframes1);
+    if (result->landmark1_out) {
+      if (user[(size_t)mf1[p]] >= 0)
+        return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT,
+                    "%s: current multiframe %d is named by pairs %d and %d: with landmark1_out a call resolves a current "
+                    "multiframe once", fn, mf1[p], user[(size_t)mf1[p]], p);
+      user[(size_t)mf1[p]] = p;
+    }
+    pr[2 * p] = mf0[p];
+    pr[2 * p + 1] = mf1[p];
+  }
+  if (n_pairs == 0) return OKVFE_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
+  hipStream_t s = pick_stream(ctx, stream);
+  const BlockLayout L = block_layout(ctx->kp_cap);
+  RingSlot slot(ctx, &ctx->pair_ring, s);  // one asynchronous copy, no host sync
+  okvfe_status st = slot.upload(prm.data(), prm.size());
+  if (st != OKVFE_OK) return st;
+  Ransac2d2dArgs A;
+  A.blocks0 = static_cast<const uint8_t*>(blocks0_dev);
+  A.blocks1 = static_cast<const uint8_t*>(blocks1_dev);
+  A.o_count = (int)L.o_count; A.o_kps = (int)L.o_kps; A.o_bp = (int)L.o_bp; A.o_bpv = (int)L.o_bpv;
+  A.block_bytes = L.total; A.kp_cap = ctx->kp_cap; A.n_cams = n_cams;
+  A.fu = slot.as<double>();
+  A.pairs = reinterpret_cast<const int32_t*>(slot.as<uint8_t>() + (size_t)n_cams * sizeof(double));
+  A.landmark0 = landmark0_dev; A.landmark1 = landmark1_dev; A.added = added_dev; A.n_landmarks = n_landmarks;
+  A.rot_hyp = rot_hyp_dev; A.rot_valid = rot_valid_dev; A.rel_hyp = rel_hyp_dev; A.rel_valid = rel_valid_dev;
+  A.n_hyp = n_hyp; A.threshold = threshold; A.remove_outliers = remove_outliers ? 1 : 0;
+  A.out = *result;
+  {
+    StageTimer t(ctx, OKVFE_STAGE_MAP, s);
+    launch_ransac2d2d_consensus(A, n_pairs, s);
+  }
+  HIP_TRY(ctx, hipGetLastError());
+  const okvfe_status rel = slot.release();
+  ctx->last_stream = s;
+  return rel;
+}
+
+// Test hook, deliberately not in include/okvfe.h: the number of correspondences the 2d2d consensus kernel scores at a
+// time, so that the tests straddle it whatever it is.
+int32_t okvfe_test_ransac2d2d_chunk_records(void) { return ransac2d2d_chunk_records(); }
+
+}  // extern "C"

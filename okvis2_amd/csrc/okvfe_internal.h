@@ -289,6 +289,7 @@ namespace okvfe {
 bool set_fp64_tree_match(int tree);
 bool set_fp64_tree_map(int tree);
 bool set_fp64_tree_ransac(int tree);
+bool set_fp64_tree_ransac2d2d(int tree);
 void launch_bow_query_l1(const int32_t* db_begin, const int32_t* db_ids, const double* db_values, int n_entries,
                          const int32_t* q_ids, const double* q_values, int n_q, double* scores,
                          hipStream_t stream);
@@ -556,6 +557,31 @@ void launch_ransac_consensus(const double* hp_W, const int32_t* obs_begin, int n
                              const uint8_t* hyp_valid, int n_hyp, double threshold, int remove_outliers,
                              const okvfe_ransac_result_device& out, hipStream_t stream);
 int ransac_chunk_records();  // correspondences the consensus kernel scores at a time
+// the consensus step of runRansac2d2d for a batch of (older, current) multiframe pairs (k_ransac2d2d.hip).  pairs
+// (n_pairs x {mf0, mf1}) and fu (n_cams) lie in the parameter block of the call; every other pointer is the caller's.
+constexpr int kRansac2SlotsLog2 = 12;  // the id table of a work-group: 4096 slots of 4 bytes
+constexpr int kRansac2dMaxKeypoints = (1 << kRansac2SlotsLog2) - 1;  // an empty slot always ends a probe
+struct Ransac2d2dArgs {
+  const uint8_t *blocks0, *blocks1;
+  int o_count, o_kps, o_bp, o_bpv;
+  size_t block_bytes;
+  int kp_cap, n_cams;
+  const int32_t* pairs;
+  const double* fu;
+  const int32_t *landmark0, *landmark1;  // landmark1 may alias out.landmark1_out
+  const uint8_t* added;
+  int n_landmarks;
+  const double* rot_hyp;
+  const uint8_t* rot_valid;
+  const double* rel_hyp;
+  const uint8_t* rel_valid;
+  int n_hyp;
+  double threshold;
+  int remove_outliers;
+  okvfe_ransac2d2d_result_device out;
+};
+void launch_ransac2d2d_consensus(const Ransac2d2dArgs& args, int n_pairs, hipStream_t stream);
+int ransac2d2d_chunk_records();
 // verifyRecognisedPlace after the descriptor matching (Frontend.cpp:347-397): the claims (k_place.hip) and the consensus
 // over LoopclosureNoncentralAbsoluteAdapter's correspondences (k_ransac.hip, the kPlace policy of the kernel above)
 constexpr int kPlaceClaimsMaxKeypoints = 12288;  // one int per keypoint in LDS

@@ -18,6 +18,7 @@
 #include <array>
 #include <cstdint>
 #include <cstring>
+#include <initializer_list>
 #include <memory>
 #include <mutex>
 #include <stdexcept>
@@ -811,6 +812,44 @@ class HipFrontend {
         c.get(), &table.get(), blocksDev, nMultiframes, 1, &cam, &T_SC, landmarkDev, reinterpret_cast<const double*>(d),
         hypValid.empty() ? nullptr : d + hypBytes, nHyp, threshold, removeOutliers ? 1 : 0, &result, stream));
   }
+  // Before initialisation (Frontend.cpp:1961-1969): the consensus step of runRansac2d2d for the pairs (older frame
+  // mf0[p] of blocks0Dev, current frame mf1[p] of blocks1Dev) of camera `cameraIndex` (ONE camera per context, so a
+  // multiframe is one gather block here; a rig whose cameras share a context calls
+  // okvfe_ransac2d2d_consensus_blocks_device itself).  rotHypotheses / relHypotheses: host, nPairs x nHyp x 9 / x 12
+  // doubles (row-major rotations / [R12 | t12], frame 1 the older one), what the caller's twopt_rotationOnly and
+  // five-point solvers produced from their samples; rotValid / relValid: host nPairs x nHyp bytes or empty (all valid).
+  // They are uploaded on `stream` as ransac3d2dBlocks uploads its hypotheses, under the same rules: the vectors stay
+  // valid and unchanged until `stream` has drained.  landmark0Dev / landmark1Dev: device ids, K per block, < 0 = none;
+  // addedDev: device nLandmarks bytes or null.  result: device pointers, landmark1_out may be landmark1Dev (then a
+  // current frame appears in one pair only).  Nothing else synchronises the host.
+  void ransac2d2dBlocks(size_t cameraIndex, const void* blocks0Dev, int nFrames0, const void* blocks1Dev, int nFrames1,
+                        const std::vector<int32_t>& mf0, const std::vector<int32_t>& mf1, const int32_t* landmark0Dev,
+                        const int32_t* landmark1Dev, const uint8_t* addedDev, int nLandmarks,
+                        const std::vector<double>& rotHypotheses, const std::vector<uint8_t>& rotValid,
+                        const std::vector<double>& relHypotheses, const std::vector<uint8_t>& relValid, int nHyp,
+                        const okvfe_ransac2d2d_result_device& result, bool removeOutliers = true, double threshold = 9.0,
+                        void* stream = nullptr) {
+    if (cameraIndex >= cameras_.size())
+      throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "Camera index exceeds number of cameras.");
+    const size_t nPairs = mf0.size(), perPair = size_t(nHyp < 1 ? 0 : nHyp);
+    if (mf1.size() != nPairs || nHyp < 1 || rotHypotheses.size() != nPairs * perPair * 9 ||
+        relHypotheses.size() != nPairs * perPair * 12 || (!rotValid.empty() && rotValid.size() != nPairs * perPair) ||
+        (!relValid.empty() && relValid.size() != nPairs * perPair))
+      throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "ransac2d2dBlocks: one (mf0, mf1) and nHyp hypotheses (and flags) of both problems per pair");
+    std::lock_guard<std::mutex> lock(mutexes_[cameraIndex]);
+    if (!extractors_[cameraIndex].isCameraAware()) extractors_[cameraIndex].setCamera(cameras_[cameraIndex]);
+    Context& c = *contexts_[cameraIndex];
+    const size_t rotBytes = rotHypotheses.size() * sizeof(double), relBytes = relHypotheses.size() * sizeof(double);
+    uint8_t* d = uploadParts(cameraIndex, {{rotHypotheses.data(), rotBytes}, {relHypotheses.data(), relBytes},
+                                           {rotValid.data(), rotValid.size()}, {relValid.data(), relValid.size()}}, stream);
+    const int32_t cam = 0, none = 0;  // slot 0 of the camera's own context
+    c.check(okvfe_ransac2d2d_consensus_blocks_device(
+        c.get(), blocks0Dev, nFrames0, blocks1Dev, nFrames1, int32_t(nPairs), nPairs ? mf0.data() : &none,
+        nPairs ? mf1.data() : &none, 1, &cam, landmark0Dev, landmark1Dev, addedDev, nLandmarks,
+        reinterpret_cast<const double*>(d), rotValid.empty() ? nullptr : d + rotBytes + relBytes,
+        reinterpret_cast<const double*>(d + rotBytes), relValid.empty() ? nullptr : d + rotBytes + relBytes + rotValid.size(),
+        nHyp, threshold, removeOutliers ? 1 : 0, &result, stream));
+  }
   // Frontend::removeOutliers (Frontend.cpp:2152-2205) for nFrames frames of camera `cameraIndex`: T_WC one pose per
   // frame (T_WS T_SC as the caller's Transformation computes it); landmarkOutDev may be landmarkDev; keptDev: device
   // nFrames int32, the reference's return value per frame.  Nothing synchronises the host.
@@ -1146,12 +1185,16 @@ class HipFrontend {
     }
   };
   std::vector<HypothesisScratch> hyp_scratch_;  // per camera
-  // hypotheses, then the flags, into the camera's scratch buffer with asynchronous copies on `stream` (mutex held)
-  uint8_t* uploadHypotheses(size_t cameraIndex, const std::vector<double>& hypotheses, const std::vector<uint8_t>& hypValid,
-                            void* stream) {
+  // host arrays, one behind the other, into the camera's scratch buffer with asynchronous copies on `stream` (mutex held)
+  struct HostPart {
+    const void* p;
+    size_t bytes;
+  };
+  uint8_t* uploadParts(size_t cameraIndex, std::initializer_list<HostPart> parts, void* stream) {
     Context& c = *contexts_[cameraIndex];
     HypothesisScratch& hs = hyp_scratch_[cameraIndex];
-    const size_t hypBytes = hypotheses.size() * sizeof(double), bytes = hypBytes + hypValid.size();
+    size_t bytes = 0;
+    for (const HostPart& part : parts) bytes += part.bytes;
     if (bytes > hs.bytes) {
       if (hs.d) {
         c.check(okvfe_stream_synchronize(nullptr));
@@ -1164,9 +1207,18 @@ class HipFrontend {
       hs.bytes = bytes;
     }
     uint8_t* d = static_cast<uint8_t*>(hs.d);
-    if (hypBytes) c.check(okvfe_copy_to_device(d, hypotheses.data(), hypBytes, stream));
-    if (!hypValid.empty()) c.check(okvfe_copy_to_device(d + hypBytes, hypValid.data(), hypValid.size(), stream));
+    size_t at = 0;
+    for (const HostPart& part : parts) {
+      if (part.bytes) c.check(okvfe_copy_to_device(d + at, part.p, part.bytes, stream));
+      at += part.bytes;
+    }
     return d;
+  }
+  // hypotheses, then the flags
+  uint8_t* uploadHypotheses(size_t cameraIndex, const std::vector<double>& hypotheses, const std::vector<uint8_t>& hypValid,
+                            void* stream) {
+    return uploadParts(cameraIndex, {{hypotheses.data(), hypotheses.size() * sizeof(double)}, {hypValid.data(), hypValid.size()}},
+                       stream);
   }
   // the context matchStereoInsertBlocks / matchStereoRig run on: every camera of the rig in a slot of its own
   Context& rigContext() {
