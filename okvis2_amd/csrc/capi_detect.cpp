@@ -214,15 +214,28 @@ void layer_sort(okvfe_ctx* L, int n_images, hipStream_t s) {
 }
 // -> the selection kernel also prepared the extractor's per-keypoint inputs (describe_setup_dev.h): asked for by the
 // plan of a single-scale call that describes what it detects
-bool layer_select(okvfe_ctx* L, int n_images, hipStream_t s, const CallPlan& plan) {
-  const DescribeSetup setup{L->d_pattern, L->d_prm, L->d_rays_ptrs, L->d_jac_ptrs, L->d_kps_tmp, L->d_desc_tmp,
-                            L->d_valid_tmp, L->d_scales, L->live_images,
-                            plan.aware_extra_box > 0 ? (plan.aware_extra_box & 0xFF) : 0};
+// *final_slots: ... and its tail assigned the keypoints' final slots in d_kps / d_desc / d_count (DescribeSetup::kps_out):
+// the batched camera-aware route served by select_lazy_kernel
+bool layer_select(okvfe_ctx* L, int n_images, hipStream_t s, const CallPlan& plan, bool* final_slots) {
+  DescribeSetup setup{L->d_pattern, L->d_prm, L->d_rays_ptrs, L->d_jac_ptrs, L->d_kps_tmp, L->d_desc_tmp,
+                      L->d_valid_tmp, L->d_scales, L->live_images,
+                      plan.aware_extra_box > 0 ? (plan.aware_extra_box & 0xFF) : 0};
   const bool fuse = plan.fuse_setup && L->d_pattern && L->d_kps_tmp && L->d_prm;
-  return launch_select(L->d_scores, L->live_layout, L->w, L->h, n_images, L->d_cand, L->cand_cap, L->d_cand_count,
-                       L->cfg.uniformity_radius, L->cfg.max_keypoints, L->d_lut, L->d_occ, L->occ_image_bytes,
-                       L->occ_rows, L->occ_cols, L->d_kps_det, L->kp_cap, L->d_det_count, L->d_sort_ws, s,
-                       fuse ? &setup : nullptr, L->map_free_live ? L->live_images : nullptr);
+  static const bool generic_describe = lab_env("OKVFE_DESC_GENERIC") != nullptr;  // (launch_describe's A/B knob leaves the route)
+  *final_slots = fuse && plan.route == DescribeRoute::kAwareBatched && !generic_describe && L->d_kps && L->d_desc && L->d_count &&
+                 select_assigns_final_slots(L->cfg.uniformity_radius, L->cfg.max_keypoints, L->kp_cap, L->d_occ,
+                                            L->occ_image_bytes, L->occ_rows, L->occ_cols);
+  if (*final_slots) {
+    setup.kps_out = L->d_kps;
+    setup.desc_out = L->d_desc;
+    setup.count_out = L->d_count;
+  }
+  const bool done = launch_select(L->d_scores, L->live_layout, L->w, L->h, n_images, L->d_cand, L->cand_cap, L->d_cand_count,
+                                  L->cfg.uniformity_radius, L->cfg.max_keypoints, L->d_lut, L->d_occ, L->occ_image_bytes,
+                                  L->occ_rows, L->occ_cols, L->d_kps_det, L->kp_cap, L->d_det_count, L->d_sort_ws, s,
+                                  fuse ? &setup : nullptr, L->map_free_live ? L->live_images : nullptr);
+  *final_slots = *final_slots && done;
+  return done;
 }
 
 // ---- scale space (octaves > 0): the steps of layer l of parent context `ctx`, shared by the two schedules below -----
@@ -285,7 +298,8 @@ void scale_layer_sort(okvfe_ctx* ctx, int l, int n_images, hipStream_t s) {
 void scale_layer_keypoints(okvfe_ctx* ctx, int l, int n_images, hipStream_t s) {
   okvfe_ctx* ch = ctx->layers[l];
   if (!brisk_scale_space(ctx)) {
-    (void)layer_select(ch, n_images, s, CallPlan{});  // (a layer only detects: the parent context describes)
+    bool no_slots;
+    (void)layer_select(ch, n_images, s, CallPlan{}, &no_slots);  // (a layer only detects: the parent context describes)
     return;
   }
   const LayerNeighbours n = layer_neighbours(ctx, l);
@@ -418,11 +432,12 @@ okvfe_status detect_layers_staged(okvfe_ctx* ctx, const uint8_t* images_dev, int
 // K1..K4: score map + NMS, sort, uniformity selection, sub-pixel -> d_kps_det / d_det_count.
 // octaves > 0: the same per layer of the scale space (k_pyramid.hip), with the cross-layer maximum
 // test between NMS and selection and the merge into image coordinates at the end.
-// *setup_done (may be null): the selection launch also ran the extractor's set-up, as plan.fuse_setup asked.
+// *setup_done (may be null): the selection launch also ran the extractor's set-up, as plan.fuse_setup asked -- into the
+// *_tmp buffers (kSetupTmp) or, compacted, into the call's output buffers (kSetupFinal: DescribeSetup::kps_out).
 okvfe_status detect_stage(okvfe_ctx* ctx, const uint8_t* images_dev, int n_images, hipStream_t s, const CallPlan& plan,
-                          bool* setup_done) {
+                          SetupDone* setup_done) {
   okvfe_status st;
-  if (setup_done) *setup_done = false;
+  if (setup_done) *setup_done = kSetupNone;
   if (ctx->n_layers == 1) {
     TokenScope token;
     if (!plan.counters_cleared) {  // (cleared together with the parameter upload of the same call otherwise)
@@ -454,8 +469,9 @@ okvfe_status detect_stage(okvfe_ctx* ctx, const uint8_t* images_dev, int n_image
     }
     {
       StageTimer t(ctx, OKVFE_STAGE_SELECT, s);
-      const bool done = layer_select(ctx, n_images, s, plan);
-      if (setup_done) *setup_done = done;
+      bool final_slots;
+      const bool done = layer_select(ctx, n_images, s, plan, &final_slots);
+      if (setup_done) *setup_done = !done ? kSetupNone : (final_slots ? kSetupFinal : kSetupTmp);
     }
   } else {
     // (stage timers and the cross-context chaining of the heavy kernels belong to the one-stream schedule)
@@ -495,19 +511,30 @@ okvfe_status find_overflow(okvfe_ctx* ctx, int first, int n_images, int* bad, in
 // K6 and compaction + back-projection of the keypoints in d_kps_det, each one launch sequence without timers (the
 // batch flow brackets them in describe_stage; okvfe_compute issues them back to back)
 void run_describe(okvfe_ctx* ctx, const uint8_t* images_dev, int n_images, hipStream_t s, const CallPlan& plan,
-                  bool setup_done) {
+                  SetupDone setup_done) {
+  if (setup_done == kSetupFinal) {  // the survivors sit in their final slots: the descriptor kernel works in place
+    launch_describe(images_dev, ctx->w, ctx->h, n_images, ctx->d_pattern, ctx->d_prm, ctx->d_rays_ptrs, ctx->d_jac_ptrs,
+                    ctx->d_kps, ctx->kp_cap, ctx->d_count, nullptr, ctx->d_desc, nullptr, ctx->d_scales, s, true, plan.route,
+                    plan.wide_boxes, plan.aware_extra_box, true);
+    return;
+  }
   launch_describe(images_dev, ctx->w, ctx->h, n_images, ctx->d_pattern, ctx->d_prm, ctx->d_rays_ptrs, ctx->d_jac_ptrs,
                   ctx->d_kps_det, ctx->kp_cap, ctx->d_det_count, ctx->d_kps_tmp, ctx->d_desc_tmp, ctx->d_valid_tmp,
-                  ctx->d_scales, s, setup_done, plan.route, plan.wide_boxes, plan.aware_extra_box);
+                  ctx->d_scales, s, setup_done != kSetupNone, plan.route, plan.wide_boxes, plan.aware_extra_box);
 }
-void run_compact(okvfe_ctx* ctx, int n_images, hipStream_t s, const CallPlan& plan) {
+void run_compact(okvfe_ctx* ctx, int n_images, hipStream_t s, const CallPlan& plan, SetupDone setup_done) {
+  if (setup_done == kSetupFinal) {  // nothing to compact: the rays of the keypoints where they are
+    launch_backproject(n_images, ctx->d_cams, ctx->d_prm, ctx->d_kps, ctx->d_count, ctx->kp_cap, ctx->d_bp, ctx->d_bpv, s,
+                       plan.rt8);
+    return;
+  }
   launch_compact(n_images, ctx->d_cams, ctx->d_prm, ctx->d_kps_tmp, ctx->d_desc_tmp, ctx->d_valid_tmp, ctx->d_det_count,
                  ctx->kp_cap, ctx->d_kps, ctx->d_desc, ctx->d_bp, ctx->d_bpv, ctx->d_count, s, plan.rt8);
 }
 
 // K6 + compaction + back-projection of the keypoints detect_stage left in d_kps_det
 okvfe_status describe_stage(okvfe_ctx* ctx, const uint8_t* images_dev, int n_images, hipStream_t s, const CallPlan& plan,
-                            bool setup_done) {
+                            SetupDone setup_done) {
   TokenScope token;
   okvfe_status st = heavy_begin(ctx, s, 1, &token);
   if (st != OKVFE_OK) return st;
@@ -518,7 +545,7 @@ okvfe_status describe_stage(okvfe_ctx* ctx, const uint8_t* images_dev, int n_ima
   if ((st = heavy_end(ctx, s, 1, &token)) != OKVFE_OK) return st;
   {
     StageTimer t(ctx, OKVFE_STAGE_COMPACT, s);
-    run_compact(ctx, n_images, s, plan);
+    run_compact(ctx, n_images, s, plan, setup_done);
   }
   HIP_TRY(ctx, hipGetLastError());
   ctx->last_stream = s;
@@ -616,7 +643,7 @@ okvfe_status detect_describe_split(okvfe_ctx* ctx, const uint8_t* images_dev, in
   // (a context set to pipelined lanes splits only the calls that can stay un-joined; everything else runs unsplit)
   const int k = ctx->lanes_pipelined && !pipelined ? 1 : lanes_for_call(ctx, n_images);
   okvfe_status st;
-  bool setup_done = false;
+  SetupDone setup_done = kSetupNone;
   if (k <= 1) {
     st = detect_stage(ctx, images_dev, n_images, s, plan, &setup_done);
     if (st != OKVFE_OK) {
@@ -710,7 +737,7 @@ okvfe_status okvfe_describe_batch_device(okvfe_ctx* ctx, const uint8_t* images_d
   BatchFacts batch;
   okvfe_status st = upload_image_params(ctx, n_images, cam_ids, gravity_C, s, false, &batch);
   if (st != OKVFE_OK) return st;
-  return describe_stage(ctx, images_dev, n_images, s, make_call_plan(ctx, batch, images_dev, false), false);
+  return describe_stage(ctx, images_dev, n_images, s, make_call_plan(ctx, batch, images_dev, false), kSetupNone);
 }
 
 okvfe_status okvfe_detect_describe_batch_device(okvfe_ctx* ctx, const uint8_t* images_dev,
@@ -1097,8 +1124,8 @@ okvfe_status okvfe_compute(okvfe_ctx* ctx, const uint8_t* image, size_t stride, 
     HIP_TRY(ctx, hipMemcpyAsync(ctx->d_det_count, ctx->h_pinned + o_kp - 256, sizeof(int32_t), hipMemcpyHostToDevice, s));
     HIP_TRY(ctx, hipMemsetAsync(ctx->d_cand_count, 0, sizeof(int32_t), s));
   }
-  run_describe(ctx, ctx->d_img_stage, 1, s, plan, false);
-  run_compact(ctx, 1, s, plan);
+  run_describe(ctx, ctx->d_img_stage, 1, s, plan, kSetupNone);
+  run_compact(ctx, 1, s, plan, kSetupNone);
   HIP_TRY(ctx, hipGetLastError());
   ctx->last_n_images = 1;
   ctx->last_stream = s;

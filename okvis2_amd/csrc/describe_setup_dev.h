@@ -1,7 +1,9 @@
 // describe_setup_dev.h -- the per-keypoint preparation of the extractor (border test, scale index,
 // camera-aware matrix M), shared by describe_setup_kernel (k_describe.hip) and the tail of
 // select_lazy_kernel (k_select.hip), which runs it for the keypoints it has just emitted when
-// detection and description are one call (one launch and ~15 us per batch less).
+// detection and description are one call (one launch and ~15 us per batch less).  On the batched camera-aware route that
+// tail also assigns the keypoints' final slots: the set-up then decides validity completely and stores nothing itself
+// (SetupDeferred below).
 #pragma once
 #include "okvfe_internal.h"
 
@@ -209,10 +211,11 @@ __device__ __forceinline__ ExtraSampleParams extra_sample_params(const Pattern* 
   return ExtraSampleParams{pat->px[e], pat->py[e], pat->sigma_half[e], pat->box_scaling[e], pat->box_scaling2[e]};
 }
 
-// extra sample e of the keypoint at (kx, ky) under M -> bytes 24 + 4 e of its descriptor slot; false: box outside the image
+// extra sample e of the keypoint at (kx, ky) under M -> extras_out[e] (bytes 24 + 4 e of its descriptor slot, or where
+// the caller parks the samples until the slot is known); false: box outside the image
 __device__ __forceinline__ bool extra_sample_one(const ExtraSampleParams& sp, const uint8_t* __restrict__ im, int w,
                                                  int h, int extra_box, int e, const float M[4], float kx, float ky,
-                                                 uint8_t* __restrict__ slot_bytes) {
+                                                 int* __restrict__ extras_out, int stride = 1) {
   const float px = sp.px, py = sp.py, sg = sp.sigma_half;
   float a = M[0] * px, b2 = M[1] * py;  // (the sequence of sample_pos, k_describe_aware.hip)
   a = a + b2;
@@ -223,8 +226,63 @@ __device__ __forceinline__ bool extra_sample_one(const ExtraSampleParams& sp, co
   int v = 0;
   const bool ok = extra_box <= 4 ? extra_sample_value<4>(im, w, h, xf, yf, sg, sp.scaling, sp.scaling2, &v)
                                  : extra_sample_value<9>(im, w, h, xf, yf, sg, sp.scaling, sp.scaling2, &v);
-  OKVFE_TAIL_STORE(*reinterpret_cast<int*>(slot_bytes + 24 + 4 * e) = v);
+  OKVFE_TAIL_STORE(extras_out[e * stride] = v);
   return ok;
+}
+
+// sample position of a pattern point under M; ok = box inside the image (NaN-safe).  ONE definition for the descriptor
+// kernels (k_describe_aware.hip) and for the set-up's validity test below: separate multiplies and adds, these comparisons.
+__device__ __forceinline__ bool aware_sample_pos(float M0, float M1, float M2, float M3, float kx, float ky, float px,
+                                                 float py, float sg, int w, int h, float* xf, float* yf) {
+  float a = M0 * px;
+  float b = M1 * py;
+  a = a + b;
+  *xf = kx + a;
+  float c = M2 * px;
+  float d = M3 * py;
+  c = c + d;
+  *yf = ky + c;
+  const float x_1 = *xf - sg, x1 = *xf + sg, y_1 = *yf - sg, y1 = *yf + sg;
+  return (x_1 >= 0.0f && y_1 >= 0.0f && x1 < (float)(w - 1) && y1 < (float)(h - 1));
+}
+
+// describe_aware_kernel's own drop test, by the set-up thread: every sample box of the pattern points first ..
+// n_points - 1 (the kernel's 64 lanes) inside the image.  The trip count and every address are uniform over the
+// workgroup (no early exit), so the pattern's constants arrive as scalar loads.
+__device__ __forceinline__ bool first_pass_boxes_inside(const Pattern* __restrict__ pat, int first, int n_points,
+                                                        const float M[4], float kx, float ky, int w, int h) {
+  typedef const float __attribute__((address_space(4))) * cfloat_p;
+  const cfloat_p px = (cfloat_p)(uintptr_t)pat->px, py = (cfloat_p)(uintptr_t)pat->py;
+  const cfloat_p sg = (cfloat_p)(uintptr_t)pat->sigma_half;
+  bool ok = true;
+#pragma unroll 1
+  for (int p = first; p < n_points; ++p) {
+    float xf, yf;
+    ok &= aware_sample_pos(M[0], M[1], M[2], M[3], kx, ky, px[p], py[p], sg[p], w, h, &xf, &yf);
+  }
+  return ok;
+}
+
+// What describe_setup_one returns instead of storing when the caller assigns the keypoint's FINAL slot itself
+// (DescribeSetup::kps_out, the selection kernel's tail): validity decided completely -- the first-pass boxes included, so
+// that describe_aware_kernel has nothing left to drop; M, the patch geometry and the extra samples wait in memory of the
+// caller's (LDS: the selection kernel's tail has no register to spare for them across the samples and the fit).
+// Word j of a thread's area is kSetupParkStride words behind word j - 1 (the areas of a workgroup's threads interleave:
+// one base register, immediate offsets, no bank conflict).
+constexpr int kSetupParkInts = kAwareMaxExtra + 2;  // extra samples | g0 | g1 (bit 31, free in g1: "patch inside", private)
+constexpr int kSetupParkStride = 256;
+struct SetupDeferred {
+  bool valid;
+  int n_extra;    // samples parked
+  int* park;      // in: the workgroup's kSetupParkInts x kSetupParkStride words; a thread's word j = park[j * stride + thread]
+  float* park_m;  // in: likewise for M, four words per thread
+};
+// the thread's index into the parked words, opaque to the optimiser: an address formed from it is formed where it is used
+// (hoisted out of the caller's loop it would be one more register held across the sub-pixel fit and the samples)
+__device__ __forceinline__ int setup_park_lane() {
+  int t = (int)threadIdx.x;
+  asm volatile("" : "+v"(t));
+  return t;
 }
 
 // What describe_setup_one needs that is the same for every keypoint of an image: the image's launch parameters, its
@@ -253,9 +311,10 @@ __device__ __forceinline__ DescribeImageParams describe_image_params(const Descr
 
 // One keypoint: valid byte (bit 0 = inside the rim and a usable ray, bits 1..6 = scale index of the
 // scale-invariant extractor), M into the first 16 bytes of the (not yet written) descriptor slot, the
-// record into kps_tmp.
+// record into kps_tmp.  later != null (camera-aware fixed-scale calls only): nothing is stored, see SetupDeferred.
 __device__ __forceinline__ void describe_setup_one(const DescribeSetup& ds, const DescribeImageParams& dp, int w, int h,
-                                                   int img, size_t slot, const okvfe_keypoint& kp) {
+                                                   int img, size_t slot, const okvfe_keypoint& kp,
+                                                   SetupDeferred* later = nullptr) {
   const ImageParams& ip = dp.ip;
   int scale = 0;
   if (ds.scales) {
@@ -274,13 +333,21 @@ __device__ __forceinline__ void describe_setup_one(const DescribeSetup& ds, cons
     const float dir[3] = {ip.dir[0], ip.dir[1], ip.dir[2]};
     valid = camera_aware_matrix(dp.rays, dp.jac, w, ip.fu, dir, kp.x, kp.y, M);
   }
-  OKVFE_TAIL_STORE(*reinterpret_cast<float4*>(ds.desc_tmp + slot * OKVFE_DESC_BYTES) = make_float4(M[0], M[1], M[2], M[3]));
+  if (later) {
+    float* pm = later->park_m + setup_park_lane();
+    for (int j = 0; j < 4; ++j) pm[j * kSetupParkStride] = M[j];
+  } else {
+    OKVFE_TAIL_STORE(*reinterpret_cast<float4*>(ds.desc_tmp + slot * OKVFE_DESC_BYTES) = make_float4(M[0], M[1], M[2], M[3]));
+  }
   if (ip.mode == kCameraAware && !ds.scales) {
     // patch geometry for describe_aware_kernel (k_describe_aware.hip), bytes 16..23 of the slot: a superset of every
     // sample box under M -- |M p|_x <= |row_x(M)| |p|, boxes are not scaled by M, a box spans at most half a pixel
     // beyond x -+ sigma_half (the 0.75 leaves a quarter pixel for the float rounding of the positions) -- clipped to
     // the image (boxes that leave it drop the keypoint).  Class 0 / 1: rows of 64 / 80 bytes in LDS; 3: neither.
     int g0 = 0, g1 = 3 << 29;
+    // the conservative patch bound lies strictly inside the image: so does every sample box (a subset of the exact test,
+    // DESIGN.md "final slots"), and first_pass_boxes_inside need not walk the points
+    bool patch_inside = false;
     if (valid) {
       const float reach = dp.reach;
       float nx = M[0] * M[0], t = M[1] * M[1];
@@ -290,6 +357,7 @@ __device__ __forceinline__ void describe_setup_one(const DescribeSetup& ds, cons
       ny = sqrtf(ny + t) * 1.001f;
       const float ex = fmaxf(nx, 1.0f) * reach + 0.75f, ey = fmaxf(ny, 1.0f) * reach + 0.75f;
       if (ex < 1024.0f && ey < 1024.0f) {  // (false for NaN)
+        patch_inside = kp.x - ex >= 0.0f && kp.x + ex < (float)(w - 1) && kp.y - ey >= 0.0f && kp.y + ey < (float)(h - 1);
         int bx0 = (int)floorf(kp.x - ex), bx1 = (int)ceilf(kp.x + ex);
         int by0 = (int)floorf(kp.y - ey), by1 = (int)ceilf(kp.y + ey);
         bx0 = bx0 < 0 ? 0 : bx0;
@@ -307,18 +375,37 @@ __device__ __forceinline__ void describe_setup_one(const DescribeSetup& ds, cons
         }
       }
     }
-    OKVFE_TAIL_STORE(*reinterpret_cast<int2*>(ds.desc_tmp + slot * OKVFE_DESC_BYTES + 16) = make_int2(g0, g1));
+    if (later) {
+      int* pk = later->park + setup_park_lane();
+      pk[kAwareMaxExtra * kSetupParkStride] = g0;
+      pk[(kAwareMaxExtra + 1) * kSetupParkStride] = g1 | (patch_inside ? (int)0x80000000u : 0);
+    } else {
+      OKVFE_TAIL_STORE(*reinterpret_cast<int2*>(ds.desc_tmp + slot * OKVFE_DESC_BYTES + 16) = make_int2(g0, g1));
+    }
     // ... and the samples beyond its 64 lanes, bytes 24.. of the slot; a box outside the image drops the keypoint
     // (extra_box == 0: the pattern has none, or describe_kernel serves the call)
     if (valid && extras) {
       const int extra = dp.extra;  // 1 .. kAwareMaxExtra (host-checked)
+      int* extras_out = later ? later->park + setup_park_lane() : reinterpret_cast<int*>(ds.desc_tmp + slot * OKVFE_DESC_BYTES + 24);
       for (int e = 0; e < extra && valid; ++e) {
         const ExtraSampleParams next = extra_sample_params(ds.pat, e + 1 < extra ? e + 1 : e);
-        valid = extra_sample_one(sp, ds.images + (size_t)img * w * h, w, h, ds.extra_box, e, M, kp.x, kp.y,
-                                 ds.desc_tmp + slot * OKVFE_DESC_BYTES);
+        valid = extra_sample_one(sp, ds.images + (size_t)img * w * h, w, h, ds.extra_box, e, M, kp.x, kp.y, extras_out,
+                                 later ? kSetupParkStride : 1);
         sp = next;
       }
     }
+    if (later) {
+      const int first = dp.extra > 0 ? dp.extra : 0;
+      if (valid && later->park[(kAwareMaxExtra + 1) * kSetupParkStride + setup_park_lane()] >= 0)
+        valid = first_pass_boxes_inside(ds.pat, first, dp.extra + 64, M, kp.x, kp.y, w, h);
+      later->valid = valid;
+      later->n_extra = extras ? dp.extra : 0;
+      return;
+    }
+  }
+  if (later) {  // (not reached: final slots are asked for on camera-aware fixed-scale calls only)
+    later->valid = false;
+    return;
   }
   OKVFE_TAIL_STORE(ds.valid_tmp[slot] = (uint8_t)((valid ? 1 : 0) | (scale << 1)));
   OKVFE_TAIL_STORE(ds.kps_tmp[slot] = kp);  // the record travels on from here; describe_kernel only rewrites the angle

@@ -766,6 +766,8 @@ __global__ __launch_bounds__(64 * kDescWaves) __attribute__((amdgpu_waves_per_eu
 }
 
 // ---- compaction + back-projection -----------------------------------------------------------
+// (fused calls on the batched camera-aware route skip the compaction -- the selection tail has assigned final slots,
+// DescribeSetup::kps_out -- and run backproject_kernel below under the same stage timer)
 // kRT8: the back-projection also knows OKVFE_DIST_RADTAN8 (launched only for calls that use such a slot)
 template <bool kRT8>
 __global__ __launch_bounds__(256) void compact_kernel(
@@ -816,6 +818,29 @@ __global__ __launch_bounds__(256) void compact_kernel(
   if (tid == 0) kp_count[img] = base_s;
 }
 
+// Back-projection alone, for calls whose selection tail assigned final slots (DescribeSetup::kps_out): one thread per
+// surviving keypoint, no barrier, the same cam::backproject as compact_kernel.
+template <bool kRT8>
+__global__ __launch_bounds__(256) void backproject_kernel(const DeviceCamera* __restrict__ cams,
+                                                          const ImageParams* __restrict__ prm,
+                                                          const okvfe_keypoint* __restrict__ kps,
+                                                          const int32_t* __restrict__ kp_count, int kp_cap,
+                                                          double* __restrict__ bp, uint8_t* __restrict__ bpv) {
+  const int img = blockIdx.y;
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  if (k >= kp_count[img]) return;
+  const size_t at = (size_t)img * kp_cap + k;
+  const int cam = prm[img].cam;
+  const float x = kps[at].x, y = kps[at].y;
+  double dir[3] = {0.0, 0.0, 0.0};
+  bool ok = false;
+  if (cam >= 0 && cams[cam].fu > 0.0) ok = cam::backproject<kRT8>(cams[cam], (double)x, (double)y, dir);
+  bp[at * 3 + 0] = dir[0];
+  bp[at * 3 + 1] = dir[1];
+  bp[at * 3 + 2] = dir[2];
+  bpv[at] = ok ? 1 : 0;
+}
+
 }  // namespace
 
 void launch_describe(const uint8_t* img, int w, int h, int n_images, const Pattern* pat,
@@ -823,7 +848,7 @@ void launch_describe(const uint8_t* img, int w, int h, int n_images, const Patte
                      const okvfe_keypoint* kps_in, int kp_cap, const int32_t* kp_count_in,
                      okvfe_keypoint* kps_tmp, uint8_t* desc_tmp, uint8_t* valid_tmp,
                      const PatternScales* scales, hipStream_t stream, bool setup_done, DescribeRoute route,
-                     bool wide_boxes, int aware_extra_box) {
+                     bool wide_boxes, int aware_extra_box, bool final_slots) {
   if (n_images <= 0) return;
   // The route is the caller's (describe_route, capi_detect.cpp).  Two A/B knobs are applied to it here:
   // OKVFE_DESC_GENERIC sends a call to the all-modes form (its WIDE instantiation for a pattern of box class 1 outside
@@ -854,7 +879,9 @@ void launch_describe(const uint8_t* img, int w, int h, int n_images, const Patte
     case DescribeRoute::kAwareBatched:
       // the production mode on cameras whose patches fit the two LDS classes (extra samples in batches, patch geometry
       // from the set-up thread, compile-time row pitches); the set-up threads have left the extra samples in the slots
-      launch_describe_aware(img, w, h, n_images, pat, kps_in, kp_cap, kp_count_in, desc_tmp, valid_tmp, wide_boxes, stream);
+      // (final_slots: the selection tail has compacted; the kernel works in place on the output buffers)
+      launch_describe_aware(img, w, h, n_images, pat, kps_in, kp_cap, kp_count_in, desc_tmp, valid_tmp, wide_boxes, stream,
+                            final_slots && setup_done);
       break;
     case DescribeRoute::kRot:
       // upright / gradient-orientation calls (the BRISK scale-space path, callers without a camera) on the same box sums
@@ -893,6 +920,14 @@ void launch_compact(int n_images, const DeviceCamera* cams, const ImageParams* p
   if (n_images <= 0) return;
   hipLaunchKernelGGL(rt8 ? compact_kernel<true> : compact_kernel<false>, dim3(n_images), dim3(256), 0, stream, cams,
                      prm, kps_tmp, desc_tmp, valid_tmp, kp_count_in, kp_cap, kps, desc, bp, bpv, kp_count);
+}
+
+void launch_backproject(int n_images, const DeviceCamera* cams, const ImageParams* prm, const okvfe_keypoint* kps,
+                        const int32_t* kp_count, int kp_cap, double* bp, uint8_t* bpv, hipStream_t stream, bool rt8) {
+  if (n_images <= 0) return;
+  const dim3 grid((kp_cap + 255) / 256, n_images);
+  hipLaunchKernelGGL(rt8 ? backproject_kernel<true> : backproject_kernel<false>, grid, dim3(256), 0, stream, cams, prm, kps,
+                     kp_count, kp_cap, bp, bpv);
 }
 
 }  // namespace okvfe

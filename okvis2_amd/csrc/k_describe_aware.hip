@@ -25,6 +25,13 @@
 //     Patches of neither class (wide-angle rims) are sampled straight from the image by plain loops -- correct, slow,
 //     and rare on the cameras this kernel is launched for (capi_context.cpp: cam_slow).
 //
+//   * IN PLACE ON THE SURVIVORS (template parameter FINAL: fused calls whose selection ran in select_lazy_kernel).  The
+//     set-up thread runs this kernel's own drop test as well (first_pass_boxes_inside, describe_setup_dev.h: the same
+//     aware_sample_pos), so the selection tail knows every keypoint's fate, compacts, and hands over the call's OUTPUT
+//     buffers: a wave meets no dropped slot, keypoints are dealt to waves by survivor index, the descriptor goes over the
+//     slot's set-up record, and neither a valid byte is read or written nor a compaction pass needed.  Every other caller
+//     (compute-only calls, select_list_kernel, describe_setup_kernel) keeps the *_tmp form, FINAL = false.
+//
 // Bit-exact to describe_kernel and to the oracle: the float set-up and the integer sums are the same operation
 // sequences (published BRISK smoothedIntensity with sub-pixel rim weights).
 #include "describe_setup_dev.h"
@@ -266,24 +273,12 @@ __device__ __forceinline__ int box_mean_plain(const uint8_t* __restrict__ im, in
   return div_nonneg_rcp(ret + scaling2 / 2, scaling2, rcp2);
 }
 
-// sample position of a pattern point under M; ok = box inside the image (NaN-safe)
-__device__ __forceinline__ bool sample_pos(float M0, float M1, float M2, float M3, float kx, float ky, float px,
-                                           float py, float sg, int w, int h, float* xf, float* yf) {
-  float a = M0 * px;
-  float b = M1 * py;
-  a = a + b;
-  *xf = kx + a;
-  float c = M2 * px;
-  float d = M3 * py;
-  c = c + d;
-  *yf = ky + c;
-  const float x_1 = *xf - sg, x1 = *xf + sg, y_1 = *yf - sg, y1 = *yf + sg;
-  return (x_1 >= 0.0f && y_1 >= 0.0f && x1 < (float)(w - 1) && y1 < (float)(h - 1));
-}
-
 // One wave per keypoint at a time, lane l = pattern point extra + l; 4 waves per workgroup, `tiles` workgroups per
 // image (all on one XCD), a wave walks the image's keypoints wave, wave + 4 * tiles, ...
-template <bool WIDE>
+// FINAL: the selection kernel's tail has decided validity completely and compacted (DescribeSetup::kps_out,
+// describe_setup_dev.h): kps_in / kp_count_in / desc_tmp are the call's OUTPUT buffers, every slot below the count is a
+// survivor whose descriptor goes over its own set-up record, and nobody is told about validity (valid_tmp is null).
+template <bool WIDE, bool FINAL>
 __global__ __launch_bounds__(64 * kAwWaves) __attribute__((amdgpu_waves_per_eu(WIDE ? 5 : 6, 8))) void describe_aware_kernel(
     const uint8_t* __restrict__ images, int w, int h, const Pattern* __restrict__ pat,
     const okvfe_keypoint* __restrict__ kps_in, int kp_cap, const int32_t* __restrict__ kp_count_in,
@@ -335,7 +330,7 @@ __global__ __launch_bounds__(64 * kAwWaves) __attribute__((amdgpu_waves_per_eu(W
     nxt_M3 = pm[3];
     nxt_g0 = ((cint_p)pm)[4];
     nxt_g1 = ((cint_p)pm)[5];
-    nxt_valid = (int)((cbyte_p)(uintptr_t)valid_tmp)[sl];
+    if (!FINAL) nxt_valid = (int)((cbyte_p)(uintptr_t)valid_tmp)[sl];
   };
   fetch(k_first < kp_cap ? k_first : kp_cap - 1);  // (a slot past the image's count holds stale bytes: read, never used)
   fill_box_masks<WIDE>(box_masks, threadIdx.x, 64 * kAwWaves);
@@ -371,7 +366,7 @@ __global__ __launch_bounds__(64 * kAwWaves) __attribute__((amdgpu_waves_per_eu(W
       const float kx = unif(nxt_x), ky = unif(nxt_y);
       const float M0 = unif(nxt_M0), M1 = unif(nxt_M1), M2 = unif(nxt_M2), M3 = unif(nxt_M3);
       const int g0 = __builtin_amdgcn_readfirstlane(nxt_g0), g1 = __builtin_amdgcn_readfirstlane(nxt_g1);
-      bool valid = (__builtin_amdgcn_readfirstlane(nxt_valid) & 1) != 0;
+      bool valid = FINAL || (__builtin_amdgcn_readfirstlane(nxt_valid) & 1) != 0;
       if (k + k_step < n) fetch(k + k_step);  // scalar branch
       if (valid) {
         const int x0 = (g1 & 0x3FF) << 2, y0 = (g1 >> 10) & 0xFFF, ph = (g1 >> 22) & 0x7F, cls = (g1 >> 29) & 3;
@@ -395,8 +390,8 @@ __global__ __launch_bounds__(64 * kAwWaves) __attribute__((amdgpu_waves_per_eu(W
         int xv = 0;
         if (lane < extra) xv = *reinterpret_cast<const int*>(desc_tmp + slot * OKVFE_DESC_BYTES + 24 + 4 * lane);
         float xf, yf;
-        const bool ok = sample_pos(M0, M1, M2, M3, kx, ky, px, py, sg, w, h, &xf, &yf);
-        valid = __all(ok || !active);
+        const bool ok = aware_sample_pos(M0, M1, M2, M3, kx, ky, px, py, sg, w, h, &xf, &yf);
+        if (!FINAL) valid = __all(ok || !active);  // (FINAL: first_pass_boxes_inside has run this very test)
         // (the loads are waited for even when the keypoint is dropped: the next keypoint's may not overtake them)
         int v = 0;
 #ifdef OKVFE_LAB
@@ -448,7 +443,7 @@ __global__ __launch_bounds__(64 * kAwWaves) __attribute__((amdgpu_waves_per_eu(W
           }
         }
       }
-      if (lane == 0) valid_tmp[slot] = valid ? 1 : 0;
+      if (!FINAL && lane == 0) valid_tmp[slot] = valid ? 1 : 0;
       __builtin_amdgcn_wave_barrier();  // vals[] / the patch are rewritten for the next keypoint
 #ifdef OKVFE_LAB
       {
@@ -598,12 +593,12 @@ __global__ __launch_bounds__(64 * kAwWaves) __attribute__((amdgpu_waves_per_eu(5
       // all samples under M -> vals[]; false: a box leaves the image
       auto sample_all = [&](float M0, float M1, float M2, float M3) -> bool {
         float xf, yf;
-        const bool ok = sample_pos(M0, M1, M2, M3, kx, ky, px, py, sg, w, h, &xf, &yf);
+        const bool ok = aware_sample_pos(M0, M1, M2, M3, kx, ky, px, py, sg, w, h, &xf, &yf);
         const int l2 = active2 ? lane : 0;
         float xf2 = 0.f, yf2 = 0.f;
         const float sg2 = ex_f[2][l2];
         bool ok2 = true;
-        if (extra > 0) ok2 = sample_pos(M0, M1, M2, M3, kx, ky, ex_f[0][l2], ex_f[1][l2], sg2, w, h, &xf2, &yf2) || !active2;
+        if (extra > 0) ok2 = aware_sample_pos(M0, M1, M2, M3, kx, ky, ex_f[0][l2], ex_f[1][l2], sg2, w, h, &xf2, &yf2) || !active2;
         const bool all_ok = __all((ok || !active) && ok2);
         if (!staged) {  // (the loads are waited for even when the keypoint is dropped: the next one's may not overtake them)
           __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the staged rows have landed in LDS
@@ -747,17 +742,20 @@ void launch_describe_rot(const uint8_t* img, int w, int h, int n_images, const P
 
 void launch_describe_aware(const uint8_t* img, int w, int h, int n_images, const Pattern* pat,
                            const okvfe_keypoint* kps_in, int kp_cap, const int32_t* kp_count_in, uint8_t* desc_tmp,
-                           uint8_t* valid_tmp, bool wide_boxes, hipStream_t stream) {
+                           uint8_t* valid_tmp, bool wide_boxes, hipStream_t stream, bool final_slots) {
   if (n_images <= 0) return;
   int tiles = (kp_cap + kAwWaves - 1) / kAwWaves;  // workgroups per image
   if (tiles > 16) tiles = 16;
   const uint32_t inv_tiles = (uint32_t)((0x100000000ull + (uint64_t)tiles - 1) / (uint64_t)tiles);
-  if (wide_boxes)
-    hipLaunchKernelGGL((describe_aware_kernel<true>), dim3(tiles * n_images), dim3(64 * kAwWaves), 0, stream, img, w, h,
-                       pat, kps_in, kp_cap, kp_count_in, desc_tmp, valid_tmp, n_images, tiles, inv_tiles);
-  else
-    hipLaunchKernelGGL((describe_aware_kernel<false>), dim3(tiles * n_images), dim3(64 * kAwWaves), 0, stream, img, w, h,
-                       pat, kps_in, kp_cap, kp_count_in, desc_tmp, valid_tmp, n_images, tiles, inv_tiles);
+#define OKVFE_AWARE_LAUNCH(WIDE, FINAL)                                                                                  \
+  hipLaunchKernelGGL((describe_aware_kernel<WIDE, FINAL>), dim3(tiles * n_images), dim3(64 * kAwWaves), 0, stream, img, w, \
+                     h, pat, kps_in, kp_cap, kp_count_in, desc_tmp, valid_tmp, n_images, tiles, inv_tiles)
+  if (wide_boxes) {
+    if (final_slots) OKVFE_AWARE_LAUNCH(true, true); else OKVFE_AWARE_LAUNCH(true, false);
+  } else {
+    if (final_slots) OKVFE_AWARE_LAUNCH(false, true); else OKVFE_AWARE_LAUNCH(false, false);
+  }
+#undef OKVFE_AWARE_LAUNCH
 }
 
 }  // namespace okvfe

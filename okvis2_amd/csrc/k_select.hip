@@ -31,6 +31,14 @@
 // measured and not kept).  What is the same for every keypoint of an image
 // (ImageParams, the camera's map pointers, border / reach / point count of the pattern) is loaded at kernel start,
 // before the first store, as scalar loads nothing waits for (describe_image_params, describe_setup_dev.h).
+// FINAL SLOTS (fused calls on the batched camera-aware route, select_lazy_kernel only; select_list_kernel keeps the
+// *_tmp hand-over: its LDS has no idle 13 words per thread in the tail): the set-up decides validity completely --
+// border, ray, extra samples and the sample boxes of describe_aware_kernel's 64 lanes -- so the tail counts the survivors
+// per pass of 256 (ballot, four wave counts in LDS, one LDS barrier) and writes record, M, patch geometry and extra
+// samples to the keypoint's final slot of d_kps / d_desc and the number valid to d_count; d_kps_det / d_det_count are
+// written as before.  describe_aware_kernel then works in place on the survivors and backproject_kernel (k_describe.hip)
+// stands in for compact_kernel: 968 + 761 + 84 -> 910 + 753 + 37 us per 6144 EuRoC images, 772 -> 794 k stereo-frames/s
+// (profiles/compact_before_describe.txt).  Resources unchanged: 80 VGPRs, 12 bytes of scratch per lane.
 #include <mutex>
 #include "describe_setup_dev.h"
 #include <type_traits>
@@ -41,11 +49,13 @@ namespace okvfe {
 namespace {
 
 // ---- K4 of the three lazy-occupancy kernels: sub-pixel refinement and emission of kept keypoint i (one lane each);
-// dp = the image's parameters, loaded once at kernel start ----
-__device__ __forceinline__ void refine_emit(const int32_t* __restrict__ scores, const ScoreLayout& layout, int w, int h,
-                                            int img, const uint8_t* __restrict__ images, const DescribeSetup& setup,
-                                            const DescribeImageParams& dp, okvfe_keypoint* __restrict__ out, int i,
-                                            size_t slot, int u, int v, int32_t score) {
+// dp = the image's parameters, loaded once at kernel start.  later != null (final slots, DescribeSetup::kps_out): the
+// set-up stores nothing and returns its results there; the record is returned for the caller to place ----
+__device__ __forceinline__ okvfe_keypoint refine_emit(const int32_t* __restrict__ scores, const ScoreLayout& layout, int w,
+                                                      int h, int img, const uint8_t* __restrict__ images,
+                                                      const DescribeSetup& setup, const DescribeImageParams& dp,
+                                                      okvfe_keypoint* __restrict__ out, int i, size_t slot, int u, int v,
+                                                      int32_t score, SetupDeferred* later = nullptr) {
   // (u, v, score): pixel position and exact score, which the caller has read back from the record the acceptance left in
   // out[i] -- three values, not the record's seven words, stay live across the nine scores
   int32_t patch[9];
@@ -72,7 +82,8 @@ __device__ __forceinline__ void refine_emit(const int32_t* __restrict__ scores, 
   OKVFE_TAIL_STORE(out[i] = kp);
   // detection and description in one call: the extractor's per-keypoint preparation right here
   // (describe_setup_dev.h) instead of a launch of its own
-  if (setup.pat) describe_setup_one(setup, dp, w, h, img, slot, kp);
+  if (setup.pat) describe_setup_one(setup, dp, w, h, img, slot, kp, later);
+  return kp;
 }
 
 // ---- lazy-occupancy selection: no grid, one workgroup of 4 waves per image ----------------------
@@ -1074,12 +1085,81 @@ __global__ __launch_bounds__(kLazyThreads) __attribute__((amdgpu_waves_per_eu(OK
 #ifdef OKVFE_LAB
   t_blocks = __builtin_amdgcn_s_memrealtime();
 #endif
-  if (!(kSelectOff & 1))
+  if (setup.kps_out) {  // block-uniform
+    // FINAL SLOTS.  The set-up decides validity completely, so the survivors can be counted here, in order, and go
+    // straight to the call's output buffers: every thread runs ceil(kept / 256) passes under a predicate; per pass a
+    // ballot of the valid lanes, four wave counts in LDS (double-buffered by pass parity: one LDS barrier per pass), and
+    // a valid keypoint's index = running base + valid lanes before it.  Pass p holds only indices below those of pass
+    // p + 1, so the order of d_kps_det is kept.  The extra samples and the patch geometry are produced before validity is
+    // final, and so are M and the score: they wait in the thread's eight words of the survivor buffer, its one of the
+    // partial sums behind it and its four of the weight table -- all idle in the tail -- so that no register is held for
+    // them across the samples and the fit.
+    static_assert(kLazyThreads == kSetupParkStride && kLazyThreads * kSetupParkInts * 4 <= kLazyBlockMax * 8 &&
+                      kLazyThreads * 16 <= kLazyTabBytes,
+                  "parked set-up results in the survivor buffer and the weight table");
+    int* park_all = reinterpret_cast<int*>(surv);  // (its word kSetupParkInts, the score, is the thread's word of `part`)
+    int base = 0;
+    if (!(kSelectOff & 1))
+      for (int i0 = 0, par = 0; i0 < kept; i0 += kLazyThreads, par ^= 1) {
+        const int i = i0 + tid;
+        SetupDeferred r;
+        r.valid = false;
+        r.n_extra = 0;
+        r.park = park_all;
+        r.park_m = tab;
+        float kx = 0.0f, ky = 0.0f;
+        if (i < kept) {
+          const okvfe_keypoint rec = out[i];
+          park_all[kSetupParkInts * kSetupParkStride + setup_park_lane()] = rec.class_id;
+          const okvfe_keypoint kp =
+              refine_emit(scores, layout, w, h, img, images, setup, dp, out, i, 0, (int)rec.x, (int)rec.y, rec.class_id, &r);
+          kx = kp.x;
+          ky = kp.y;
+        }
+        const uint64_t b = __ballot(r.valid);
+        if (lane == 0) s_surv[par][wave] = __popcll(b);
+        lds_barrier();
+        const int c0 = s_surv[par][0], c1 = s_surv[par][1], c2 = s_surv[par][2], c3 = s_surv[par][3];
+        if (r.valid) {
+          const int pos = base + (wave > 0 ? c0 : 0) + (wave > 1 ? c1 : 0) + (wave > 2 ? c2 : 0) +
+                          (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
+          const size_t at = (size_t)img * kp_cap + pos;
+          const int* park = park_all + setup_park_lane();
+          const float* park_m = tab + setup_park_lane();
+          uint8_t* sl = setup.desc_out + at * OKVFE_DESC_BYTES;
+          okvfe_keypoint kp;  // the record refine_emit left in d_kps_det
+          kp.x = kx;
+          kp.y = ky;
+          kp.size = 12.0f;
+          kp.angle = -1.0f;
+          kp.response = (float)park[kSetupParkInts * kSetupParkStride];
+          kp.octave = 0;
+          kp.class_id = -1;
+          OKVFE_TAIL_STORE(setup.kps_out[at] = kp);
+          OKVFE_TAIL_STORE(*reinterpret_cast<float4*>(sl) =
+                               make_float4(park_m[0], park_m[kSetupParkStride], park_m[2 * kSetupParkStride],
+                                           park_m[3 * kSetupParkStride]));
+          OKVFE_TAIL_STORE(*reinterpret_cast<int2*>(sl + 16) =
+                               make_int2(park[kAwareMaxExtra * kSetupParkStride],
+                                         park[(kAwareMaxExtra + 1) * kSetupParkStride] & 0x7FFFFFFF));
+          // (all six words of the slot, whatever the pattern's number of samples: describe_aware_kernel reads the first
+          // n_extra of them and writes the descriptor over all)
+          static_assert(kAwareMaxExtra == 6, "the slot's words behind M and the geometry");
+          OKVFE_TAIL_STORE(*reinterpret_cast<int2*>(sl + 24) = make_int2(park[0], park[kSetupParkStride]));
+          OKVFE_TAIL_STORE(*reinterpret_cast<int4*>(sl + 32) =
+                               make_int4(park[2 * kSetupParkStride], park[3 * kSetupParkStride],
+                                         park[4 * kSetupParkStride], park[5 * kSetupParkStride]));
+        }
+        base += c0 + c1 + c2 + c3;
+      }
+    if (tid == 0) setup.count_out[img] = base;
+  } else if (!(kSelectOff & 1)) {
     for (int i = tid; i < kept; i += kLazyThreads) {
       const okvfe_keypoint kp = out[i];
       refine_emit(scores, layout, w, h, img, images, setup, dp, out, i, (size_t)img * kp_cap + i, (int)kp.x, (int)kp.y,
                   kp.class_id);
     }
+  }
   if (tid == 0) kp_count[img] = kept;
 #ifdef OKVFE_LAB
   __syncthreads();
@@ -1420,6 +1500,10 @@ bool select_recomputes_scores(float radius, int max_kpts, int kp_cap, const uint
                               int occ_rows, int occ_cols) {
   const LazyPlan p = lazy_plan(radius, max_kpts, kp_cap, occupancy, occ_image_bytes, occ_rows, occ_cols);
   return p.array || p.list;
+}
+bool select_assigns_final_slots(float radius, int max_kpts, int kp_cap, const uint8_t* occupancy, size_t occ_image_bytes,
+                                int occ_rows, int occ_cols) {
+  return lazy_plan(radius, max_kpts, kp_cap, occupancy, occ_image_bytes, occ_rows, occ_cols).array;
 }
 // true: launch_select orders the candidates itself for this configuration -- no launch_sort before it
 bool select_sorts_candidates(float radius, int max_kpts, int kp_cap, const uint8_t* occupancy, size_t occ_image_bytes,

@@ -36,6 +36,10 @@ struct CallPlan {  // (the default is a detect-only call's: nothing fused, no ba
   bool fuse_setup = false;        // the call describes what it detects: the set-up rides in the selection kernel
   bool counters_cleared = false;  // BatchFacts::counters_cleared
 };
+// What a call's selection launch did for its extractor: nothing (describe_setup_kernel runs), the per-keypoint set-up into
+// the *_tmp buffers, or the set-up with final slots assigned in d_kps / d_desc / d_count (DescribeSetup::kps_out: the
+// descriptor kernel works in place and a back-projection kernel stands in for the compaction pass).
+enum SetupDone : int { kSetupNone = 0, kSetupTmp = 1, kSetupFinal = 2 };
 
 struct okvfe_ctx {
   okvfe_config cfg{};

@@ -354,6 +354,14 @@ struct DescribeSetup {  // pat == nullptr: not requested
   // (4 or 9); 0 = not wanted (the call will run describe_kernel)
   const uint8_t* images = nullptr;
   int extra_box = 0;
+  // FINAL SLOTS (set for a fused call on the batched camera-aware route whose selection runs in select_lazy_kernel,
+  // null otherwise): the selection tail decides validity completely, counts the survivors in order and writes each one's
+  // record to kps_out and its M / patch geometry / extra samples to its slot of desc_out -- the call's output buffers --
+  // and the number valid to count_out; describe_aware_kernel<.., true> then works in place and no compaction pass runs.
+  // kps_tmp / desc_tmp / valid_tmp stay unwritten.
+  okvfe_keypoint* kps_out = nullptr;
+  uint8_t* desc_out = nullptr;
+  int32_t* count_out = nullptr;
 };
 constexpr int kAwareMaxExtra = 6;  // ints that fit the descriptor slot behind M (16 B) and the patch geometry (8 B)
 // cells of the occupancy grid of a w x h image at a uniformity radius (> 0): 15 cells per radius, a stamp's reach of
@@ -380,6 +388,10 @@ bool launch_select(const int32_t* score, ScoreLayout layout, int w, int h, int n
                    const uint8_t* images = nullptr);  // images != null: map-free call, see select_recomputes_scores
 bool select_recomputes_scores(float radius, int max_kpts, int kp_cap, const uint8_t* occupancy, size_t occ_image_bytes,
                               int occ_rows, int occ_cols);
+// true: launch_select runs select_lazy_kernel for this configuration, whose tail can assign final slots
+// (DescribeSetup::kps_out); select_list_kernel and the grid kernels keep the *_tmp hand-over
+bool select_assigns_final_slots(float radius, int max_kpts, int kp_cap, const uint8_t* occupancy, size_t occ_image_bytes,
+                                int occ_rows, int occ_cols);
 // Which descriptor kernel serves a call, one value per form launch_describe can launch: describe_aware_kernel (every
 // image camera-aware, extra samples batched), describe_rot_kernel (no image camera-aware), describe_kernel<4, true, true>,
 // <4, false, true>, <4, false, false> (all modes), <5, true, false>, <6, true, false>
@@ -400,19 +412,21 @@ struct RouteFacts {
 // selection kernel's fused set-up) is told, whichever route serves the call.
 DescribeRoute describe_route(const RouteFacts& f, int* aware_extra_box);
 // setup_done: the selection kernel has prepared the per-keypoint inputs (detection and description in one call);
-// wide_boxes: the pattern is of box class 1 (the WIDE slots of describe_aware_kernel)
+// wide_boxes: the pattern is of box class 1 (the WIDE slots of describe_aware_kernel);
+// final_slots (route kAwareBatched with setup_done only): the selection tail assigned final slots -- kps_in /
+// kp_count_in / desc_tmp are the call's output buffers, valid_tmp is not touched
 void launch_describe(const uint8_t* img, int w, int h, int n_images, const Pattern* pat,
                      const ImageParams* prm, const float* const* rays, const float* const* jac,
                      const okvfe_keypoint* kps_in, int kp_cap, const int32_t* kp_count_in,
                      okvfe_keypoint* kps_tmp, uint8_t* desc_tmp, uint8_t* valid_tmp,
                      const PatternScales* scales, hipStream_t stream, bool setup_done, DescribeRoute route,
-                     bool wide_boxes, int aware_extra_box);
+                     bool wide_boxes, int aware_extra_box, bool final_slots = false);
 bool describe_patch_fits(float nx, float ny, int border);
 // k_describe_aware.hip: the camera-aware-only extractor with batched extra samples (round 6)
 int describe_aware_patch_class(float nx, float ny, float reach);
 void launch_describe_aware(const uint8_t* img, int w, int h, int n_images, const Pattern* pat,
                            const okvfe_keypoint* kps_in, int kp_cap, const int32_t* kp_count_in, uint8_t* desc_tmp,
-                           uint8_t* valid_tmp, bool wide_boxes, hipStream_t stream);
+                           uint8_t* valid_tmp, bool wide_boxes, hipStream_t stream, bool final_slots);
 // Quarter-wave lookup of the pattern's 1024-step rotation tables: sin(k) = +-Q[r or 256 - r] with Q = the first 257
 // entries of the sine table, cos(k) = sin(k + 256).  describe_rot_kernel keeps Q (ints and floats, 2 KB) in LDS instead
 // of gathering from the 16 KB of global tables inside every keypoint's chain; the host verifies once per pattern that the
@@ -435,6 +449,9 @@ void launch_compact(int n_images, const DeviceCamera* cams, const ImageParams* p
                     const uint8_t* valid_tmp, const int32_t* kp_count_in, int kp_cap,
                     okvfe_keypoint* kps, uint8_t* desc, double* bp, uint8_t* bpv,
                     int32_t* kp_count, hipStream_t stream, bool rt8 = false);
+// back-projection of keypoints that already sit in their final slots (DescribeSetup::kps_out): one thread per keypoint
+void launch_backproject(int n_images, const DeviceCamera* cams, const ImageParams* prm, const okvfe_keypoint* kps,
+                        const int32_t* kp_count, int kp_cap, double* bp, uint8_t* bpv, hipStream_t stream, bool rt8);
 void launch_match_stereo(const PairParams* pairs, int n_pairs, const okvfe_keypoint* kps,
                          const uint8_t* desc, const double* bp, const uint8_t* bpv,
                          const int32_t* counts, int kp_cap, int threshold,
