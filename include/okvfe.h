@@ -701,8 +701,10 @@ okvfe_status okvfe_match_motion_stereo_blocks_device(okvfe_ctx* ctx, int32_t cam
  * (lm.quality < acos(cos_quality)) and setLandmark / addLandmark / addObservation (:1940-1956) need estimator state
  * and a libm acos.  A caller that needs that coupling refreshes its skip0 rows between the calls, on the device or the
  * host; with skip0 fixed up front the sweep equals the reference whenever no such landmark exists.  A landmark observed
- * by two keypoints of one older image is not modelled.  The choice and order of the older frames (:1742-1767) stay
- * with the caller as well.  The consensus of runRansac2d2d (:1964-1969, before initialisation only) is
+ * by two keypoints of one older image is not modelled.  The order of the older frames (:1751-1767) is
+ * okvfe_overlap_pairs_blocks_device + okvfe_overlap_fraction + okvfe_motion_frame_order, whose output fills the host
+ * idx0 / idx1 of this call; which frames are candidates (allFrames, isKeyframe: :1742-1749) stays with the caller.
+ * The consensus of runRansac2d2d (:1964-1969, before initialisation only) is
  * okvfe_ransac2d2d_consensus_blocks_device, queued after each step of the sweep; its sampler and minimal solvers are
  * the caller's.
  *
@@ -1404,8 +1406,8 @@ okvfe_status okvfe_bow_database_check_device(okvfe_ctx* ctx, const okvfe_bow_dat
  * `detections` and, if the keypoint carries a landmark, into `matches`; it then counts the non-zero pixels of
  * matches & detections and of matches | detections (:1074-1101, :1123-1149).  The coverage calls return these counts
  * per image, okvfe_keyframe_decision turns the records of the current multiframe and of the other multiframes into
- * the verdict.  The counts are exposed because ViSlamBackend::overlapFraction / trackingQuality
- * (ViSlamBackend.cpp:157-196, 2341-2427) are a few host lines over the same primitive.
+ * the verdict.  ViSlamBackend::overlapFraction / trackingQuality (ViSlamBackend.cpp:157-196, 2341-2427) work on the
+ * same masks: see the next section.
  *
  * What stays with the caller, because it needs estimator state: the two early returns at :1060-1065 (fewer than
  * 4 frames in the estimator -> keyframe; front-end not initialised -> no keyframe), which come BEFORE anything here,
@@ -1452,6 +1454,71 @@ okvfe_status okvfe_keyframe_coverage(okvfe_ctx* ctx, const okvfe_keypoint* keypo
 okvfe_status okvfe_keyframe_decision(const okvfe_coverage* current, int32_t n_cameras, const okvfe_coverage* others,
                                      int32_t n_others, float overlap_threshold, int32_t* need_keyframe,
                                      double* overlap);
+
+/* ---- overlapFraction, the order of the motion-stereo sweep, trackingQuality ---- */
+/* ViSlamBackend::overlapFraction(frameA, frameB) (ViSlamBackend.cpp:2341-2427) on the same masks: per side f (0 = A,
+ * 1 = B) and camera every keypoint is painted into `detections`, and into `matches` iff its landmark id is in
+ * landmarks(A) n landmarks(B), the sets taken over ALL cameras of each multiframe (:2372-2384, :2402).  An id of this
+ * side is in its own set by construction, so that is: id != 0 and some keypoint of any camera of the OTHER multiframe
+ * carries it.  Callers: the order of the motion-stereo sweep (Frontend.cpp:1742-1767, once per keyframe and frame)
+ * and the back-end's keyframe management (ViSlamBackend.cpp:2237, :2261, :2299).  kptrad there is
+ * 0.09 * uniformityRadius / 36 (ViSlamBackend.hpp:209).  Mask size, radius, centre rounding and disc: as above
+ * (PARITY UNPINNED for cv::circle, as above).
+ *
+ * What stays with the caller: which frames are in allFrames (:1742-1749: keyframes, and IMU-window frames that are
+ * keyframes, i.e. estimator.isKeyframe), and for okvfe_tracking_quality the observed-elsewhere test of
+ * ViSlamBackend.cpp:178-187, which walks the estimator's observations. */
+typedef struct okvfe_overlap_counts {  /* one ordered pair (A, B); [0] = side A, [1] = side B; 32 bytes */
+  int32_t n_keypoints[2];              /* each field summed over the cameras of its side */
+  int32_t n_matched[2];                /* keypoints painted into matches; [0] == 0 iff [1] == 0 iff no common id */
+  int32_t intersection_area[2];        /* sum of countNonZero(matches & detections), :2420 */
+  int32_t union_area[2];               /* sum of countNonZero(matches | detections), :2421 */
+} okvfe_overlap_counts;
+/* The counts of n_pairs ordered pairs of multiframes in ONE launch (two work-groups per pair); nothing synchronises
+ * the host.  Multiframes are addressed as in okvfe_stereo_insert_blocks_device: the block of (multiframe m, camera c)
+ * is block m * block_stride_m + c * block_stride_c of blocks_dev, for m < n_multiframes and c < n_cams (<= 32); two
+ * (m, c) on one block, or a negative stride, is OKVFE_ERR_INVALID_ARGUMENT.  landmark_ids_dev: device, K u64 per
+ * block AT THAT BLOCK INDEX (K = okvfe_device_outputs.max_keypoints), 0 = none: the ids of
+ * okvfe_keyframe_coverage_blocks_device.  Rows at or past a block's count are never read, neither for painting nor
+ * as part of the other side's set.  pair_a / pair_b: HOST arrays of n_pairs multiframe indices (a == b is allowed;
+ * an index outside [0, n_multiframes) is OKVFE_ERR_INVALID_ARGUMENT and the message names the pair); they travel
+ * through the pinned parameter ring, 8 bytes per pair.  n_pairs == 0 is OKVFE_OK and launches nothing; n_pairs < 2^30.
+ * counts_dev: device, n_pairs records.  coverage_dev (may be NULL): device, n_pairs x 2 x n_cams per-image records
+ * [pair][side][camera], equal to what okvfe_keyframe_coverage_blocks_device reports for that image with the other
+ * multiframe's counted ids as the set.  Nothing past n_pairs records is written.
+ * Limits (OKVFE_ERR_UNSUPPORTED): those of the coverage call -- radius <= 127, masks + id table within its LDS
+ * budget, of which this call uses 256 bytes for the keypoint counts of the two sides. */
+okvfe_status okvfe_overlap_pairs_blocks_device(okvfe_ctx* ctx, const void* blocks_dev, int32_t block_stride_m,
+                                               int32_t block_stride_c, int32_t n_multiframes, int32_t n_cams,
+                                               const uint64_t* landmark_ids_dev, const int32_t* pair_a,
+                                               const int32_t* pair_b, int32_t n_pairs, double kptrad,
+                                               okvfe_overlap_counts* counts_dev, okvfe_coverage* coverage_dev /* or NULL */,
+                                               void* stream);
+/* pure host arithmetic, no context: :2386-2389 and :2410-2426 for n_pairs records.  `matches` is empty iff
+ * n_matched[0] == 0, and the result is then 0.0; otherwise o[f] = double(intersection_area[f]) / double(union_area[f])
+ * and the result is std::min(o[0], o[1]), i.e. o[1] < o[0] ? o[1] : o[0].  0 / 0 is NaN and goes through exactly like
+ * that (a NaN o[0] is returned, a NaN o[1] alone is not).  A record where exactly one n_matched is 0 (the device call
+ * cannot produce one) or with a negative count is OKVFE_ERR_INVALID_ARGUMENT; nothing is written then. */
+okvfe_status okvfe_overlap_fraction(const okvfe_overlap_counts* counts, int32_t n_pairs, double* overlap_out);
+/* pure host arithmetic, no context: Frontend.cpp:1751-1767.  overlap[i] / frame_ids[i]: overlapFraction(previous
+ * frame, frame i) and the frame's StateId value, n entries; the entry at index `previous` (-1 = none) gets 1.0 without
+ * its overlap being looked at (:1753-1755).  order_out (n entries of room) receives the INDICES of the frames in
+ * descending lexicographic (overlap, id) order -- the reverse of std::sort on the pairs -- cut at the first overlap
+ * <= 1.0e-8 (:1765); *n_order their number.  Duplicate ids are OKVFE_ERR_INVALID_ARGUMENT (allFrames is a set).
+ * DEFINED DEVIATION: a NaN overlap (other than at `previous`) is OKVFE_ERR_INVALID_ARGUMENT, because std::sort on
+ * pairs with a NaN is undefined behaviour in the reference; *n_order then receives the index of the first such
+ * entry.  On any other error *n_order is -1. */
+okvfe_status okvfe_motion_frame_order(const double* overlap, const uint64_t* frame_ids, int32_t n, int32_t previous,
+                                      int32_t* order_out, int32_t* n_order);
+/* pure host arithmetic, no context: ViSlamBackend::trackingQuality (ViSlamBackend.cpp:157-196) from the n_cams records
+ * that a coverage call WITHOUT an id set (id_set == NULL) returns for the frame, after the caller has zeroed the ids
+ * whose landmark is not observed in another frame (:178-187).  rows = height / 10, cols = width / 10;
+ * radius = double(min(rows, cols)) * kptrad stays a double here and pointArea = int(radius * radius * M_PI) (:191; 65
+ * for 752 x 480 at 0.095, while the painted disc has 49 pixels); per image intersectionCount += max(0, matches_area -
+ * pointArea) and unionCount += rows * cols - pointArea; the result is 0.0 if the n_matched sum to less than 8, else
+ * double(intersectionCount) / double(unionCount).  Negative counts are rejected. */
+okvfe_status okvfe_tracking_quality(const okvfe_coverage* coverage, int32_t n_cams, int32_t width, int32_t height,
+                                    double kptrad, double* quality_out);
 
 /* ---- cross-camera gather collective (RCCL over xGMI) ---------------------- */
 /* The one exchange step of the path (okvis_frontend/src/Frontend.cpp:1990-2026 needs the keypoints

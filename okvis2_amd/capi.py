@@ -31,6 +31,8 @@ MOTION_MATCH_DTYPE = np.dtype([("k1", "<i4"), ("dist", "<i4"), ("initialisable",
                                ("accepted", "<i4"), ("cos_quality", "<f8"), ("hp_W", "<f8", (4,))])
 COVERAGE_DTYPE = np.dtype([("n_keypoints", "<i4"), ("n_matched", "<i4"), ("detections_area", "<i4"),
                            ("matches_area", "<i4"), ("intersection_area", "<i4"), ("union_area", "<i4")])
+OVERLAP_COUNTS_DTYPE = np.dtype([("n_keypoints", "<i4", (2,)), ("n_matched", "<i4", (2,)),
+                                 ("intersection_area", "<i4", (2,)), ("union_area", "<i4", (2,))])
 KPTRAD = 0.09  # Frontend.cpp:104
 KEYFRAME_OVERLAP_THRESHOLD = 0.55  # keyframeInsertionOverlapThreshold_, Frontend.cpp:145
 
@@ -123,6 +125,8 @@ EXPORTS = [
     "okvfe_bow_database_add_blocks_device", "okvfe_bow_database_check_device",
     "okvfe_stereo_insert_blocks_device",
     "okvfe_ransac2d2d_consensus_blocks_device",
+    "okvfe_overlap_pairs_blocks_device", "okvfe_overlap_fraction", "okvfe_motion_frame_order",
+    "okvfe_tracking_quality",
 ]
 
 STAGES = ["harris", "nms", "sort", "select", "map", "describe", "compact", "match"]
@@ -300,6 +304,15 @@ def lib():
         L.okvfe_bow_database_add_blocks_device.argtypes = [V, V, V, C.c_int32, V, C.c_int32, V]
         L.okvfe_bow_database_check_device.restype = C.c_int32
         L.okvfe_bow_database_check_device.argtypes = [V, V, V]
+        L.okvfe_overlap_pairs_blocks_device.restype = C.c_int32
+        L.okvfe_overlap_pairs_blocks_device.argtypes = [
+            V, V, C.c_int32, C.c_int32, C.c_int32, C.c_int32, V, V, V, C.c_int32, C.c_double, V, V, V]
+        L.okvfe_overlap_fraction.restype = C.c_int32
+        L.okvfe_overlap_fraction.argtypes = [V, C.c_int32, V]
+        L.okvfe_motion_frame_order.restype = C.c_int32
+        L.okvfe_motion_frame_order.argtypes = [V, V, C.c_int32, C.c_int32, V, V]
+        L.okvfe_tracking_quality.restype = C.c_int32
+        L.okvfe_tracking_quality.argtypes = [V, C.c_int32, C.c_int32, C.c_int32, C.c_double, V]
         _LIB = L
     return _LIB
 
@@ -491,6 +504,48 @@ def keyframe_decision(current, others=None, overlap_threshold=KEYFRAME_OVERLAP_T
     if st != OK:
         raise OkvfeError(st, "okvfe_keyframe_decision")
     return bool(need.value), overlap.value
+
+
+def overlap_fraction(counts):
+    """okvfe_overlap_fraction (ViSlamBackend.cpp:2386-2389, :2410-2426; host arithmetic, no context): one double per
+    OVERLAP_COUNTS_DTYPE record.  NaN (0 / 0) goes through as in the reference."""
+    c = np.ascontiguousarray(counts, dtype=OVERLAP_COUNTS_DTYPE).reshape(-1)
+    out = np.zeros(len(c), dtype=np.float64)
+    st = lib().okvfe_overlap_fraction(_p(c) if len(c) else None, len(c), _p(out) if len(c) else None)
+    if st != OK:
+        raise OkvfeError(st, "okvfe_overlap_fraction: a negative count, or exactly one side without matched keypoints")
+    return out
+
+
+def motion_frame_order(overlap, frame_ids, previous=-1):
+    """okvfe_motion_frame_order (Frontend.cpp:1751-1767; host arithmetic, no context): the indices of the frames in
+    the order of the motion-stereo sweep.  The entry at index `previous` (-1 = none) counts as overlap 1.0.  A NaN
+    overlap is refused (std::sort is undefined there), as are duplicate ids."""
+    ov = np.ascontiguousarray(overlap, dtype=np.float64).reshape(-1)
+    ids = np.ascontiguousarray(frame_ids, dtype=np.uint64).reshape(-1)
+    if len(ids) != len(ov):
+        raise ValueError("frame_ids: one per overlap")
+    n = len(ov)
+    order = np.zeros(max(n, 1), dtype=np.int32)
+    n_order = C.c_int32()
+    st = lib().okvfe_motion_frame_order(_p(ov) if n else None, _p(ids) if n else None, n, int(previous), _p(order),
+                                        C.byref(n_order))
+    if st != OK:
+        what = f"entry {n_order.value}: NaN overlap" if n_order.value >= 0 else "bad argument or duplicate frame ids"
+        raise OkvfeError(st, "okvfe_motion_frame_order: " + what)
+    return order[:n_order.value].copy()
+
+
+def tracking_quality(coverage, width, height, kptrad):
+    """okvfe_tracking_quality (ViSlamBackend.cpp:157-196; host arithmetic, no context): coverage = the records of a
+    coverage call without an id set, one per camera, taken with the not-observed-elsewhere ids zeroed."""
+    c = np.ascontiguousarray(coverage, dtype=COVERAGE_DTYPE).reshape(-1)
+    q = C.c_double()
+    st = lib().okvfe_tracking_quality(_p(c) if len(c) else None, len(c), int(width), int(height), C.c_double(kptrad),
+                                      C.byref(q))
+    if st != OK:
+        raise OkvfeError(st, "okvfe_tracking_quality")
+    return q.value
 
 
 def set_heavy_kernel_chaining(mode: int):
@@ -1245,6 +1300,23 @@ class Frontend:
                                                   _p(ids) if len(ids) else None, _p(s), n_set,
                                                   C.c_double(kptrad), _p(out)))
         return out[0]
+
+    def overlap_pairs_blocks_device(self, blocks_ptr, block_stride_m, block_stride_c, n_multiframes, n_cams,
+                                    landmark_ids_ptr, pair_a, pair_b, counts_ptr, coverage_ptr=None, kptrad=KPTRAD,
+                                    stream=None):
+        """ViSlamBackend::overlapFraction up to its counts for len(pair_a) ordered multiframe pairs in one launch.
+        The block of (m, c) is block m * block_stride_m + c * block_stride_c; landmark_ids_ptr: device u64, K per block
+        at that block index; pair_a / pair_b: host int sequences; counts_ptr: device OVERLAP_COUNTS_DTYPE [n_pairs];
+        coverage_ptr: None, or device COVERAGE_DTYPE [n_pairs][2][n_cams]."""
+        a = np.ascontiguousarray(pair_a, dtype=np.int32).reshape(-1)
+        b = np.ascontiguousarray(pair_b, dtype=np.int32).reshape(-1)
+        if len(a) != len(b):
+            raise ValueError("pair_a / pair_b: one multiframe index each per pair")
+        n = len(a)
+        self._check(lib().okvfe_overlap_pairs_blocks_device(
+            self._h, _p(blocks_ptr), int(block_stride_m), int(block_stride_c), int(n_multiframes), int(n_cams),
+            _p(landmark_ids_ptr), _p(a) if n else None, _p(b) if n else None, n, C.c_double(kptrad), _p(counts_ptr),
+            _p(coverage_ptr), _s(stream)))
 
     # -- gather blocks --------------------------------------------------------------------
     def gather_block_bytes(self) -> int:

@@ -296,6 +296,23 @@ okvfe_status lanes_join_host(okvfe_ctx* ctx) {
   return OKVFE_OK;
 }
 
+okvfe_status check_block_strides(okvfe_ctx* ctx, const char* who, int stride_m, int stride_c, int n_multiframes,
+                                 int n_cams) {
+  const int64_t last = (int64_t)(n_multiframes - 1) * stride_m + (int64_t)(n_cams - 1) * stride_c;
+  if (n_multiframes > 0 && last > (int64_t)INT32_MAX)
+    return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "%s: block index %lld does not fit an int32", who, (long long)last);
+  std::vector<int64_t> idx;
+  idx.reserve((size_t)n_multiframes * (size_t)n_cams);
+  for (int m = 0; m < n_multiframes; ++m)
+    for (int c = 0; c < n_cams; ++c) idx.push_back((int64_t)m * stride_m + (int64_t)c * stride_c);
+  std::sort(idx.begin(), idx.end());
+  const auto dup = std::adjacent_find(idx.begin(), idx.end());
+  if (dup != idx.end())
+    return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "%s: strides (%d, %d) put two (multiframe, camera) on block %lld", who,
+                stride_m, stride_c, (long long)*dup);
+  return OKVFE_OK;
+}
+
 void layer_size(int w, int h, int l, int* lw, int* lh) {  // oracle: orc_layer_size
   if (l == 0) {
     *lw = w; *lh = h;

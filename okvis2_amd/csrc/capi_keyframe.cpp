@@ -25,31 +25,43 @@ void circle_half_widths(int r, uint8_t* hw) {
     }
   }
 }
+okvfe_status coverage_geometry(okvfe_ctx* ctx, const char* who, double kptrad, int64_t n_ids, size_t extra_lds,
+                               CoverageGeometry* g) {
+  g->rows = ctx->h / 10;  // Frontend.cpp:1075-1076
+  g->cols = ctx->w / 10;
+  const double radius = double(std::min(g->rows, g->cols)) * kptrad;  // :1083
+  if (!(radius <= (double)kCoverageMaxRadius))
+    return fail(ctx, OKVFE_ERR_UNSUPPORTED, "%s: disc radius %g exceeds %d mask pixels", who, radius, kCoverageMaxRadius);
+  g->r = int(radius);
+  circle_half_widths(g->r, g->hw);
+  const size_t mask_bytes = (size_t)2 * g->rows * ((g->cols + 31) / 32) * sizeof(uint32_t) + extra_lds;
+  g->log2_slots = 0;
+  if (n_ids >= 0) {  // table of twice the set, 256 .. 4096 slots, smaller where the masks leave less room
+    g->log2_slots = 8;
+    while (g->log2_slots < 12 && ((int64_t)1 << g->log2_slots) < 2 * n_ids) ++g->log2_slots;
+    while (g->log2_slots > 8 && mask_bytes + ((size_t)8 << g->log2_slots) > kCoverageLdsBudget) --g->log2_slots;
+  }
+  g->lds = mask_bytes + (n_ids >= 0 ? (size_t)8 << g->log2_slots : 0);
+  if (g->lds > kCoverageLdsBudget)
+    return fail(ctx, OKVFE_ERR_UNSUPPORTED, "%s: two %d x %d bit masks need %zu bytes of LDS (limit %zu)", who, g->rows,
+                g->cols, g->lds, kCoverageLdsBudget);
+  return OKVFE_OK;
+}
 }  // namespace okvfe
 
 namespace {
 // geometry, LDS budget and launch, shared by the device entry point and the host seam
 okvfe_status coverage_launch(okvfe_ctx* ctx, const char* who, CoverageArgs A, int n_frames, double kptrad,
                              okvfe_coverage* out_dev, hipStream_t s) {
-  A.rows = ctx->h / 10;  // Frontend.cpp:1075-1076
-  A.cols = ctx->w / 10;
-  const double radius = double(std::min(A.rows, A.cols)) * kptrad;  // :1083
-  if (!(radius <= (double)kCoverageMaxRadius))
-    return fail(ctx, OKVFE_ERR_UNSUPPORTED, "%s: disc radius %g exceeds %d mask pixels", who, radius, kCoverageMaxRadius);
-  A.r = int(radius);
-  circle_half_widths(A.r, A.hw);
-  const size_t mask_bytes = (size_t)2 * A.rows * ((A.cols + 31) / 32) * sizeof(uint32_t);
-  A.log2_slots = 0;
-  if (A.has_set) {  // table of twice the set, 256 .. 4096 slots, smaller where the masks leave less room
-    A.log2_slots = 8;
-    while (A.log2_slots < 12 && (1 << A.log2_slots) < 2 * A.n_id_set) ++A.log2_slots;
-    while (A.log2_slots > 8 && mask_bytes + ((size_t)8 << A.log2_slots) > kCoverageLdsBudget) --A.log2_slots;
-  }
-  const size_t lds = mask_bytes + (A.has_set ? (size_t)8 << A.log2_slots : 0);
-  if (lds > kCoverageLdsBudget)
-    return fail(ctx, OKVFE_ERR_UNSUPPORTED, "%s: two %d x %d bit masks need %zu bytes of LDS (limit %zu)", who, A.rows,
-                A.cols, lds, kCoverageLdsBudget);
-  launch_keyframe_coverage(A, n_frames, lds, out_dev, s);
+  CoverageGeometry g;
+  const okvfe_status st = coverage_geometry(ctx, who, kptrad, A.has_set ? (int64_t)A.n_id_set : -1, 0, &g);
+  if (st != OKVFE_OK) return st;
+  A.rows = g.rows;
+  A.cols = g.cols;
+  A.r = g.r;
+  std::memcpy(A.hw, g.hw, sizeof(A.hw));
+  A.log2_slots = g.log2_slots;
+  launch_keyframe_coverage(A, n_frames, g.lds, out_dev, s);
   HIP_TRY(ctx, hipGetLastError());
   return OKVFE_OK;
 }

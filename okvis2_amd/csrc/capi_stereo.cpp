@@ -40,20 +40,8 @@ okvfe_status okvfe_stereo_insert_blocks_device(
   if ((int64_t)T->n_landmarks + (int64_t)n_pairs * K > (int64_t)INT32_MAX)
     return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "%s: %d table rows + %d x %d created ids do not fit an int32", kName,
                 T->n_landmarks, n_pairs, K);
-  {  // every (m, c) on a block of its own
-    const int64_t last = (int64_t)(n_multiframes - 1) * block_stride_m + (int64_t)(n_cams - 1) * block_stride_c;
-    if (n_multiframes > 0 && last > (int64_t)INT32_MAX)
-      return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "%s: block index %lld does not fit an int32", kName, (long long)last);
-    std::vector<int64_t> idx;
-    idx.reserve((size_t)n_multiframes * (size_t)n_cams);
-    for (int m = 0; m < n_multiframes; ++m)
-      for (int c = 0; c < n_cams; ++c) idx.push_back((int64_t)m * block_stride_m + (int64_t)c * block_stride_c);
-    std::sort(idx.begin(), idx.end());
-    const auto dup = std::adjacent_find(idx.begin(), idx.end());
-    if (dup != idx.end())
-      return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "%s: strides (%d, %d) put two (multiframe, camera) on block %lld", kName,
-                  block_stride_m, block_stride_c, (long long)*dup);
-  }
+  okvfe_status st = check_block_strides(ctx, kName, block_stride_m, block_stride_c, n_multiframes, n_cams);
+  if (st != OKVFE_OK) return st;
   int ov_log2 = 0, kh_log2 = 0;
   const size_t lds = stereo_insert_lds_bytes(n_cams, K, &ov_log2, &kh_log2);
   if (lds > kStereoInsertMaxLds)
@@ -71,7 +59,7 @@ okvfe_status okvfe_stereo_insert_blocks_device(
   std::memcpy(block.data(), cam_ids, (size_t)n_cams * sizeof(int32_t));
   std::memcpy(block.data() + slots_bytes, T_WC, poses_bytes);
   RingSlot params(ctx, &ctx->pair_ring, s);
-  okvfe_status st = params.upload(block.data(), block.size());
+  st = params.upload(block.data(), block.size());
   if (st != OKVFE_OK) return st;
   A.hp_W = T->hp_W;
   A.initialised = initialised_dev;

@@ -302,6 +302,13 @@ okvfe_status check_size_classes(okvfe_ctx* ctx, const okvfe_keypoint* kp, int n,
 hipStream_t pick_stream(okvfe_ctx* ctx, void* stream);      // joins pending pipelined lanes onto the stream it returns
 hipStream_t pick_stream_raw(okvfe_ctx* ctx, void* stream);  // no join (the lane-aware entry points)
 okvfe_status lanes_join_host(okvfe_ctx* ctx);               // host-side join of pending pipelined lanes
+// Mask size, disc and LDS of the coverage kernels (capi_keyframe.cpp): n_ids < 0 = no id table, else a table for up to
+// n_ids ids (chunked beyond half of it); extra_lds bytes follow the masks.  OKVFE_ERR_UNSUPPORTED beyond the limits.
+okvfe_status coverage_geometry(okvfe_ctx* ctx, const char* who, double kptrad, int64_t n_ids, size_t extra_lds,
+                               CoverageGeometry* g);
+// every (m, c), m < n_multiframes, c < n_cams, on a block m * stride_m + c * stride_c of its own, all within an int32
+okvfe_status check_block_strides(okvfe_ctx* ctx, const char* who, int stride_m, int stride_c, int n_multiframes,
+                                 int n_cams);
 void layer_size(int w, int h, int l, int* lw, int* lh);
 void layer_scale(int l, int* num, int* den);
 

@@ -647,8 +647,33 @@ struct CoverageArgs {
 };
 // OpenCV's filled midpoint circle of radius r as half-widths per row offset 0..r (capi_keyframe.cpp)
 void circle_half_widths(int r, uint8_t* hw);
+struct CoverageGeometry {  // of a context's image size and a kptrad (coverage_geometry, okvfe_ctx.h)
+  int rows, cols, r;
+  int log2_slots;  // 0 without an id table
+  size_t lds;      // dynamic LDS of a work-group
+  uint8_t hw[kCoverageMaxRadius + 1];
+};
 void launch_keyframe_coverage(const CoverageArgs& args, int n_frames, size_t lds_bytes, okvfe_coverage* out,
                               hipStream_t stream);
+// overlap counts of ordered multiframe pairs (k_keyframe.hip): two work-groups per pair, one per side.  The block of
+// (multiframe m, camera c) is block m * stride_m + c * stride_c; its ids are the kp_cap values at ids + block * kp_cap.
+constexpr int kOverlapMaxCams = 32;
+constexpr size_t kOverlapCountsLds = 2 * kOverlapMaxCams * sizeof(int32_t);  // keypoint counts of both sides, behind the masks
+struct OverlapArgs {
+  const uint8_t* blocks;
+  size_t block_bytes;
+  int o_count, o_kps, kp_cap;
+  const uint64_t* ids;
+  const int32_t* pairs;  // device, (a, b) per pair
+  int stride_m, stride_c, n_cams;
+  int tiles;       // ceil(kp_cap / 256): hit bits a lane keeps per camera
+  int log2_slots;  // LDS hash table of the other side's ids, filled to half at most per chunk
+  int rows, cols, r;
+  okvfe_overlap_counts* counts;
+  okvfe_coverage* coverage;  // or null: [pair][side][camera]
+  uint8_t hw[kCoverageMaxRadius + 1];
+};
+void launch_overlap_pairs(const OverlapArgs& args, int n_pairs, size_t lds_bytes, hipStream_t stream);
 
 // place recognition on device-resident batches (k_bow.hip): one work-group per multiframe
 constexpr int kBowMaxFeatures = 8192;            // n_cams x max_keypoints: the sort keys of a multiframe, padded to a power of two

@@ -9,6 +9,8 @@
 //   okvis::Frontend::detectAndDescribe            (okvis_frontend/src/Frontend.cpp:221-269)
 //   okvis::Frontend::matchStereo inner loops      (okvis_frontend/src/Frontend.cpp:2016-2076)
 //   okvis::Frontend::doWeNeedANewKeyframe         (okvis_frontend/src/Frontend.cpp:1058-1167)
+//   okvis::ViSlamBackend::overlapFraction / trackingQuality (okvis_ceres/src/ViSlamBackend.cpp:2341-2427, :157-196)
+//   the order of the motion-stereo sweep          (okvis_frontend/src/Frontend.cpp:1751-1767)
 // okvfe_opencv_adapters.hpp wraps these in the real cv:: base classes when OpenCV is available.
 //
 // Every call goes to libokvfe.so (HIP kernels).  Failures throw okvfe::Exception, the analogue of
@@ -1126,6 +1128,113 @@ class HipFrontend {
     if (st != OKVFE_OK) throw Exception(st, "okvfe_keyframe_decision");
     if (overlapOut) *overlapOut = overlap;
     return need != 0;
+  }
+
+  // kptradius_ after ViSlamBackend::setDetectorUniformityRadius (ViSlamBackend.hpp:208-210)
+  double backendKeypointRadius() const { return 0.09 * double(params_.detection_threshold) / 36.0; }
+
+  // ViSlamBackend::overlapFraction(frameA, frameB) (ViSlamBackend.cpp:2341-2427), the B = 1 form: one FrameData per
+  // camera on each side; per image the masks are painted and counted by okvfe_keyframe_coverage with the OTHER
+  // multiframe's ids, all cameras concatenated, as the set (an id of this side is in its own set by construction), the
+  // sums go through okvfe_overlap_fraction.  kptrad < 0: backendKeypointRadius().  countsOut: the summed counts.
+  double overlapFraction(const std::vector<FrameData>& frameA, const std::vector<FrameData>& frameB, double kptrad = -1.0,
+                         okvfe_overlap_counts* countsOut = nullptr) {
+    const size_t nc = cameras_.size();
+    if (frameA.size() != nc || frameB.size() != nc)
+      throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "overlapFraction: one FrameData per camera on both sides");
+    if (kptrad < 0.0) kptrad = backendKeypointRadius();
+    const std::vector<FrameData>* frames[2] = {&frameA, &frameB};
+    okvfe_overlap_counts counts{};
+    for (int f = 0; f < 2; ++f) {
+      std::vector<uint64_t> otherIds;  // as a list: the library ignores order, duplicates and zeros
+      for (const FrameData& o : *frames[1 - f]) {
+        if (o.landmarkIds.size() != o.keypoints.size())
+          throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "landmarkIds: one entry per keypoint");
+        otherIds.insert(otherIds.end(), o.landmarkIds.begin(), o.landmarkIds.end());
+      }
+      if (otherIds.empty()) otherIds.push_back(0);  // an empty set is still a set (non-null pointer)
+      for (size_t im = 0; im < nc; ++im) {
+        const FrameData& fd = (*frames[f])[im];
+        okvfe_coverage c{};
+        std::lock_guard<std::mutex> lock(mutexes_[im]);
+        contexts_[im]->check(okvfe_keyframe_coverage(contexts_[im]->get(), fd.keypoints.data(), int32_t(fd.keypoints.size()),
+                                                     fd.landmarkIds.data(), otherIds.data(), int32_t(otherIds.size()),
+                                                     kptrad, &c));
+        counts.n_keypoints[f] += c.n_keypoints;
+        counts.n_matched[f] += c.n_matched;
+        counts.intersection_area[f] += c.intersection_area;
+        counts.union_area[f] += c.union_area;
+      }
+    }
+    if (countsOut) *countsOut = counts;
+    double overlap = 0.0;
+    const okvfe_status st = okvfe_overlap_fraction(&counts, 1, &overlap);
+    if (st != OKVFE_OK) throw Exception(st, "okvfe_overlap_fraction");
+    return overlap;
+  }
+  // The counts of overlapFraction for pairA.size() ordered pairs of multiframes that live in device memory as gather
+  // blocks, in one launch on the rig's shared context (okvfe_overlap_pairs_blocks_device; addressing as in
+  // matchStereoInsertBlocks).  landmarkIdsDev: K u64 per block at the block's index.  countsDev: one record per pair;
+  // coverageDev: null, or pairs x 2 x numCameras() per-image records.  Nothing synchronises the host: download the
+  // counts and hand them to okvfe_overlap_fraction.
+  void overlapFractionBlocks(const void* blocksDev, int blockStrideM, int blockStrideC, int nMultiframes,
+                             const uint64_t* landmarkIdsDev, const std::vector<int32_t>& pairA,
+                             const std::vector<int32_t>& pairB, okvfe_overlap_counts* countsDev,
+                             okvfe_coverage* coverageDev = nullptr, double kptrad = -1.0, void* stream = nullptr) {
+    if (pairA.size() != pairB.size())
+      throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "overlapFractionBlocks: pairA / pairB: one multiframe index each per pair");
+    if (kptrad < 0.0) kptrad = backendKeypointRadius();
+    Context& c = rigContext();
+    std::lock_guard<std::mutex> lock(rigMutex_);
+    c.check(okvfe_overlap_pairs_blocks_device(c.get(), blocksDev, blockStrideM, blockStrideC, nMultiframes,
+                                              int32_t(cameras_.size()), landmarkIdsDev, pairA.data(), pairB.data(),
+                                              int32_t(pairA.size()), kptrad, countsDev, coverageDev, stream));
+  }
+  // ViSlamBackend::trackingQuality(id) (ViSlamBackend.cpp:157-196): frame one FrameData per camera;
+  // observedElsewhere[im][k] != 0 iff the landmark of keypoint k exists and has an observation in another frame
+  // (:178-187, estimator state: the caller's).  The matches masks are painted by okvfe_keyframe_coverage.
+  double trackingQuality(const std::vector<FrameData>& frame, const std::vector<std::vector<uint8_t>>& observedElsewhere,
+                         double kptrad = -1.0) {
+    const size_t nc = cameras_.size();
+    if (frame.size() != nc || observedElsewhere.size() != nc)
+      throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "trackingQuality: one FrameData and one flag row per camera");
+    if (kptrad < 0.0) kptrad = backendKeypointRadius();
+    std::vector<okvfe_coverage> records(nc);
+    for (size_t im = 0; im < nc; ++im) {
+      const FrameData& fd = frame[im];
+      if (fd.landmarkIds.size() != fd.keypoints.size() || observedElsewhere[im].size() != fd.keypoints.size())
+        throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "trackingQuality: one landmark id and one flag per keypoint");
+      if (cameras_[im].base.width != cameras_[0].base.width || cameras_[im].base.height != cameras_[0].base.height)
+        throw Exception(OKVFE_ERR_UNSUPPORTED, "trackingQuality: cameras of one image size");
+      std::vector<uint64_t> ids(fd.landmarkIds);
+      for (size_t k = 0; k < ids.size(); ++k)
+        if (!observedElsewhere[im][k]) ids[k] = 0;
+      std::lock_guard<std::mutex> lock(mutexes_[im]);
+      contexts_[im]->check(okvfe_keyframe_coverage(contexts_[im]->get(), fd.keypoints.data(), int32_t(fd.keypoints.size()),
+                                                   ids.data(), nullptr, 0, kptrad, &records[im]));
+    }
+    double quality = 0.0;
+    const okvfe_status st = okvfe_tracking_quality(records.data(), int32_t(nc), cameras_[0].base.width,
+                                                   cameras_[0].base.height, kptrad, &quality);
+    if (st != OKVFE_OK) throw Exception(st, "okvfe_tracking_quality");
+    return quality;
+  }
+  // The order of the motion-stereo sweep (Frontend.cpp:1751-1767): overlaps[i] = overlapFraction(previous frame, frame
+  // i), frameIds[i] its StateId; previous: index of the previous frame among them, -1 = not among them.  Returns the
+  // indices in sweep order.  Which frames are candidates (:1742-1749) is the caller's.  A NaN overlap throws.
+  static std::vector<int32_t> motionStereoFrameOrder(const std::vector<double>& overlaps,
+                                                     const std::vector<uint64_t>& frameIds, int32_t previous = -1) {
+    if (overlaps.size() != frameIds.size())
+      throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "motionStereoFrameOrder: one id per overlap");
+    std::vector<int32_t> order(overlaps.size());
+    int32_t n = 0;
+    const okvfe_status st = okvfe_motion_frame_order(overlaps.data(), frameIds.data(), int32_t(overlaps.size()), previous,
+                                                     order.data(), &n);
+    if (st != OKVFE_OK)
+      throw Exception(st, n >= 0 ? "okvfe_motion_frame_order: entry " + std::to_string(n) + ": NaN overlap"
+                                 : std::string("okvfe_motion_frame_order"));
+    order.resize(size_t(n));
+    return order;
   }
 
  private:
