@@ -128,6 +128,11 @@ EXPORTS = [
     "okvfe_overlap_pairs_blocks_device", "okvfe_overlap_fraction", "okvfe_motion_frame_order",
     "okvfe_tracking_quality",
 ]
+# exported for the tests and deliberately not declared in include/okvfe.h (EXPORTS is exactly what the header declares)
+TEST_HOOKS = [
+    "okvfe_test_set_map_table_workspace_limit", "okvfe_test_ransac_chunk_records", "okvfe_test_ransac_ring_records",
+    "okvfe_test_ransac2d2d_chunk_records", "okvfe_test_ransac2d2d_ring_records", "okvfe_test_ransac2d2d_id_slot",
+]
 
 STAGES = ["harris", "nms", "sort", "select", "map", "describe", "compact", "match"]
 
@@ -1262,6 +1267,29 @@ class Frontend:
         f = lib().okvfe_test_ransac2d2d_chunk_records
         f.restype = C.c_int32
         return int(f())
+
+    @staticmethod
+    def _test_ransac_ring_records() -> int:
+        """test hook (not part of include/okvfe.h): records of the consensus kernel's LDS ring"""
+        f = lib().okvfe_test_ransac_ring_records
+        f.restype = C.c_int32
+        return int(f())
+
+    @staticmethod
+    def _test_ransac2d2d_ring_records() -> int:
+        """test hook (not part of include/okvfe.h): records of the 2d2d consensus kernel's LDS ring"""
+        f = lib().okvfe_test_ransac2d2d_ring_records
+        f.restype = C.c_int32
+        return int(f())
+
+    @staticmethod
+    def _test_ransac2d2d_id_slot(landmark_id) -> int:
+        """test hook (not part of include/okvfe.h): the home slot of a landmark id in the 2d2d consensus kernel's id
+        table of RANSAC2D2D_MAX_KEYPOINTS + 1 slots"""
+        f = lib().okvfe_test_ransac2d2d_id_slot
+        f.argtypes = [C.c_int32]
+        f.restype = C.c_int32
+        return int(f(int(landmark_id)))
 
     def _test_set_map_table_workspace_limit(self, nbytes):
         """test hook (not part of include/okvfe.h): the workspace size above which the call above slices its frames"""

@@ -142,5 +142,7 @@ okvfe_status okvfe_place_consensus_blocks_device(
 // Test hook, deliberately not in include/okvfe.h: the number of correspondences the consensus kernel scores at a time,
 // so that the tests straddle it whatever it is.
 int32_t okvfe_test_ransac_chunk_records(void) { return ransac_chunk_records(); }
+// ... and the records of its LDS ring, so that the tests run whole laps of it
+int32_t okvfe_test_ransac_ring_records(void) { return ransac_ring_records(); }
 
 }  // extern "C"

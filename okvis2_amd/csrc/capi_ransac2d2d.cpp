@@ -80,5 +80,9 @@ okvfe_status okvfe_ransac2d2d_consensus_blocks_device(
 // Test hook, deliberately not in include/okvfe.h: the number of correspondences the 2d2d consensus kernel scores at a
 // time, so that the tests straddle it whatever it is.
 int32_t okvfe_test_ransac2d2d_chunk_records(void) { return ransac2d2d_chunk_records(); }
+// Test hooks of the same kind: the records of the kernel's LDS ring, and the home slot of a landmark id in its id
+// table (the kernel's own function), so that the tests wrap the one and crowd the other whatever their constants are.
+int32_t okvfe_test_ransac2d2d_ring_records(void) { return ransac2d2d_ring_records(); }
+int32_t okvfe_test_ransac2d2d_id_slot(int32_t id) { return (int32_t)ransac2d2d_id_slot(id); }
 
 }  // extern "C"

@@ -314,6 +314,7 @@ void launch_place_consensus(const double* hp, int n_landmarks, const BlockLayout
 }
 
 int ransac_chunk_records() { return kRansacChunk; }
+int ransac_ring_records() { return kRansacRing; }
 
 bool set_fp64_tree_ransac(int tree) {
   g_fp64_ltr_ransac[current_device_slot()].store(tree ? 0 : 1);  // (the caller has set and drained the device)

@@ -146,11 +146,9 @@ __device__ __forceinline__ double relative_pose_distance(const double* H /* [R |
   return score_of_errors<kTree>(e1, e2, R.s1, R.s2);
 }
 
-__device__ __forceinline__ uint32_t id_slot(int id) { return ((uint32_t)id * 2654435761u) >> (32 - kRansac2SlotsLog2); }
-
 // the current keypoint the adapter's idMap holds for `id` (the first one, FrameRelativeAdapter.cpp:151), -1 = none
 __device__ __forceinline__ int id_lookup(const int* tab, const int32_t* lm1, int id) {
-  for (uint32_t s = id_slot(id);; s = (s + 1) & (uint32_t)(kRansac2Slots - 1)) {
+  for (uint32_t s = ransac2d2d_id_slot(id);; s = (s + 1) & (uint32_t)(kRansac2Slots - 1)) {
     const int k = tab[s];
     if (k < 0) return -1;
     if (lm1[k] == id) return k;
@@ -228,7 +226,7 @@ __global__ __launch_bounds__(kRansac2Threads) void ransac2d2d_consensus_kernel(R
       const int id = lm1[k];
       if (id < 0) continue;                                                  // :143
       if (A.added && (id >= A.n_landmarks || A.added[id] == 0)) continue;    // :147
-      for (uint32_t s = id_slot(id);; s = (s + 1) & (uint32_t)(kRansac2Slots - 1)) {
+      for (uint32_t s = ransac2d2d_id_slot(id);; s = (s + 1) & (uint32_t)(kRansac2Slots - 1)) {
         const int old = atomicCAS(&s_tab[s], -1, k);
         if (old < 0) break;
         if (lm1[old] == id) {  // the slot is this id's (it only ever holds keypoints of one id): :151 keeps the first
@@ -370,6 +368,7 @@ void launch_ransac2d2d_consensus(const Ransac2d2dArgs& args, int n_pairs, hipStr
 }
 
 int ransac2d2d_chunk_records() { return kRansac2Chunk; }
+int ransac2d2d_ring_records() { return kRansac2Ring; }
 
 bool set_fp64_tree_ransac2d2d(int tree) {
   g_fp64_ltr_ransac2d2d[current_device_slot()].store(tree ? 0 : 1);  // (the caller has set and drained the device)

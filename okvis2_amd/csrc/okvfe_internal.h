@@ -574,10 +574,15 @@ void launch_ransac_consensus(const double* hp_W, const int32_t* obs_begin, int n
                              const uint8_t* hyp_valid, int n_hyp, double threshold, int remove_outliers,
                              const okvfe_ransac_result_device& out, hipStream_t stream);
 int ransac_chunk_records();  // correspondences the consensus kernel scores at a time
+int ransac_ring_records();   // records of its LDS ring
 // the consensus step of runRansac2d2d for a batch of (older, current) multiframe pairs (k_ransac2d2d.hip).  pairs
 // (n_pairs x {mf0, mf1}) and fu (n_cams) lie in the parameter block of the call; every other pointer is the caller's.
 constexpr int kRansac2SlotsLog2 = 12;  // the id table of a work-group: 4096 slots of 4 bytes
 constexpr int kRansac2dMaxKeypoints = (1 << kRansac2SlotsLog2) - 1;  // an empty slot always ends a probe
+// the home slot of a landmark id in that table: the ONE definition, the kernel's and the test hook's
+__host__ __device__ inline uint32_t ransac2d2d_id_slot(int32_t id) {
+  return ((uint32_t)id * 2654435761u) >> (32 - kRansac2SlotsLog2);
+}
 struct Ransac2d2dArgs {
   const uint8_t *blocks0, *blocks1;
   int o_count, o_kps, o_bp, o_bpv;
@@ -599,6 +604,7 @@ struct Ransac2d2dArgs {
 };
 void launch_ransac2d2d_consensus(const Ransac2d2dArgs& args, int n_pairs, hipStream_t stream);
 int ransac2d2d_chunk_records();
+int ransac2d2d_ring_records();
 // verifyRecognisedPlace after the descriptor matching (Frontend.cpp:347-397): the claims (k_place.hip) and the consensus
 // over LoopclosureNoncentralAbsoluteAdapter's correspondences (k_ransac.hip, the kPlace policy of the kernel above)
 constexpr int kPlaceClaimsMaxKeypoints = 12288;  // one int per keypoint in LDS

@@ -48,6 +48,54 @@ def rig_scene(oracle, voc, n_cams, K, seed=3, n_places=4, per_place=90):
     return dict(feats=feats, counts=counts, n_cams=n_cams, K=K, places=places, place_of=[m % n_places for m in range(12)])
 
 
+# ---- capacity: BOW_MAX_FEATURES keys, long runs, runs on round boundaries -------------------------------------------------
+CAPACITY_CAMS, CAPACITY_K = 4, 2048          # n_cams K = capi.BOW_MAX_FEATURES
+CAPACITY_COUNTS = (8192, 8191, 4097, 4096)   # multiframes 0 .. 3: the 8192-key sort, one key of padding, 4096 + 1, 4096
+LONG_RUN = 5000                              # multiframes 4 and 5: copies of one leaf's descriptor
+BOUNDARY_COUNTS = (256, 300, 212) + (300,) * 14 + (152, 300, 300)   # multiframe 6: copies per leaf, in word order
+ROUND = 256                                  # sorted keys the run-length pass of bow_vectors_kernel takes per round
+LDS_BUDGET, LDS_NODES = 61 * 1024, 1024      # kBowLdsBudget, kVocLdsNodes
+
+
+def nodes_in_lds(n_nodes, n_features):
+    """bow_vectors_lds_bytes restated: the node descriptors are staged in LDS iff they fit beside the sort keys"""
+    keys_cap = 256
+    while keys_cap < n_features:
+        keys_cap *= 2
+    return n_nodes <= LDS_NODES and n_nodes * 48 + keys_cap * 4 <= LDS_BUDGET
+
+
+def _deal(feats, n_cams, K):
+    """features in order onto the cameras, K per camera while they last"""
+    assert len(feats) <= n_cams * K
+    return [feats[c * K:(c + 1) * K] for c in range(n_cams)]
+
+
+def capacity_scene(oracle, voc, seed=13):
+    """seven multiframes of CAPACITY_CAMS cameras with K = CAPACITY_K: the CAPACITY_COUNTS; LONG_RUN copies of one
+    leaf; the same among 40 features of leaves with smaller and larger words; BOUNDARY_COUNTS copies of 20 leaves, shuffled.
+    The copied leaves are leaves whose own descriptor descends to them."""
+    rng = np.random.default_rng(seed)
+    n_cams, K = CAPACITY_CAMS, CAPACITY_K
+    leaves = np.flatnonzero(voc["word"] >= 0)
+    words, _ = oracle.voc_transform(voc["desc"][leaves], voc["desc"], voc["cb"], voc["ci"], voc["word"])
+    own = leaves[(words == voc["word"][leaves]) & (voc["ww"][voc["word"][leaves]] > 0)]
+    own = own[np.argsort(voc["word"][own])]
+    assert len(own) >= 60
+    feats = [_deal(view(voc, rng, leaves, n), n_cams, K) for n in CAPACITY_COUNTS]
+    middle = own[len(own) // 2]
+    feats.append(_deal(np.repeat(voc["desc"][[middle]], LONG_RUN, axis=0), n_cams, K))
+    around = np.concatenate([own[3:23], own[-23:-3]])
+    mixed = np.concatenate([np.repeat(voc["desc"][[middle]], LONG_RUN, axis=0), voc["desc"][around]])
+    feats.append(_deal(mixed[rng.permutation(len(mixed))], n_cams, K))
+    twenty = own[np.linspace(0, len(own) - 1, len(BOUNDARY_COUNTS)).astype(int)]
+    runs = np.repeat(voc["desc"][twenty], BOUNDARY_COUNTS, axis=0)
+    feats.append(_deal(runs[rng.permutation(len(runs))], n_cams, K))
+    places = place_leaves(voc, rng, 4, 90)
+    return dict(feats=feats, counts=[[len(c) for c in cams] for cams in feats], n_cams=n_cams, K=K, places=places,
+                long_word=int(voc["word"][middle]), boundary_words=voc["word"][twenty].astype(np.int32))
+
+
 def reference_vectors(oracle, voc, scene):
     """per multiframe (words per camera, ids, values) of the concatenated features"""
     out = []

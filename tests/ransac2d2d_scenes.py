@@ -12,6 +12,9 @@ number of hypotheses.
   knife_rotation / knife_relative   the threshold 9 bisected to adjacent values
   chunk_scene       chunk - 1, chunk, chunk + 1 and 2 chunk + 1 correspondences
   edge_scene        counts 0, 1 and K (every packed scene carries a valid id at or past the count)
+  ring_scene / ring_restart_scene / full_table_scene / collision_scene   for contexts of 1100 keypoints and of the
+                    call's limit: whole laps of the kernel's record ring (restarted per camera), its id table with one
+                    empty slot, probe runs across the table's end, duplicate ids inside them
 
 The hand-set scenes place bearings directly (a block's back-projections are data).  With the rotation hypothesis R and
 the relative hypothesis [R | t], a correspondence is of one of four kinds:
@@ -407,8 +410,184 @@ def reference(tree, sc, remove_outliers=True, use_valid=True, census=None, thres
     return out
 
 
+# ---- capacity: the ring's wrap, the full id table, probe runs across the table's end -----------------------------
+# These scenes are built for a context of `Kc` keypoints (1100 or the call's limit), not for K, and take the kernel's
+# constants from its test hooks: `ring` / `chunk` records, `slot(id)` the home slot of an id in a table of `n_slots`.
+HASH_MULTIPLIER = 2654435761
+
+
+def host_slot(ids, n_slots):
+    """the kernel's home slot restated: ((id * 2654435761) mod 2^32) >> (32 - log2 n_slots), on an array of ids"""
+    log2 = int(n_slots).bit_length() - 1
+    assert 1 << log2 == n_slots
+    return (((np.asarray(ids, dtype=np.int64) & 0xFFFFFFFF) * HASH_MULTIPLIER) % (1 << 32)) >> (32 - log2)
+
+
+def _relabel(fr0, fr1, new_ids):
+    """the matched ids 3 + 7 i of a hand camera become new_ids[i] in both blocks"""
+    new_ids = np.asarray(new_ids, np.int32)
+    for fr in (fr0, fr1):
+        has = fr["lm"] >= 0
+        fr["lm"][has] = new_ids[(fr["lm"][has] - 3) // 7]
+
+
+def _mixed_camera(oracle, rng, total, Kc, free0=None, free1=5):
+    """`total` correspondences of kinds C / B / D in the proportions of chunk_scene; the older block's free rows lie
+    between the matched ones, so that its 256-keypoint tiles add uneven numbers of records"""
+    nD, nB = total // 8, total // 3
+    free0 = min(Kc - total, total // 2) if free0 is None else free0
+    return hand_camera(oracle, rng, total - nD - nB, 0, nB, nD, free0=free0, free1=min(Kc - total, free1))
+
+
+def ring_totals(ring, chunk, Kc):
+    return (ring - 1, ring, ring + 1, 2 * ring + chunk - 1, Kc)
+
+
+def ring_scene(oracle, ring, chunk, Kc, seed=61):
+    """one camera; pairs with ring - 1, ring, ring + 1, 2 ring + chunk - 1 and Kc correspondences"""
+    assert 2 * ring + chunk - 1 < Kc, "the context no longer spans two laps of the ring"
+    rng = np.random.default_rng([seed, Kc])
+    rot_H, rel_H = lists("true first")
+    pairs = []
+    for total in ring_totals(ring, chunk, Kc):
+        fr0, fr1, _ = _mixed_camera(oracle, rng, total, Kc)
+        pairs.append([cam_entry(fr0, fr1, rot_H, rel_H)])
+    return scene("ring-%d" % Kc, euroc_pair()[:1], pairs)
+
+
+def ring_restart_totals(ring, chunk):
+    return ((ring + chunk + 5, chunk + 3), (chunk + 3, ring + chunk + 5), (ring + 7, ring + 7))
+
+
+def ring_restart_scene(oracle, ring, chunk, Kc, seed=62):
+    """two cameras: the first wraps the ring and the second does not, the other way round, and both wrap"""
+    rng = np.random.default_rng([seed, Kc])
+    rot_H, rel_H = lists("true first")
+    pairs = []
+    for totals in ring_restart_totals(ring, chunk):
+        pair = []
+        for total in totals:
+            fr0, fr1, _ = _mixed_camera(oracle, rng, total, Kc)
+            pair.append(cam_entry(fr0, fr1, rot_H, rel_H))
+        pairs.append(pair)
+    return scene("ring-restart-%d" % Kc, euroc_pair(), pairs)
+
+
+FULL_TABLE_IDS = 20000   # the id space (and the size of the isLandmarkAdded table) of full_table_scene
+
+
+def full_table_scene(oracle, Kc, with_added, n_present=2500, n_absent=1000, seed=63):
+    """one camera, one pair: the current block holds Kc keypoints with Kc distinct ids (with_added: every one of them
+    added), so that a table of Kc + 1 slots keeps ONE empty slot; the older block holds n_present of those ids,
+    n_absent ids >= 0 that no current keypoint carries (their lookups end at the empty slot alone) and -1 in the rest"""
+    rng = np.random.default_rng([seed, Kc])
+    rot_H, rel_H = lists("true first")
+    fr0, fr1, _ = _mixed_camera(oracle, rng, n_present, Kc, free0=Kc - n_present, free1=Kc - n_present)
+    assert len(fr0["lm"]) == len(fr1["lm"]) == Kc
+    ids = rng.permutation(FULL_TABLE_IDS)[:Kc + n_absent].astype(np.int32)
+    _relabel(fr0, fr1, ids[:n_present])
+    fr1["lm"][fr1["lm"] < 0] = ids[n_present:Kc]
+    free = np.flatnonzero(fr0["lm"] < 0)
+    fr0["lm"][free[:n_absent]] = ids[Kc:]
+    added = np.ones(FULL_TABLE_IDS, np.uint8) if with_added else None
+    sc = scene("full-table-%d-%s" % (Kc, "added" if with_added else "null"), euroc_pair()[:1],
+               [[cam_entry(fr0, fr1, rot_H, rel_H)]], added)
+    sc["absent"] = ids[Kc:]
+    return sc
+
+
+def id_table(lm1, added, slot, n_slots, last_wins=False):
+    """the kernel's open-addressed table after the insertion of a current block's ids, keypoints ascending: per slot
+    the keypoint it holds (-1: empty).  The SET of occupied slots of linear probing does not depend on the order of
+    insertion, and a slot's id does not change once set, so the concurrent insertion on the device differs from this
+    one only in which id sits in which slot of a run."""
+    tab = np.full(n_slots, -1, np.int64)
+    lm1 = np.asarray(lm1)
+    for k, lm in enumerate(lm1.tolist()):
+        if lm < 0 or (added is not None and (lm >= len(added) or not added[lm])):
+            continue
+        s = int(slot(lm))
+        while tab[s] >= 0 and lm1[tab[s]] != lm:
+            s = (s + 1) % n_slots
+        if tab[s] < 0 or last_wins:
+            tab[s] = k
+    return tab
+
+
+def table_lookup(tab, lm1, slot, lm, wrap=True):
+    """the keypoint the table holds for id `lm` (-1: none) and the slots probed; wrap=False: a lookup that gives up at
+    the table's end"""
+    s, steps = int(slot(lm)), 1
+    while tab[s] >= 0 and lm1[tab[s]] != lm:
+        s, steps = s + 1, steps + 1
+        if s == len(tab):
+            if not wrap:
+                return -1, steps
+            s = 0
+    return int(tab[s]), steps
+
+
+COLLISION_CLUSTER, COLLISION_SECOND, COLLISION_BACKGROUND, COLLISION_DUPLICATES = 320, 100, 300, 40
+
+
+def collision_scene(oracle, slot, n_slots, Kc, seed=64, id_limit=1 << 22):
+    """one camera, one pair, added = None.  The current block's ids: COLLISION_CLUSTER distinct ids whose home is slot
+    n_slots - 3 (their probe run crosses the table's end into slot 0), COLLISION_SECOND ids whose home is the slot
+    where that run ends, COLLISION_BACKGROUND ids anywhere; COLLISION_DUPLICATES cluster ids sit on a second current
+    keypoint of the same 256-keypoint tile and as many on one of another tile.  The older block looks up all of them,
+    and absent ids whose home is the first cluster's home, the second's, or a slot inside the first's run.
+    sc["clusters"] names the homes and the ids; sc["duplicates"] the (id, row, other row, same tile) placements."""
+    rng = np.random.default_rng([seed, Kc])
+    rot_H, rel_H = lists("true first")
+    home_a = n_slots - 3
+    pool = np.arange(id_limit, dtype=np.int64)
+    home = host_slot(pool, n_slots)
+
+    def supply(h, n):
+        ids = rng.permutation(pool[home == h])[:n]
+        assert len(ids) == n and all(int(slot(int(i))) == h for i in ids), "the restated hash is not the kernel's"
+        return ids.astype(np.int32)
+
+    a_all = supply(home_a, COLLISION_CLUSTER + 40)
+    a_ids, a_absent = a_all[:COLLISION_CLUSTER], a_all[COLLISION_CLUSTER:]
+    home_b = (home_a + COLLISION_CLUSTER) % n_slots         # the first empty slot behind the first cluster alone
+    b_all = supply(home_b, COLLISION_SECOND + 20)
+    b_ids, b_absent = b_all[:COLLISION_SECOND], b_all[COLLISION_SECOND:]
+    inside_absent = supply(7, 20)                            # a home inside the first cluster's run, past the table's end
+    taken = set(a_all.tolist()) | set(b_all.tolist()) | set(inside_absent.tolist())
+    bg = np.array([i for i in rng.permutation(id_limit)[:2 * COLLISION_BACKGROUND].tolist() if i not in taken]
+                  [:COLLISION_BACKGROUND], np.int32)
+    ids = rng.permutation(np.concatenate([a_ids, b_ids, bg]))
+    n = len(ids)
+    n_dup, n_abs = 2 * COLLISION_DUPLICATES, len(a_absent) + len(b_absent) + len(inside_absent)
+    assert n + n_dup + 20 <= Kc
+    fr0, fr1, _ = _mixed_camera(oracle, rng, n, Kc, free0=n_abs + 30, free1=Kc - n)
+    _relabel(fr0, fr1, ids)
+    # the duplicates: a second current keypoint of a cluster id, in a free row of the same tile or of another one
+    cluster = set(a_ids.tolist()) | set(b_ids.tolist())
+    rows = [k for k in rng.permutation(len(fr1["lm"])).tolist() if int(fr1["lm"][k]) in cluster]
+    free = set(np.flatnonzero(fr1["lm"] < 0).tolist())
+    dups = []
+    for same in (True, False):
+        for _ in range(COLLISION_DUPLICATES):
+            k = rows.pop()
+            other = next(f for f in sorted(free, key=lambda f: (f * 7919) % 1009) if (f // 256 == k // 256) == same)
+            free.remove(other)
+            dups.append((int(fr1["lm"][k]), k, other, same))
+    for lm, k, other, same in dups:
+        fr1["lm"][other] = lm
+        fr1["bp"][other] = rng.normal(size=3)
+    absent = np.concatenate([a_absent, b_absent, inside_absent])
+    free0 = np.flatnonzero(fr0["lm"] < 0)
+    fr0["lm"][free0[:n_abs]] = absent
+    sc = scene("collision-%d" % Kc, euroc_pair()[:1], [[cam_entry(fr0, fr1, rot_H, rel_H)]])
+    sc["clusters"] = dict(home_a=home_a, a_ids=a_ids, home_b=home_b, b_ids=b_ids, absent=absent)
+    sc["duplicates"] = dups
+    return sc
+
+
 # ---- GPU side ----------------------------------------------------------------------------------------------------
-PER_CAM = ("n_corr", "rot_best", "rot_inliers", "rel_best", "rel_inliers", "branch", "removed")
+PER_CAM =("n_corr", "rot_best", "rot_inliers", "rel_best", "rel_inliers", "branch", "removed")
 PER_PAIR = ("total_inliers", "rotation_only", "success")
 U8 = ("branch", "removed", "rotation_only", "success")
 

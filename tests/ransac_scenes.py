@@ -337,8 +337,43 @@ def chunk_scene(oracle, chunk, seed=31):
     return scene("chunks", cams, T_SC, m["hp"], m["obs_begin"], mfs)
 
 
+LAP_K = 260   # the smallest multiple of 4 at which the five-camera rig holds 2 ring + chunk + 7 keypoints (ring = 2 * 256)
+
+
+def lap_totals(ring, chunk):
+    return (2 * ring - 1, 2 * ring, 2 * ring + 1, 2 * ring + chunk + 7)
+
+
+def lap_scene(oracle, ring, chunk, Kc=LAP_K, seed=71):
+    """the five-camera rig on contexts of Kc keypoints (K's 1280 slots do not hold the last total); multiframes with
+    exactly 2 ring - 1, 2 ring, 2 ring + 1 and 2 ring + chunk + 7 correspondences: two whole laps of the kernel's ring
+    and a partial chunk behind them.  Every block is full; the keypoints without a landmark lie between the others, so
+    that the 256-slot tiles add uneven numbers of records.  The second multiframe has too many wrong landmarks to be
+    accepted; the others are accepted and lose their outliers."""
+    m = table()
+    cams, T_SC = rig("hilti")
+    assert lap_totals(ring, chunk)[-1] <= len(cams) * Kc, "the rig no longer holds two laps and a chunk: raise Kc"
+    rng = np.random.default_rng([seed, Kc])
+    usable = usable_rows(m)
+    T_WS = m["T1"]
+    mfs = []
+    for mi, total in enumerate(lap_totals(ring, chunk)):
+        share = np.full(len(cams), total // len(cams))
+        share[:total % len(cams)] += 1
+        shift = int(min(Kc - share.max(), share.min(), 40))   # (uneven blocks, the same total)
+        share[0] += shift
+        share[-1] -= shift
+        frames = []
+        for c, cam in enumerate(cams):
+            fr = make_frame(oracle, cam, compose(T_WS, T_SC[c]), m["p"], usable, Kc, rng, wrong=0.3 if mi == 1 else 0.15, none=0.0)
+            fr["lm"][rng.permutation(Kc)[:Kc - share[c]]] = -1
+            frames.append(fr)
+        mfs.append(dict(frames=frames, H=hypotheses(T_WS, 8, rng, n_random=2), valid=None, T_WS=T_WS))
+    return scene("laps", cams, T_SC, m["hp"], m["obs_begin"], mfs)
+
+
 def reference(tree, sc, remove_outliers=True, use_valid=True, census=None, threshold=R.THRESHOLD):
-    fus = [c.fu for c in sc["cams"]]
+    fus =[c.fu for c in sc["cams"]]
     return [R.consensus(tree, sc["hp"], sc["obs_begin"], mf["frames"], [f["lm"] for f in mf["frames"]], fus, sc["T_SC"],
                         mf["H"], mf["valid"] if use_valid else None, threshold, remove_outliers, census)
             for mf in sc["mfs"]]

@@ -64,8 +64,12 @@ def junk_points(rng, n):
 
 
 # ---- rigs built from geometry ---------------------------------------------------------------------------------------
-def rig_scene(oracle, name, cams, T_SC, pairs, counts, seed, keyframes=None):
-    """counts: per multiframe the keypoints per camera"""
+def rig_scene(oracle, name, cams, T_SC, pairs, counts, seed, keyframes=None, K=K, L=L, dense=False):
+    """counts: per multiframe the keypoints per camera.  K, L: the keypoint capacity of the context and the rows of the
+    table the scene is built for (default: the module's).  dense: every keypoint carries a table row of its own, no row
+    is initialised, every k0 matches a k1 of its own and every match is initialisable (equal counts per multiframe), so
+    that a pair's key table holds 2 count entries and every row whose first camera comes to the pair with its ids still
+    untouched re-initialises its landmark into the overlay."""
     rng = np.random.default_rng(seed)
     n_cams, n_pts = len(cams), 300
     d = rng.normal(size=(n_pts, 3))
@@ -75,12 +79,15 @@ def rig_scene(oracle, name, cams, T_SC, pairs, counts, seed, keyframes=None):
     scale = rng.choice(np.array([1.0, 1.0, 2.0, -1.0, 0.25]), n_pts)  # homogeneous: any non-zero multiple, sign included
     hp = np.concatenate([hp * scale[:, None], junk_points(rng, L - n_pts)])
     initialised = (rng.random(L) < 0.55).astype(np.uint8)
+    if dense:
+        initialised[:] = 0
     bad_ids = np.array([-2, L, L + 5, -1000, 2 ** 31 - 1], np.int64)
     mfs = []
     for mi, cnt in enumerate(counts):
         T_WS = (rodrigues(rng.normal(size=3), 0.03 * rng.random()), 0.05 * rng.normal(size=3))
         T_WC = [RS.compose(T_WS, T_SC[c]) for c in range(n_cams)]
         kps, ids, pt_of, kp_of = [], [], [], []
+        own_rows = rng.permutation(L)[:sum(cnt)] if dense else None
         for c, cam in enumerate(cams):
             C, r = T_WC[c][0].reshape(3, 3), T_WC[c][1]
             xy, pts = [], []
@@ -106,6 +113,8 @@ def rig_scene(oracle, name, cams, T_SC, pairs, counts, seed, keyframes=None):
             idc[other] = rng.integers(0, L, int(other.sum()))       # any table row
             bad = (u >= 0.45) & (u < 0.5)
             idc[bad] = rng.choice(bad_ids, int(bad.sum()))          # outside [-1, L): read as none
+            if dense:
+                idc = own_rows[sum(cnt[:c]):sum(cnt[:c + 1])]
             kps.append(k), ids.append(idc.astype(np.int32)), pt_of.append(pts_a)
             kp_of.append({j: i for i, j in reversed(list(enumerate(pts))) if j >= 0})
         matches = []
@@ -113,10 +122,15 @@ def rig_scene(oracle, name, cams, T_SC, pairs, counts, seed, keyframes=None):
             n0, n1 = cnt[c0], cnt[c1]
             r = rows(n0)
             hubs = rng.integers(0, n1, 4) if n1 else np.zeros(0, np.int64)
+            if dense:
+                assert n0 == n1
+                k1_of = rng.permutation(n1)
             for k0 in range(n0):
                 j = int(pt_of[c0][k0])
                 u = rng.random()
-                if j >= 0 and j in kp_of[c1] and u < 0.8:
+                if dense:
+                    k1, p = int(k1_of[k0]), P[j] if j >= 0 else rng.uniform(-4, 4, 3)
+                elif j >= 0 and j in kp_of[c1] and u < 0.8:
                     k1, p = kp_of[c1][j], P[j] + rng.normal(0, 0.004, 3)
                 elif n1 and u < 0.9:
                     k1 = int(rng.choice(hubs)) if rng.random() < 0.7 else int(rng.integers(0, n1))
@@ -126,13 +140,51 @@ def rig_scene(oracle, name, cams, T_SC, pairs, counts, seed, keyframes=None):
                 else:
                     continue
                 r["k1"][k0], r["dist"][k0] = k1, int(rng.integers(0, 60))
-                r["initialisable"][k0] = int(rng.choice([0, 1, 1, 7]))
+                r["initialisable"][k0] = int(rng.choice([1, 7] if dense else [0, 1, 1, 7]))
                 s = 1.0 if r["initialisable"][k0] else rng.choice([1.0, 0.5, -0.5])  # (not normalised when parallel)
                 r["hp_W"][k0] = np.concatenate([p * s, [s]])
             matches.append(r)
         kf = True if keyframes is None else bool(keyframes[mi])
         mfs.append(dict(kps=kps, ids=ids, T_WC=T_WC, matches=matches, keyframe=kf))
-    return dict(name=name, cams=cams, hp=hp, initialised=initialised, pairs=list(pairs), mfs=mfs)
+    return dict(name=name, cams=cams, hp=hp, initialised=initialised, pairs=list(pairs), mfs=mfs, K=K)
+
+
+# ---- the edges of the kernel's two open-addressed tables ---------------------------------------------------------------
+MAX_LDS = 65280   # the call's limit on the LDS of one work-group
+
+
+def lds_bytes(n_cams, Kc):
+    """stereo_insert_lds_bytes restated: (bytes, log2 of the overlay's slots, log2 of the key table's slots) -- both
+    tables have the first power of two ABOVE what they may hold (n_cams Kc re-initialising rows, 2 Kc keys)"""
+    a = b = 1
+    while (1 << a) <= n_cams * Kc:
+        a += 1
+    while (1 << b) <= 2 * Kc:
+        b += 1
+    return 4 * (n_cams * Kc + (1 << a) + 3 * Kc + (1 << b)), a, b
+
+
+def largest_capacity(n_cams):
+    """the largest keypoint capacity whose tables fit MAX_LDS"""
+    return max(k for k in range(1, 4097) if lds_bytes(n_cams, k)[0] <= MAX_LDS)
+
+
+def table_edge_scene(oracle, n_cams, Kc, seed=7):
+    """one dense multiframe of full blocks on a rig of dyadic cameras in a ring of pairs (0, 1), (1, 2), ..., (n - 1, 0):
+    every camera is once the first of a pair, so n_cams Kc rows re-initialise a landmark -- all the overlay may hold"""
+    cams = [camera("dyadic")] * n_cams
+    T_SC = [(I3.copy(), np.array([0.125 * c, 0.0, 0.0])) for c in range(n_cams)]
+    pairs = [(c, (c + 1) % n_cams) for c in range(n_cams)]
+    return rig_scene(oracle, "table-edge-%dx%d" % (n_cams, Kc), cams, T_SC, pairs, [(Kc,) * n_cams], seed, K=Kc,
+                     L=n_cams * Kc + 77, dense=True)
+
+
+def reference_of(oracle, tree, sc):
+    """(per multiframe results, census) of a scene, uncached"""
+    oracle.set_reduction(tree)
+    census = SR.new_census()
+    return [SR.stereo_insert(oracle, tree, sc["hp"], sc["initialised"], sc["cams"], sc["pairs"], sc["K"], mf["kps"],
+                             mf["ids"], mf["T_WC"], mf["matches"], mf["keyframe"], census) for mf in sc["mfs"]], census
 
 
 def euroc_T_SC():
@@ -431,6 +483,7 @@ def prepare(fe, sc, layout="multiframe-major", alias=False, optional=True, keyfr
     """the device tensors of one call over the multiframes `only` (default all); synchronises"""
     import torch
     from okvis2_amd import multigpu
+    K = sc.get("K", globals()["K"])
     assert fe.max_keypoints == K
     mfs = sc["mfs"] if only is None else [sc["mfs"][i] for i in only]
     B, n_cams, n_pairs = len(mfs), len(sc["cams"]), len(sc["pairs"])

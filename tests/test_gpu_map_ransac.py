@@ -2,8 +2,8 @@
 (remove_outliers_frames_kernel) against ransac_ref.py under both orders of the FP64 sums: counts, verdicts, states and
 landmark rows for equality, distances as uint64 patterns; rows at or past a block's keypoint count keep their
 sentinels.  Scenes: ransac_scenes.py (general rigs of 1, 2 and 5 cameras over the four camera models, the directed
-cases, both knife edges, the verdict table, the chunk edges; the projection statuses, the max_error edge and mixed
-camera slots of removeOutliers)."""
+cases, both knife edges, the verdict table, the chunk edges, whole laps of the kernel's record ring under both of its
+policies; the projection statuses, the max_error edge and mixed camera slots of removeOutliers)."""
 import ctypes as C
 import dataclasses
 
@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import gpu_common as G
+import place_scenes as PS
 import ransac_ref as R
 import ransac_scenes as S
 from okvis2_amd import capi, synth
@@ -21,12 +22,12 @@ torch = pytest.importorskip("torch")
 _FRONTENDS = {}
 
 
-def _frontend(cams, n_set=None):
-    """a context of the first camera's size with K = ransac_scenes.K whose first n_set slots hold `cams`"""
+def _frontend(cams, n_set=None, Kc=S.K):
+    """a context of the first camera's size with K = ransac_scenes.K (or Kc) whose first n_set slots hold `cams`"""
     n_set = len(cams) if n_set is None else n_set
-    key = tuple((c.w, c.h, c.fu, c.fv, c.cu, c.cv, c.dist_type, tuple(c.d)) for c in cams) + (n_set,)
+    key = tuple((c.w, c.h, c.fu, c.fv, c.cu, c.cv, c.dist_type, tuple(c.d)) for c in cams) + (n_set, Kc)
     if key not in _FRONTENDS:
-        cfg = dataclasses.replace(synth.euroc_config(), w=cams[0].w, h=cams[0].h, cams=list(cams), max_kpts=S.K)
+        cfg = dataclasses.replace(synth.euroc_config(), w=cams[0].w, h=cams[0].h, cams=list(cams), max_kpts=Kc)
         fe = G.make_frontend(cfg)
         for i, c in enumerate(cams[:n_set]):
             fe.set_camera(i, c)
@@ -118,6 +119,46 @@ def test_chunk_edges(oracle, fp64_order):
     refs = S.reference(tree, sc)
     got = _run(_frontend(sc["cams"]), sc, refs, (sc["name"], fp64_order))
     assert got["n_corr"].tolist() == [chunk - 1, chunk, chunk + 1, 2 * chunk + 1]
+
+
+def test_whole_laps_of_the_ring(oracle, fp64_order):
+    """2 ring - 1, 2 ring, 2 ring + 1 and 2 ring + chunk + 7 correspondences: every ring position is written at least
+    twice, and the last partial chunk lies behind the second wrap"""
+    tree = _tree(fp64_order)
+    ring, chunk = capi.Frontend._test_ransac_ring_records(), capi.Frontend._test_ransac_chunk_records()
+    sc = S.lap_scene(oracle, ring, chunk)
+    fe = _frontend(sc["cams"], Kc=S.LAP_K)
+    assert fe.max_keypoints == S.LAP_K
+    refs = S.reference(tree, sc)
+    got = _run(fe, sc, refs, (sc["name"], fp64_order))
+    print(sc["name"], fp64_order, "correspondences", got["n_corr"].tolist(), "inliers", got["n_inl"].tolist())
+    assert got["n_corr"].tolist() == list(S.lap_totals(ring, chunk)) and min(got["n_corr"].tolist()) // ring == 1
+    assert got["n_corr"].tolist()[1] == 2 * ring and np.all(got["best"] >= 0) and got["accepted"].tolist() == [1, 0, 1, 1]
+    _run(fe, sc, refs, (sc["name"], fp64_order, "in place"), alias=True)
+    _run(fe, sc, S.reference(tree, sc, remove_outliers=False), (sc["name"], fp64_order, "no removal"), remove_outliers=False)
+
+
+def test_whole_laps_of_the_ring_place_policy(oracle, fp64_order):
+    """the same multiframes through okvfe_place_consensus_blocks_device (the kPlace policy of the kernel), their
+    landmark rows as hand-built claims: ungated, and with the gates 0, 1, 2, 2 (a gated multiframe compacts its two
+    laps and scores nothing)"""
+    tree = _tree(fp64_order)
+    ring, chunk = capi.Frontend._test_ransac_ring_records(), capi.Frontend._test_ransac_chunk_records()
+    base = S.lap_scene(oracle, ring, chunk)
+    fe = _frontend(base["cams"], Kc=S.LAP_K)
+    for gates in (None, (0, 1, 2, 2)):
+        mfs = [PS._mf(mf["frames"], None, None, mf["H"], T_WS=mf["T_WS"], ml=[f["lm"].astype(np.int32) for f in mf["frames"]],
+                      gate=None if gates is None else gates[i]) for i, mf in enumerate(base["mfs"])]
+        sc = PS.scene("laps-place", base["cams"], base["T_SC"], base["hp"], mfs)
+        refs = PS.consensus_reference(tree, sc, [mf["ml"] for mf in mfs], gates)
+        T = PS.prepare(fe, sc)
+        PS.launch_consensus(fe, sc, T)
+        got = PS.download(T)
+        PS.check_consensus(sc, got, refs, (sc["name"], fp64_order, gates))
+        print(sc["name"], fp64_order, "gates", gates, "correspondences", got["n_corr"].tolist(), "verdicts", got["verdict"].tolist())
+        assert got["n_corr"].tolist() == list(S.lap_totals(ring, chunk))
+        assert got["verdict"].tolist() == [3 if gates is None else 0, 2, 3, 3]
+        assert (got["best"][0] == -1) == (gates is not None) and np.all(got["best"][1:] >= 0)
 
 
 def test_batches_slices_and_a_side_stream(oracle, fp64_order):

@@ -378,6 +378,41 @@ def test_equal_to_the_b1_chain(oracle):
     assert np.array_equal(dev.get("scores", np.uint64, M, 40)[m], scores.view(np.uint64))
 
 
+def test_the_largest_feature_count(oracle):
+    """four cameras of 2048 keypoints, BOW_MAX_FEATURES keys: the 8192-key sort and its 32 run-length rounds (8192, 8191,
+    4097 features; 4096 next to them), the descent of the SMALL tree out of LDS (8192 keys leave no room for its nodes),
+    a run of 5000 keys (rounds without a run head; one weight added 5000 times) alone and behind smaller words, and runs
+    that start and end on round boundaries; under the summing weightings with and without normalise_l1.  Then one query
+    of these vectors against 40 entries.  The scene's premises: test_capacity_scenes_host.py."""
+    base = R.shipped_vocabulary(oracle)
+    scene = S.capacity_scene(oracle, base)
+    n_cams, K, M = scene["n_cams"], scene["K"], len(scene["feats"])
+    assert n_cams * K == capi.BOW_MAX_FEATURES and [sum(c) for c in scene["counts"]][:4] == list(S.CAPACITY_COUNTS)
+    n_nodes = len(base["word"])
+    assert n_nodes <= S.LDS_NODES and n_nodes * 48 + n_cams * K * 4 > S.LDS_BUDGET  # the nodes do not fit beside the keys
+    assert not S.nodes_in_lds(n_nodes, n_cams * K)
+    fe, dev = _frontend(K), S.Dev(torch)
+    seen = set()
+    for weighting in (0, 1):
+        for norm in (True, False):
+            voc = dict(base, weighting=weighting, normalise_l1=norm)
+            refs = S.reference_vectors(oracle, voc, scene)
+            vec, stride = _vectors(fe, dev, voc, scene)
+            S.check_vectors(dev, refs, stride, ("capacity", weighting, norm))
+            _check_word_ids(dev, scene, refs)
+            assert refs[4][1].tolist() == [scene["long_word"]] and len(refs[5][1]) == 41
+            seen.add(refs[4][2].tobytes())
+    assert len(seen) == 2  # 1.0 normalised, 5000 additions of the weight otherwise
+    refs = S.reference_vectors(oracle, base, scene)
+    vec, stride = _vectors(fe, dev, base, scene)
+    S.check_vectors(dev, refs, stride, "capacity")
+    db = S.host_database(oracle, base, scene, 40)
+    dbd = dev.database(db)
+    scores, walks = _query(fe, dev, oracle, dbd, db, vec, refs, None, 0.02, 40, True, "capacity")
+    print("capacity: words", [len(r[1]) for r in refs], "listed", [w[0] for w in walks], "candidates", [len(w[1]) for w in walks])
+    assert max(w[0] for w in walks) >= 30
+
+
 def test_refusals(oracle):
     """errors before anything is launched: a stride that could truncate, more features than the sort holds, NULLs"""
     K = 700

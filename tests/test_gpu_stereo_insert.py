@@ -2,7 +2,8 @@
 landmark_out and counts of every row of every scene of stereo_insert_scenes.py (whose census floor
 test_stereo_insert_scenes_host.py holds), rows at or past a block's count keeping their sentinels.  Under both orders of
 the FP64 sums; both block layouts; landmark_out in place and apart; without action / lm; without keyframe flags; a batch
-cut into two calls; the chain detection -> matcher per pair -> bookkeeping on a side stream with nothing waited for in
+cut into two calls; the edges of the kernel's two tables
+(an overlay with one slot to spare, the largest capacity the LDS limit admits); the chain detection -> matcher per pair -> bookkeeping on a side stream with nothing waited for in
 between, for a stereo pair and Hilti's five cameras; the C++ mirror through its CLI; the error paths, which launch
 nothing."""
 import ctypes
@@ -91,6 +92,54 @@ def test_scene(oracle, fp64_order, name):
                 assert np.all(part["lm_out"][:rows] == S.SENTINEL)
             S.launch_slice(fe, sc, T, 0, B // 2)
             S.check(sc, T, refs, what + ("two calls", layout))
+
+
+def _edge_frontend(n_cams, Kc):
+    fe = capi.Frontend(S.W, S.H, 10.0, 0, 50, Kc, match_threshold=60, num_cameras=n_cams)
+    for c in range(n_cams):
+        fe.set_camera(c, S.camera("dyadic"))
+    return fe
+
+
+@pytest.mark.parametrize("which", ("overlay-one-slot-spare", "largest-capacity"))
+def test_table_edges(oracle, fp64_order, which):
+    """(a) three cameras of 341 keypoints: n_cams K = 1023 rows re-initialise a landmark into an overlay of 1024 slots;
+    (b) two cameras of the largest capacity the LDS limit admits (one more is refused): 3250 overlay entries and 3250 keys
+    per pair in tables of 4096 slots.  One dense multiframe of the scene generator each: every keypoint carries a row of
+    its own and is matched, every match re-initialises (premises: test_capacity_scenes_host.py)."""
+    tree = _tree(fp64_order)
+    if which == "overlay-one-slot-spare":
+        n_cams = 3
+        Kc = next(k for k in range(S.K + 1, 4097) if n_cams * k == (1 << S.lds_bytes(n_cams, k)[1]) - 1)
+        assert (Kc, S.lds_bytes(n_cams, Kc)[1]) == (341, 10)
+    else:
+        n_cams = 2
+        Kc = S.largest_capacity(n_cams)
+        assert S.lds_bytes(n_cams, Kc)[0] <= S.MAX_LDS < S.lds_bytes(n_cams, Kc + 1)[0]
+        # the call's own answer one keypoint further: refused before anything is read or launched
+        over = _edge_frontend(n_cams, Kc + 1)
+        try:
+            d = torch.zeros(64, dtype=torch.uint8, device="cuda")
+            tab = over.make_landmark_table_device(0, 0, 0, 0, 0, 0, 0, 0, 0, 0)
+            res = over.make_stereo_insert_device(None, None, d.data_ptr(), d.data_ptr())
+            with pytest.raises(capi.OkvfeError) as e:
+                over.stereo_insert_blocks_device(tab, None, d.data_ptr(), n_cams, 1, 1, [(0, 1)], list(range(n_cams)),
+                                                 [(S.I3, np.zeros(3))] * n_cams, d.data_ptr(), d.data_ptr(), None, res)
+            assert e.value.status == capi.ERR_UNSUPPORTED and str(S.lds_bytes(n_cams, Kc + 1)[0]) in str(e.value), str(e.value)
+        finally:
+            over.close()
+    sc = S.table_edge_scene(oracle, n_cams, Kc)
+    refs, _ = S.reference_of(oracle, tree, sc)
+    fe = _edge_frontend(n_cams, Kc)
+    try:
+        got = _run(fe, sc, refs, (fp64_order,))
+        _, ov_log2, kh_log2 = S.lds_bytes(n_cams, Kc)
+        print(sc["name"], fp64_order, "counts", got["counts"][0].tolist(), "| overlay load %d / %d" % (got["counts"][0, 2], 1 << ov_log2),
+              "| key table load %d / %d per pair" % (2 * Kc, 1 << kh_log2))
+        assert got["counts"][0].tolist() == [n_cams * Kc, 0, n_cams * Kc, 0]
+        _run(fe, sc, refs, (fp64_order, "camera-major, in place"), layout="camera-major", alias=True)
+    finally:
+        fe.close()
 
 
 def test_edge_verdicts_on_the_device(oracle, fp64_order):
