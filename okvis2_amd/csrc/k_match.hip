@@ -19,10 +19,13 @@
 // running best, so "first k1 reaching the smallest gated distance" is found in rounds: a
 // branch-free scan yields the two smallest admissible (dist, k1) keys per lane, the FP64 gate runs
 // once per key for all lanes together, rejected lanes raise their floor and rescan; the segments
-// are merged by (dist, segment).  Integer-ALU bound (v_xor + v_bcnt_u32_b32, 24 VALU per pair);
-// inputs are 2 x 33.6 KB per EuRoC stereo frame, so HBM is not the limit.
+// are merged by (dist, segment).  Integer-ALU bound: per descriptor and wave the first scan issues
+// 27 vector instructions (12 v_xor, 12 v_bcnt_u32_b32, 1 for the key, 2 to insert it), a re-scan 32
+// (scan_top; the counts of the listing are in profiles/match_scan.txt); inputs are 2 x 33.6 KB per
+// EuRoC stereo frame, so HBM is not the limit.
 #include "camera_dev.h"
 #include <algorithm>
+#include <cassert>
 
 #include "okvfe_internal.h"
 #include "bow_dev.h"
@@ -181,14 +184,34 @@ constexpr uint32_t kNoKey = 0xFFFFFFFFu;
 #endif
 constexpr int kNarrowScans = 1;  // scans of a segment that keep two keys; every later one keeps OKVFE_MATCH_MORE
 
-// One scan of segment [k1_lo, k1_hi) of the other side's descriptors: the two smallest keys
-// ((dist << 22) | k1) + 1 that exceed floor_key, have dist < threshold and are not flagged in
-// skip1 (may be null).  The descriptors (and flags) are staged in LDS by coalesced vector loads
-// and read back as broadcasts; a segment of at most kStereoChunk descriptors stays resident
-// (`resident`: already loaded by load_scan_chunk before the first round).
+// One scan of segment [k1_lo, k1_hi) of the other side's descriptors: the K smallest keys
+// (dist << 22) | (k1 + 1) that exceed floor_key, have dist < threshold and are not flagged in
+// skip1 (may be null).  The descriptors are staged in LDS by coalesced vector loads and read back
+// as broadcasts; a segment of at most kStereoChunk descriptors stays resident (`resident`: already
+// loaded by load_scan_chunk before the first round).
+//
+// The scan costs 12 v_xor + 12 v_bcnt + 1 (key) + K (insertion) vector instructions per descriptor,
+// and one subtraction more above a floor (profiles/match_scan.txt has the listing's counts):
+//   popcount   one chain through v_bcnt_u32_b32's own accumulator operand, no adds.  (Left to the
+//              compiler the sum becomes twelve v_bcnt + five v_add3.)  The four descriptors of the
+//              unrolled body are four independent chains.
+//   key        k1 + 1 <= 2^22 - 1 (kScanMaxN1), so "| (k1 + 1)" equals the "| k1, + 1" of the key's
+//              definition and is ONE v_lshl_or_b32 with a wave-uniform third operand.
+//   threshold  is the sentinel: c[] starts at LIM = (threshold << 22) + 1.  A key with dist >=
+//              threshold is >= LIM and displaces nothing, one with dist < threshold is < LIM.
+//   floor      the scan works on u = key - (floor_key + 1), unsigned, against LIM - (floor_key + 1):
+//              keys at or below the floor wrap above every limit.  FLOOR = false is the first
+//              scan's form (floor_key == 0): no subtraction.
+//   skip       the flag sits in the staged low word (kNoKey instead of k1 + 1): such a key is
+//              >= LIM in either form.  No select.
+//   insertion  c[] ascending, so min(c[t], max(c[t-1], key)) = med3(c[t-1], c[t], key): K - 1
+//              v_med3_u32 and one v_min_u32.
+// Entries still at the limit leave as kNoKey, survivors get floor_key + 1 back: once per scan.
+constexpr uint32_t kMaxDist = 8 * OKVFE_DESC_BYTES;  // a distance is at most 384, so min(threshold, 385) decides the same
+constexpr int kScanMaxN1 = (1 << 22) - 1;            // k1 + 1 must leave the key's distance bits alone
 struct ScanChunk {
   uint4* desc;     // kStereoChunk * 3
-  uint8_t* skip;   // kStereoChunk
+  uint32_t* low;   // kStereoChunk: the key's low word, k1 + 1 or kNoKey for a flagged k1 (HAS_SKIP only)
 };
 __device__ __forceinline__ void load_scan_chunk(const ScanChunk& C, const uint8_t* __restrict__ desc1,
                                                 const uint8_t* __restrict__ skip1, int c0, int cnt) {
@@ -196,56 +219,88 @@ __device__ __forceinline__ void load_scan_chunk(const ScanChunk& C, const uint8_
   __builtin_amdgcn_wave_barrier();
   for (int i = threadIdx.x; i < cnt * 3; i += 64) C.desc[i] = src[i];
   if (skip1)
-    for (int i = threadIdx.x; i < cnt; i += 64) C.skip[i] = skip1[c0 + i];
+    for (int i = threadIdx.x; i < cnt; i += 64) C.low[i] = skip1[c0 + i] ? kNoKey : (uint32_t)(c0 + i + 1);
   __builtin_amdgcn_wave_barrier();
 }
-// K smallest admissible keys, ascending in c[0 .. K)
-template <int K, bool HAS_SKIP>
+__device__ __forceinline__ uint32_t bcnt_first(uint32_t x) {
+  uint32_t d;
+  asm("v_bcnt_u32_b32 %0, %1, 0" : "=v"(d) : "v"(x));
+  return d;
+}
+__device__ __forceinline__ uint32_t bcnt_acc(uint32_t x, uint32_t acc) {  // popcount(x) + acc
+  uint32_t d;
+  asm("v_bcnt_u32_b32 %0, %1, %2" : "=v"(d) : "v"(x), "v"(acc));
+  return d;
+}
+__device__ __forceinline__ uint32_t med3_u32(uint32_t a, uint32_t b, uint32_t c) {
+  uint32_t d;
+  asm("v_med3_u32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
+  return d;
+}
+__device__ __forceinline__ uint32_t hamming_chain(const Desc12& a, const uint32_t* __restrict__ b) {
+  uint32_t c = bcnt_first(a.w[0] ^ b[0]);
+#pragma unroll
+  for (int i = 1; i < 12; ++i) c = bcnt_acc(a.w[i] ^ b[i], c);
+  return c;
+}
+// K smallest admissible keys, ascending in c[0 .. K); kNoKey where there are fewer
+template <int K, bool HAS_SKIP, bool FLOOR>
 __device__ __forceinline__ void scan_top(const Desc12& d0, const ScanChunk& C,
                                          const uint8_t* __restrict__ desc1,
                                          const uint8_t* __restrict__ skip1, int k1_lo, int k1_hi,
                                          bool resident, uint32_t floor_key, uint32_t threshold,
                                          uint32_t (&c)[K]) {
+  const uint32_t lim = (min(threshold, kMaxDist + 1u) << 22) + 1u;
+  const uint32_t base = FLOOR ? floor_key + 1u : 0u;  // (a floor is a key this lane was given: < lim)
+  const uint32_t lim_u = lim - base;
 #pragma unroll
-  for (int t = 0; t < K; ++t) c[t] = kNoKey;
+  for (int t = 0; t < K; ++t) c[t] = lim_u;
   for (int c0 = k1_lo; c0 < k1_hi; c0 += kStereoChunk) {
     const int cnt = min(kStereoChunk, k1_hi - c0);
     if (!resident) load_scan_chunk(C, desc1, HAS_SKIP ? skip1 : nullptr, c0, cnt);
     auto insert = [&](uint32_t dist, int jj) {
-      uint32_t key = ((dist << 22) | (uint32_t)(c0 + jj)) + 1u;
-      bool ok = key > floor_key && dist < threshold;
-      if (HAS_SKIP) ok = ok && C.skip[jj] == 0;
-      key = ok ? key : kNoKey;
+      const uint32_t low = HAS_SKIP ? C.low[jj] : (uint32_t)(c0 + jj + 1);
+      uint32_t key = (dist << 22) | low;
+      if (FLOOR) key -= base;
 #pragma unroll
-      for (int t = K - 1; t > 0; --t) c[t] = min(c[t], max(c[t - 1], key));  // insertion into the sorted K
+      for (int t = K - 1; t > 0; --t) c[t] = med3_u32(c[t - 1], c[t], key);  // insertion into the sorted K
       c[0] = min(c[0], key);
     };
-    int j = 0;  // (declared out here on purpose: `for (int j = 0; ...)` compiles to a different schedule of the stereo kernels)
-#pragma unroll 4
+    // four descriptors per trip, unrolled by hand: `#pragma unroll 4` is refused for a body that holds asm statements
+    int j = 0;
+    for (; j + 4 <= cnt; j += 4) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        insert(hamming_chain(d0, reinterpret_cast<const uint32_t*>(C.desc + 3 * (j + u))), j + u);
+    }
     for (; j < cnt; ++j)
-      insert((uint32_t)hamming(d0, reinterpret_cast<const uint32_t*>(C.desc + 3 * j)), j);
+      insert(hamming_chain(d0, reinterpret_cast<const uint32_t*>(C.desc + 3 * j)), j);
   }
+#pragma unroll
+  for (int t = 0; t < K; ++t) c[t] = c[t] < lim_u ? c[t] + base : kNoKey;
 }
+// the first scan of a segment: two keys, no floor yet
+static_assert(kNarrowScans == 1, "scan_top2 is the floor-free form: only a lane's first scan may use it");
 template <bool HAS_SKIP>
 __device__ __forceinline__ void scan_top2(const Desc12& d0, const ScanChunk& C,
                                           const uint8_t* __restrict__ desc1,
                                           const uint8_t* __restrict__ skip1, int k1_lo, int k1_hi,
-                                          bool resident, uint32_t floor_key, uint32_t threshold,
+                                          bool resident, uint32_t threshold,
                                           uint32_t* c1_out, uint32_t* c2_out) {
   uint32_t c[2];
-  scan_top<2, HAS_SKIP>(d0, C, desc1, skip1, k1_lo, k1_hi, resident, floor_key, threshold, c);
+  scan_top<2, HAS_SKIP, false>(d0, C, desc1, skip1, k1_lo, k1_hi, resident, 0u, threshold, c);
   *c1_out = c[0];
   *c2_out = c[1];
 }
 
 // The reference walks k1 upwards and runs the geometric gate whenever dist < best; as the gate does not depend on
 // `best`, its outcome is the gated candidate with the smallest (dist, k1).  Each round therefore scans the segment
-// branch-free for the smallest keys above the last rejected one (wave-uniform descriptor loads, 24 VALU per k1) and
+// branch-free for the smallest keys above the last rejected one (wave-uniform descriptor loads, 27 VALU per k1) and
 // the FP64 gate runs for many lanes together, instead of once per k1 for the one or two lanes that improved there.
 // The first scan brings the two smallest admissible keys of the segment: a rejected best candidate usually has its
 // successor at hand, so the tail of the kernel is not set by re-scans.  A lane that is still undecided after them sits
 // in look-alike content (repetitive texture: 5-15 candidates below the threshold, most of them rejected by the gate):
-// every further scan then brings SIX keys (insertion costs 5 min/max pairs more per descriptor, a re-scan 24 + 7).
+// every further scan then brings SIX keys (insertion costs four v_med3 more per descriptor and the floor one subtraction: 32).
 // POOLED gates (round 6; the per-segment, shared-bound and one-global-order forms it was measured against are in
 // LAB_NOTES.md).  The FP64 gate is ~700 instructions and runs wave-wide for whichever lanes hold a
 // candidate -- a dozen of 64 in a typical segment wave, so the four waves of a block each paid a whole gate for a
@@ -305,12 +360,12 @@ __device__ void match_stereo_rows(const PairParams& P, const BlockView& I0, cons
     // ---- scan: a wave scans when none of its lanes still holds a key (the lanes of a wave advance in step)
     if (!__any(state == kHave) && __any(state == kNeedScan)) {  // wave-uniform
       if (n_scans < kNarrowScans) {
-        scan_top2<false>(d0, chunk, I1.desc, nullptr, k1_lo, k1_hi, resident, floor_key, (uint32_t)threshold, &cs[0], &cs[1]);
+        scan_top2<false>(d0, chunk, I1.desc, nullptr, k1_lo, k1_hi, resident, (uint32_t)threshold, &cs[0], &cs[1]);
 #pragma unroll
         for (int u = 2; u < kMore; ++u) cs[u] = kNoKey;
         n_c = 2;
       } else {
-        scan_top<kMore, false>(d0, chunk, I1.desc, nullptr, k1_lo, k1_hi, resident, floor_key, (uint32_t)threshold, cs);
+        scan_top<kMore, false, true>(d0, chunk, I1.desc, nullptr, k1_lo, k1_hi, resident, floor_key, (uint32_t)threshold, cs);
         n_c = kMore;
       }
       ++n_scans;
@@ -630,7 +685,7 @@ __device__ void match_motion_rows(const PairParams& P, const DeviceCamera& camer
                                   okvfe_motion_match* __restrict__ out) {
   __shared__ SegBestMotion seg_best[kStereoSegs - 1][64];
   __shared__ uint4 seg_desc[kStereoSegs][kStereoChunk * 3];
-  __shared__ uint8_t seg_skip[kStereoSegs][kStereoChunk];
+  __shared__ uint32_t seg_low[kStereoSegs][kStereoChunk];
   const int seg = threadIdx.y;
   const int per_seg = (I1.n + kStereoSegs - 1) / kStereoSegs;
   const int k1_lo = min(seg * per_seg, I1.n), k1_hi = min(k1_lo + per_seg, I1.n);
@@ -653,7 +708,7 @@ __device__ void match_motion_rows(const PairParams& P, const DeviceCamera& camer
   double hps[4] = {0, 0, 0, 0};
   uint32_t floor_key = 0;
   bool done = !active;
-  const ScanChunk chunk{seg_desc[seg], seg_skip[seg]};
+  const ScanChunk chunk{seg_desc[seg], seg_low[seg]};
   const bool resident = k1_hi - k1_lo <= kStereoChunk;
   const bool has_skip = I1.flag != nullptr;  // kernel-uniform
   if (resident) load_scan_chunk(chunk, I1.desc, I1.flag, k1_lo, k1_hi - k1_lo);
@@ -667,16 +722,14 @@ __device__ void match_motion_rows(const PairParams& P, const DeviceCamera& camer
     int n_c = 2;
     if (n_scans < kNarrowScans) {
       if (has_skip)
-        scan_top2<true>(d0, chunk, I1.desc, I1.flag, k1_lo, k1_hi, resident, floor_key,
-                        (uint32_t)threshold, &cs[0], &cs[1]);
+        scan_top2<true>(d0, chunk, I1.desc, I1.flag, k1_lo, k1_hi, resident, (uint32_t)threshold, &cs[0], &cs[1]);
       else
-        scan_top2<false>(d0, chunk, I1.desc, nullptr, k1_lo, k1_hi, resident, floor_key,
-                         (uint32_t)threshold, &cs[0], &cs[1]);
+        scan_top2<false>(d0, chunk, I1.desc, nullptr, k1_lo, k1_hi, resident, (uint32_t)threshold, &cs[0], &cs[1]);
     } else {
       if (has_skip)
-        scan_top<kMore, true>(d0, chunk, I1.desc, I1.flag, k1_lo, k1_hi, resident, floor_key, (uint32_t)threshold, cs);
+        scan_top<kMore, true, true>(d0, chunk, I1.desc, I1.flag, k1_lo, k1_hi, resident, floor_key, (uint32_t)threshold, cs);
       else
-        scan_top<kMore, false>(d0, chunk, I1.desc, nullptr, k1_lo, k1_hi, resident, floor_key, (uint32_t)threshold, cs);
+        scan_top<kMore, false, true>(d0, chunk, I1.desc, nullptr, k1_lo, k1_hi, resident, floor_key, (uint32_t)threshold, cs);
       n_c = kMore;
     }
     ++n_scans;
@@ -1543,12 +1596,15 @@ BlockOffsets block_offsets(const BlockLayout& L) {
 MapBatch map_batch(const uint8_t* blocks, const BlockLayout& L, int kp_cap, size_t frame_stride) {
   return {blocks, (int)L.o_kps, (int)L.o_desc, (int)L.o_bp, (int)L.total, kp_cap, frame_stride, nullptr};
 }
+// the gated matchers' keys hold k1 + 1 in 22 bits (scan_top): n1 = the most keypoints the scanned side can have
+void check_scan_range(int n1) { assert(n1 <= kScanMaxN1 && "more keypoints than the scan's keys can index"); }
 }  // namespace
 
 void launch_match_motion_blocks(const PairParams& pair, const DeviceCamera* camera, int w, int h,
                                 const BlockLayout& L, const uint8_t* block0, const uint8_t* block1,
                                 const uint8_t* skip0, const uint8_t* matched1, int kp_cap,
                                 int threshold, okvfe_motion_match* out, hipStream_t stream, bool rt8) {
+  check_scan_range(kp_cap);
   hipLaunchKernelGGL(rt8 ? match_motion_blocks_kernel<true> : match_motion_blocks_kernel<false>, dim3((kp_cap + 63) / 64), dim3(64, kStereoSegs), 0,
                      stream, pair, camera, w, h, block_offsets(L), block0, block1, skip0, matched1, threshold, out);
 }
@@ -1557,6 +1613,7 @@ void launch_match_motion_pairs(const MotionPairRecord* recs, int n_pairs, const 
                                const BlockLayout& L, const uint8_t* blocks0, const uint8_t* blocks1,
                                const uint8_t* skip0, const uint8_t* matched1, int kp_cap, int threshold,
                                okvfe_motion_match* out, hipStream_t stream, bool rt8) {
+  check_scan_range(kp_cap);
   if (n_pairs <= 0 || kp_cap <= 0) return;
   constexpr int kMaxGridY = 65535;
   for (int first = 0; first < n_pairs; first += kMaxGridY) {
@@ -1588,6 +1645,7 @@ void launch_match_stereo_blocks(const PairParams& pair, const BlockLayout& L, co
                                 const uint8_t* blocks1, int n_frames, int kp_cap, int threshold,
                                 okvfe_stereo_match* out, hipStream_t stream) {
   if (n_frames <= 0) return;
+  check_scan_range(kp_cap);
   hipLaunchKernelGGL(match_stereo_blocks_kernel, dim3((kp_cap + 63) / 64, n_frames), dim3(64, kStereoSegs), 0,
                      stream, pair, block_offsets(L), blocks0, blocks1, kp_cap, threshold, out);
 }
@@ -1623,6 +1681,7 @@ void launch_match_motion(const PairParams* pair, const DeviceCamera* camera, int
                          const uint8_t* matched1, int n1, int threshold, okvfe_motion_match* out,
                          hipStream_t stream, bool rt8) {
   if (n0 <= 0) return;
+  check_scan_range(n1);
   hipLaunchKernelGGL(rt8 ? match_motion_kernel<true> : match_motion_kernel<false>, dim3((n0 + 63) / 64), dim3(64, kStereoSegs), 0, stream, pair, camera, w,
                      h, desc0, kp0, bp0, bpv0, skip0, n0, desc1, kp1, bp1, bpv1, matched1, n1,
                      threshold, out);
@@ -1683,6 +1742,7 @@ void launch_match_stereo(const PairParams* pairs, int n_pairs, const okvfe_keypo
                          const int32_t* counts, int kp_cap, int threshold,
                          okvfe_stereo_match* out, hipStream_t stream) {
   if (n_pairs <= 0) return;
+  check_scan_range(kp_cap);
   hipLaunchKernelGGL(match_stereo_kernel, dim3((kp_cap + 63) / 64, n_pairs), dim3(64, kStereoSegs), 0, stream,
                      pairs, kps, desc, bp, bpv, counts, kp_cap, threshold, out);
 }
@@ -1694,6 +1754,7 @@ void launch_match_stereo_arrays(const PairParams* pair, const uint8_t* desc0, co
                                 okvfe_stereo_match* out, hipStream_t stream, const okvfe_keypoint* kp0,
                                 const okvfe_keypoint* kp1) {
   if (max_rows <= 0) return;
+  check_scan_range(n1);
   hipLaunchKernelGGL(match_stereo_arrays_kernel, dim3((max_rows + 63) / 64), dim3(64, kStereoSegs), 0, stream,
                      pair, desc0, bp0, bpv0, n0p, n0, desc1, bp1, bpv1, n1p, n1, threshold, out, kp0, kp1);
 }
