@@ -1184,6 +1184,8 @@ okvfe_status okvfe_stereo_insert_blocks_device(
  *   okvfe_verify_place_blocks_device          the descriptor matching of :330-346 (k_min / dist_min per block and row)
  *   okvfe_place_claims_blocks_device          :347-351, :359, :380: the `matches` map, the counts and the gate
  *   okvfe_place_consensus_blocks_device       :372-397: the consensus over the caller's pose hypotheses and the verdict
+ *   okvfe_place_hessian_blocks_device         :529-551: the Hessian H at the caller's pose, and the residual and minimal
+ *                                             Jacobian of every inlier, which the refinement of :399-527 asks for
  * Landmarks of a set are rows 0 .. L - 1 in ascending landmark id: the rows and the order of the okvfe_map_device
  * (desc_begin, pool) that okvfe_verify_place_blocks_device is given.  Multiframe m owns gather blocks m n_cams + c, as
  * in okvfe_ransac3d2d_consensus_blocks_device, so the rows of k_min_dev / dist_min_dev of block b start at b L.
@@ -1192,9 +1194,11 @@ okvfe_status okvfe_stereo_insert_blocks_device(
  *
  * What stays with the caller: the walk over the DBoW results and its non-maximum suppression with the estimator's
  * predicates (:771-819); the sampler and opengv's gp3p; opengv's adaptive stop, which only ever shortens the
- * hypothesis list; the ceres refinement (:399-527); the Hessian H (:529-551), which is evaluated at the refined pose
- * through ReprojectionError; attemptLoopClosure and everything after it.  PARITY UNPINNED: opengv's winner rule, as for
- * okvfe_ransac3d2d_consensus_blocks_device. */
+ * hypothesis list; the solver of the ceres refinement (:399-527: the Cauchy loss, ceres' corrector, the 2 x 7 Jacobian
+ * through PoseManifold::minusJacobian and the iteration itself; its cost terms are what
+ * okvfe_place_hessian_blocks_device evaluates); the choice of the pose at which the Hessian H (:529-551) is taken -- the
+ * reference takes it at the refined pose, the call takes it wherever poses_dev says; attemptLoopClosure and everything
+ * after it.  PARITY UNPINNED: opengv's winner rule, as for okvfe_ransac3d2d_consensus_blocks_device. */
 
 /* The landmark set of the old frame (Frontend.cpp:289-327).  Host helper, no context.  The old frame's keypoints of all
  * n_cams cameras, camera-major and ascending (n_kps[c] of camera c): landmark_ids (0 = none, :293; the use_cnn filter of
@@ -1273,6 +1277,62 @@ okvfe_status okvfe_place_consensus_blocks_device(
     const int32_t* match_landmark_dev, const uint8_t* gate_dev /* or NULL */, const double* hypotheses_dev,
     const uint8_t* hyp_valid_dev /* or NULL */, int32_t n_hyp, double threshold, int32_t min_inliers,
     const okvfe_ransac_result_device* result, uint8_t* verdict_dev, void* stream);
+
+typedef struct okvfe_place_hessian_device {
+  double* H;                /* device, n_multiframes x 36, row-major 6 x 6 */
+  int32_t* n_terms;         /* device, per multiframe */
+  int32_t* n_singular;      /* device, per multiframe */
+  double* residual;         /* optional: device, blocks x K x 2 */
+  double* jacobian_minimal; /* optional: device, blocks x K x 12, row-major 2 x 6 */
+} okvfe_place_hessian_device;
+/* The Hessian H of verifyRecognisedPlace (Frontend.cpp:529-551), the information of the pose-graph edge that
+ * attemptLoopClosure adds, and its terms: per inlier of the consensus one ReprojectionError::EvaluateWithMinimalJacobians
+ * with jacobians[0] only (okvis_ceres ReprojectionError.hpp:99-183).  The next link of the chain above, on the same
+ * stream; set, blocks_dev, n_multiframes, n_cams, cam_ids and match_landmark_dev are those of
+ * okvfe_place_consensus_blocks_device.
+ * T_SC_params: HOST, n_cams x 7 doubles in PoseParameterBlock layout (t[3], qx qy qz qw), the extrinsics as
+ * estimator.extrinsics() gives them (:421).  poses_dev: device, n_multiframes x 7 doubles in the same layout:
+ * T_Sold_Snew as the caller's solver left it (:527), or any iterate of it.  state_dev: blocks x K, the consensus call's
+ * optional `state`.  verdict_dev: u8 per multiframe, or NULL: every multiframe counts.
+ * Terms, in the order of LoopclosureNoncentralAbsoluteAdapter (camera-major, keypoints ascending): keypoint k < count of
+ * block (m, c) iff state == 2 and match_landmark[k] is in [0, L) and (verdict_dev == NULL or verdict_dev[m] == 3).  For
+ * a multiframe that is not verified H is 36 zeros and both counts are 0: the reference has returned false by then.
+ * Per term, with the 3- and 4-term sums in the order of okvfe_set_fp64_reduction and no FMA:
+ *   q.normalize() and toRotationMatrix() of both poses.  PARITY UNPINNED: they are Eigen's, restated from the published
+ *   source: the coefficients are divided by sqrt(z), z the four-term sum of their squares, iff z > 0 (a zero or NaN
+ *   quaternion stays as it is); the matrix is Eigen's, from tx = 2 x, twx = tx w, ... (Geometry/Quaternion.h).
+ *   T_CS and T_SW as full 4 x 4 matrices (rotation transposed, translation (-C^T) t), hp_S = T_SW hp_W, hp_C = T_CS hp_S.
+ *   projectHomogeneous (PinholeCamera.hpp:506-526): the head is negated when hp_C[3] < 0 and the 2 x 3 Jacobian is that
+ *   of the negated head, not negated back; column 3 of Jh is zero.  The projection status is ignored, as the reference
+ *   ignores it: OutsideImage and Behind rows contribute, and so does a RADTAN8 point past the model's guard (rho > 9),
+ *   whose projection and Jacobian are the model's formulas evaluated there (the reference reads indeterminate memory).
+ *   squareRootInformation = sqrt(64.0 / (size size)) I with size = double(keypoint.size) (:464); error = measurement -
+ *   projection; residual = squareRootInformation error.
+ *   J0_minimal = ((squareRootInformation Jh) T_CS) J, J = [C_SW hp_W[3] | -C_SW crossMx(hp_W.head<3>() - t_WS hp_W[3])]
+ *   over a zero row (ReprojectionError.hpp:155-163).
+ * The matrix products are full: the zeros of T_CS, J, Jh and the square-root information are multiplied and added, so a
+ * non-finite operand spreads as it does in Eigen.
+ * DEFINED DEVIATION: in two cases the residual and the twelve entries of J0_minimal are NaN and the term is counted in
+ * n_singular[m]; it still takes part in H, so the NaN is loud.  (1) fabs(head[2]) < 1.0e-12: project returns before it
+ * writes imagePoint or the Jacobian (PinholeCamera.hpp:302-304) and the reference goes on with indeterminate memory.
+ * (2) size is not a positive finite number.
+ * H = the sum over the terms of J0_minimal^T J0_minimal (:550): entry (i, j) of a term is J(0,i) J(0,j) + J(1,i) J(1,j),
+ * and the terms are added to H one after the other in adapter order, from zero.  That order is the contract: a fixed
+ * lane per entry walks the Jacobians staged in LDS; there is no tree over the terms.  H is symmetric byte for byte.
+ * result: H, n_terms and n_singular are required.  residual and jacobian_minimal are optional and written at term rows
+ * only: every other row, and every row at or past a block's count, is untouched.  Not returned: the 2 x 7 Jacobian
+ * through PoseManifold::minusJacobian, the Cauchy loss and ceres' corrector, which depend on the caller's solver.
+ * One work-group per multiframe, one camera after another; the keypoints are tiled, so there is no limit on
+ * max_keypoints.  Nothing synchronises the host; no workspace; 64 bytes per camera go through the pinned parameter
+ * ring.  A camera slot without intrinsics: OKVFE_ERR_NOT_READY.  A NULL or negative argument:
+ * OKVFE_ERR_INVALID_ARGUMENT before any device work; n_multiframes == 0 is OK and launches nothing. */
+okvfe_status okvfe_place_hessian_blocks_device(okvfe_ctx* ctx, const okvfe_place_set_device* set, const void* blocks_dev,
+                                               int32_t n_multiframes, int32_t n_cams,
+                                               const int32_t* cam_ids /* HOST, n_cams */,
+                                               const double* T_SC_params /* HOST, n_cams x 7 */, const double* poses_dev,
+                                               const int32_t* match_landmark_dev, const uint8_t* state_dev,
+                                               const uint8_t* verdict_dev /* or NULL */,
+                                               const okvfe_place_hessian_device* result, void* stream);
 
 /* ---- place recognition: the DBoW2 query and database on device-resident batches ----------------
  * What decides which old frames verifyRecognisedPlace is run against.  The reference runs

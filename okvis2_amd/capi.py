@@ -121,6 +121,7 @@ EXPORTS = [
     "okvfe_ransac3d2d_consensus_blocks_device", "okvfe_remove_outliers_blocks_device",
     "okvfe_match_motion_stereo_blocks_batch_device",
     "okvfe_place_landmark_set", "okvfe_place_claims_blocks_device", "okvfe_place_consensus_blocks_device",
+    "okvfe_place_hessian_blocks_device",
     "okvfe_vocabulary_check", "okvfe_bow_vectors_blocks_device", "okvfe_place_query_blocks_device",
     "okvfe_bow_database_add_blocks_device", "okvfe_bow_database_check_device",
     "okvfe_stereo_insert_blocks_device",
@@ -132,6 +133,7 @@ EXPORTS = [
 TEST_HOOKS = [
     "okvfe_test_set_map_table_workspace_limit", "okvfe_test_ransac_chunk_records", "okvfe_test_ransac_ring_records",
     "okvfe_test_ransac2d2d_chunk_records", "okvfe_test_ransac2d2d_ring_records", "okvfe_test_ransac2d2d_id_slot",
+    "okvfe_test_place_hessian_chunk_terms",
 ]
 
 STAGES = ["harris", "nms", "sort", "select", "map", "describe", "compact", "match"]
@@ -194,6 +196,12 @@ class PlaceClaimsDevice(C.Structure):
     """okvfe_place_claims_device: device pointers, all required."""
     _fields_ = [("n_matches", C.c_void_p), ("n_points", C.c_void_p), ("n_correspondences", C.c_void_p),
                 ("gate", C.c_void_p), ("match_landmark", C.c_void_p)]
+
+
+class PlaceHessianDevice(C.Structure):
+    """okvfe_place_hessian_device: device pointers; residual and jacobian_minimal are optional (None)."""
+    _fields_ = [("H", C.c_void_p), ("n_terms", C.c_void_p), ("n_singular", C.c_void_p), ("residual", C.c_void_p),
+                ("jacobian_minimal", C.c_void_p)]
 
 
 class VocabularyDevice(C.Structure):
@@ -299,6 +307,8 @@ def lib():
         L.okvfe_place_consensus_blocks_device.restype = C.c_int32
         L.okvfe_place_consensus_blocks_device.argtypes = [
             V, V, V, C.c_int32, C.c_int32, V, V, V, V, V, V, C.c_int32, C.c_double, C.c_int32, V, V, V]
+        L.okvfe_place_hessian_blocks_device.restype = C.c_int32
+        L.okvfe_place_hessian_blocks_device.argtypes = [V, V, V, C.c_int32, C.c_int32, V, V, V, V, V, V, V, V]
         L.okvfe_vocabulary_check.restype = C.c_int32
         L.okvfe_vocabulary_check.argtypes = [V]
         L.okvfe_bow_vectors_blocks_device.restype = C.c_int32
@@ -1219,6 +1229,30 @@ class Frontend:
             _p(hypotheses_ptr), _p(hyp_valid_ptr), int(n_hyp), C.c_double(threshold), int(min_inliers),
             C.byref(result) if result is not None else None, _p(verdict_ptr), _s(stream)))
 
+    @staticmethod
+    def make_place_hessian_device(H_ptr, n_terms_ptr, n_singular_ptr, residual_ptr=None,
+                                  jacobian_minimal_ptr=None) -> PlaceHessianDevice:
+        return PlaceHessianDevice(*[int(p) if p else None for p in (
+            H_ptr, n_terms_ptr, n_singular_ptr, residual_ptr, jacobian_minimal_ptr)])
+
+    def place_hessian_blocks_device(self, place_set: PlaceSetDevice, blocks_ptr, n_multiframes, cam_ids, T_SC_params,
+                                    poses_ptr, match_landmark_ptr, state_ptr, verdict_ptr, result: PlaceHessianDevice,
+                                    stream=None):
+        """The Hessian H of verifyRecognisedPlace (Frontend.cpp:529-551) and the residual and minimal Jacobian of every
+        inlier of the consensus.  T_SC_params: host, one (t[3], qx, qy, qz, qw) per camera; poses_ptr: device,
+        n_multiframes x 7 doubles in the same layout; state_ptr: the consensus call's state rows; verdict_ptr: its
+        verdict bytes, or None (every multiframe counts)."""
+        cams = np.ascontiguousarray(cam_ids, dtype=np.int32)
+        n_cams = len(cams)
+        prm = np.ascontiguousarray(T_SC_params, dtype=np.float64).reshape(-1)
+        if len(prm) != 7 * n_cams:
+            raise ValueError("cam_ids and T_SC_params: seven doubles per camera")
+        self._check(lib().okvfe_place_hessian_blocks_device(
+            self._h, C.byref(place_set) if place_set is not None else None, _p(blocks_ptr), int(n_multiframes), n_cams,
+            _p(cams) if n_cams else _p(np.zeros(1, np.int32)), _p(prm) if n_cams else _p(np.zeros(7)), _p(poses_ptr),
+            _p(match_landmark_ptr), _p(state_ptr), _p(verdict_ptr), C.byref(result) if result is not None else None,
+            _s(stream)))
+
     # -- place recognition: the DBoW2 query and database on device-resident batches -----------
     def bow_vectors_blocks_device(self, vocabulary: VocabularyDevice, blocks_ptr, n_multiframes, n_cams,
                                   vectors: BowVectorsDevice, word_ids_ptr=None, stream=None):
@@ -1258,6 +1292,13 @@ class Frontend:
     def _test_ransac_chunk_records() -> int:
         """test hook (not part of include/okvfe.h): correspondences the consensus kernel scores at a time"""
         f = lib().okvfe_test_ransac_chunk_records
+        f.restype = C.c_int32
+        return int(f())
+
+    @staticmethod
+    def _test_place_hessian_chunk_terms() -> int:
+        """test hook (not part of include/okvfe.h): terms the Hessian kernel evaluates at a time"""
+        f = lib().okvfe_test_place_hessian_chunk_terms
         f.restype = C.c_int32
         return int(f())
 

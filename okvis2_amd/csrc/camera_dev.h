@@ -27,10 +27,11 @@ namespace cam {
 // kRT8: the form that also knows OKVFE_DIST_RADTAN8 (radtan8_distortion.h).  The host launches it only
 // when a camera slot of the call holds such a camera, so the kernels of the other three models keep
 // their code (and registers) exactly.  distort returns false where the model fails (RADTAN8, rho > 9).
-template <bool kRT8 = false>
+// kPastFold: out / J are written there as well (radtan8_distortion.h), for project_jacobian below.
+template <bool kRT8 = false, bool kPastFold = false>
 __device__ inline bool distort(const DeviceCamera& c, double u0, double u1, double out[2], double J[4]) {
   if constexpr (kRT8) {
-    if (c.distortion == OKVFE_DIST_RADTAN8) return radtan8_distort(u0, u1, c.d, out, J);
+    if (c.distortion == OKVFE_DIST_RADTAN8) return radtan8_distort<kPastFold>(u0, u1, c.d, out, J);
   }
   if (c.distortion == OKVFE_DIST_NONE) {
     out[0] = u0; out[1] = u1;
@@ -134,6 +135,33 @@ __device__ inline int project(const DeviceCamera& c, int w, int h, const double 
   if (!distort<kRT8>(c, p[0] * rz, p[1] * rz, dist, J)) return 4;
   pt[0] = c.fu * dist[0] + c.cu;
   pt[1] = c.fv * dist[1] + c.cv;
+  if (pt[0] < 0.0 || pt[1] < 0.0) return 1;
+  if (pt[0] >= (double)w || pt[1] >= (double)h) return 1;
+  return p[2] > 0.0 ? 0 : 3;
+}
+
+// PinholeCamera::project with the 2 x 3 point Jacobian J23 (row-major; PinholeCamera.hpp:296-374), for callers that
+// ignore the status as ReprojectionError.hpp:133 does.  The same statuses.  Status 4 of a singular depth
+// (fabs(p[2]) < 1.0e-12, :302-304) returns before anything is written, as the reference does; status 4 of a distortion
+// failure (RADTAN8, rho > 9) comes with pt and J23 of the model's formulas evaluated past their guard, where the
+// reference leaves imagePoint2 and distortionJacobian indeterminate (:339-358).
+template <bool kRT8 = false>
+__device__ inline int project_jacobian(const DeviceCamera& c, int w, int h, const double p[3], double pt[2],
+                                       double J23[6]) {
+  if (fabs(p[2]) < 1.0e-12) return 4;
+  const double rz = 1.0 / p[2];
+  const double rz2 = rz * rz;
+  double dist[2], D[4];
+  const bool ok = distort<kRT8, true>(c, p[0] * rz, p[1] * rz, dist, D);
+  J23[0] = c.fu * D[0] * rz;
+  J23[1] = c.fu * D[1] * rz;
+  J23[2] = -c.fu * (p[0] * D[0] + p[1] * D[1]) * rz2;
+  J23[3] = c.fv * D[2] * rz;
+  J23[4] = c.fv * D[3] * rz;
+  J23[5] = -c.fv * (p[0] * D[2] + p[1] * D[3]) * rz2;
+  pt[0] = c.fu * dist[0] + c.cu;
+  pt[1] = c.fv * dist[1] + c.cv;
+  if (!ok) return 4;
   if (pt[0] < 0.0 || pt[1] < 0.0) return 1;
   if (pt[0] >= (double)w || pt[1] >= (double)h) return 1;
   return p[2] > 0.0 ? 0 : 3;

@@ -87,4 +87,62 @@ okvfe_status okvfe_place_claims_blocks_device(okvfe_ctx* ctx, const okvfe_place_
   return OKVFE_OK;
 }
 
+// The Hessian H of Frontend::verifyRecognisedPlace (Frontend.cpp:529-551) behind the consensus of
+// okvfe_place_consensus_blocks_device, and the residual and minimal Jacobian of every term (k_place_hessian.hip).
+okvfe_status okvfe_place_hessian_blocks_device(okvfe_ctx* ctx, const okvfe_place_set_device* set, const void* blocks_dev,
+                                               int32_t n_multiframes, int32_t n_cams, const int32_t* cam_ids,
+                                               const double* T_SC_params, const double* poses_dev,
+                                               const int32_t* match_landmark_dev, const uint8_t* state_dev,
+                                               const uint8_t* verdict_dev, const okvfe_place_hessian_device* result,
+                                               void* stream) {
+  if (!ctx) return OKVFE_ERR_INVALID_ARGUMENT;
+  if (!set || set->n_landmarks < 0 || (set->n_landmarks > 0 && !set->hp) || !blocks_dev || n_multiframes < 0 || n_cams < 1 ||
+      n_cams > (int)ctx->h_cams.size() || !cam_ids || !T_SC_params || !poses_dev || !match_landmark_dev || !state_dev ||
+      !result || !result->H || !result->n_terms || !result->n_singular)
+    return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_place_hessian_blocks_device: bad argument");
+  if ((int64_t)n_cams * ctx->kp_cap >= (int64_t)1 << 30 || (int64_t)n_multiframes * n_cams >= (int64_t)1 << 30)
+    return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_place_hessian_blocks_device: too many keypoints or blocks");
+  bool rt8 = false;  // the 8-coefficient form of the projection only when a slot this call uses holds that model
+  std::vector<HessianCamParams> cp((size_t)n_cams);
+  for (int c = 0; c < n_cams; ++c) {
+    const DeviceCamera* dc = slot_camera(ctx, cam_ids[c]);
+    if (!dc)
+      return fail(ctx, OKVFE_ERR_NOT_READY,
+                  "okvfe_place_hessian_blocks_device: frame %d: camera slot %d has no intrinsics (okvfe_set_camera)", c,
+                  cam_ids[c]);
+    rt8 = rt8 || dc->distortion == OKVFE_DIST_RADTAN8;
+    cp[(size_t)c] = HessianCamParams{};
+    std::copy_n(T_SC_params + 7 * (size_t)c, 7, cp[(size_t)c].pose);
+    cp[(size_t)c].cam = cam_ids[c];
+  }
+  if (n_multiframes == 0) return OKVFE_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
+  hipStream_t s = pick_stream(ctx, stream);
+  const BlockLayout L = block_layout(ctx->kp_cap);
+  // the rig: 64 bytes per camera through the pinned parameter ring (one asynchronous copy, no host sync)
+  RingSlot rig(ctx, &ctx->pair_ring, s);
+  okvfe_status st = rig.upload(cp.data(), cp.size() * sizeof(HessianCamParams));
+  if (st != OKVFE_OK) return st;
+  PlaceHessianArgs A;
+  A.hp = set->hp; A.n_landmarks = set->n_landmarks; A.blocks = static_cast<const uint8_t*>(blocks_dev);
+  A.o_count = (int)L.o_count; A.o_kps = (int)L.o_kps; A.block_bytes = L.total;
+  A.kp_cap = ctx->kp_cap; A.n_cams = n_cams; A.w = ctx->w; A.h = ctx->h;
+  A.cams = rig.as<HessianCamParams>(); A.dcams = ctx->d_cams; A.poses = poses_dev;
+  A.match_landmark = match_landmark_dev; A.state = state_dev; A.verdict = verdict_dev;
+  A.H = result->H; A.n_terms = result->n_terms; A.n_singular = result->n_singular;
+  A.residual = result->residual; A.jacobian = result->jacobian_minimal;
+  {
+    StageTimer t(ctx, OKVFE_STAGE_MAP, s);
+    launch_place_hessian(A, n_multiframes, rt8, s);
+  }
+  HIP_TRY(ctx, hipGetLastError());
+  const okvfe_status rel = rig.release();
+  ctx->last_stream = s;
+  return rel;
+}
+
+// Test hook, deliberately not in include/okvfe.h: the number of terms the Hessian kernel evaluates at a time, so that the
+// tests straddle it whatever it is.
+int32_t okvfe_test_place_hessian_chunk_terms(void) { return place_hessian_chunk_terms(); }
+
 }  // extern "C"

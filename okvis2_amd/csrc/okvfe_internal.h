@@ -616,6 +616,35 @@ void launch_place_consensus(const double* hp, int n_landmarks, const BlockLayout
                             const uint8_t* gate, const double* hypotheses, const uint8_t* hyp_valid, int n_hyp,
                             double threshold, int min_inliers, const okvfe_ransac_result_device& out, uint8_t* verdict,
                             hipStream_t stream);
+// the Hessian H of verifyRecognisedPlace (Frontend.cpp:529-551) and its terms for a batch of multiframes
+// (k_place_hessian.hip).  cams (one record per camera) lies in the parameter block of the call, dcams are the context's
+// camera slots; every other pointer is the caller's.
+struct HessianCamParams {
+  double pose[7];  // T_SC as a PoseParameterBlock holds it: t[3], qx qy qz qw
+  int32_t cam;     // camera slot
+  int32_t pad;
+};
+static_assert(sizeof(HessianCamParams) == 64, "64 bytes per camera");
+struct PlaceHessianArgs {
+  const double* hp;  // L x 4
+  int n_landmarks;
+  const uint8_t* blocks;
+  int o_count, o_kps;
+  size_t block_bytes;
+  int kp_cap, n_cams, w, h;
+  const HessianCamParams* cams;
+  const DeviceCamera* dcams;
+  const double* poses;  // n_multiframes x 7
+  const int32_t* match_landmark;
+  const uint8_t* state;
+  const uint8_t* verdict;  // or null
+  double* H;
+  int32_t *n_terms, *n_singular;
+  double *residual, *jacobian;  // optional
+};
+void launch_place_hessian(const PlaceHessianArgs& args, int n_multiframes, bool rt8, hipStream_t stream);
+int place_hessian_chunk_terms();  // terms the kernel evaluates at a time
+bool set_fp64_tree_place_hessian(int tree);
 // scale space (k_pyramid.hip)
 void launch_halfsample(const uint8_t* src, int w, int h, int n_images, uint8_t* dst, hipStream_t stream);
 void launch_twothird(const uint8_t* src, int w, int h, int n_images, uint8_t* dst, hipStream_t stream);

@@ -18,13 +18,18 @@ namespace okvfe {
 
 // Returns false for rho = |u|^2 > 9 (the reference's guard against the model's fold-over; out / J
 // are then left untouched).  J row-major {J00, J01, J10, J11}; may be null.
+// kPastFold: the same value is returned, but out / J are written past the guard as well: the
+// formulas below evaluated at u, for a caller that ignores the status as ReprojectionError does
+// (the reference reads indeterminate memory there; tests/radtan8_ref.py project defines it so).
+template <bool kPastFold = false>
 OKVFE_HD bool radtan8_distort(double u0, double u1, const double* k, double out[2], double* J) {
   const double k1 = k[0], k2 = k[1], p1 = k[2], p2 = k[3], k3 = k[4], k4 = k[5], k5 = k[6], k6 = k[7];
   const double mx = u0 * u0;
   const double my = u1 * u1;
   const double mxy = u0 * u1;
   const double rho = mx + my;
-  if (rho > 9.0) return false;
+  const bool fold = rho > 9.0;
+  if (fold && !kPastFold) return false;
   const double qn = k2 + k3 * rho;  // inner terms of the numerator / denominator polynomials
   const double pn = k1 + rho * qn;
   const double num = rho * pn + 1.0;
@@ -34,7 +39,7 @@ OKVFE_HD bool radtan8_distort(double u0, double u1, const double* k, double out[
   const double rad = num / den;
   out[0] = u0 * rad + 2.0 * p1 * mxy + p2 * (rho + 2.0 * mx);
   out[1] = u1 * rad + 2.0 * p2 * mxy + p1 * (rho + 2.0 * my);
-  if (!J) return true;
+  if (!J) return !fold;
   const double den2 = den * den;
   // d num / d u_j and d den / d u_j
   const double dn0 = rho * (u0 * qn * 2.0 + k3 * u0 * rho * 2.0) + u0 * pn * 2.0;
@@ -45,7 +50,7 @@ OKVFE_HD bool radtan8_distort(double u0, double u1, const double* k, double out[
   J[1] = p1 * u0 * 2.0 + p2 * u1 * 2.0 + (u0 * dn1) / den - u0 * dd1 * num / den2;
   J[2] = p1 * u0 * 2.0 + p2 * u1 * 2.0 + (u1 * dn0) / den - u1 * dd0 * num / den2;
   J[3] = p1 * u1 * 6.0 + p2 * u0 * 2.0 + num / den + (u1 * dn1) / den - u1 * dd1 * num / den2;
-  return true;
+  return !fold;
 }
 
 }  // namespace okvfe

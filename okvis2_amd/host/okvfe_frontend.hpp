@@ -546,6 +546,26 @@ class HipFrontend {
         reinterpret_cast<const double*>(d), hypValid.empty() ? nullptr : d + hypBytes, nHyp, threshold, minInliers, &result,
         verdictDev, stream));
   }
+  // Frontend.cpp:529-551 for the same frames: the Hessian H of the relative pose, the information of the pose-graph edge
+  // that attemptLoopClosure adds, and per inlier the residual and minimal Jacobian of its ReprojectionError (what the
+  // ceres problem of :399-527 asks for at every iterate).  T_SC_params: the camera's extrinsics as a PoseParameterBlock
+  // holds them (t[3], qx qy qz qw); posesDev: device, nMultiframes x 7 doubles in that layout, T_Sold_Snew as the
+  // caller's solver left it; matchLandmarkDev / stateDev / verdictDev as verifyPlaceConsensusBlocks wrote them
+  // (verdictDev may be null: every multiframe counts).  Nothing synchronises the host.
+  void verifyPlaceHessianBlocks(size_t cameraIndex, const DevicePlaceSet& set, const void* blocksDev, int nMultiframes,
+                                const std::array<double, 7>& T_SC_params, const double* posesDev,
+                                const int32_t* matchLandmarkDev, const uint8_t* stateDev, const uint8_t* verdictDev,
+                                const okvfe_place_hessian_device& result, void* stream = nullptr) {
+    if (cameraIndex >= cameras_.size())
+      throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "Camera index exceeds number of cameras.");
+    if (nMultiframes < 0) throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "verifyPlaceHessianBlocks: nMultiframes");
+    std::lock_guard<std::mutex> lock(mutexes_[cameraIndex]);
+    if (!extractors_[cameraIndex].isCameraAware()) extractors_[cameraIndex].setCamera(cameras_[cameraIndex]);
+    Context& c = *contexts_[cameraIndex];
+    const int32_t cam = 0;  // slot 0 of the camera's own context
+    c.check(okvfe_place_hessian_blocks_device(c.get(), &set.get(), blocksDev, nMultiframes, 1, &cam, T_SC_params.data(),
+                                              posesDev, matchLandmarkDev, stateDev, verdictDev, &result, stream));
+  }
   // Place recognition: dBow_->database.query / add (Frontend.cpp:660-672, :752-766, :896-898) with the vocabulary and the
   // database in device memory, and the estimator-free part of the walk over the results (:771-802).  A context of this
   // class holds ONE camera, so a multiframe is one gather block here (a rig whose cameras share a context calls the C
