@@ -133,7 +133,7 @@ EXPORTS = [
 TEST_HOOKS = [
     "okvfe_test_set_map_table_workspace_limit", "okvfe_test_ransac_chunk_records", "okvfe_test_ransac_ring_records",
     "okvfe_test_ransac2d2d_chunk_records", "okvfe_test_ransac2d2d_ring_records", "okvfe_test_ransac2d2d_id_slot",
-    "okvfe_test_place_hessian_chunk_terms",
+    "okvfe_test_place_hessian_chunk_terms", "okvfe_test_context_sizes",
 ]
 
 STAGES = ["harris", "nms", "sort", "select", "map", "describe", "compact", "match"]
@@ -1337,6 +1337,17 @@ class Frontend:
         f = lib().okvfe_test_set_map_table_workspace_limit
         f.argtypes = [C.c_void_p, C.c_uint64]
         self._check(f(self._h, int(nbytes)))
+
+    def _test_context_sizes(self, stream=None) -> dict:
+        """test hook (not part of include/okvfe.h), read-only: slot size and device address of the pair ring, size and
+        address of `stream`'s entries in the two per-stream workspace lists (0 without one), the entries of each list"""
+        f = lib().okvfe_test_context_sizes
+        f.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+        out = (C.c_uint64 * 8)()
+        self._check(f(self._h, _s(stream), out))
+        keys = ("ring_slot_bytes", "ring_dev", "table_ws_bytes", "table_ws_dev", "perm_bytes", "perm_dev",
+                "table_ws_entries", "perm_entries")
+        return dict(zip(keys, (int(v) for v in out)))
 
     def verify_place_blocks_device(self, blocks_ptr, n_frames, map_dev, k_min_ptr, dist_min_ptr, stream=None):
         self._check(lib().okvfe_verify_place_blocks_device(

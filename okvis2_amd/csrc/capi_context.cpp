@@ -71,7 +71,10 @@ okvfe_status ensure_pinned(okvfe_ctx* ctx, size_t bytes) {
   return OKVFE_OK;
 }
 
-// (re)sizes a ring; only called while nothing of the ring is in flight (creation, or after a drain)
+// (re)sizes a ring.  ring_upload calls it on every upload, so slots may be in flight, on any stream: growing waits on
+// the host for every pending slot (its release event, or its stream where the call has not released it yet) before it
+// frees both halves, and every slot of the new ring starts free.  A device address handed out before the growth is dead
+// after it: a call uploads to a ring at most once before it launches the slot's readers.
 okvfe_status ring_reserve(okvfe_ctx* ctx, okvfe_ctx::ParamRing* r, size_t slot_bytes) {
   slot_bytes = align_up(std::max<size_t>(slot_bytes, 256), 256);
   if (slot_bytes <= r->slot_bytes) return OKVFE_OK;
@@ -386,6 +389,25 @@ okvfe_status okvfe_set_fp64_reduction(okvfe_ctx* ctx, int32_t order) {
   if (!okvfe::set_fp64_tree_match(order) || !okvfe::set_fp64_tree_map(order) || !okvfe::set_fp64_tree_ransac(order) ||
       !okvfe::set_fp64_tree_ransac2d2d(order) || !okvfe::set_fp64_tree_place_hessian(order))
     return fail(ctx, OKVFE_ERR_DEVICE, "okvfe_set_fp64_reduction: writing the device flag failed");
+  return OKVFE_OK;
+}
+
+// Test hook, deliberately not in include/okvfe.h, read-only: what a call on `stream` has left of the context's growing
+// buffers, so that a test can tell that a ring grew or a workspace was reallocated or evicted.  out[0] pair_ring's
+// slot_bytes, out[1] the address of its device half, out[2] / out[3] size and address of the stream's map_table_ws entry
+// (0 without one), out[4] / out[5] the same of its map_perm entry, out[6] / out[7] the entries either list holds.
+okvfe_status okvfe_test_context_sizes(okvfe_ctx* ctx, void* stream, uint64_t out[8]) {
+  if (!ctx || !out) return OKVFE_ERR_INVALID_ARGUMENT;
+  const hipStream_t s = pick_stream_raw(ctx, stream);
+  std::fill_n(out, 8, (uint64_t)0);
+  out[0] = ctx->pair_ring.slot_bytes;
+  out[1] = (uint64_t)reinterpret_cast<uintptr_t>(ctx->pair_ring.d);
+  for (const auto& m : ctx->map_table_ws)
+    if (m.stream == s) out[2] = m.bytes, out[3] = (uint64_t)reinterpret_cast<uintptr_t>(m.d);
+  for (const auto& m : ctx->map_perm)
+    if (m.stream == s) out[4] = m.bytes, out[5] = (uint64_t)reinterpret_cast<uintptr_t>(m.d);
+  out[6] = ctx->map_table_ws.size();
+  out[7] = ctx->map_perm.size();
   return OKVFE_OK;
 }
 
