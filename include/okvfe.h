@@ -1580,6 +1580,77 @@ okvfe_status okvfe_motion_frame_order(const double* overlap, const uint64_t* fra
 okvfe_status okvfe_tracking_quality(const okvfe_coverage* coverage, int32_t n_cams, int32_t width, int32_t height,
                                     double kptrad, double* quality_out);
 
+/* ---- IMU propagation: the pose guess of a frame, its Jacobian and covariance --------------------
+ * ViFrontendInterface::propagation, i.e. ImuError::propagation (okvis_ceres/src/ImuError.cpp:557-779): what the
+ * reference runs for every frame before anything else (ThreadedSlam.cpp:397-409), the pose matchToMap starts from and,
+ * through T_WC = T_WS T_SC (:434-444), the extraction direction T_WC.inverse().C() * (0, 0, -1) of detectAndDescribe
+ * (Frontend.cpp:246-251).  Transcribed line by line into one sequence of IEEE operations that the host and the device
+ * compile alike (okvis2_amd/csrc/imu_dev.h, which lists every source line it restates); tests/imu_ref.py is the numpy
+ * restatement both are held to byte for byte.
+ *
+ * Layout (host arrays for okvfe_imu_propagation, device arrays for okvfe_imu_propagation_blocks_device):
+ *   samples       one record of 8 doubles per IMU sample.  The FIRST double's eight bytes hold the timestamp as two
+ *                 uint32, sec in bytes 0-3 and nsec in bytes 4-7 (okvis::Time); doubles 1-3 the gyroscope, 4-6 the
+ *                 accelerometer, 7 unused.
+ *   sample_begin  n_multiframes + 1 int32 offsets into samples, in records: multiframe m owns
+ *                 [sample_begin[m], sample_begin[m + 1]), its ImuMeasurementDeque in order.
+ *   states        18 doubles per multiframe: t_start and t_end (each in a sample's timestamp format), the 7 doubles of
+ *                 T_WS in PoseParameterBlock layout (t[3], qx qy qz qw; poses_dev of okvfe_place_hessian_blocks_device),
+ *                 the 9 of speedAndBias.
+ *   T_SC_params   HOST in both calls: n_cams x 7 doubles in the same pose layout.
+ * Arithmetic: FP64 without FMA, Eigen expressions in source order, left to right.  3-term sums and the 4-term sums of
+ * squaredNorm() follow okvfe_set_fp64_reduction (`order` in the host call); the quaternion product's sums run left to
+ * right.  The 15-term sums of F_delta P_delta F_delta^T ((F_delta P_delta) first) and T P_delta T^T run in ascending k
+ * from the first product and the switch does not apply to them; zeros are multiplied and added.  PARITY UNPINNED: Eigen's
+ * own order for these expressions and products, and its normalized(), inverse() and toRotationMatrix(), are restated
+ * from the published sources.  Time - Time and Duration::toSec() are okvis_time's, so a caller's dt comes out bit-equal.
+ * DEFINED DEVIATIONS:
+ *   - cos / sinc of theta_half and cos / sin of Phi (rightJacobian) are the fixed sequences of
+ *     okvis2_amd/csrc/elementary_fixed.h: within 1 ulp of libm for |x| <= pi / 4, NaN beyond.  The NaN spreads into the
+ *     outputs; n_out_of_range counts the intervals in which one of them was called outside its domain (a NaN argument
+ *     included).  At 200 Hz that takes a rate above 157 rad/s.
+ *   - The reference reads element it + 1 before it knows that it exists; here it is read only where it exists.
+ *   - t_end <= t_start: zero increments and n_propagated = 0 (the epilogue still normalises the quaternion).
+ *   - status bit 1: front().timeStamp > t_start (the reference's assertion); bit 2: an empty sample list.  Nothing but
+ *     status and n_out_of_range (= 0) is written for such a multiframe.
+ *   - back().timeStamp < t_end: n_propagated = -1 as in the reference; pose and speed_and_bias receive the inputs
+ *     unchanged and the per-camera outputs are those of that pose; jacobian and covariance are not written.
+ * Not covered: ImuError::initPose, redoPreintegration, Evaluate*. */
+typedef struct okvfe_imu_params {
+  double a_max, g_max;                                /* saturation thresholds (strict >) */
+  double sigma_g_c, sigma_a_c, sigma_gw_c, sigma_aw_c; /* okvis::ImuParameters */
+  double g;                                           /* gravity magnitude */
+} okvfe_imu_params;
+typedef struct okvfe_imu_result_device {
+  double* pose;            /* n_multiframes x 7 */
+  double* speed_and_bias;  /* n_multiframes x 9 */
+  int32_t* n_propagated;   /* per multiframe: the reference's return value */
+  int32_t* status;         /* per multiframe: 0, or the bits above */
+  int32_t* n_out_of_range; /* per multiframe */
+  double* jacobian;        /* optional: n_multiframes x 225, row-major 15 x 15 */
+  double* covariance;      /* optional: n_multiframes x 225 */
+  double* T_WC;            /* optional: n_multiframes x n_cams x 7 */
+  float* gravity_C;        /* optional: n_multiframes x n_cams x 3, the extraction direction: the layout
+                            * okvfe_detect_describe_batch_device takes as its HOST gravity_C, so one download feeds it */
+} okvfe_imu_result_device;
+/* Host loop, no context: the struct filled with HOST pointers; order: OKVFE_SUM3_*.  n_multiframes == 1 is the seam for
+ * ViFrontendInterface::propagation.  Optional pointers that are NULL are not written. */
+okvfe_status okvfe_imu_propagation(const okvfe_imu_params* params, const double* samples, const int32_t* sample_begin,
+                                   const double* states, int32_t n_multiframes, int32_t n_cams,
+                                   const double* T_SC_params /* n_cams x 7, or NULL when n_cams == 0 */, int32_t order,
+                                   const okvfe_imu_result_device* result);
+/* The same on device-resident batches, in one launch.  The form follows the outputs asked for: the mean only and the
+ * mean with F run a lane per multiframe; with P a wave per multiframe keeps P_delta, F_delta P_delta and F_delta in LDS,
+ * a fixed lane per group of entries.  params and T_SC_params (HOST) travel through the pinned parameter ring, 64 + 56
+ * n_cams bytes; n_cams <= 64.  The caller keeps sample_begin within samples_dev: the call cannot check it.  Nothing
+ * synchronises the host; no workspace.  A NULL required pointer or a negative count: OKVFE_ERR_INVALID_ARGUMENT before
+ * any device work; n_multiframes == 0 is OK and launches nothing. */
+okvfe_status okvfe_imu_propagation_blocks_device(okvfe_ctx* ctx, const okvfe_imu_params* params, const double* samples_dev,
+                                                 const int32_t* sample_begin_dev, const double* states_dev,
+                                                 int32_t n_multiframes, int32_t n_cams,
+                                                 const double* T_SC_params /* HOST, n_cams x 7 */,
+                                                 const okvfe_imu_result_device* result, void* stream);
+
 /* ---- cross-camera gather collective (RCCL over xGMI) ---------------------- */
 /* The one exchange step of the path (okvis_frontend/src/Frontend.cpp:1990-2026 needs the keypoints
  * of BOTH cameras of a pair; with one camera per GPU they live on different ranks): an all-gather of

@@ -128,6 +128,7 @@ EXPORTS = [
     "okvfe_ransac2d2d_consensus_blocks_device",
     "okvfe_overlap_pairs_blocks_device", "okvfe_overlap_fraction", "okvfe_motion_frame_order",
     "okvfe_tracking_quality",
+    "okvfe_imu_propagation", "okvfe_imu_propagation_blocks_device",
 ]
 # exported for the tests and deliberately not declared in include/okvfe.h (EXPORTS is exactly what the header declares)
 TEST_HOOKS = [
@@ -202,6 +203,23 @@ class PlaceHessianDevice(C.Structure):
     """okvfe_place_hessian_device: device pointers; residual and jacobian_minimal are optional (None)."""
     _fields_ = [("H", C.c_void_p), ("n_terms", C.c_void_p), ("n_singular", C.c_void_p), ("residual", C.c_void_p),
                 ("jacobian_minimal", C.c_void_p)]
+
+
+class ImuParams(C.Structure):
+    """okvfe_imu_params"""
+    _fields_ = [(k, C.c_double) for k in ("a_max", "g_max", "sigma_g_c", "sigma_a_c", "sigma_gw_c", "sigma_aw_c", "g")]
+
+
+class ImuResultDevice(C.Structure):
+    """okvfe_imu_result_device: device pointers (host pointers for okvfe_imu_propagation); the last four are optional
+    (None)."""
+    _fields_ = [("pose", C.c_void_p), ("speed_and_bias", C.c_void_p), ("n_propagated", C.c_void_p),
+                ("status", C.c_void_p), ("n_out_of_range", C.c_void_p), ("jacobian", C.c_void_p),
+                ("covariance", C.c_void_p), ("T_WC", C.c_void_p), ("gravity_C", C.c_void_p)]
+
+
+IMU_SAMPLE_DOUBLES, IMU_STATE_DOUBLES = 8, 18
+IMU_STATUS_FRONT_AFTER_START, IMU_STATUS_EMPTY = 1, 2
 
 
 class VocabularyDevice(C.Structure):
@@ -328,6 +346,10 @@ def lib():
         L.okvfe_motion_frame_order.argtypes = [V, V, C.c_int32, C.c_int32, V, V]
         L.okvfe_tracking_quality.restype = C.c_int32
         L.okvfe_tracking_quality.argtypes = [V, C.c_int32, C.c_int32, C.c_int32, C.c_double, V]
+        L.okvfe_imu_propagation.restype = C.c_int32
+        L.okvfe_imu_propagation.argtypes = [V, V, V, V, C.c_int32, C.c_int32, V, C.c_int32, V]
+        L.okvfe_imu_propagation_blocks_device.restype = C.c_int32
+        L.okvfe_imu_propagation_blocks_device.argtypes = [V, V, V, V, V, C.c_int32, C.c_int32, V, V, V]
         _LIB = L
     return _LIB
 
@@ -529,6 +551,57 @@ def overlap_fraction(counts):
     st = lib().okvfe_overlap_fraction(_p(c) if len(c) else None, len(c), _p(out) if len(c) else None)
     if st != OK:
         raise OkvfeError(st, "okvfe_overlap_fraction: a negative count, or exactly one side without matched keypoints")
+    return out
+
+
+def make_imu_params(params) -> ImuParams:
+    """okvfe_imu_params from a mapping (or an object) with a_max, g_max, sigma_g_c, sigma_a_c, sigma_gw_c, sigma_aw_c, g"""
+    get = params.__getitem__ if hasattr(params, "__getitem__") else (lambda k: getattr(params, k))
+    return ImuParams(*[float(get(k)) for k, _ in ImuParams._fields_])
+
+
+def make_imu_result(pose_ptr, speed_and_bias_ptr, n_propagated_ptr, status_ptr, n_out_of_range_ptr, jacobian_ptr=None,
+                    covariance_ptr=None, T_WC_ptr=None, gravity_C_ptr=None) -> ImuResultDevice:
+    return ImuResultDevice(*[int(p) if p else None for p in (
+        pose_ptr, speed_and_bias_ptr, n_propagated_ptr, status_ptr, n_out_of_range_ptr, jacobian_ptr, covariance_ptr,
+        T_WC_ptr, gravity_C_ptr)])
+
+
+def _imu_T_SC(T_SC_params):
+    prm = np.ascontiguousarray(T_SC_params if T_SC_params is not None else np.zeros((0, 7)), dtype=np.float64).reshape(-1)
+    if len(prm) % 7:
+        raise ValueError("T_SC_params: seven doubles per camera")
+    return prm, len(prm) // 7
+
+
+def imu_propagation(params, samples, sample_begin, states, T_SC_params=None, eigen_tree=True, jacobian=True,
+                    covariance=True):
+    """okvfe_imu_propagation (ImuError::propagation, ImuError.cpp:557-779; the host loop, no context) over a batch in
+    the layout of include/okvfe.h: samples [total, 8], sample_begin [n + 1] int32, states [n, 18].  Returns a dict of
+    arrays with one record per multiframe; rows the call leaves alone hold NaN (-1 in the int32 outputs)."""
+    smp = np.ascontiguousarray(samples, dtype=np.float64).reshape(-1, IMU_SAMPLE_DOUBLES)
+    beg = np.ascontiguousarray(sample_begin, dtype=np.int32).reshape(-1)
+    sta = np.ascontiguousarray(states, dtype=np.float64).reshape(-1, IMU_STATE_DOUBLES)
+    n = len(sta)
+    if len(beg) != n + 1 or (n and int(beg.max()) > len(smp)):
+        raise ValueError("sample_begin: n_multiframes + 1 offsets within samples")
+    prm, n_cams = _imu_T_SC(T_SC_params)
+    out = dict(pose=np.full((n, 7), np.nan), speed_and_bias=np.full((n, 9), np.nan),
+               n_propagated=np.full(n, -1, np.int32), status=np.full(n, -1, np.int32),
+               n_out_of_range=np.full(n, -1, np.int32),
+               jacobian=np.full((n, 225), np.nan) if jacobian or covariance else None,
+               covariance=np.full((n, 225), np.nan) if covariance else None,
+               T_WC=np.full((n, n_cams, 7), np.nan) if n_cams else None,
+               gravity_C=np.full((n, n_cams, 3), np.nan, np.float32) if n_cams else None)
+    # (an empty array has no address worth passing: the required outputs of an empty batch point at one spare record)
+    spare = np.zeros(32)
+    ptr = lambda a: None if a is None else (a.ctypes.data if a.size else spare.ctypes.data)
+    res = make_imu_result(*[ptr(out[k]) for k, _ in ImuResultDevice._fields_])
+    p = make_imu_params(params)
+    st = lib().okvfe_imu_propagation(C.byref(p), _p(smp if len(smp) else spare), _p(beg), _p(sta if n else spare), n,
+                                     n_cams, _p(prm) if n_cams else None, 1 if eigen_tree else 0, C.byref(res))
+    if st != OK:
+        raise OkvfeError(st, "okvfe_imu_propagation: bad argument")
     return out
 
 
@@ -1252,6 +1325,19 @@ class Frontend:
             _p(cams) if n_cams else _p(np.zeros(1, np.int32)), _p(prm) if n_cams else _p(np.zeros(7)), _p(poses_ptr),
             _p(match_landmark_ptr), _p(state_ptr), _p(verdict_ptr), C.byref(result) if result is not None else None,
             _s(stream)))
+
+    # -- IMU propagation on device-resident batches -------------------------------------------
+    def imu_propagation_blocks_device(self, params, samples_ptr, sample_begin_ptr, states_ptr, n_multiframes,
+                                      T_SC_params, result: ImuResultDevice, stream=None):
+        """ImuError::propagation (ImuError.cpp:557-779) for n_multiframes multiframes in one launch.  params: a mapping
+        or an ImuParams; samples_ptr / sample_begin_ptr / states_ptr: device, the layout of include/okvfe.h;
+        T_SC_params: host, one (t[3], qx, qy, qz, qw) per camera (None: no cameras); result: make_imu_result -- the
+        form follows the optional outputs asked for."""
+        p = params if isinstance(params, ImuParams) else make_imu_params(params)
+        prm, n_cams = _imu_T_SC(T_SC_params)
+        self._check(lib().okvfe_imu_propagation_blocks_device(
+            self._h, C.byref(p), _p(samples_ptr), _p(sample_begin_ptr), _p(states_ptr), int(n_multiframes), n_cams,
+            _p(prm) if n_cams else None, C.byref(result) if result is not None else None, _s(stream)))
 
     # -- place recognition: the DBoW2 query and database on device-resident batches -----------
     def bow_vectors_blocks_device(self, vocabulary: VocabularyDevice, blocks_ptr, n_multiframes, n_cams,

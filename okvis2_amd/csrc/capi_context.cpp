@@ -387,7 +387,8 @@ okvfe_status okvfe_set_fp64_reduction(okvfe_ctx* ctx, int32_t order) {
   if (hipSetDevice(ctx->cfg.device) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
     return fail(ctx, OKVFE_ERR_DEVICE, "okvfe_set_fp64_reduction: device %d", ctx->cfg.device);
   if (!okvfe::set_fp64_tree_match(order) || !okvfe::set_fp64_tree_map(order) || !okvfe::set_fp64_tree_ransac(order) ||
-      !okvfe::set_fp64_tree_ransac2d2d(order) || !okvfe::set_fp64_tree_place_hessian(order))
+      !okvfe::set_fp64_tree_ransac2d2d(order) || !okvfe::set_fp64_tree_place_hessian(order) ||
+      !okvfe::set_fp64_tree_imu(order))
     return fail(ctx, OKVFE_ERR_DEVICE, "okvfe_set_fp64_reduction: writing the device flag failed");
   return OKVFE_OK;
 }

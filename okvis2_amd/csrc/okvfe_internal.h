@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/okvfe.h"
+#include "imu_dev.h"
 
 namespace okvfe {
 
@@ -645,6 +646,21 @@ struct PlaceHessianArgs {
 void launch_place_hessian(const PlaceHessianArgs& args, int n_multiframes, bool rt8, hipStream_t stream);
 int place_hessian_chunk_terms();  // terms the kernel evaluates at a time
 bool set_fp64_tree_place_hessian(int tree);
+// ImuError::propagation for a batch of multiframes (k_imu.hip; the arithmetic is imu_dev.h).  rig lies in the parameter
+// block of the call: the seven doubles of okvfe_imu_params, one unused, then seven per camera of T_SC; every other pointer
+// is the caller's.  The form follows out: covariance != null -> a wave per multiframe, else a lane per multiframe with
+// or without F.
+constexpr int kImuRigHeaderDoubles = 8;
+struct ImuArgs {
+  const double* samples;        // records of kImuSampleDoubles
+  const int32_t* sample_begin;  // n_multiframes + 1
+  const double* states;         // n_multiframes x kImuStateDoubles
+  const double* rig;
+  int n_multiframes, n_cams;
+  ImuResultPtrs out;
+};
+void launch_imu_propagation(const ImuArgs& args, hipStream_t stream);
+bool set_fp64_tree_imu(int tree);
 // scale space (k_pyramid.hip)
 void launch_halfsample(const uint8_t* src, int w, int h, int n_images, uint8_t* dst, hipStream_t stream);
 void launch_twothird(const uint8_t* src, int w, int h, int n_images, uint8_t* dst, hipStream_t stream);

@@ -17,6 +17,7 @@
 // okvis::Frontend::Exception (okvis_util/include/okvis/assert_macros.hpp:49-113).
 #pragma once
 
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <cstring>
@@ -565,6 +566,108 @@ class HipFrontend {
     const int32_t cam = 0;  // slot 0 of the camera's own context
     c.check(okvfe_place_hessian_blocks_device(c.get(), &set.get(), blocksDev, nMultiframes, 1, &cam, T_SC_params.data(),
                                               posesDev, matchLandmarkDev, stateDev, verdictDev, &result, stream));
+  }
+  // ViFrontendInterface::propagation, i.e. ImuError::propagation (okvis_ceres/src/ImuError.cpp:557-779): the pose guess
+  // of a frame from the IMU samples since the last one, its 15 x 15 Jacobian and covariance, and per camera
+  // T_WC = T_WS T_SC with the extraction direction of detectAndDescribe (Frontend.cpp:246-251).  The arithmetic, its
+  // order and its defined deviations are those of okvfe_imu_propagation (include/okvfe.h).  The host form, no device
+  // work: imuMeasurements in deque order; T_WS as a PoseParameterBlock holds it (t[3], qx qy qz qw); T_SC_params one
+  // such pose per camera.  eigenTree: the order of okvfe_set_fp64_reduction.
+  struct ImuSample {
+    uint32_t sec = 0, nsec = 0;  // okvis::Time
+    std::array<double, 3> gyroscopes{}, accelerometers{};
+  };
+  struct Propagation {
+    int nPropagated = 0;   // the reference's return value (-1: the samples end before t_end; the state is unchanged)
+    int status = 0;        // bit 1: the first sample is later than t_start; bit 2: no samples (nothing else is set then)
+    int nOutOfRange = 0;   // intervals whose angle lies beyond pi / 4 (their results are NaN)
+    std::array<double, 7> T_WS{};
+    std::array<double, 9> speedAndBias{};
+    std::vector<double> jacobian, covariance;     // 225 each, row-major; empty where not asked for (or nPropagated < 0)
+    std::vector<std::array<double, 7>> T_WC;      // per camera
+    std::vector<std::array<float, 3>> gravity_C;  // per camera: the extraction direction
+  };
+  static double imuTimestamp(uint32_t sec, uint32_t nsec) {  // (sec, nsec) in the eight bytes of a record's first double
+    const uint64_t bits = uint64_t(sec) | (uint64_t(nsec) << 32);
+    double v;
+    std::memcpy(&v, &bits, sizeof v);
+    return v;
+  }
+  static Propagation propagation(const std::vector<ImuSample>& imuMeasurements, const okvfe_imu_params& imuParams,
+                                 const std::array<double, 7>& T_WS, const std::array<double, 9>& speedAndBias,
+                                 uint32_t tStartSec, uint32_t tStartNsec, uint32_t tEndSec, uint32_t tEndNsec,
+                                 const std::vector<std::array<double, 7>>& T_SC_params = {}, bool wantJacobian = false,
+                                 bool wantCovariance = false, bool eigenTree = true) {
+    const size_t n = imuMeasurements.size(), nc = T_SC_params.size();
+    std::vector<double> samples(8 * n + 8, 0.0), state(18), T_SC(7 * nc + 7);
+    for (size_t i = 0; i < n; ++i) {
+      samples[8 * i] = imuTimestamp(imuMeasurements[i].sec, imuMeasurements[i].nsec);
+      for (size_t k = 0; k < 3; ++k) {
+        samples[8 * i + 1 + k] = imuMeasurements[i].gyroscopes[k];
+        samples[8 * i + 4 + k] = imuMeasurements[i].accelerometers[k];
+      }
+    }
+    state[0] = imuTimestamp(tStartSec, tStartNsec);
+    state[1] = imuTimestamp(tEndSec, tEndNsec);
+    std::copy(T_WS.begin(), T_WS.end(), state.begin() + 2);
+    std::copy(speedAndBias.begin(), speedAndBias.end(), state.begin() + 9);
+    for (size_t c = 0; c < nc; ++c) std::copy(T_SC_params[c].begin(), T_SC_params[c].end(), T_SC.begin() + 7 * c);
+    const int32_t begin[2] = {0, int32_t(n)};
+    Propagation out;
+    int32_t ints[3] = {0, 0, 0};
+    std::vector<double> jac(225), cov(225), T_WC(7 * nc + 7);
+    std::vector<float> grav(3 * nc + 3);
+    okvfe_imu_result_device res{};
+    res.pose = out.T_WS.data();
+    res.speed_and_bias = out.speedAndBias.data();
+    res.n_propagated = &ints[0];
+    res.status = &ints[1];
+    res.n_out_of_range = &ints[2];
+    res.jacobian = wantJacobian ? jac.data() : nullptr;
+    res.covariance = wantCovariance ? cov.data() : nullptr;
+    res.T_WC = nc ? T_WC.data() : nullptr;
+    res.gravity_C = nc ? grav.data() : nullptr;
+    const okvfe_status st = okvfe_imu_propagation(&imuParams, samples.data(), begin, state.data(), 1, int32_t(nc),
+                                                  nc ? T_SC.data() : nullptr, eigenTree ? 1 : 0, &res);
+    if (st != OKVFE_OK) throw Exception(st, "okvfe_imu_propagation");
+    out.nPropagated = ints[0];
+    out.status = ints[1];
+    out.nOutOfRange = ints[2];
+    if (out.status != 0) return out;
+    if (wantJacobian && out.nPropagated >= 0) out.jacobian = jac;
+    if (wantCovariance && out.nPropagated >= 0) out.covariance = cov;
+    out.T_WC.resize(nc);
+    out.gravity_C.resize(nc);
+    for (size_t c = 0; c < nc; ++c) {
+      std::copy_n(T_WC.begin() + 7 * c, 7, out.T_WC[c].begin());
+      std::copy_n(grav.begin() + 3 * c, 3, out.gravity_C[c].begin());
+    }
+    return out;
+  }
+  // okvfe_set_fp64_reduction: the order of the 3- and 4-term FP64 sums of every device call, device-wide (true: Eigen's
+  // tree, the default).  Drains the device.
+  void setFp64Reduction(bool eigenTree) {
+    std::lock_guard<std::mutex> lock(mutexes_[0]);
+    contexts_[0]->check(okvfe_set_fp64_reduction(contexts_[0]->get(), eigenTree ? OKVFE_SUM3_EIGEN_TREE : OKVFE_SUM3_LEFT_TO_RIGHT));
+  }
+  // The same for nMultiframes multiframes that live in device memory, in one launch on `stream`: samplesDev,
+  // sampleBeginDev and statesDev in the layout of okvfe_imu_propagation_blocks_device; result: device pointers, the
+  // optional ones null where not wanted (the form of the kernel follows them).  Runs on the context of cameraIndex; no
+  // camera of the context is read.  Nothing synchronises the host.
+  void propagationBlocks(size_t cameraIndex, const okvfe_imu_params& imuParams, const double* samplesDev,
+                         const int32_t* sampleBeginDev, const double* statesDev, int nMultiframes,
+                         const std::vector<std::array<double, 7>>& T_SC_params, const okvfe_imu_result_device& result,
+                         void* stream = nullptr) {
+    if (cameraIndex >= cameras_.size())
+      throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "Camera index exceeds number of cameras.");
+    if (nMultiframes < 0) throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "propagationBlocks: nMultiframes");
+    std::vector<double> T_SC(7 * T_SC_params.size() + 7);
+    for (size_t c = 0; c < T_SC_params.size(); ++c) std::copy(T_SC_params[c].begin(), T_SC_params[c].end(), T_SC.begin() + 7 * c);
+    std::lock_guard<std::mutex> lock(mutexes_[cameraIndex]);
+    Context& c = *contexts_[cameraIndex];
+    c.check(okvfe_imu_propagation_blocks_device(c.get(), &imuParams, samplesDev, sampleBeginDev, statesDev, nMultiframes,
+                                                int32_t(T_SC_params.size()), T_SC_params.empty() ? nullptr : T_SC.data(),
+                                                &result, stream));
   }
   // Place recognition: dBow_->database.query / add (Frontend.cpp:660-672, :752-766, :896-898) with the vocabulary and the
   // database in device memory, and the estimator-free part of the walk over the results (:771-802).  A context of this
