@@ -1,7 +1,8 @@
 """GPU: seeded random configurations (image size, content, threshold, radius, cap, extraction mode,
 scale invariance) through detect + describe against the oracle -- the shapes no hand-written case
 names: partial strips and tiles of the fused score kernel, overflowing hit stacks (noise at low
-thresholds), flagged plateaus, caps inside a selection window, patterns leaving the image."""
+thresholds), flagged plateaus, caps inside a selection window, patterns leaving the image.  Every width drawn here is a
+multiple of 4 (the fused chain); test_gpu_unaligned_fuzz.py runs the same generators on the other widths."""
 import numpy as np
 import pytest
 
