@@ -19,7 +19,10 @@
 // profiles/round2_valu_rate_ubench.txt).
 //
 // The production kernel is harris_kernel<61, true[, PACK]> further down: the same walk with the
-// gradients on the matrix pipe (v_mfma_i32_4x4x4i8), the detector's non-maximum suppression fused in
+// gradients on the matrix pipe (v_mfma_i32_4x4x4i8), the values of the neighbouring lanes (pixels, covariance products,
+// scores: eight per row step) handed over through two LDS rows per wave instead of DPP moves, so that they cost no
+// vector-ALU issue (lane_neighbours; LAB_NOTES.md "K1: lane exchange through LDS"), the detector's non-maximum
+// suppression fused in
 // (hits pushed as {score, position} on per-lane LDS stacks, candidate records written through an LDS
 // stage), whole-line stores through the slotted score layout, and its MEMONLY instantiation -- the
 // byte mover that bench.py times next to it.  harris_generic_kernel / harris_kernel<30, false> are the
@@ -226,8 +229,8 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void harris_generic_kernel(
 
 // ---- fast path (w % 4 == 0): no redundant halo columns ------------------------------------------
 // Lane l of strip s owns dword d = 62*s + l of every row (4 pixels).  Horizontal neighbours come
-// from the adjacent lanes through DPP wave shifts, so each lane computes the vertical filters and
-// the covariance entries of its own 4 columns only.  Lane 0 / lane 63 of interior strip borders
+// from the adjacent lanes through the wave's LDS exchange rows (lane_neighbours below), so each lane computes the
+// vertical filters and the covariance entries of its own 4 columns only.  Lane 0 / lane 63 of interior strip borders
 // have no neighbour on one side: they are halo lanes (strips overlap by 2 dwords) and do not
 // store; at the image border no halo is needed (the rim is zero by definition).  752 px = 188
 // dwords = 63 + 62 + 63 valid lanes in 3 waves.
@@ -236,37 +239,35 @@ __device__ __forceinline__ int mulhi24(int a, int b) {  // (a * b) >> 32 of the 
   asm("v_mul_hi_i32_i24 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
   return d;
 }
-// DPP reads of a VGPR written by a VALU op need 2 wait states; the compiler inserts them for
-// its own instructions but cannot see through inline asm, so values produced by mulhi24 pass
-// through this fence before they are shifted across lanes.
-__device__ __forceinline__ void dpp_fence(int& a, int& b, int& c, int& d, int& e, int& f) {
-  asm volatile("s_nop 1" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f));
+// Neighbour values travel through LDS: l = `a` of lane - 1, r = `b` of lane + 1, 0 beyond the wave.  (Until the lane
+// exchange of LAB_NOTES.md they were eight v_mov_b32_dpp per row step, 4.1 cycles of vector-ALU issue each plus the
+// s_nop 1 of the DPP read-after-write hazard at every exchange point; LDS instructions take no vector-ALU issue slot.)
+// A wave owns two rows of 66 dwords, A then B; slots 0 and 65 of both stay zero (written once in the prologue), lane l
+// writes `a` to A[l + 1] and `b` to B[l + 1] (one ds_write2_b32) and reads A[l] and B[l + 2] (one ds_read2_b32): the
+// zeros that lane 0 and lane 63 read come from the end slots.  xp = this lane's &A[l].  The LDS operations of ONE wave
+// execute in order, so the wave needs no barrier and every exchange point reuses the same two rows.  The compiler
+// reasons per thread, and per thread the stored and the loaded addresses never overlap (it could hoist a load over the
+// store, or take two loads of A[l] for the same value): the memory clobbers pin store -> load -> next store.  The
+// accesses are plain ones, so s_waitcnt lgkmcnt is the compiler's.  Hazards: the ISA's table of required wait states
+// has rows for a VALU write of a VGPR followed by DPP (2) and by v_readlane / v_permlane (1), and for VALU-written
+// SGPRs and EXEC; it has none for a VALU-written VGPR that an LDS instruction reads as address or data -- so the
+// values of the inline-asm multiplies go straight into the ds_write, without an s_nop.
+typedef __attribute__((address_space(3))) int32_t lds_i32;
+constexpr int kXRow = 66;  // dwords per exchange row
+__device__ __forceinline__ void lane_neighbours(lds_i32* xp, int a, int b, int& l, int& r) {
+  xp[1] = a;
+  xp[kXRow + 1] = b;
+  asm volatile("" ::: "memory");
+  l = xp[0];
+  r = xp[kXRow + 2];
+  asm volatile("" ::: "memory");
 }
-__device__ __forceinline__ void dpp_fence4(int& a, int& b, int& c, int& d) {
-  asm volatile("s_nop 1" : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
-}
-__device__ __forceinline__ void dpp_fence2(int& a, int& b) {
-  asm volatile("s_nop 1" : "+v"(a), "+v"(b));
-}
-// Neighbour reads with their wait states INSIDE the asm (round 6).  A DPP read of a VGPR needs two wait states behind the
-// VALU write of that VGPR; the compiler keeps them by counting instructions, and it counts a v_mfma scheduled in between
-// as one -- but on gfx950 the matrix instruction issues BESIDE the vector ALU when its pipe is free, so "v_xor; s_...;
-// v_mfma; v_mov_dpp" can reach the DPP one state early.  Whether it does depends on what else runs on the SIMD: the
-// map-writing PACK instantiation did it beside the generic score kernel of another scale-space layer (lanes 12..15 of
-// every 16 -- DPP bank 3, the last quarter of a row to be written -- read the stale register: ~50 wrong score-map
-// entries per call, tools/lab/ss_dump.py), never alone.  l = `a` of lane - 1, r = `b` of lane + 1, 0 beyond the wave.
-__device__ __forceinline__ void lane_neighbours(int a, int b, int& l, int& r) {
-  asm("s_nop 1\n\t"
-      "v_mov_b32_dpp %0, %2 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-      "v_mov_b32_dpp %1, %3 wave_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1"
-      : "=&v"(l), "=&v"(r)
-      : "v"(a), "v"(b));
-}
-__device__ __forceinline__ int from_left(int v) {   // value of lane-1
-  return __builtin_amdgcn_update_dpp(0, v, 0x138, 0xf, 0xf, true);
-}
-__device__ __forceinline__ int from_right(int v) {  // value of lane+1
-  return __builtin_amdgcn_update_dpp(0, v, 0x130, 0xf, 0xf, true);
+__device__ __forceinline__ void lane_neighbours(lds_i32* xp, int a, int& l, int& r) {  // a == b: row A alone
+  xp[1] = a;
+  asm volatile("" ::: "memory");
+  l = xp[0];
+  r = xp[2];
+  asm volatile("" ::: "memory");
 }
 
 constexpr int kStripLanes = 62;
@@ -422,7 +423,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) OKVFE_K1_WAVES void harris_ker
     d = strip * kStripLanes + lane;
   }
   const int ys_own = row_tile * kTHF;
-  if (ys_own >= h) return;  // wave-uniform; all 64 lanes of a live wave stay active (DPP sources)
+  if (ys_own >= h) return;  // wave-uniform; all 64 lanes of a live wave stay active (every lane writes its exchange slots)
   const int ye_own = ys_own + kTHF < h ? ys_own + kTHF : h;
   const int ys = NMS ? ys_own - 1 : ys_own;  // first score row computed (with NMS one above the tile)
   const bool last_strip = PACK ? packed_block : strip * kStripLanes + 64 >= nd;
@@ -485,10 +486,19 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) OKVFE_K1_WAVES void harris_ker
   int A_below = r4 == 0 ? taps(-24, 0, 24, 0) : r4 == 1 ? taps(0, -24, 0, 24)
               : r4 == 2 ? taps(24, 80, 24, 0) : taps(0, 24, 80, 24);
   asm volatile("" : "+v"(A_above), "+v"(A_centre), "+v"(A_below));
+  // lane exchange rows (see lane_neighbours): [wave][A | B][66]; xp = this lane's &A[lane]
+  __shared__ int32_t xrows[MEMONLY ? 1 : kWavesPerBlock * 2 * kXRow];
+  uint32_t xa = (uint32_t)(uintptr_t)(lds_i32*)xrows + (uint32_t)(wave * (2 * kXRow * 4) + lane * 4);
+  asm volatile("" : "+v"(xa));  // opaque: the loads and stores through it keep their program order
+  lds_i32* const xp = (lds_i32*)(uintptr_t)xa;
+  if (!MEMONLY && lane < 2) {  // the end slots of both rows: zero for good
+    xp[lane * (kXRow - 2)] = 0;
+    xp[kXRow + lane * (kXRow - 2)] = 0;
+  }
   auto make_windows = [&](uint32_t dw, int wn[2]) {
     const int x = (int)(dw ^ 0x80808080u);
     int l, r;
-    lane_neighbours(x, x, l, r);
+    lane_neighbours(xp, x, l, r);
     wn[0] = (int)__builtin_amdgcn_alignbyte((uint32_t)x, (uint32_t)l, 3);  // l.b3 x.b0 x.b1 x.b2
     wn[1] = (int)__builtin_amdgcn_alignbyte((uint32_t)r, (uint32_t)x, 1);  // x.b1 x.b2 x.b3 r.b0
   };
@@ -615,11 +625,10 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) OKVFE_K1_WAVES void harris_ker
       G[0][i] = g0;
       G[1][i] = mulhi24(gx[i], gy[i]);
     }
-    dpp_fence4(G[0][0], G[0][3], G[1][0], G[1][3]);
 #pragma unroll
     for (int ch = 0; ch < 2; ++ch) {
       int gl, gr;
-      lane_neighbours(G[ch][3], G[ch][0], gl, gr);
+      lane_neighbours(xp, G[ch][3], G[ch][0], gl, gr);
       const int pm = gl + G[ch][0];
       const int p0 = G[ch][0] + G[ch][1];
       const int p1 = G[ch][1] + G[ch][2];
@@ -672,7 +681,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) OKVFE_K1_WAVES void harris_ker
   // roll the state
   auto nms_row = [&](const int sc[4], int q, bool test, int r) {  // r = the centre row (scalar)
     int l, r2;
-    lane_neighbours(sc[3], sc[0], l, r2);
+    lane_neighbours(xp, sc[3], sc[0], l, r2);
     const int hn[4] = {max3i(l, sc[0], sc[1]), max3i(sc[0], sc[1], sc[2]),
                        max3i(sc[1], sc[2], sc[3]), max3i(sc[2], sc[3], r2)};
 #ifndef OKVFE_K1_SKIP
@@ -729,8 +738,10 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) OKVFE_K1_WAVES void harris_ker
     const uint32_t t0 = load_next(), t1 = load_next();
 #pragma unroll
     for (int i = 0; i < kAhead; ++i) ring[i] = load_next();
-    make_windows(t0, win[0]);
-    make_windows(t1, win[1]);
+    if constexpr (!MEMONLY) {
+      make_windows(t0, win[0]);
+      make_windows(t1, win[1]);
+    }
   }
   int y = ys - 2;  // score row completed by the current step (meaningful from step 2 on)
   // step j (compile-time phase PH = j % 6): pixel row ys+j, covariance row g = ys+j-1, score row
