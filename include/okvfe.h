@@ -1184,8 +1184,10 @@ okvfe_status okvfe_stereo_insert_blocks_device(
  *   okvfe_verify_place_blocks_device          the descriptor matching of :330-346 (k_min / dist_min per block and row)
  *   okvfe_place_claims_blocks_device          :347-351, :359, :380: the `matches` map, the counts and the gate
  *   okvfe_place_consensus_blocks_device       :372-397: the consensus over the caller's pose hypotheses and the verdict
+ *   okvfe_place_refine_blocks_device          :399-527: the refinement of T_Sold_Snew as a defined algorithm, and H at
+ *                                             the pose out
  *   okvfe_place_hessian_blocks_device         :529-551: the Hessian H at the caller's pose, and the residual and minimal
- *                                             Jacobian of every inlier, which the refinement of :399-527 asks for
+ *                                             Jacobian of every inlier, for a caller that runs a solver of its own
  * Landmarks of a set are rows 0 .. L - 1 in ascending landmark id: the rows and the order of the okvfe_map_device
  * (desc_begin, pool) that okvfe_verify_place_blocks_device is given.  Multiframe m owns gather blocks m n_cams + c, as
  * in okvfe_ransac3d2d_consensus_blocks_device, so the rows of k_min_dev / dist_min_dev of block b start at b L.
@@ -1194,9 +1196,9 @@ okvfe_status okvfe_stereo_insert_blocks_device(
  *
  * What stays with the caller: the walk over the DBoW results and its non-maximum suppression with the estimator's
  * predicates (:771-819); the sampler and opengv's gp3p; opengv's adaptive stop, which only ever shortens the
- * hypothesis list; the solver of the ceres refinement (:399-527: the Cauchy loss, ceres' corrector, the 2 x 7 Jacobian
- * through PoseManifold::minusJacobian and the iteration itself; its cost terms are what
- * okvfe_place_hessian_blocks_device evaluates); the choice of the pose at which the Hessian H (:529-551) is taken -- the
+ * hypothesis list; the solver of the ceres refinement, for a caller that wants ceres' own and not the defined algorithm
+ * of okvfe_place_refine_blocks_device (:399-527: ceres' corrector, the 2 x 7 Jacobian through PoseManifold::minusJacobian
+ * and DENSE_QR; its cost terms are what okvfe_place_hessian_blocks_device evaluates); the choice of the pose at which the Hessian H (:529-551) is taken -- the
  * reference takes it at the refined pose, the call takes it wherever poses_dev says; attemptLoopClosure and everything
  * after it.  PARITY UNPINNED: opengv's winner rule, as for okvfe_ransac3d2d_consensus_blocks_device. */
 
@@ -1333,6 +1335,70 @@ okvfe_status okvfe_place_hessian_blocks_device(okvfe_ctx* ctx, const okvfe_place
                                                const int32_t* match_landmark_dev, const uint8_t* state_dev,
                                                const uint8_t* verdict_dev /* or NULL */,
                                                const okvfe_place_hessian_device* result, void* stream);
+
+typedef struct okvfe_place_refine_device {
+  double* poses;         /* device, n_multiframes x 7: T_Sold_Snew out (t[3], qx qy qz qw) */
+  int32_t* status;       /* device, per multiframe: 0 .. 4, see below */
+  int32_t* n_iterations; /* optional: device, per multiframe */
+  int32_t* n_accepted;   /* optional: device, per multiframe */
+  int32_t* n_terms;      /* optional: device, per multiframe */
+  double* cost;          /* optional: device, n_multiframes x 2: the cost at the start and at the pose out */
+  double* start_poses;   /* optional: device, n_multiframes x 7 */
+  double* H;             /* optional: device, n_multiframes x 36 */
+  int32_t* n_singular;   /* optional: device, per multiframe; written only where H is given */
+} okvfe_place_refine_device;
+/* The refinement of T_Sold_Snew between the consensus and H (Frontend.cpp:399-527): the ceres problem of one
+ * ReprojectionError per inlier with CauchyLoss(3) over one pose with PoseManifold, at most max_iterations iterations (the
+ * reference: 10), as the DEFINED ALGORITHM that tests/place_refine_ref.py states one IEEE operation per line:
+ * Levenberg-Marquardt with ceres' published trust-region rules and the defaults the reference leaves untouched (radius
+ * 1e4, eta 1e-3, the Jacobi scaling 1 / (1 + sqrt(A_jj)), min/max diagonal 1e-6 / 1e32, gradient, parameter and function
+ * tolerances 1e-10, 1e-8, 1e-6, minimum radius 1e-32).  The next link of the chain above, on the same stream; set,
+ * blocks_dev, n_multiframes, n_cams, cam_ids, T_SC_params, match_landmark_dev, state_dev and verdict_dev are those of
+ * okvfe_place_hessian_blocks_device, and the terms and their order are that call's.
+ * The start: initial_poses_dev (device, n_multiframes x 7) where given; else Transformation(Matrix4d) of hypothesis
+ * best_hypothesis_dev[m] of hypotheses_dev (device, n_multiframes x n_hyp x 12, row-major 3 x 4; best_hypothesis_dev is
+ * the consensus call's best_hypothesis), the quaternion by Eigen's Quaterniond(Matrix3d), not normalised.  A winner
+ * outside [0, n_hyp) starts at a NaN pose: the multiframe is still evaluated and ends with status 4 and its n_terms.
+ * hypotheses_dev and best_hypothesis_dev may be NULL if and only if initial_poses_dev is given.
+ * Per term of an evaluation: the residual r and J0_minimal of okvfe_place_hessian_blocks_device at the pose, then
+ * s = r0 r0 + r1 r1, total = 1 + s / 9 (as a product with the double nearest 1 / 9), rho0 = 9 log(total),
+ * rho1 = max(DBL_MIN, 1 / total), w = sqrt(rho1), and w r, w J enter A = sum (wJ)^T (wJ), g = sum (wJ)^T (w r) and the
+ * cost 0.5 sum rho0, every entry added term after term in adapter order from zero by a fixed lane (no tree over the
+ * terms).  log, and the sin and cos of PoseManifold::plus, are the fixed sequences of csrc/elementary_fixed.h (within
+ * 2 ulp resp. 1 ulp of libm).  The 3-term sum of plus and the 4-term sums of normalized() follow
+ * okvfe_set_fp64_reduction, as do the sums of the term; every other sum runs left to right.  No FMA.
+ * DEFINED DEVIATIONS from ceres: (1) the 6 x 6 step is a Cholesky factorisation of the scaled normal equations in a
+ * written-out order (ceres' default is DENSE_QR on the stacked system: the same minimiser, another rounding); (2) the
+ * gradient test takes max |g_j| itself where ceres goes through plus(x, -g).  PARITY UNPINNED: ceres' loop and Eigen's
+ * conversion, product and normalized() are restated from their published sources (neither is in the tree).
+ * status: 0 = not verified (verdict_dev given and verdict_dev[m] != 3): only status, the counts (0) and cost (0, 0) are
+ * written, the multiframe's rows of poses and start_poses are untouched and H is zeros; 1 = converged (gradient,
+ * parameter or function tolerance); 2 = the iteration limit; 3 = no term: the pose out is the start; 4 = failed: a
+ * non-finite cost, gradient or A at the start or at an accepted point, or a radius below 1e-32.  The pose out is the last
+ * accepted point.  n_iterations counts every iteration begun, also one whose step was invalid (a failed pivot, a model
+ * change that is not > 0, a half-angle beyond pi / 4) and used no evaluation.
+ * H, n_singular: okvfe_place_hessian_blocks_device's H and n_singular at result->poses with the same verdict_dev, queued
+ * behind the last step.
+ * Launches: 1 (start) + 2 (evaluation, step) + 2 max_iterations (evaluation, step) + 1 where H is asked for; every launch
+ * is either a near copy of the Hessian kernel (one work-group per multiframe; a work-group whose multiframe has ended
+ * returns after one load) or per-lane arithmetic, a lane per multiframe, that also compiles for the host
+ * (csrc/place_refine_dev.h).  After the last step every multiframe has ended: an evaluation is asked for only by an
+ * iteration that was counted, so at most max_iterations candidates are evaluated, and the step behind the last of them
+ * meets it >= max_iterations before it can ask for another.  0 <= max_iterations <= 64.
+ * Nothing synchronises the host.  The per-multiframe records (under 1 KB each) live in a workspace per stream, so two
+ * calls on one stream reuse it in order; 64 bytes per camera go once through the pinned parameter ring.  A camera slot
+ * without intrinsics: OKVFE_ERR_NOT_READY.  A NULL or negative argument, or max_iterations outside [0, 64]:
+ * OKVFE_ERR_INVALID_ARGUMENT before any device work; n_multiframes == 0 is OK and launches nothing. */
+okvfe_status okvfe_place_refine_blocks_device(okvfe_ctx* ctx, const okvfe_place_set_device* set, const void* blocks_dev,
+                                              int32_t n_multiframes, int32_t n_cams,
+                                              const int32_t* cam_ids /* HOST, n_cams */,
+                                              const double* T_SC_params /* HOST, n_cams x 7 */,
+                                              const double* hypotheses_dev, int32_t n_hyp,
+                                              const int32_t* best_hypothesis_dev,
+                                              const double* initial_poses_dev /* or NULL */,
+                                              const int32_t* match_landmark_dev, const uint8_t* state_dev,
+                                              const uint8_t* verdict_dev /* or NULL */, int32_t max_iterations,
+                                              const okvfe_place_refine_device* result, void* stream);
 
 /* ---- place recognition: the DBoW2 query and database on device-resident batches ----------------
  * What decides which old frames verifyRecognisedPlace is run against.  The reference runs

@@ -121,7 +121,7 @@ EXPORTS = [
     "okvfe_ransac3d2d_consensus_blocks_device", "okvfe_remove_outliers_blocks_device",
     "okvfe_match_motion_stereo_blocks_batch_device",
     "okvfe_place_landmark_set", "okvfe_place_claims_blocks_device", "okvfe_place_consensus_blocks_device",
-    "okvfe_place_hessian_blocks_device",
+    "okvfe_place_hessian_blocks_device", "okvfe_place_refine_blocks_device",
     "okvfe_vocabulary_check", "okvfe_bow_vectors_blocks_device", "okvfe_place_query_blocks_device",
     "okvfe_bow_database_add_blocks_device", "okvfe_bow_database_check_device",
     "okvfe_stereo_insert_blocks_device",
@@ -203,6 +203,12 @@ class PlaceHessianDevice(C.Structure):
     """okvfe_place_hessian_device: device pointers; residual and jacobian_minimal are optional (None)."""
     _fields_ = [("H", C.c_void_p), ("n_terms", C.c_void_p), ("n_singular", C.c_void_p), ("residual", C.c_void_p),
                 ("jacobian_minimal", C.c_void_p)]
+
+
+class PlaceRefineDevice(C.Structure):
+    """okvfe_place_refine_device: device pointers; all but poses and status are optional (None)."""
+    _fields_ = [(k, C.c_void_p) for k in ("poses", "status", "n_iterations", "n_accepted", "n_terms", "cost", "start_poses",
+                                          "H", "n_singular")]
 
 
 class ImuParams(C.Structure):
@@ -348,6 +354,9 @@ def lib():
         L.okvfe_tracking_quality.argtypes = [V, C.c_int32, C.c_int32, C.c_int32, C.c_double, V]
         L.okvfe_imu_propagation.restype = C.c_int32
         L.okvfe_imu_propagation.argtypes = [V, V, V, V, C.c_int32, C.c_int32, V, C.c_int32, V]
+        L.okvfe_place_refine_blocks_device.restype = C.c_int32
+        L.okvfe_place_refine_blocks_device.argtypes = [V, V, V, C.c_int32, C.c_int32, V, V, V, C.c_int32, V, V, V, V, V,
+                                                       C.c_int32, V, V]
         L.okvfe_imu_propagation_blocks_device.restype = C.c_int32
         L.okvfe_imu_propagation_blocks_device.argtypes = [V, V, V, V, V, C.c_int32, C.c_int32, V, V, V]
         _LIB = L
@@ -1324,6 +1333,32 @@ class Frontend:
             self._h, C.byref(place_set) if place_set is not None else None, _p(blocks_ptr), int(n_multiframes), n_cams,
             _p(cams) if n_cams else _p(np.zeros(1, np.int32)), _p(prm) if n_cams else _p(np.zeros(7)), _p(poses_ptr),
             _p(match_landmark_ptr), _p(state_ptr), _p(verdict_ptr), C.byref(result) if result is not None else None,
+            _s(stream)))
+
+    @staticmethod
+    def make_place_refine_device(poses_ptr, status_ptr, n_iterations_ptr=None, n_accepted_ptr=None, n_terms_ptr=None,
+                                 cost_ptr=None, start_poses_ptr=None, H_ptr=None, n_singular_ptr=None) -> PlaceRefineDevice:
+        return PlaceRefineDevice(*[int(p) if p else None for p in (
+            poses_ptr, status_ptr, n_iterations_ptr, n_accepted_ptr, n_terms_ptr, cost_ptr, start_poses_ptr, H_ptr,
+            n_singular_ptr)])
+
+    def place_refine_blocks_device(self, place_set: PlaceSetDevice, blocks_ptr, n_multiframes, cam_ids, T_SC_params,
+                                   hypotheses_ptr, n_hyp, best_hypothesis_ptr, initial_poses_ptr, match_landmark_ptr,
+                                   state_ptr, verdict_ptr, max_iterations, result: PlaceRefineDevice, stream=None):
+        """The refinement of T_Sold_Snew of verifyRecognisedPlace (Frontend.cpp:399-527) as the defined algorithm of
+        include/okvfe.h, and H at the pose out.  The start: initial_poses_ptr (device, n_multiframes x 7) where given,
+        else hypothesis best_hypothesis_ptr[m] of hypotheses_ptr (device, n_multiframes x n_hyp x 12).  The other
+        arguments are those of place_hessian_blocks_device.  Nothing waits for the device."""
+        cams = np.ascontiguousarray(cam_ids, dtype=np.int32)
+        n_cams = len(cams)
+        prm = np.ascontiguousarray(T_SC_params, dtype=np.float64).reshape(-1)
+        if len(prm) != 7 * n_cams:
+            raise ValueError("cam_ids and T_SC_params: seven doubles per camera")
+        self._check(lib().okvfe_place_refine_blocks_device(
+            self._h, C.byref(place_set) if place_set is not None else None, _p(blocks_ptr), int(n_multiframes), n_cams,
+            _p(cams) if n_cams else _p(np.zeros(1, np.int32)), _p(prm) if n_cams else _p(np.zeros(7)),
+            _p(hypotheses_ptr), int(n_hyp), _p(best_hypothesis_ptr), _p(initial_poses_ptr), _p(match_landmark_ptr),
+            _p(state_ptr), _p(verdict_ptr), int(max_iterations), C.byref(result) if result is not None else None,
             _s(stream)))
 
     # -- IMU propagation on device-resident batches -------------------------------------------

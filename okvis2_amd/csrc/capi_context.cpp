@@ -388,7 +388,7 @@ okvfe_status okvfe_set_fp64_reduction(okvfe_ctx* ctx, int32_t order) {
     return fail(ctx, OKVFE_ERR_DEVICE, "okvfe_set_fp64_reduction: device %d", ctx->cfg.device);
   if (!okvfe::set_fp64_tree_match(order) || !okvfe::set_fp64_tree_map(order) || !okvfe::set_fp64_tree_ransac(order) ||
       !okvfe::set_fp64_tree_ransac2d2d(order) || !okvfe::set_fp64_tree_place_hessian(order) ||
-      !okvfe::set_fp64_tree_imu(order))
+      !okvfe::set_fp64_tree_place_refine(order) || !okvfe::set_fp64_tree_imu(order))
     return fail(ctx, OKVFE_ERR_DEVICE, "okvfe_set_fp64_reduction: writing the device flag failed");
   return OKVFE_OK;
 }
@@ -699,7 +699,7 @@ void okvfe_destroy(okvfe_ctx* ctx) {
   for (uint8_t* p : ctx->d_layer_img)
     if (p) (void)hipFree(p);
   if (ctx->d_virtual) (void)hipFree(ctx->d_virtual);
-  for (auto* list : {&ctx->map_perm, &ctx->map_table_ws})
+  for (auto* list : {&ctx->map_perm, &ctx->map_table_ws, &ctx->place_refine_ws})
     for (auto& m : *list)
       if (m.d) (void)hipFree(m.d);
   for (void* p : ctx->allocs) (void)hipFree(p);

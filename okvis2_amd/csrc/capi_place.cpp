@@ -141,6 +141,88 @@ okvfe_status okvfe_place_hessian_blocks_device(okvfe_ctx* ctx, const okvfe_place
   return rel;
 }
 
+// The refinement of T_Sold_Snew between the consensus and H (Frontend.cpp:399-527) as the defined algorithm of
+// tests/place_refine_ref.py: 3 + 2 max_iterations short launches (k_place_refine.hip) and, where H is asked for, the
+// Hessian kernel at the pose out.  Nothing here waits for the device.
+okvfe_status okvfe_place_refine_blocks_device(okvfe_ctx* ctx, const okvfe_place_set_device* set, const void* blocks_dev,
+                                              int32_t n_multiframes, int32_t n_cams, const int32_t* cam_ids,
+                                              const double* T_SC_params, const double* hypotheses_dev, int32_t n_hyp,
+                                              const int32_t* best_hypothesis_dev, const double* initial_poses_dev,
+                                              const int32_t* match_landmark_dev, const uint8_t* state_dev,
+                                              const uint8_t* verdict_dev, int32_t max_iterations,
+                                              const okvfe_place_refine_device* result, void* stream) {
+  if (!ctx) return OKVFE_ERR_INVALID_ARGUMENT;
+  if (!set || set->n_landmarks < 0 || (set->n_landmarks > 0 && !set->hp) || !blocks_dev || n_multiframes < 0 || n_cams < 1 ||
+      n_cams > (int)ctx->h_cams.size() || !cam_ids || !T_SC_params || !match_landmark_dev || !state_dev || !result ||
+      !result->poses || !result->status || max_iterations < 0 || max_iterations > kRefineMaxIterations ||
+      (!initial_poses_dev && (!hypotheses_dev || !best_hypothesis_dev || n_hyp < 0)))
+    return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_place_refine_blocks_device: bad argument");
+  if ((int64_t)n_cams * ctx->kp_cap >= (int64_t)1 << 30 || (int64_t)n_multiframes * n_cams >= (int64_t)1 << 30)
+    return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_place_refine_blocks_device: too many keypoints or blocks");
+  bool rt8 = false;  // the 8-coefficient form of the projection only when a slot this call uses holds that model
+  std::vector<HessianCamParams> cp((size_t)n_cams);
+  for (int c = 0; c < n_cams; ++c) {
+    const DeviceCamera* dc = slot_camera(ctx, cam_ids[c]);
+    if (!dc)
+      return fail(ctx, OKVFE_ERR_NOT_READY,
+                  "okvfe_place_refine_blocks_device: frame %d: camera slot %d has no intrinsics (okvfe_set_camera)", c,
+                  cam_ids[c]);
+    rt8 = rt8 || dc->distortion == OKVFE_DIST_RADTAN8;
+    cp[(size_t)c] = HessianCamParams{};
+    std::copy_n(T_SC_params + 7 * (size_t)c, 7, cp[(size_t)c].pose);
+    cp[(size_t)c].cam = cam_ids[c];
+  }
+  if (n_multiframes == 0) return OKVFE_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
+  hipStream_t s = pick_stream(ctx, stream);
+  const BlockLayout L = block_layout(ctx->kp_cap);
+  // the stream's workspace: a record and an evaluation per multiframe, and the two counts of the Hessian call where the
+  // caller does not ask for them
+  const size_t n = (size_t)n_multiframes;
+  const size_t o_evals = n * sizeof(PlaceRefineRecord), o_counts = o_evals + n * sizeof(PlaceRefineEval);
+  uint8_t* ws = nullptr;
+  okvfe_status st = stream_workspace(ctx, &ctx->place_refine_ws, s, o_counts + 2 * n * sizeof(int32_t), &ws);
+  if (st != OKVFE_OK) return st;
+  // the rig: 64 bytes per camera through the pinned parameter ring, once for every launch of the call
+  RingSlot rig(ctx, &ctx->pair_ring, s);
+  st = rig.upload(cp.data(), cp.size() * sizeof(HessianCamParams));
+  if (st != OKVFE_OK) return st;
+  PlaceRefineArgs R{};
+  PlaceHessianArgs& A = R.term;
+  A.hp = set->hp; A.n_landmarks = set->n_landmarks; A.blocks = static_cast<const uint8_t*>(blocks_dev);
+  A.o_count = (int)L.o_count; A.o_kps = (int)L.o_kps; A.block_bytes = L.total;
+  A.kp_cap = ctx->kp_cap; A.n_cams = n_cams; A.w = ctx->w; A.h = ctx->h;
+  A.cams = rig.as<HessianCamParams>(); A.dcams = ctx->d_cams; A.poses = result->poses;
+  A.match_landmark = match_landmark_dev; A.state = state_dev; A.verdict = verdict_dev;
+  A.H = result->H;
+  A.n_terms = reinterpret_cast<int32_t*>(ws + o_counts);
+  A.n_singular = result->n_singular ? result->n_singular : A.n_terms + n;
+  A.residual = nullptr; A.jacobian = nullptr;
+  R.records = reinterpret_cast<PlaceRefineRecord*>(ws);
+  R.evals = reinterpret_cast<PlaceRefineEval*>(ws + o_evals);
+  R.n_multiframes = n_multiframes; R.n_hyp = n_hyp; R.max_iterations = max_iterations;
+  R.hypotheses = hypotheses_dev; R.best = best_hypothesis_dev; R.initial = initial_poses_dev;
+  R.poses = result->poses; R.start_poses = result->start_poses; R.cost = result->cost;
+  R.status = result->status; R.n_iterations = result->n_iterations; R.n_accepted = result->n_accepted;
+  R.n_terms = result->n_terms;
+  {
+    StageTimer t(ctx, OKVFE_STAGE_MAP, s);
+    launch_place_refine_start(R, s);
+    launch_place_refine_eval(R, rt8, s);
+    launch_place_refine_step(R, true, s);
+    // at most max_iterations candidates are evaluated; the step behind the last one meets it >= max_iterations
+    for (int i = 0; i < max_iterations; ++i) {
+      launch_place_refine_eval(R, rt8, s);
+      launch_place_refine_step(R, false, s);
+    }
+    if (result->H) launch_place_hessian(A, n_multiframes, rt8, s);
+  }
+  HIP_TRY(ctx, hipGetLastError());
+  const okvfe_status rel = rig.release();  // behind the last launch that reads the rig
+  ctx->last_stream = s;
+  return rel;
+}
+
 // Test hook, deliberately not in include/okvfe.h: the number of terms the Hessian kernel evaluates at a time, so that the
 // tests straddle it whatever it is.
 int32_t okvfe_test_place_hessian_chunk_terms(void) { return place_hessian_chunk_terms(); }

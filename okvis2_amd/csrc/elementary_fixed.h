@@ -1,6 +1,6 @@
 // elementary_fixed.h -- FP64 log, sin and cos as ONE fixed sequence of IEEE-754 operations each, compiling for the host
 // and for gfx950: what the Cauchy loss and PoseManifold::plus of the refinement of Frontend::verifyRecognisedPlace
-// (okvis_frontend/src/Frontend.cpp:399-527) need.  No kernel includes it yet.
+// (okvis_frontend/src/Frontend.cpp:399-527) need (place_refine_dev.h, k_place_refine.hip), and the IMU propagation (imu_dev.h).
 //
 // Why: a refinement on the device is to be held byte for byte to a numpy restatement (tests/place_refine_ref.py); the
 // device math library's log, sin and cos differ from a host libm in the last bit for some arguments.  As in atan_fixed.h the

@@ -66,7 +66,8 @@ struct okvfe_ctx {
     uint8_t* d = nullptr;
     size_t bytes = 0;
   };
-  std::vector<StreamWorkspace> map_perm, map_table_ws;
+  // place_refine_ws: okvfe_place_refine_blocks_device's per-multiframe records, evaluations and spare counts
+  std::vector<StreamWorkspace> map_perm, map_table_ws, place_refine_ws;
   size_t map_table_ws_limit = (size_t)1 << 30;  // more than this per call: the frames go in slices
   ScoreLayout score_layout{0, 0};  // of d_scores: slotted where the fused score+NMS kernel applies
   ScoreLayout live_layout{0, 0};   // the layout the LAST score launch actually wrote (dense when the fused kernel refused the call)

@@ -13,6 +13,7 @@
 
 #include "../../include/okvfe.h"
 #include "imu_dev.h"
+#include "place_refine_dev.h"
 
 namespace okvfe {
 
@@ -646,6 +647,24 @@ struct PlaceHessianArgs {
 void launch_place_hessian(const PlaceHessianArgs& args, int n_multiframes, bool rt8, hipStream_t stream);
 int place_hessian_chunk_terms();  // terms the kernel evaluates at a time
 bool set_fp64_tree_place_hessian(int tree);
+// the refinement of verifyRecognisedPlace's pose (Frontend.cpp:399-527) for a batch of multiframes (k_place_refine.hip; the
+// solver is place_refine_dev.h, the term place_term_dev.h).  term: the Hessian call's arguments (poses, H and the rows are
+// not read: an evaluation takes its pose from the multiframe's record); records and evals lie in the call's workspace.
+struct PlaceRefineArgs {
+  PlaceHessianArgs term;
+  PlaceRefineRecord* records;  // n_multiframes
+  PlaceRefineEval* evals;      // n_multiframes
+  int n_multiframes, n_hyp, max_iterations;
+  const double* hypotheses;    // n_multiframes x n_hyp x 12, or null where initial is given
+  const int32_t* best;         // per multiframe, or null where initial is given
+  const double* initial;       // n_multiframes x 7, or null
+  double *poses, *start_poses, *cost;  // start_poses, cost: optional
+  int32_t *status, *n_iterations, *n_accepted, *n_terms;  // all but status optional
+};
+void launch_place_refine_start(const PlaceRefineArgs& args, hipStream_t stream);
+void launch_place_refine_eval(const PlaceRefineArgs& args, bool rt8, hipStream_t stream);
+void launch_place_refine_step(const PlaceRefineArgs& args, bool first, hipStream_t stream);
+bool set_fp64_tree_place_refine(int tree);
 // ImuError::propagation for a batch of multiframes (k_imu.hip; the arithmetic is imu_dev.h).  rig lies in the parameter
 // block of the call: the seven doubles of okvfe_imu_params, one unused, then seven per camera of T_SC; every other pointer
 // is the caller's.  The form follows out: covariance != null -> a wave per multiframe, else a lane per multiframe with

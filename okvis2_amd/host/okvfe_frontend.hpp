@@ -567,6 +567,28 @@ class HipFrontend {
     c.check(okvfe_place_hessian_blocks_device(c.get(), &set.get(), blocksDev, nMultiframes, 1, &cam, T_SC_params.data(),
                                               posesDev, matchLandmarkDev, stateDev, verdictDev, &result, stream));
   }
+  // Frontend.cpp:399-527 for the same frames: the refinement of T_Sold_Snew between the consensus and H, as the defined
+  // algorithm of okvfe_place_refine_blocks_device (include/okvfe.h: its two deviations from ceres, PARITY UNPINNED), and
+  // H at the pose out.  The start of multiframe m is initialPosesDev (nMultiframes x 7) where given, else hypothesis
+  // bestHypothesisDev[m] of hypothesesDev (nMultiframes x nHyp x 12), both as verifyPlaceConsensusBlocks holds them on
+  // the device; maxIterations: the reference's 10.  3 + 2 maxIterations short launches (+ 1 for H); nothing
+  // synchronises the host.
+  void verifyPlaceRefineBlocks(size_t cameraIndex, const DevicePlaceSet& set, const void* blocksDev, int nMultiframes,
+                               const std::array<double, 7>& T_SC_params, const double* hypothesesDev, int nHyp,
+                               const int32_t* bestHypothesisDev, const double* initialPosesDev,
+                               const int32_t* matchLandmarkDev, const uint8_t* stateDev, const uint8_t* verdictDev,
+                               int maxIterations, const okvfe_place_refine_device& result, void* stream = nullptr) {
+    if (cameraIndex >= cameras_.size())
+      throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "Camera index exceeds number of cameras.");
+    if (nMultiframes < 0) throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "verifyPlaceRefineBlocks: nMultiframes");
+    std::lock_guard<std::mutex> lock(mutexes_[cameraIndex]);
+    if (!extractors_[cameraIndex].isCameraAware()) extractors_[cameraIndex].setCamera(cameras_[cameraIndex]);
+    Context& c = *contexts_[cameraIndex];
+    const int32_t cam = 0;  // slot 0 of the camera's own context
+    c.check(okvfe_place_refine_blocks_device(c.get(), &set.get(), blocksDev, nMultiframes, 1, &cam, T_SC_params.data(),
+                                             hypothesesDev, nHyp, bestHypothesisDev, initialPosesDev, matchLandmarkDev,
+                                             stateDev, verdictDev, maxIterations, &result, stream));
+  }
   // ViFrontendInterface::propagation, i.e. ImuError::propagation (okvis_ceres/src/ImuError.cpp:557-779): the pose guess
   // of a frame from the IMU samples since the last one, its 15 x 15 Jacobian and covariance, and per camera
   // T_WC = T_WS T_SC with the extraction direction of detectAndDescribe (Frontend.cpp:246-251).  The arithmetic, its
