@@ -871,7 +871,8 @@ okvfe_status okvfe_landmark_table_check_device(okvfe_ctx* ctx, const okvfe_landm
  * The second pass of Frontend::matchToMap over the landmarks that are not 3-D yet is
  * okvfe_match_to_map_table_uninitialised_blocks_device below, on what pool_out leaves on the device.  Between the two
  * passes (Frontend.cpp:1411-1430): okvfe_ransac3d2d_consensus_blocks_device and okvfe_remove_outliers_blocks_device
- * further below.  Not covered: the minimal solver and the sampler of the RANSAC, and optimiseRealtimeGraph. */
+ * further below, their hypotheses from okvfe_ransac3d2d_hypotheses_blocks_device (a defined sampler and P3P, not
+ * opengv's).  Not covered: optimiseRealtimeGraph. */
 okvfe_status okvfe_match_to_map_table_blocks_device(
     okvfe_ctx* ctx, const okvfe_landmark_table_device* table, const void* blocks_dev, int32_t n_frames,
     const int32_t* cam_ids /* HOST, n_frames */, const okvfe_pose* T_WC1 /* HOST, n_frames */,
@@ -948,8 +949,9 @@ okvfe_status okvfe_match_to_map_table_uninitialised_blocks_device(
  * such in list order; accepted = n_inliers >= 10 && double(n_inliers) / double(n_correspondences) > 0.7.  The winning
  * pose is hypotheses[best_hypothesis], which the caller owns.
  *
- * NOT restated: the minimal solver (opengv's gp3p) and the sampler, which work on three correspondences at a time and
- * stay with the caller; opengv's adaptive stop, which only ever shortens the list (this call scores every hypothesis
+ * NOT restated: opengv's gp3p and its rand() sampler.  okvfe_ransac3d2d_hypotheses_blocks_device (further below)
+ * offers a defined sampler and a central P3P in their place, under the deviations stated there; a caller may as well
+ * bring hypotheses of its own.  Nor opengv's adaptive stop, which only ever shortens the list (this call scores every hypothesis
  * it is given).  PARITY UNPINNED: opengv is not in the reference tree; the winner rule (replace on strictly more
  * inliers) is restated from the published source of opengv::sac::Ransac::computeModel.
  *
@@ -1279,6 +1281,82 @@ okvfe_status okvfe_place_consensus_blocks_device(
     const int32_t* match_landmark_dev, const uint8_t* gate_dev /* or NULL */, const double* hypotheses_dev,
     const uint8_t* hyp_valid_dev /* or NULL */, int32_t n_hyp, double threshold, int32_t min_inliers,
     const okvfe_ransac_result_device* result, uint8_t* verdict_dev, void* stream);
+
+/* ---- the pose hypotheses of the two consensus calls: sampler and P3P solver -------------------
+ * What fills hypotheses_dev / hyp_valid_dev of okvfe_ransac3d2d_consensus_blocks_device and
+ * okvfe_place_consensus_blocks_device without a host step in between.  A DEFINED ALGORITHM, PARITY UNPINNED: opengv (not
+ * in the reference tree) samples with rand() and solves gp3p, so sample-for-sample parity is impossible by construction;
+ * what is stated here is restated in tests/ransac_hyp_ref.py one IEEE operation per line, and host, device and
+ * restatement agree byte for byte.  The caller's own solver remains an option: the consensus calls take any hypotheses.
+ *
+ * Correspondences: exactly those of the consensus call of the same policy (the same device function), camera-major
+ * with keypoints ascending; n of them in multiframe m.
+ * Sampler (counter-based: a multiframe's samples do not depend on its place in the batch).  With key = sample_keys_dev[m]
+ * (or m where that pointer is NULL), hypothesis h and draw j = 0 .. 3:
+ *   z = seed + (key 512 + h 8 + j + 1) 0x9E3779B97F4A7C15 (mod 2^64); z ^= z >> 30; z *= 0xBF58476D1CE4E5B9;
+ *   z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31;  r(j, range) = ((z >> 32) range) >> 32.
+ * i0 = r(0, n); its camera c owns the contiguous range [b_c, e_c) of the list, n_c = e_c - b_c.  n_c < 4: invalid.
+ * Draws 1 .. 3: t = r(j, n_c - j), then, over the already chosen positions x of camera c in ascending order, t += 1
+ * where x <= t (no rejection loop).  Samples 0 .. 2 go to the solver, sample 3 chooses among its solutions.
+ * DEVIATION from gp3p: all four samples come from ONE camera and the solver is a central P3P lifted through T_SC[c]
+ * (on a one-camera multiframe: the whole list; on a rig the consensus still scores every camera).
+ * Solver: Grunert's P3P in the distance form, a^2 = |P2 - P3|^2, b^2 = |P1 - P3|^2, c^2 = |P1 - P2|^2, ca = f2.f3,
+ * cb = f1.f3, cg = f1.f2, k = (a^2 - c^2) / b^2, k2 = (a^2 + c^2) / b^2; the quartic in v = s3 / s1 with
+ *   A4 = (k - 1)^2 - 4 (c^2/b^2) ca^2,  A3 = 4 [k (1 - k) cb - (1 - k2) ca cg + 2 (c^2/b^2) ca^2 cb],
+ *   A2 = 2 [k^2 - 1 + 2 k^2 cb^2 + 2 ((b^2 - c^2)/b^2) ca^2 - 4 k2 ca cb cg + 2 ((b^2 - a^2)/b^2) cg^2],
+ *   A1 = 4 [-k (1 + k) cb + 2 (a^2/b^2) cg^2 cb - (1 - k2) ca cg],  A0 = (1 + k)^2 - 4 (a^2/b^2) cg^2;
+ * A4 == 0 or a non-finite coefficient: no solution.  Real roots: Ferrari on the depressed quartic y^4 + p y^2 + q y + r
+ * (v = y - A3 / (4 A4)); q == 0: the biquadratic, y = +-sqrt(w) for the two w = (-p +- sqrt(p p - 4 r)) / 2 that are
+ * >= 0, in the order +sqrt(w+), -sqrt(w+), +sqrt(w-), -sqrt(w-); otherwise the positive root m of
+ * 8 m^3 + 8 p m^2 + (2 p^2 - 8 r) m - q^2 by bisection on [0, hi], hi doubled from 1 until the resolvent is positive
+ * there, at most 64 times (else: no root), bisected until the midpoint equals an end, at most 128 steps, m = the upper
+ * end; s = sqrt(2 m), t0 = p / 2 + m, u0 = q / (2 s); y = (s +- sqrt(s s - 4 (t0 + u0))) / 2, then
+ * y = (-s +- sqrt(s s - 4 (t0 - u0))) / 2, each pair iff its discriminant is >= 0, + before -.  Equal roots are listed as
+ * often as they occur.  Each root takes exactly 3 Newton steps on the original quartic (a step whose derivative is
+ * exactly 0 leaves v unchanged).  ROOT ORDER IS SOLUTION ORDER.  u = s2 / s1 = ((k - 1) v^2 - 2 k cb v + 1 + k) /
+ * (2 (cg - v ca)), s1^2 = b^2 / (1 + v^2 - 2 v cb); a root counts (n_solutions) iff v > 0 && u > 0 && s1^2 > 0 (a NaN
+ * fails).  Pose: Q_i = s_i f_i; R_CW from the two orthonormal triads e1 = (X2 - X1) / |..|, e3 = e1 x (X3 - X1)
+ * normalised, e2 = e3 x e1 (no SVD); t_CW = Q1 - R_CW P1; inverted; T_WS = T_WC T_SC^-1.  Every sum of the solver runs
+ * left to right, whatever okvfe_set_fp64_reduction says.
+ * Choice: the distance of the consensus call (the same function, which does follow okvfe_set_fp64_reduction) of sample
+ * 3 under every solution; the smallest wins, the first on ties, a NaN or infinite distance never.
+ * Invalid (hyp_valid 0, the 12 doubles zero): n_c < 4, no solution, no finite distance, a non-finite output.
+ *
+ * okvfe_p3p_hypothesis: the solver and the choice for ONE sample on the host, no context (what a caller at B = 1, or
+ * one with its own sampler, uses).  points / bearings: 4 x 3 doubles (world points, unit bearings in the camera frame;
+ * rows 0 .. 2 are solved, row 3 chooses), sigma: of the fourth correspondence, T_SC: of the samples' camera,
+ * order: OKVFE_SUM3_EIGEN_TREE or OKVFE_SUM3_LEFT_TO_RIGHT.  hypothesis: 12 doubles, row-major [R | t] = T_WS;
+ * valid, n_solutions (optional): one each. */
+okvfe_status okvfe_p3p_hypothesis(const double* points, const double* bearings, double sigma, const okvfe_pose* T_SC,
+                                  int32_t order, double* hypothesis, uint8_t* valid, int32_t* n_solutions);
+/* The device calls: layouts and argument rules of the consensus calls (table / set, blocks_dev, n_cams, cam_ids, T_SC,
+ * landmark_dev / match_landmark_dev, gate_dev).  sample_keys_dev: n_multiframes uint64 or NULL; n_hyp in
+ * 1 .. OKVFE_RANSAC_MAX_HYPOTHESES.  With gate_dev[m] == 0 every hypothesis of multiframe m is invalid and nothing is
+ * solved (samples -1, n_solutions 0).  result->hypotheses (n_multiframes x n_hyp x 12 doubles) and result->hyp_valid
+ * (n_multiframes x n_hyp bytes) ARE the consensus calls' hypotheses_dev / hyp_valid_dev; optional: n_correspondences
+ * (int32 per multiframe), samples (n_multiframes x n_hyp x 4 int32: c K + k of the drawn keypoint, -1 where nothing
+ * was drawn), n_solutions (int32 per hypothesis).  One work-group per multiframe; the camera-major list of a multiframe
+ * is 4 bytes per keypoint slot in LDS: n_cams x K + n_cams + 1 ints above 60 KiB is OKVFE_ERR_UNSUPPORTED.  Nothing
+ * synchronises the host; no workspace; 112 bytes per camera go through the pinned parameter ring.  A NULL or negative
+ * argument or n_hyp outside its range: OKVFE_ERR_INVALID_ARGUMENT before anything is launched; n_multiframes == 0 is
+ * OK and launches nothing. */
+typedef struct okvfe_ransac_hypotheses_device {
+  double* hypotheses;
+  uint8_t* hyp_valid;
+  int32_t* n_correspondences; /* optional */
+  int32_t* samples;           /* optional */
+  int32_t* n_solutions;       /* optional */
+} okvfe_ransac_hypotheses_device;
+okvfe_status okvfe_ransac3d2d_hypotheses_blocks_device(
+    okvfe_ctx* ctx, const okvfe_landmark_table_device* table, const void* blocks_dev, int32_t n_multiframes,
+    int32_t n_cams, const int32_t* cam_ids /* HOST, n_cams */, const okvfe_pose* T_SC /* HOST, n_cams */,
+    const int32_t* landmark_dev, const uint64_t* sample_keys_dev /* or NULL */, uint64_t seed, int32_t n_hyp,
+    const okvfe_ransac_hypotheses_device* result, void* stream);
+okvfe_status okvfe_place_hypotheses_blocks_device(
+    okvfe_ctx* ctx, const okvfe_place_set_device* set, const void* blocks_dev, int32_t n_multiframes, int32_t n_cams,
+    const int32_t* cam_ids /* HOST, n_cams */, const okvfe_pose* T_SC /* HOST, n_cams */,
+    const int32_t* match_landmark_dev, const uint8_t* gate_dev /* or NULL */, const uint64_t* sample_keys_dev /* or NULL */,
+    uint64_t seed, int32_t n_hyp, const okvfe_ransac_hypotheses_device* result, void* stream);
 
 typedef struct okvfe_place_hessian_device {
   double* H;                /* device, n_multiframes x 36, row-major 6 x 6 */

@@ -129,6 +129,7 @@ EXPORTS = [
     "okvfe_overlap_pairs_blocks_device", "okvfe_overlap_fraction", "okvfe_motion_frame_order",
     "okvfe_tracking_quality",
     "okvfe_imu_propagation", "okvfe_imu_propagation_blocks_device",
+    "okvfe_p3p_hypothesis", "okvfe_ransac3d2d_hypotheses_blocks_device", "okvfe_place_hypotheses_blocks_device",
 ]
 # exported for the tests and deliberately not declared in include/okvfe.h (EXPORTS is exactly what the header declares)
 TEST_HOOKS = [
@@ -178,6 +179,12 @@ class RansacResultDevice(C.Structure):
     _fields_ = [("n_correspondences", C.c_void_p), ("best_hypothesis", C.c_void_p), ("n_inliers", C.c_void_p),
                 ("accepted", C.c_void_p), ("hyp_inliers", C.c_void_p), ("state", C.c_void_p),
                 ("distance", C.c_void_p), ("landmark_out", C.c_void_p)]
+
+
+class RansacHypothesesDevice(C.Structure):
+    """okvfe_ransac_hypotheses_device: device pointers; the last three are optional (None)."""
+    _fields_ = [("hypotheses", C.c_void_p), ("hyp_valid", C.c_void_p), ("n_correspondences", C.c_void_p),
+                ("samples", C.c_void_p), ("n_solutions", C.c_void_p)]
 
 
 class Ransac2d2dResultDevice(C.Structure):
@@ -331,6 +338,14 @@ def lib():
         L.okvfe_place_consensus_blocks_device.restype = C.c_int32
         L.okvfe_place_consensus_blocks_device.argtypes = [
             V, V, V, C.c_int32, C.c_int32, V, V, V, V, V, V, C.c_int32, C.c_double, C.c_int32, V, V, V]
+        L.okvfe_p3p_hypothesis.restype = C.c_int32
+        L.okvfe_p3p_hypothesis.argtypes = [V, V, C.c_double, V, C.c_int32, V, V, V]
+        L.okvfe_ransac3d2d_hypotheses_blocks_device.restype = C.c_int32
+        L.okvfe_ransac3d2d_hypotheses_blocks_device.argtypes = [
+            V, V, V, C.c_int32, C.c_int32, V, V, V, V, C.c_uint64, C.c_int32, V, V]
+        L.okvfe_place_hypotheses_blocks_device.restype = C.c_int32
+        L.okvfe_place_hypotheses_blocks_device.argtypes = [
+            V, V, V, C.c_int32, C.c_int32, V, V, V, V, V, C.c_uint64, C.c_int32, V, V]
         L.okvfe_place_hessian_blocks_device.restype = C.c_int32
         L.okvfe_place_hessian_blocks_device.argtypes = [V, V, V, C.c_int32, C.c_int32, V, V, V, V, V, V, V, V]
         L.okvfe_vocabulary_check.restype = C.c_int32
@@ -531,6 +546,24 @@ def place_landmark_set(n_kps, landmark_ids, landmarks, initialised, descriptors,
         raise OkvfeError(st, "okvfe_place_landmark_set")
     L, R = nl.value, nr.value
     return dict(ids=out["ids"][:L], hp=out["hp"][:L], desc_begin=out["desc_begin"][:L + 1], pool=out["pool"][:R])
+
+
+def p3p_hypothesis(points, bearings, sigma, T_SC, eigen_tree=True):
+    """okvfe_p3p_hypothesis (host arithmetic, no context): points / bearings [4, 3] (rows 0 .. 2 are solved, row 3
+    chooses among the solutions), sigma of the fourth, T_SC = (C, r) of their camera.
+    -> (hypothesis [12] = row-major [R | t] of T_WS, valid, n_solutions)"""
+    P = np.ascontiguousarray(points, dtype=np.float64).reshape(-1)
+    f = np.ascontiguousarray(bearings, dtype=np.float64).reshape(-1)
+    if len(P) != 12 or len(f) != 12:
+        raise ValueError("four points and four bearings")
+    pose = make_pose(*T_SC)
+    H = np.zeros(12)
+    valid, n_sol = C.c_uint8(0), C.c_int32(0)
+    st = lib().okvfe_p3p_hypothesis(_p(P), _p(f), C.c_double(sigma), C.byref(pose), 1 if eigen_tree else 0, _p(H),
+                                    C.byref(valid), C.byref(n_sol))
+    if st != OK:
+        raise OkvfeError(st, "okvfe_p3p_hypothesis")
+    return H, int(valid.value), int(n_sol.value)
 
 
 def keyframe_decision(current, others=None, overlap_threshold=KEYFRAME_OVERLAP_THRESHOLD):
@@ -1198,6 +1231,46 @@ class Frontend:
             self._h, C.byref(table), _p(blocks_ptr), int(n_multiframes), n_cams,
             _p(cams) if n_cams else _p(np.zeros(1, np.int32)), P, _p(landmark_ptr), _p(hypotheses_ptr),
             _p(hyp_valid_ptr), int(n_hyp), C.c_double(threshold), int(bool(remove_outliers)),
+            C.byref(result) if result is not None else None, _s(stream)))
+
+    # -- the hypotheses of the two consensus calls: sampler and P3P on the device --------------
+    @staticmethod
+    def make_ransac_hypotheses_device(hypotheses_ptr, hyp_valid_ptr, n_correspondences_ptr=None, samples_ptr=None,
+                                      n_solutions_ptr=None) -> RansacHypothesesDevice:
+        return RansacHypothesesDevice(*[int(p) if p else None for p in (
+            hypotheses_ptr, hyp_valid_ptr, n_correspondences_ptr, samples_ptr, n_solutions_ptr)])
+
+    def ransac3d2d_hypotheses_blocks_device(self, table: LandmarkTableDevice, blocks_ptr, n_multiframes, cam_ids,
+                                            poses_T_SC, landmark_ptr, sample_keys_ptr, seed, n_hyp,
+                                            result: RansacHypothesesDevice, stream=None):
+        """n_hyp pose hypotheses per multiframe for ransac3d2d_consensus_blocks_device (the defined sampler and P3P of
+        include/okvfe.h).  sample_keys_ptr: device n_multiframes uint64 or None (the multiframe's index);
+        result.hypotheses / result.hyp_valid are that call's hypotheses_ptr / hyp_valid_ptr."""
+        cams = np.ascontiguousarray(cam_ids, dtype=np.int32)
+        n_cams = len(cams)
+        if len(poses_T_SC) != n_cams:
+            raise ValueError("cam_ids and poses_T_SC: one per camera")
+        P = (Pose * max(n_cams, 1))(*[make_pose(*T) for T in poses_T_SC])
+        self._check(lib().okvfe_ransac3d2d_hypotheses_blocks_device(
+            self._h, C.byref(table) if table is not None else None, _p(blocks_ptr), int(n_multiframes), n_cams,
+            _p(cams) if n_cams else _p(np.zeros(1, np.int32)), P, _p(landmark_ptr), _p(sample_keys_ptr),
+            C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), int(n_hyp), C.byref(result) if result is not None else None,
+            _s(stream)))
+
+    def place_hypotheses_blocks_device(self, place_set: PlaceSetDevice, blocks_ptr, n_multiframes, cam_ids, poses_T_SC,
+                                       match_landmark_ptr, gate_ptr, sample_keys_ptr, seed, n_hyp,
+                                       result: RansacHypothesesDevice, stream=None):
+        """The same for place_consensus_blocks_device; with gate_ptr[m] == 0 every hypothesis of multiframe m is
+        invalid and nothing is solved."""
+        cams = np.ascontiguousarray(cam_ids, dtype=np.int32)
+        n_cams = len(cams)
+        if len(poses_T_SC) != n_cams:
+            raise ValueError("cam_ids and poses_T_SC: one per camera")
+        P = (Pose * max(n_cams, 1))(*[make_pose(*T) for T in poses_T_SC])
+        self._check(lib().okvfe_place_hypotheses_blocks_device(
+            self._h, C.byref(place_set) if place_set is not None else None, _p(blocks_ptr), int(n_multiframes), n_cams,
+            _p(cams) if n_cams else _p(np.zeros(1, np.int32)), P, _p(match_landmark_ptr), _p(gate_ptr),
+            _p(sample_keys_ptr), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), int(n_hyp),
             C.byref(result) if result is not None else None, _s(stream)))
 
     def remove_outliers_blocks_device(self, table: LandmarkTableDevice, blocks_ptr, n_frames, cam_ids, poses_T_WC,

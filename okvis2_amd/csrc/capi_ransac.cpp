@@ -139,6 +139,91 @@ okvfe_status okvfe_place_consensus_blocks_device(
   return rel;
 }
 
+// The solver and the choice of ransac_hyp_dev.h for one sample on the host (k_ransac_hyp.hip): the B = 1 seam of the two
+// calls below.
+okvfe_status okvfe_p3p_hypothesis(const double* points, const double* bearings, double sigma, const okvfe_pose* T_SC,
+                                  int32_t order, double* hypothesis, uint8_t* valid, int32_t* n_solutions) {
+  if (!points || !bearings || !T_SC || !hypothesis || !valid ||
+      (order != OKVFE_SUM3_LEFT_TO_RIGHT && order != OKVFE_SUM3_EIGEN_TREE))
+    return OKVFE_ERR_INVALID_ARGUMENT;
+  int n_sol = 0;
+  const bool ok = p3p_hypothesis_host(order == OKVFE_SUM3_EIGEN_TREE, points, bearings, sigma, T_SC->C, T_SC->r, hypothesis, &n_sol);
+  *valid = ok ? 1 : 0;
+  if (n_solutions) *n_solutions = n_sol;
+  return OKVFE_OK;
+}
+
+// The hypotheses of okvfe_ransac3d2d_consensus_blocks_device: sampler and P3P on the device (k_ransac_hyp.hip).
+okvfe_status okvfe_ransac3d2d_hypotheses_blocks_device(
+    okvfe_ctx* ctx, const okvfe_landmark_table_device* T, const void* blocks_dev, int32_t n_multiframes, int32_t n_cams,
+    const int32_t* cam_ids, const okvfe_pose* T_SC, const int32_t* landmark_dev, const uint64_t* sample_keys_dev,
+    uint64_t seed, int32_t n_hyp, const okvfe_ransac_hypotheses_device* result, void* stream) {
+  if (!ctx) return OKVFE_ERR_INVALID_ARGUMENT;
+  if (!T || T->n_landmarks < 0 || (T->n_landmarks > 0 && (!T->hp_W || !T->obs_begin)) || !blocks_dev ||
+      n_multiframes < 0 || n_cams < 1 || n_cams > (int)ctx->h_cams.size() || !cam_ids || !T_SC || !landmark_dev ||
+      n_hyp < 1 || n_hyp > OKVFE_RANSAC_MAX_HYPOTHESES || !result || !result->hypotheses || !result->hyp_valid)
+    return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_ransac3d2d_hypotheses_blocks_device: bad argument");
+  if (!ransac_hypotheses_fits(n_cams, ctx->kp_cap))
+    return fail(ctx, OKVFE_ERR_UNSUPPORTED,
+                "okvfe_ransac3d2d_hypotheses_blocks_device: the list of %d x %d keypoint slots does not fit in LDS", n_cams,
+                ctx->kp_cap);
+  std::vector<RansacCamParams> cp;
+  okvfe_status st = rig_params(ctx, "okvfe_ransac3d2d_hypotheses_blocks_device", n_cams, cam_ids, T_SC, &cp);
+  if (st != OKVFE_OK) return st;
+  if (n_multiframes == 0) return OKVFE_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
+  hipStream_t s = pick_stream(ctx, stream);
+  const BlockLayout L = block_layout(ctx->kp_cap);
+  RingSlot rig(ctx, &ctx->pair_ring, s);
+  if ((st = rig.upload(cp.data(), cp.size() * sizeof(RansacCamParams))) != OKVFE_OK) return st;
+  {
+    StageTimer t(ctx, OKVFE_STAGE_MAP, s);
+    launch_ransac_hypotheses(T->hp_W, T->obs_begin, T->n_landmarks, L, static_cast<const uint8_t*>(blocks_dev),
+                             n_multiframes, n_cams, ctx->kp_cap, rig.as<RansacCamParams>(), landmark_dev, sample_keys_dev,
+                             seed, n_hyp, *result, s);
+  }
+  HIP_TRY(ctx, hipGetLastError());
+  const okvfe_status rel = rig.release();
+  ctx->last_stream = s;
+  return rel;
+}
+
+// ... and of okvfe_place_consensus_blocks_device: the same kernel under its kPlace policy.
+okvfe_status okvfe_place_hypotheses_blocks_device(
+    okvfe_ctx* ctx, const okvfe_place_set_device* set, const void* blocks_dev, int32_t n_multiframes, int32_t n_cams,
+    const int32_t* cam_ids, const okvfe_pose* T_SC, const int32_t* match_landmark_dev, const uint8_t* gate_dev,
+    const uint64_t* sample_keys_dev, uint64_t seed, int32_t n_hyp, const okvfe_ransac_hypotheses_device* result,
+    void* stream) {
+  if (!ctx) return OKVFE_ERR_INVALID_ARGUMENT;
+  if (!set || set->n_landmarks < 0 || (set->n_landmarks > 0 && !set->hp) || !blocks_dev || n_multiframes < 0 ||
+      n_cams < 1 || n_cams > (int)ctx->h_cams.size() || !cam_ids || !T_SC || !match_landmark_dev || n_hyp < 1 ||
+      n_hyp > OKVFE_RANSAC_MAX_HYPOTHESES || !result || !result->hypotheses || !result->hyp_valid)
+    return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_place_hypotheses_blocks_device: bad argument");
+  if (!ransac_hypotheses_fits(n_cams, ctx->kp_cap))
+    return fail(ctx, OKVFE_ERR_UNSUPPORTED,
+                "okvfe_place_hypotheses_blocks_device: the list of %d x %d keypoint slots does not fit in LDS", n_cams,
+                ctx->kp_cap);
+  std::vector<RansacCamParams> cp;
+  okvfe_status st = rig_params(ctx, "okvfe_place_hypotheses_blocks_device", n_cams, cam_ids, T_SC, &cp);
+  if (st != OKVFE_OK) return st;
+  if (n_multiframes == 0) return OKVFE_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
+  hipStream_t s = pick_stream(ctx, stream);
+  const BlockLayout L = block_layout(ctx->kp_cap);
+  RingSlot rig(ctx, &ctx->pair_ring, s);
+  if ((st = rig.upload(cp.data(), cp.size() * sizeof(RansacCamParams))) != OKVFE_OK) return st;
+  {
+    StageTimer t(ctx, OKVFE_STAGE_MAP, s);
+    launch_place_hypotheses(set->hp, set->n_landmarks, L, static_cast<const uint8_t*>(blocks_dev), n_multiframes, n_cams,
+                            ctx->kp_cap, rig.as<RansacCamParams>(), match_landmark_dev, gate_dev, sample_keys_dev, seed,
+                            n_hyp, *result, s);
+  }
+  HIP_TRY(ctx, hipGetLastError());
+  const okvfe_status rel = rig.release();
+  ctx->last_stream = s;
+  return rel;
+}
+
 // Test hook, deliberately not in include/okvfe.h: the number of correspondences the consensus kernel scores at a time,
 // so that the tests straddle it whatever it is.
 int32_t okvfe_test_ransac_chunk_records(void) { return ransac_chunk_records(); }

@@ -1,7 +1,7 @@
 // k_ransac.hip -- the consensus step of Frontend::runRansac3d2d (okvis_frontend/src/Frontend.cpp:2208-2261) for a
 // batch of multiframes: the correspondences of FrameNoncentralAbsoluteAdapter (FrameNoncentralAbsoluteAdapter.cpp:
 // 50-148), the distance of every correspondence to every pose hypothesis (FrameAbsolutePoseSacProblem.hpp:135-167),
-// the winner, the acceptance rule and the outlier removal.  The minimal solver and the sampler stay with the caller.
+// the winner, the acceptance rule and the outlier removal.  The hypotheses: the caller's, or those of k_ransac_hyp.hip.
 // The same kernel under the policy kPlace is the consensus of Frontend::verifyRecognisedPlace (Frontend.cpp:372-397)
 // over the correspondences of LoopclosureNoncentralAbsoluteAdapter (LoopclosureNoncentralAbsoluteAdapter.cpp:69-154):
 // the rows are those of the old frame's landmark set, there is no test on observations, seven correspondences are the
@@ -13,6 +13,8 @@
 //                             A final sweep over the keypoints with the winner writes state / distance / landmark_out.
 // FP64, 3- and 4-term sums in the order of okvfe_set_fp64_reduction (a template argument: the host launches the kernel
 // compiled for the order in force), no FMA.
+// The sums, the inverse of a hypothesis and the distance also compile for the host: the choice among the solutions of a
+// P3P sample (k_ransac_hyp.hip, included at the end of this file so that it uses these copies) runs there as well.
 #include "okvfe_internal.h"
 
 namespace okvfe {
@@ -26,13 +28,13 @@ int current_device_slot() {
   return hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < kMaxAttrDevices ? dev : 0;
 }
 template <bool kTree>
-__device__ __forceinline__ double sum3m(double p0, double p1, double p2) {
+__host__ __device__ __forceinline__ double sum3m(double p0, double p1, double p2) {
   if constexpr (kTree) return p0 + (p1 + p2);
   return (p0 + p1) + p2;
 }
 // four terms: Eigen's redux_novec_unroller splits at Length / 2, (x0 + x1) + (x2 + x3); left to right ((x0 + x1) + x2) + x3
 template <bool kTree>
-__device__ __forceinline__ double sum4m(double p0, double p1, double p2, double p3) {
+__host__ __device__ __forceinline__ double sum4m(double p0, double p1, double p2, double p3) {
   if constexpr (kTree) return (p0 + p1) + (p2 + p3);
   return ((p0 + p1) + p2) + p3;
 }
@@ -118,7 +120,7 @@ __device__ __forceinline__ bool make_correspondence(const RansacArgs& A, const u
 
 // FrameAbsolutePoseSacProblem.hpp:142-143: inv[0..8] = R^T row-major, inv[9..11] = (-R^T) t
 template <bool kTree>
-__device__ __forceinline__ void invert_hypothesis(const double* H /* 3 x 4 row-major */, double* inv) {
+__host__ __device__ __forceinline__ void invert_hypothesis(const double* H /* 3 x 4 row-major */, double* inv) {
   for (int i = 0; i < 3; ++i)
     for (int j = 0; j < 3; ++j) inv[3 * i + j] = H[4 * j + i];
   for (int i = 0; i < 3; ++i)
@@ -127,8 +129,8 @@ __device__ __forceinline__ void invert_hypothesis(const double* H /* 3 x 4 row-m
 
 // FrameAbsolutePoseSacProblem.hpp:151-165.  The ONE copy of the distance: the scoring loop and the final sweep call it.
 template <bool kTree>
-__device__ __forceinline__ double ransac_distance(const double* inv, const double p[3], const double C_SC[9],
-                                                  const double r_SC[3], const double b[3], double sigma) {
+__host__ __device__ __forceinline__ double ransac_distance(const double* inv, const double p[3], const double C_SC[9],
+                                                           const double r_SC[3], const double b[3], double sigma) {
   double d[3], rep[3], e[3];
   for (int i = 0; i < 3; ++i) {
     const double body = sum4m<kTree>(inv[3 * i] * p[0], inv[3 * i + 1] * p[1], inv[3 * i + 2] * p[2], inv[9 + i] * 1.0);
@@ -322,3 +324,6 @@ bool set_fp64_tree_ransac(int tree) {
 }
 
 }  // namespace okvfe
+
+// the pose hypotheses of both policies: their kernel uses make_correspondence, invert_hypothesis and ransac_distance above
+#include "k_ransac_hyp.hip"

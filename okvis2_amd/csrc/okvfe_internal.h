@@ -575,6 +575,20 @@ void launch_ransac_consensus(const double* hp_W, const int32_t* obs_begin, int n
                              const RansacCamParams* cams, const int32_t* landmark, const double* hypotheses,
                              const uint8_t* hyp_valid, int n_hyp, double threshold, int remove_outliers,
                              const okvfe_ransac_result_device& out, hipStream_t stream);
+// the pose hypotheses of both consensus calls (k_ransac_hyp.hip, a part of k_ransac.hip's translation unit): sampler,
+// P3P, the choice by the fourth sample
+bool p3p_hypothesis_host(bool tree, const double* points, const double* bearings, double sigma, const double* C_SC,
+                         const double* r_SC, double* hypothesis, int* n_solutions);
+size_t ransac_hypotheses_lds_bytes(int n_cams, int kp_cap);
+bool ransac_hypotheses_fits(int n_cams, int kp_cap);
+void launch_ransac_hypotheses(const double* hp_W, const int32_t* obs_begin, int n_landmarks, const BlockLayout& L,
+                              const uint8_t* blocks, int n_multiframes, int n_cams, int kp_cap, const RansacCamParams* cams,
+                              const int32_t* landmark, const uint64_t* keys, uint64_t seed, int n_hyp,
+                              const okvfe_ransac_hypotheses_device& out, hipStream_t stream);
+void launch_place_hypotheses(const double* hp, int n_landmarks, const BlockLayout& L, const uint8_t* blocks,
+                             int n_multiframes, int n_cams, int kp_cap, const RansacCamParams* cams,
+                             const int32_t* match_landmark, const uint8_t* gate, const uint64_t* keys, uint64_t seed,
+                             int n_hyp, const okvfe_ransac_hypotheses_device& out, hipStream_t stream);
 int ransac_chunk_records();  // correspondences the consensus kernel scores at a time
 int ransac_ring_records();   // records of its LDS ring
 // the consensus step of runRansac2d2d for a batch of (older, current) multiframe pairs (k_ransac2d2d.hip).  pairs

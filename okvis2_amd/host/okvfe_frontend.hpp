@@ -547,6 +547,22 @@ class HipFrontend {
         reinterpret_cast<const double*>(d), hypValid.empty() ? nullptr : d + hypBytes, nHyp, threshold, minInliers, &result,
         verdictDev, stream));
   }
+  // The hypotheses verifyPlaceConsensusBlocks scores, made on the device: okvfe_place_hypotheses_blocks_device over the
+  // rows verifyPlaceClaimsBlocks wrote; with gateDev[m] == 0 nothing of multiframe m is solved.  The other arguments as
+  // in ransacHypothesesBlocks.  Nothing synchronises the host.
+  void verifyPlaceHypothesesBlocks(size_t cameraIndex, const DevicePlaceSet& set, const void* blocksDev, int nMultiframes,
+                                   const okvfe_pose& T_SC, const int32_t* matchLandmarkDev, const uint8_t* gateDev,
+                                   const uint64_t* sampleKeysDev, uint64_t seed, int nHyp,
+                                   const okvfe_ransac_hypotheses_device& result, void* stream = nullptr) {
+    if (cameraIndex >= cameras_.size())
+      throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "Camera index exceeds number of cameras.");
+    std::lock_guard<std::mutex> lock(mutexes_[cameraIndex]);
+    if (!extractors_[cameraIndex].isCameraAware()) extractors_[cameraIndex].setCamera(cameras_[cameraIndex]);
+    Context& c = *contexts_[cameraIndex];
+    const int32_t cam = 0;  // slot 0 of the camera's own context
+    c.check(okvfe_place_hypotheses_blocks_device(c.get(), &set.get(), blocksDev, nMultiframes, 1, &cam, &T_SC,
+                                                 matchLandmarkDev, gateDev, sampleKeysDev, seed, nHyp, &result, stream));
+  }
   // Frontend.cpp:529-551 for the same frames: the Hessian H of the relative pose, the information of the pose-graph edge
   // that attemptLoopClosure adds, and per inlier the residual and minimal Jacobian of its ReprojectionError (what the
   // ceres problem of :399-527 asks for at every iterate).  T_SC_params: the camera's extrinsics as a PoseParameterBlock
@@ -958,6 +974,23 @@ class HipFrontend {
     c.check(okvfe_ransac3d2d_consensus_blocks_device(
         c.get(), &table.get(), blocksDev, nMultiframes, 1, &cam, &T_SC, landmarkDev, reinterpret_cast<const double*>(d),
         hypValid.empty() ? nullptr : d + hypBytes, nHyp, threshold, removeOutliers ? 1 : 0, &result, stream));
+  }
+  // The hypotheses ransac3d2dBlocks scores, made on the device instead of on the host: the defined sampler and P3P of
+  // okvfe_ransac3d2d_hypotheses_blocks_device (include/okvfe.h: not opengv's; all four samples from one camera).
+  // sampleKeysDev: device nMultiframes uint64 or null (the multiframe's index); result.hypotheses / result.hyp_valid are
+  // what okvfe_ransac3d2d_consensus_blocks_device takes as hypotheses_dev / hyp_valid_dev.  Nothing synchronises the host.
+  void ransacHypothesesBlocks(size_t cameraIndex, const DeviceLandmarkTable& table, const void* blocksDev, int nMultiframes,
+                              const okvfe_pose& T_SC, const int32_t* landmarkDev, const uint64_t* sampleKeysDev,
+                              uint64_t seed, int nHyp, const okvfe_ransac_hypotheses_device& result,
+                              void* stream = nullptr) {
+    if (cameraIndex >= cameras_.size())
+      throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "Camera index exceeds number of cameras.");
+    std::lock_guard<std::mutex> lock(mutexes_[cameraIndex]);
+    if (!extractors_[cameraIndex].isCameraAware()) extractors_[cameraIndex].setCamera(cameras_[cameraIndex]);
+    Context& c = *contexts_[cameraIndex];
+    const int32_t cam = 0;  // slot 0 of the camera's own context
+    c.check(okvfe_ransac3d2d_hypotheses_blocks_device(c.get(), &table.get(), blocksDev, nMultiframes, 1, &cam, &T_SC,
+                                                      landmarkDev, sampleKeysDev, seed, nHyp, &result, stream));
   }
   // Before initialisation (Frontend.cpp:1961-1969): the consensus step of runRansac2d2d for the pairs (older frame
   // mf0[p] of blocks0Dev, current frame mf1[p] of blocks1Dev) of camera `cameraIndex` (ONE camera per context, so a
