@@ -37,7 +37,14 @@ okvfe_status fail(okvfe_ctx* ctx, okvfe_status st, const char* fmt, ...) {
   return st;
 }
 
-
+const DeviceCamera* rig_slot(okvfe_ctx* ctx, const RigWho& who, int index, int cam) {
+  if (const DeviceCamera* dc = slot_camera(ctx, cam)) return dc;
+  char where[160] = "";
+  const int k = who.fn ? snprintf(where, sizeof(where), "%s: ", who.fn) : 0;
+  if (who.noun) snprintf(where + k, sizeof(where) - (size_t)k, "%s %d: ", who.noun, index);
+  (void)fail(ctx, who.bad, "%scamera slot %d has no intrinsics (okvfe_set_camera)", where, cam);
+  return nullptr;
+}
 
 okvfe_status ensure_scratch(okvfe_ctx* ctx, size_t bytes) {
   if (bytes <= ctx->scratch_bytes) return OKVFE_OK;

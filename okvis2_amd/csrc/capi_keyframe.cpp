@@ -106,36 +106,32 @@ okvfe_status okvfe_keyframe_coverage(okvfe_ctx* ctx, const okvfe_keypoint* keypo
     return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_keyframe_coverage: bad argument");
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
   hipStream_t s = pick_stream(ctx, nullptr);  // the context's own stream, behind pending pipelined lanes
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = off; off = align_up(off + std::max<size_t>(bytes, 1), 256); return o; };
-  const size_t o_n = take(4), o_k = take((size_t)n * sizeof(okvfe_keypoint)), o_id = take((size_t)n * 8),
-               o_set = take((size_t)n_id_set * 8), o_out = take(sizeof(okvfe_coverage));
-  okvfe_status st = ensure_scratch(ctx, off);
+  ScratchLayout lay;
+  const size_t o_n = lay.take(4), o_k = lay.take((size_t)n * sizeof(okvfe_keypoint)), o_id = lay.take((size_t)n * 8),
+               o_set = lay.take((size_t)n_id_set * 8), o_out = lay.take(sizeof(okvfe_coverage));
+  ScratchCall call(ctx, s);
+  okvfe_status st = call.reserve(lay);
   if (st != OKVFE_OK) return st;
-  uint8_t* base = static_cast<uint8_t*>(ctx->scratch);
-  auto up = [&](size_t o, const void* src, size_t bytes) -> hipError_t {
-    return bytes ? hipMemcpyAsync(base + o, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
-  };
-  HIP_TRY(ctx, up(o_n, &n, 4));
-  HIP_TRY(ctx, up(o_k, keypoints, (size_t)n * sizeof(okvfe_keypoint)));
-  HIP_TRY(ctx, up(o_id, landmark_ids, (size_t)n * 8));
-  HIP_TRY(ctx, up(o_set, id_set, (size_t)n_id_set * 8));
-  HIP_TRY(ctx, hipStreamSynchronize(s));  // pageable sources
+  HIP_TRY(ctx, call.up(o_n, &n, 4));
+  HIP_TRY(ctx, call.up(o_k, keypoints, (size_t)n * sizeof(okvfe_keypoint)));
+  HIP_TRY(ctx, call.up(o_id, landmark_ids, (size_t)n * 8));
+  HIP_TRY(ctx, call.up(o_set, id_set, (size_t)n_id_set * 8));
+  HIP_TRY(ctx, call.sync());  // pageable sources
   CoverageArgs A{};
-  A.base = base;
+  A.base = call.dev(0);
   A.frame_stride = 0;
   A.o_count = (int)o_n;
   A.o_kps = (int)o_k;
   A.kp_limit = n;
-  A.ids = reinterpret_cast<const uint64_t*>(base + o_id);
+  A.ids = call.dev<const uint64_t>(o_id);
   A.id_stride = 0;
-  A.id_set = reinterpret_cast<const uint64_t*>(base + o_set);
+  A.id_set = call.dev<const uint64_t>(o_set);
   A.n_id_set = n_id_set;
   A.has_set = id_set ? 1 : 0;
-  st = coverage_launch(ctx, "okvfe_keyframe_coverage", A, 1, kptrad, reinterpret_cast<okvfe_coverage*>(base + o_out), s);
+  st = coverage_launch(ctx, "okvfe_keyframe_coverage", A, 1, kptrad, call.dev<okvfe_coverage>(o_out), s);
   if (st != OKVFE_OK) return st;
-  HIP_TRY(ctx, hipMemcpyAsync(out, base + o_out, sizeof(okvfe_coverage), hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipStreamSynchronize(s));
+  HIP_TRY(ctx, call.down(out, o_out, sizeof(okvfe_coverage)));
+  HIP_TRY(ctx, call.sync());
   return OKVFE_OK;
 }
 

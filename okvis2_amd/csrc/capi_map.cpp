@@ -37,32 +37,28 @@ okvfe_status okvfe_match_to_map(okvfe_ctx* ctx, const uint8_t* desc, const okvfe
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
   hipStream_t s = ctx->stream;
   const int n_pool = desc_begin[n_landmarks];
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = off; off = align_up(off + std::max<size_t>(bytes, 1), 256); return o; };
-  const size_t o_d = take((size_t)n_kps * 48), o_k = take((size_t)n_kps * sizeof(okvfe_keypoint)), o_u = take(n_kps);
-  const size_t o_p = take((size_t)n_landmarks * 16), o_b = take((size_t)(n_landmarks + 1) * 4), o_pool = take((size_t)n_pool * 48);
-  const size_t o_lm = take((size_t)n_kps * 4), o_bd = take((size_t)n_kps * 4);
-  okvfe_status st = ensure_scratch(ctx, off);
+  ScratchLayout lay;
+  const size_t o_d = lay.take((size_t)n_kps * 48), o_k = lay.take((size_t)n_kps * sizeof(okvfe_keypoint)),
+               o_u = lay.take(n_kps), o_p = lay.take((size_t)n_landmarks * 16),
+               o_b = lay.take((size_t)(n_landmarks + 1) * 4), o_pool = lay.take((size_t)n_pool * 48),
+               o_lm = lay.take((size_t)n_kps * 4), o_bd = lay.take((size_t)n_kps * 4);
+  ScratchCall call(ctx, s);
+  const okvfe_status st = call.reserve(lay);
   if (st != OKVFE_OK) return st;
-  uint8_t* base = static_cast<uint8_t*>(ctx->scratch);
-  auto up = [&](size_t o, const void* src, size_t bytes) -> hipError_t {
-    return bytes ? hipMemcpyAsync(base + o, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
-  };
-  HIP_TRY(ctx, up(o_d, desc, (size_t)n_kps * 48));
-  HIP_TRY(ctx, up(o_k, kps, (size_t)n_kps * sizeof(okvfe_keypoint)));
-  HIP_TRY(ctx, up(o_u, use, n_kps));
-  HIP_TRY(ctx, up(o_p, projections_l2, (size_t)n_landmarks * 16));
-  HIP_TRY(ctx, up(o_b, desc_begin, (size_t)(n_landmarks + 1) * 4));
-  HIP_TRY(ctx, up(o_pool, pool, (size_t)n_pool * 48));
-  HIP_TRY(ctx, hipStreamSynchronize(s));
-  launch_match_to_map(base + o_d, reinterpret_cast<okvfe_keypoint*>(base + o_k), base + o_u, n_kps,
-                      reinterpret_cast<double*>(base + o_p), reinterpret_cast<int32_t*>(base + o_b), n_landmarks,
-                      base + o_pool, reprojection_threshold * reprojection_threshold, ctx->cfg.match_threshold,
-                      reinterpret_cast<int32_t*>(base + o_lm), reinterpret_cast<int32_t*>(base + o_bd), s);
+  HIP_TRY(ctx, call.up(o_d, desc, (size_t)n_kps * 48));
+  HIP_TRY(ctx, call.up(o_k, kps, (size_t)n_kps * sizeof(okvfe_keypoint)));
+  HIP_TRY(ctx, call.up(o_u, use, n_kps));
+  HIP_TRY(ctx, call.up(o_p, projections_l2, (size_t)n_landmarks * 16));
+  HIP_TRY(ctx, call.up(o_b, desc_begin, (size_t)(n_landmarks + 1) * 4));
+  HIP_TRY(ctx, call.up(o_pool, pool, (size_t)n_pool * 48));
+  HIP_TRY(ctx, call.sync());
+  launch_match_to_map(call.dev(o_d), call.dev<okvfe_keypoint>(o_k), call.dev(o_u), n_kps, call.dev<double>(o_p),
+                      call.dev<int32_t>(o_b), n_landmarks, call.dev(o_pool), reprojection_threshold * reprojection_threshold,
+                      ctx->cfg.match_threshold, call.dev<int32_t>(o_lm), call.dev<int32_t>(o_bd), s);
   HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipMemcpyAsync(best_landmark, base + o_lm, (size_t)n_kps * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipMemcpyAsync(best_dist, base + o_bd, (size_t)n_kps * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipStreamSynchronize(s));
+  HIP_TRY(ctx, call.down(best_landmark, o_lm, (size_t)n_kps * 4));
+  HIP_TRY(ctx, call.down(best_dist, o_bd, (size_t)n_kps * 4));
+  HIP_TRY(ctx, call.sync());
   return OKVFE_OK;
 }
 
@@ -93,73 +89,69 @@ okvfe_status okvfe_match_to_map_landmarks(okvfe_ctx* ctx, int32_t cam, const okv
   if (nl == 0) return OKVFE_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
   hipStream_t s = ctx->stream;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = off; off = align_up(off + std::max<size_t>(bytes, 1), 256); return o; };
+  ScratchLayout lay;
   // inputs
-  const size_t o_hp = take((size_t)nl * 32), o_q = take((size_t)nl * 8), o_ob = take((size_t)(nl + 1) * 4),
-               o_op = take((size_t)no * 4), o_od = take((size_t)no * 48), o_obp = take((size_t)no * 24),
-               o_poses = take((size_t)T->n_poses * sizeof(okvfe_pose));
-  const size_t o_d = take((size_t)n_kps * 48), o_k = take((size_t)n_kps * sizeof(okvfe_keypoint)), o_u = take(n_kps);
+  const size_t o_hp = lay.take((size_t)nl * 32), o_q = lay.take((size_t)nl * 8), o_ob = lay.take((size_t)(nl + 1) * 4),
+               o_op = lay.take((size_t)no * 4), o_od = lay.take((size_t)no * 48), o_obp = lay.take((size_t)no * 24),
+               o_poses = lay.take((size_t)T->n_poses * sizeof(okvfe_pose));
+  const size_t o_d = lay.take((size_t)n_kps * 48), o_k = lay.take((size_t)n_kps * sizeof(okvfe_keypoint)),
+               o_u = lay.take(n_kps);
   // pooling results
-  const size_t o_st = take((size_t)nl * 4), o_nd = take((size_t)nl * 4), o_rows = take((size_t)nl * 12),
-               o_proj = take((size_t)nl * 16), o_e = take((size_t)nl * 48), o_r = take((size_t)nl * 48);
+  const size_t o_st = lay.take((size_t)nl * 4), o_nd = lay.take((size_t)nl * 4), o_rows = lay.take((size_t)nl * 12),
+               o_proj = lay.take((size_t)nl * 16), o_e = lay.take((size_t)nl * 48), o_r = lay.take((size_t)nl * 48);
   // packed 3-D set + matcher outputs
-  const size_t o_idx = take((size_t)nl * 4), o_p3 = take((size_t)nl * 16), o_b3 = take((size_t)(nl + 1) * 4),
-               o_pool3 = take((size_t)nl * 2 * 48), o_n3 = take(8), o_lm = take((size_t)n_kps * 4),
-               o_bd = take((size_t)n_kps * 4);
-  okvfe_status st = ensure_scratch(ctx, off);
+  const size_t o_idx = lay.take((size_t)nl * 4), o_p3 = lay.take((size_t)nl * 16), o_b3 = lay.take((size_t)(nl + 1) * 4),
+               o_pool3 = lay.take((size_t)nl * 2 * 48), o_n3 = lay.take(8), o_lm = lay.take((size_t)n_kps * 4),
+               o_bd = lay.take((size_t)n_kps * 4);
+  ScratchCall call(ctx, s);
+  const okvfe_status st = call.reserve(lay);
   if (st != OKVFE_OK) return st;
-  uint8_t* base = static_cast<uint8_t*>(ctx->scratch);
-  auto up = [&](size_t o, const void* src, size_t bytes) -> hipError_t {
-    return bytes ? hipMemcpyAsync(base + o, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
-  };
-  HIP_TRY(ctx, up(o_hp, T->hp_W, (size_t)nl * 32));
-  HIP_TRY(ctx, up(o_q, T->quality, (size_t)nl * 8));
-  HIP_TRY(ctx, up(o_ob, T->obs_begin, (size_t)(nl + 1) * 4));
-  HIP_TRY(ctx, up(o_op, T->obs_pose, (size_t)no * 4));
-  HIP_TRY(ctx, up(o_od, T->obs_desc, (size_t)no * 48));
-  HIP_TRY(ctx, up(o_obp, T->obs_backproj, (size_t)no * 24));
-  HIP_TRY(ctx, up(o_poses, T->poses, (size_t)T->n_poses * sizeof(okvfe_pose)));
-  HIP_TRY(ctx, up(o_d, desc, (size_t)n_kps * 48));
-  HIP_TRY(ctx, up(o_k, kps, (size_t)n_kps * sizeof(okvfe_keypoint)));
-  HIP_TRY(ctx, up(o_u, use, n_kps));
-  HIP_TRY(ctx, hipStreamSynchronize(s));  // pageable sources
+  HIP_TRY(ctx, call.up(o_hp, T->hp_W, (size_t)nl * 32));
+  HIP_TRY(ctx, call.up(o_q, T->quality, (size_t)nl * 8));
+  HIP_TRY(ctx, call.up(o_ob, T->obs_begin, (size_t)(nl + 1) * 4));
+  HIP_TRY(ctx, call.up(o_op, T->obs_pose, (size_t)no * 4));
+  HIP_TRY(ctx, call.up(o_od, T->obs_desc, (size_t)no * 48));
+  HIP_TRY(ctx, call.up(o_obp, T->obs_backproj, (size_t)no * 24));
+  HIP_TRY(ctx, call.up(o_poses, T->poses, (size_t)T->n_poses * sizeof(okvfe_pose)));
+  HIP_TRY(ctx, call.up(o_d, desc, (size_t)n_kps * 48));
+  HIP_TRY(ctx, call.up(o_k, kps, (size_t)n_kps * sizeof(okvfe_keypoint)));
+  HIP_TRY(ctx, call.up(o_u, use, n_kps));
+  HIP_TRY(ctx, call.sync());  // pageable sources
   const DeviceCamera& dc = ctx->h_cams[cam];
   const double focal = dc.fu + dc.fv;  // the SUM, as at Frontend.cpp:1213-1215
-  auto I = [&](size_t o) { return reinterpret_cast<int32_t*>(base + o); };
-  auto D = [&](size_t o) { return reinterpret_cast<double*>(base + o); };
-  launch_prepare_landmarks(D(o_hp), D(o_q), I(o_ob), nl, I(o_op), D(o_obp),
-                           reinterpret_cast<const okvfe_pose*>(base + o_poses), *T_WC1, ctx->d_cams + cam, ctx->w,
-                           ctx->h, reprojection_threshold, exclusive ? 1 : 0, std::cos(10.0 / focal), std::cos(0.6),
-                           I(o_st), I(o_nd), I(o_rows), D(o_proj), D(o_e), D(o_r), s,
+  auto I = [&](size_t o) { return call.dev<int32_t>(o); };
+  auto D = [&](size_t o) { return call.dev<double>(o); };
+  launch_prepare_landmarks(D(o_hp), D(o_q), I(o_ob), nl, I(o_op), D(o_obp), call.dev<const okvfe_pose>(o_poses), *T_WC1,
+                           ctx->d_cams + cam, ctx->w, ctx->h, reprojection_threshold, exclusive ? 1 : 0,
+                           std::cos(10.0 / focal), std::cos(0.6), I(o_st), I(o_nd), I(o_rows), D(o_proj), D(o_e), D(o_r), s,
                            dc.distortion == OKVFE_DIST_RADTAN8);
-  launch_compact_landmarks(I(o_st), I(o_nd), I(o_rows), D(o_proj), base + o_od, nl, 1, I(o_idx), D(o_p3), I(o_b3),
-                           base + o_pool3, I(o_n3), s);
+  launch_compact_landmarks(I(o_st), I(o_nd), I(o_rows), D(o_proj), call.dev(o_od), nl, 1, I(o_idx), D(o_p3), I(o_b3),
+                           call.dev(o_pool3), I(o_n3), s);
   HIP_TRY(ctx, hipGetLastError());
   int32_t n3[2] = {0, 0};
-  HIP_TRY(ctx, hipMemcpyAsync(n3, base + o_n3, 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipStreamSynchronize(s));  // the matcher's grid depends on the number of 3-D landmarks only
+  HIP_TRY(ctx, call.down(n3, o_n3, 8));
+  HIP_TRY(ctx, call.sync());  // the matcher's grid depends on the number of 3-D landmarks only
   if (n_kps > 0 && n3[0] > 0) {
-    launch_match_to_map(base + o_d, reinterpret_cast<okvfe_keypoint*>(base + o_k), base + o_u, n_kps, D(o_p3),
-                        I(o_b3), n3[0], base + o_pool3, reprojection_threshold * reprojection_threshold,
-                        ctx->cfg.match_threshold, I(o_lm), I(o_bd), s);
+    launch_match_to_map(call.dev(o_d), call.dev<okvfe_keypoint>(o_k), call.dev(o_u), n_kps, D(o_p3), I(o_b3), n3[0],
+                        call.dev(o_pool3), reprojection_threshold * reprojection_threshold, ctx->cfg.match_threshold,
+                        I(o_lm), I(o_bd), s);
     HIP_TRY(ctx, hipGetLastError());
     std::vector<int32_t> idx(n3[0]);
-    HIP_TRY(ctx, hipMemcpyAsync(best_landmark, base + o_lm, (size_t)n_kps * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(ctx, hipMemcpyAsync(best_dist, base + o_bd, (size_t)n_kps * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(ctx, hipMemcpyAsync(idx.data(), base + o_idx, (size_t)n3[0] * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(ctx, hipStreamSynchronize(s));
+    HIP_TRY(ctx, call.down(best_landmark, o_lm, (size_t)n_kps * 4));
+    HIP_TRY(ctx, call.down(best_dist, o_bd, (size_t)n_kps * 4));
+    HIP_TRY(ctx, call.down(idx.data(), o_idx, (size_t)n3[0] * 4));
+    HIP_TRY(ctx, call.sync());
     for (int k = 0; k < n_kps; ++k)
       if (best_landmark[k] >= 0) best_landmark[k] = idx[best_landmark[k]];  // packed -> table index
   }
   if (pool_out) {
-    if (pool_out->status) HIP_TRY(ctx, hipMemcpyAsync(pool_out->status, base + o_st, (size_t)nl * 4, hipMemcpyDeviceToHost, s));
-    if (pool_out->n_desc) HIP_TRY(ctx, hipMemcpyAsync(pool_out->n_desc, base + o_nd, (size_t)nl * 4, hipMemcpyDeviceToHost, s));
-    if (pool_out->obs_rows) HIP_TRY(ctx, hipMemcpyAsync(pool_out->obs_rows, base + o_rows, (size_t)nl * 12, hipMemcpyDeviceToHost, s));
-    if (pool_out->projection) HIP_TRY(ctx, hipMemcpyAsync(pool_out->projection, base + o_proj, (size_t)nl * 16, hipMemcpyDeviceToHost, s));
-    if (pool_out->e_W) HIP_TRY(ctx, hipMemcpyAsync(pool_out->e_W, base + o_e, (size_t)nl * 48, hipMemcpyDeviceToHost, s));
-    if (pool_out->r_W) HIP_TRY(ctx, hipMemcpyAsync(pool_out->r_W, base + o_r, (size_t)nl * 48, hipMemcpyDeviceToHost, s));
-    HIP_TRY(ctx, hipStreamSynchronize(s));
+    if (pool_out->status) HIP_TRY(ctx, call.down(pool_out->status, o_st, (size_t)nl * 4));
+    if (pool_out->n_desc) HIP_TRY(ctx, call.down(pool_out->n_desc, o_nd, (size_t)nl * 4));
+    if (pool_out->obs_rows) HIP_TRY(ctx, call.down(pool_out->obs_rows, o_rows, (size_t)nl * 12));
+    if (pool_out->projection) HIP_TRY(ctx, call.down(pool_out->projection, o_proj, (size_t)nl * 16));
+    if (pool_out->e_W) HIP_TRY(ctx, call.down(pool_out->e_W, o_e, (size_t)nl * 48));
+    if (pool_out->r_W) HIP_TRY(ctx, call.down(pool_out->r_W, o_r, (size_t)nl * 48));
+    HIP_TRY(ctx, call.sync());
   }
   return OKVFE_OK;
 }
@@ -185,48 +177,42 @@ okvfe_status okvfe_match_to_map_uninitialised(okvfe_ctx* ctx, const uint8_t* des
     return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_match_to_map_uninitialised: null pool");
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
   hipStream_t s = ctx->stream;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = off; off = align_up(off + std::max<size_t>(bytes, 1), 256); return o; };
-  const size_t o_pair = take(sizeof(PairParams)), o_d = take((size_t)n_kps * 48), o_bp = take((size_t)n_kps * 24),
-               o_u = take(n_kps), o_prev = take((size_t)n_kps * 4), o_b = take((size_t)(n_landmarks + 1) * 4),
-               o_pool = take((size_t)n_pool * 48), o_e = take((size_t)n_pool * 24), o_r = take((size_t)n_pool * 24),
-               o_lm = take((size_t)n_kps * 4), o_bd = take((size_t)n_kps * 4), o_hp = take((size_t)n_kps * 32),
-               o_hs = take(n_kps), o_ctr = take(4);
-  okvfe_status st = ensure_scratch(ctx, off);
+  ScratchLayout lay;
+  const size_t o_pair = lay.take(sizeof(PairParams)), o_d = lay.take((size_t)n_kps * 48), o_bp = lay.take((size_t)n_kps * 24),
+               o_u = lay.take(n_kps), o_prev = lay.take((size_t)n_kps * 4), o_b = lay.take((size_t)(n_landmarks + 1) * 4),
+               o_pool = lay.take((size_t)n_pool * 48), o_e = lay.take((size_t)n_pool * 24),
+               o_r = lay.take((size_t)n_pool * 24), o_lm = lay.take((size_t)n_kps * 4), o_bd = lay.take((size_t)n_kps * 4),
+               o_hp = lay.take((size_t)n_kps * 32), o_hs = lay.take(n_kps), o_ctr = lay.take(4);
+  ScratchCall call(ctx, s);
+  const okvfe_status st = call.reserve(lay);
   if (st != OKVFE_OK) return st;
-  uint8_t* base = static_cast<uint8_t*>(ctx->scratch);
   const PairParams pp = uninit_pair_params(*T_WC1, focal_length);
-  auto up = [&](size_t o, const void* src, size_t bytes) -> hipError_t {
-    return bytes ? hipMemcpyAsync(base + o, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
-  };
-  HIP_TRY(ctx, up(o_pair, &pp, sizeof(pp)));
-  HIP_TRY(ctx, up(o_d, desc, (size_t)n_kps * 48));
-  HIP_TRY(ctx, up(o_bp, backproj, (size_t)n_kps * 24));
-  HIP_TRY(ctx, up(o_u, use, n_kps));
-  HIP_TRY(ctx, up(o_prev, previous_landmark, (size_t)n_kps * 4));
-  HIP_TRY(ctx, up(o_b, desc_begin, (size_t)(n_landmarks + 1) * 4));
-  HIP_TRY(ctx, up(o_pool, pool, (size_t)n_pool * 48));
-  HIP_TRY(ctx, up(o_e, e0_W, (size_t)n_pool * 24));
-  HIP_TRY(ctx, up(o_r, r0_W, (size_t)n_pool * 24));
-  HIP_TRY(ctx, hipMemsetAsync(base + o_ctr, 0, 4, s));
-  HIP_TRY(ctx, hipStreamSynchronize(s));
-  launch_match_to_map_uninit(reinterpret_cast<PairParams*>(base + o_pair), base + o_d,
-                             reinterpret_cast<double*>(base + o_bp), base + o_u,
-                             reinterpret_cast<int32_t*>(base + o_prev), n_kps, reinterpret_cast<int32_t*>(base + o_b),
-                             n_landmarks, base + o_pool, reinterpret_cast<double*>(base + o_e),
-                             reinterpret_cast<double*>(base + o_r), ctx->cfg.match_threshold,
-                             reinterpret_cast<int32_t*>(base + o_lm), reinterpret_cast<int32_t*>(base + o_bd),
-                             reinterpret_cast<double*>(base + o_hp), base + o_hs,
-                             reinterpret_cast<int32_t*>(base + o_ctr), s);
+  HIP_TRY(ctx, call.up(o_pair, &pp, sizeof(pp)));
+  HIP_TRY(ctx, call.up(o_d, desc, (size_t)n_kps * 48));
+  HIP_TRY(ctx, call.up(o_bp, backproj, (size_t)n_kps * 24));
+  HIP_TRY(ctx, call.up(o_u, use, n_kps));
+  HIP_TRY(ctx, call.up(o_prev, previous_landmark, (size_t)n_kps * 4));
+  HIP_TRY(ctx, call.up(o_b, desc_begin, (size_t)(n_landmarks + 1) * 4));
+  HIP_TRY(ctx, call.up(o_pool, pool, (size_t)n_pool * 48));
+  HIP_TRY(ctx, call.up(o_e, e0_W, (size_t)n_pool * 24));
+  HIP_TRY(ctx, call.up(o_r, r0_W, (size_t)n_pool * 24));
+  HIP_TRY(ctx, hipMemsetAsync(call.dev(o_ctr), 0, 4, s));
+  HIP_TRY(ctx, call.sync());
+  launch_match_to_map_uninit(call.dev<PairParams>(o_pair), call.dev(o_d), call.dev<double>(o_bp), call.dev(o_u),
+                             call.dev<int32_t>(o_prev), n_kps, call.dev<int32_t>(o_b), n_landmarks, call.dev(o_pool),
+                             call.dev<double>(o_e), call.dev<double>(o_r), ctx->cfg.match_threshold,
+                             call.dev<int32_t>(o_lm), call.dev<int32_t>(o_bd), call.dev<double>(o_hp), call.dev(o_hs),
+                             call.dev<int32_t>(o_ctr), s);
   HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipMemcpyAsync(best_landmark, base + o_lm, (size_t)n_kps * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipMemcpyAsync(best_dist, base + o_bd, (size_t)n_kps * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipMemcpyAsync(hps_W, base + o_hp, (size_t)n_kps * 32, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipMemcpyAsync(hp_set, base + o_hs, n_kps, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipMemcpyAsync(already_matched, base + o_ctr, 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipStreamSynchronize(s));
+  HIP_TRY(ctx, call.down(best_landmark, o_lm, (size_t)n_kps * 4));
+  HIP_TRY(ctx, call.down(best_dist, o_bd, (size_t)n_kps * 4));
+  HIP_TRY(ctx, call.down(hps_W, o_hp, (size_t)n_kps * 32));
+  HIP_TRY(ctx, call.down(hp_set, o_hs, n_kps));
+  HIP_TRY(ctx, call.down(already_matched, o_ctr, 4));
+  HIP_TRY(ctx, call.sync());
   return OKVFE_OK;
 }
+
 okvfe_status okvfe_verify_place_match(okvfe_ctx* ctx, const uint8_t* landmark_desc, const int32_t* desc_begin,
                                       int32_t n_landmarks, const uint8_t* frame_desc, int32_t n_kps,
                                       int32_t* k_min, uint32_t* dist_min) {
@@ -248,23 +234,23 @@ okvfe_status okvfe_verify_place_match(okvfe_ctx* ctx, const uint8_t* landmark_de
   if ((int64_t)3 * n_kps >= (int64_t)1 << 31) return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "too many keypoints");
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
   hipStream_t s = ctx->stream;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = off; off = align_up(off + std::max<size_t>(bytes, 1), 256); return o; };
-  const size_t o_pool = take((size_t)n_pool * 48), o_b = take((size_t)(n_landmarks + 1) * 4),
-               o_f = take((size_t)n_kps * 48), o_k = take((size_t)n_landmarks * 4), o_d = take((size_t)n_landmarks * 4);
-  okvfe_status st = ensure_scratch(ctx, off);
+  ScratchLayout lay;
+  const size_t o_pool = lay.take((size_t)n_pool * 48), o_b = lay.take((size_t)(n_landmarks + 1) * 4),
+               o_f = lay.take((size_t)n_kps * 48), o_k = lay.take((size_t)n_landmarks * 4),
+               o_d = lay.take((size_t)n_landmarks * 4);
+  ScratchCall call(ctx, s);
+  const okvfe_status st = call.reserve(lay);
   if (st != OKVFE_OK) return st;
-  uint8_t* base = static_cast<uint8_t*>(ctx->scratch);
-  HIP_TRY(ctx, hipMemcpyAsync(base + o_pool, landmark_desc, (size_t)n_pool * 48, hipMemcpyHostToDevice, s));
-  HIP_TRY(ctx, hipMemcpyAsync(base + o_b, desc_begin, (size_t)(n_landmarks + 1) * 4, hipMemcpyHostToDevice, s));
-  HIP_TRY(ctx, hipMemcpyAsync(base + o_f, frame_desc, (size_t)n_kps * 48, hipMemcpyHostToDevice, s));
-  HIP_TRY(ctx, hipStreamSynchronize(s));
-  launch_verify_place(base + o_pool, reinterpret_cast<int32_t*>(base + o_b), n_landmarks, base + o_f, n_kps, thr,
-                      reinterpret_cast<int32_t*>(base + o_k), reinterpret_cast<uint32_t*>(base + o_d), s);
+  HIP_TRY(ctx, call.up(o_pool, landmark_desc, (size_t)n_pool * 48));
+  HIP_TRY(ctx, call.up(o_b, desc_begin, (size_t)(n_landmarks + 1) * 4));
+  HIP_TRY(ctx, call.up(o_f, frame_desc, (size_t)n_kps * 48));
+  HIP_TRY(ctx, call.sync());
+  launch_verify_place(call.dev(o_pool), call.dev<int32_t>(o_b), n_landmarks, call.dev(o_f), n_kps, thr,
+                      call.dev<int32_t>(o_k), call.dev<uint32_t>(o_d), s);
   HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipMemcpyAsync(k_min, base + o_k, (size_t)n_landmarks * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipMemcpyAsync(dist_min, base + o_d, (size_t)n_landmarks * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipStreamSynchronize(s));
+  HIP_TRY(ctx, call.down(k_min, o_k, (size_t)n_landmarks * 4));
+  HIP_TRY(ctx, call.down(dist_min, o_d, (size_t)n_landmarks * 4));
+  HIP_TRY(ctx, call.sync());
   return OKVFE_OK;
 }
 
@@ -296,29 +282,28 @@ okvfe_status okvfe_fbrisk_transform(okvfe_ctx* ctx, const uint8_t* descriptors, 
   if (n == 0) return OKVFE_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
   hipStream_t s = ctx->stream;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = off; off = align_up(off + std::max<size_t>(bytes, 1), 256); return o; };
-  const size_t o_d = take((size_t)n * 48), o_n = take((size_t)n_nodes * 48), o_cb = take((size_t)(n_nodes + 1) * 4),
-               o_ci = take((size_t)n_child * 4), o_w = take((size_t)n_nodes * 4), o_wo = take((size_t)n * 4),
-               o_no = take((size_t)n * 4);
-  okvfe_status st = ensure_scratch(ctx, off);
+  ScratchLayout lay;
+  const size_t o_d = lay.take((size_t)n * 48), o_n = lay.take((size_t)n_nodes * 48), o_cb = lay.take((size_t)(n_nodes + 1) * 4),
+               o_ci = lay.take((size_t)n_child * 4), o_w = lay.take((size_t)n_nodes * 4), o_wo = lay.take((size_t)n * 4),
+               o_no = lay.take((size_t)n * 4);
+  ScratchCall call(ctx, s);
+  const okvfe_status st = call.reserve(lay);
   if (st != OKVFE_OK) return st;
-  uint8_t* base = static_cast<uint8_t*>(ctx->scratch);
-  HIP_TRY(ctx, hipMemcpyAsync(base + o_d, descriptors, (size_t)n * 48, hipMemcpyHostToDevice, s));
-  HIP_TRY(ctx, hipMemcpyAsync(base + o_n, node_descriptors, (size_t)n_nodes * 48, hipMemcpyHostToDevice, s));
-  HIP_TRY(ctx, hipMemcpyAsync(base + o_cb, child_begin, (size_t)(n_nodes + 1) * 4, hipMemcpyHostToDevice, s));
-  if (n_child) HIP_TRY(ctx, hipMemcpyAsync(base + o_ci, child_index, (size_t)n_child * 4, hipMemcpyHostToDevice, s));
-  HIP_TRY(ctx, hipMemcpyAsync(base + o_w, node_word, (size_t)n_nodes * 4, hipMemcpyHostToDevice, s));
-  HIP_TRY(ctx, hipStreamSynchronize(s));
-  launch_voc_transform(base + o_d, n, base + o_n, n_nodes, reinterpret_cast<int32_t*>(base + o_cb),
-                       reinterpret_cast<int32_t*>(base + o_ci), reinterpret_cast<int32_t*>(base + o_w),
-                       reinterpret_cast<int32_t*>(base + o_wo), reinterpret_cast<int32_t*>(base + o_no), s);
+  HIP_TRY(ctx, call.up(o_d, descriptors, (size_t)n * 48));
+  HIP_TRY(ctx, call.up(o_n, node_descriptors, (size_t)n_nodes * 48));
+  HIP_TRY(ctx, call.up(o_cb, child_begin, (size_t)(n_nodes + 1) * 4));
+  HIP_TRY(ctx, call.up(o_ci, child_index, (size_t)n_child * 4));
+  HIP_TRY(ctx, call.up(o_w, node_word, (size_t)n_nodes * 4));
+  HIP_TRY(ctx, call.sync());
+  launch_voc_transform(call.dev(o_d), n, call.dev(o_n), n_nodes, call.dev<int32_t>(o_cb), call.dev<int32_t>(o_ci),
+                       call.dev<int32_t>(o_w), call.dev<int32_t>(o_wo), call.dev<int32_t>(o_no), s);
   HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipMemcpyAsync(word_ids, base + o_wo, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-  if (leaf_nodes) HIP_TRY(ctx, hipMemcpyAsync(leaf_nodes, base + o_no, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipStreamSynchronize(s));
+  HIP_TRY(ctx, call.down(word_ids, o_wo, (size_t)n * 4));
+  if (leaf_nodes) HIP_TRY(ctx, call.down(leaf_nodes, o_no, (size_t)n * 4));
+  HIP_TRY(ctx, call.sync());
   return OKVFE_OK;
 }
+
 okvfe_status okvfe_bow_vector(const int32_t* word_ids, int32_t n_features, const double* word_weight,
                               int32_t n_words, int32_t weighting, int32_t normalise_l1, int32_t* ids_out,
                               double* values_out, int32_t cap, int32_t* n_out) {
@@ -388,31 +373,26 @@ okvfe_status okvfe_bow_query_l1(okvfe_ctx* ctx, const int32_t* db_begin, const i
   if (m > 0 && (!db_ids || !db_values)) return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_bow_query_l1: null database");
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
   hipStream_t s = ctx->stream;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = off; off = align_up(off + std::max<size_t>(bytes, 1), 256); return o; };
-  const size_t o_b = take((size_t)(n_entries + 1) * 4), o_i = take((size_t)m * 4), o_v = take((size_t)m * 8),
-               o_qi = take((size_t)n_q * 4), o_qv = take((size_t)n_q * 8), o_s = take((size_t)n_entries * 8);
-  okvfe_status st = ensure_scratch(ctx, off);
+  ScratchLayout lay;
+  const size_t o_b = lay.take((size_t)(n_entries + 1) * 4), o_i = lay.take((size_t)m * 4), o_v = lay.take((size_t)m * 8),
+               o_qi = lay.take((size_t)n_q * 4), o_qv = lay.take((size_t)n_q * 8), o_s = lay.take((size_t)n_entries * 8);
+  ScratchCall call(ctx, s);
+  const okvfe_status st = call.reserve(lay);
   if (st != OKVFE_OK) return st;
-  uint8_t* base = static_cast<uint8_t*>(ctx->scratch);
-  HIP_TRY(ctx, hipMemcpyAsync(base + o_b, db_begin, (size_t)(n_entries + 1) * 4, hipMemcpyHostToDevice, s));
-  if (m) {
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_i, db_ids, (size_t)m * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_v, db_values, (size_t)m * 8, hipMemcpyHostToDevice, s));
-  }
-  if (n_q) {
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_qi, q_ids, (size_t)n_q * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_qv, q_values, (size_t)n_q * 8, hipMemcpyHostToDevice, s));
-  }
-  HIP_TRY(ctx, hipStreamSynchronize(s));  // pageable host buffers: the copies above have completed
-  launch_bow_query_l1(reinterpret_cast<int32_t*>(base + o_b), reinterpret_cast<int32_t*>(base + o_i),
-                      reinterpret_cast<double*>(base + o_v), n_entries, reinterpret_cast<int32_t*>(base + o_qi),
-                      reinterpret_cast<double*>(base + o_qv), n_q, reinterpret_cast<double*>(base + o_s), s);
+  HIP_TRY(ctx, call.up(o_b, db_begin, (size_t)(n_entries + 1) * 4));
+  HIP_TRY(ctx, call.up(o_i, db_ids, (size_t)m * 4));
+  HIP_TRY(ctx, call.up(o_v, db_values, (size_t)m * 8));
+  HIP_TRY(ctx, call.up(o_qi, q_ids, (size_t)n_q * 4));
+  HIP_TRY(ctx, call.up(o_qv, q_values, (size_t)n_q * 8));
+  HIP_TRY(ctx, call.sync());  // pageable host buffers: the copies above have completed
+  launch_bow_query_l1(call.dev<int32_t>(o_b), call.dev<int32_t>(o_i), call.dev<double>(o_v), n_entries,
+                      call.dev<int32_t>(o_qi), call.dev<double>(o_qv), n_q, call.dev<double>(o_s), s);
   HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipMemcpyAsync(scores, base + o_s, (size_t)n_entries * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipStreamSynchronize(s));
+  HIP_TRY(ctx, call.down(scores, o_s, (size_t)n_entries * 8));
+  HIP_TRY(ctx, call.sync());
   return OKVFE_OK;
 }
+
 // ---- device-resident, batched map matchers (frame f = gather block f) --------------------------
 namespace {
 okvfe_status map_args_ok(okvfe_ctx* ctx, const char* who, const void* blocks, int n_frames, const okvfe_map_device* map) {
@@ -480,10 +460,7 @@ okvfe_status okvfe_match_to_map_uninitialised_blocks_device(okvfe_ctx* ctx, cons
                                       map->r0_W, ctx->cfg.match_threshold, best_landmark_dev, best_dist_dev, hps_W_dev,
                                       hp_set_dev, already_matched_dev, s);
   }
-  HIP_TRY(ctx, hipGetLastError());
-  const okvfe_status rel = pairs.release();
-  ctx->last_stream = s;
-  return rel;
+  return finish_call(ctx, &pairs, s);
 }
 
 // ---- matchToMap from a device-resident landmark table, a batch of frames -----------------------
@@ -534,15 +511,14 @@ okvfe_status okvfe_match_to_map_table_blocks_device(okvfe_ctx* ctx, const okvfe_
       !best_landmark_dev || !best_dist_dev)
     return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_match_to_map_table_blocks_device: bad argument");
   bool rt8 = false;  // the 8-coefficient form of the projection only when a slot this call uses holds that model
-  for (int f = 0; f < n_frames; ++f) {
-    const DeviceCamera* dc = slot_camera(ctx, cam_ids[f]);
-    if (!dc)
-      return fail(ctx, OKVFE_ERR_NOT_READY,
-                  "okvfe_match_to_map_table_blocks_device: frame %d: camera slot %d has no intrinsics (okvfe_set_camera)", f,
-                  cam_ids[f]);
-    rt8 = rt8 || dc->distortion == OKVFE_DIST_RADTAN8;
-  }
-  if (n_frames == 0) return OKVFE_OK;
+  std::vector<MapFrameParams> fp((size_t)n_frames);  // poses and camera slots: one record per frame
+  okvfe_status st = rig_slots(ctx, RigWho{"okvfe_match_to_map_table_blocks_device", "frame"}, n_frames, cam_ids, &rt8,
+                              [&](int f, const DeviceCamera& dc) {
+                                fp[(size_t)f].T1 = T_WC1[f];
+                                fp[(size_t)f].cos10 = std::cos(10.0 / (dc.fu + dc.fv));  // the SUM, as at Frontend.cpp:1213-1215
+                                fp[(size_t)f].cam = cam_ids[f];
+                              });
+  if (st != OKVFE_OK || n_frames == 0) return st;
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
   hipStream_t s = pick_stream(ctx, stream);
   const BlockLayout L = block_layout(ctx->kp_cap);
@@ -555,17 +531,8 @@ okvfe_status okvfe_match_to_map_table_blocks_device(okvfe_ctx* ctx, const okvfe_
                o_cnt = align_up(o_perm + (size_t)slice * K * sizeof(int32_t), 256),
                total = o_cnt + (size_t)slice * sizeof(int32_t);
   uint8_t* ws = nullptr;
-  okvfe_status st = map_table_workspace(ctx, s, total, &ws);
-  if (st != OKVFE_OK) return st;
-  // poses and camera slots: one record per frame through the pinned parameter ring (one asynchronous copy, no host sync)
-  std::vector<MapFrameParams> fp((size_t)n_frames);
-  for (int f = 0; f < n_frames; ++f) {
-    const DeviceCamera& dc = ctx->h_cams[cam_ids[f]];
-    fp[(size_t)f] = MapFrameParams{};
-    fp[(size_t)f].T1 = T_WC1[f];
-    fp[(size_t)f].cos10 = std::cos(10.0 / (dc.fu + dc.fv));  // the SUM, as at Frontend.cpp:1213-1215
-    fp[(size_t)f].cam = cam_ids[f];
-  }
+  if ((st = map_table_workspace(ctx, s, total, &ws)) != OKVFE_OK) return st;
+  // the records through the pinned parameter ring (one asynchronous copy, no host sync)
   RingSlot frames(ctx, &ctx->pair_ring, s);
   if ((st = frames.upload(fp.data(), fp.size() * sizeof(MapFrameParams))) != OKVFE_OK) return st;
   {
@@ -607,12 +574,13 @@ okvfe_status okvfe_match_to_map_table_uninitialised_blocks_device(
       !best_dist_dev || !hps_W_dev || !hp_set_dev || !already_matched_dev ||
       (T->n_landmarks > 0 && (!T->obs_desc || !pool->status || !pool->n_desc || !pool->obs_rows || !pool->e_W || !pool->r_W)))
     return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_match_to_map_table_uninitialised_blocks_device: bad argument");
-  for (int f = 0; f < n_frames; ++f)
-    if (!slot_camera(ctx, cam_ids[f]))
-      return fail(ctx, OKVFE_ERR_NOT_READY,
-                  "okvfe_match_to_map_table_uninitialised_blocks_device: frame %d: camera slot %d has no intrinsics (okvfe_set_camera)",
-                  f, cam_ids[f]);
-  if (n_frames == 0) return OKVFE_OK;
+  // the pose NOW and the gate constants of the frame's camera slot: one record per frame
+  std::vector<PairParams> pp((size_t)n_frames);
+  okvfe_status st = rig_slots(ctx, RigWho{"okvfe_match_to_map_table_uninitialised_blocks_device", "frame"}, n_frames,
+                              cam_ids, nullptr, [&](int f, const DeviceCamera& dc) {
+                                pp[(size_t)f] = uninit_pair_params(T_WC1[f], 0.5 * (dc.fu + dc.fv));
+                              });
+  if (st != OKVFE_OK || n_frames == 0) return st;
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
   hipStream_t s = pick_stream(ctx, stream);
   const BlockLayout L = block_layout(ctx->kp_cap);
@@ -623,15 +591,8 @@ okvfe_status okvfe_match_to_map_table_uninitialised_blocks_device(
   const size_t o_cnt = align_up((size_t)slice * nl * sizeof(MapUninitPacked), 256),
                total = o_cnt + (size_t)slice * sizeof(int32_t);
   uint8_t* ws = nullptr;
-  okvfe_status st = map_table_workspace(ctx, s, total, &ws);
-  if (st != OKVFE_OK) return st;
-  // the pose NOW and the gate constants of the frame's camera slot: one record per frame through the pinned parameter
-  // ring (one asynchronous copy, no host sync)
-  std::vector<PairParams> pp((size_t)n_frames);
-  for (int f = 0; f < n_frames; ++f) {
-    const DeviceCamera& dc = ctx->h_cams[cam_ids[f]];
-    pp[(size_t)f] = uninit_pair_params(T_WC1[f], 0.5 * (dc.fu + dc.fv));
-  }
+  if ((st = map_table_workspace(ctx, s, total, &ws)) != OKVFE_OK) return st;
+  // the records through the pinned parameter ring (one asynchronous copy, no host sync)
   RingSlot pairs(ctx, &ctx->pair_ring, s);
   if ((st = pairs.upload(pp.data(), pp.size() * sizeof(PairParams))) != OKVFE_OK) return st;
   HIP_TRY(ctx, hipMemsetAsync(already_matched_dev, 0, (size_t)n_frames * sizeof(int32_t), s));

@@ -110,59 +110,43 @@ okvfe_status okvfe_match_stereo(okvfe_ctx* ctx, const uint8_t* desc0, const okvf
   if (multi && (!kp0 || !kp1)) return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_match_stereo: keypoints needed");
   if (n0 == 0) return OKVFE_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
-  hipStream_t s = ctx->stream;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = off; off = align_up(off + std::max<size_t>(bytes, 1), 256); return o; };
-  const size_t o_pair = take(sizeof(PairParams)), o_cls = take(kClassTableDoubles * sizeof(double));
-  const size_t o_d0 = take((size_t)n0 * 48), o_b0 = take((size_t)n0 * 24), o_v0 = take(n0),
-               o_k0 = take((size_t)n0 * sizeof(okvfe_keypoint));
-  const size_t o_d1 = take((size_t)n1 * 48), o_b1 = take((size_t)n1 * 24), o_v1 = take(n1),
-               o_k1 = take((size_t)n1 * sizeof(okvfe_keypoint));
-  const size_t o_out = take((size_t)n0 * sizeof(okvfe_stereo_match));
-  if ((st = ensure_scratch(ctx, off)) != OKVFE_OK) return st;
-  if ((st = ensure_pinned(ctx, off)) != OKVFE_OK) return st;
-  uint8_t* base = static_cast<uint8_t*>(ctx->scratch);
-  uint8_t* hb = ctx->h_pinned;  // the same layout in pinned host memory
+  ScratchLayout lay;
+  const size_t o_pair = lay.take(sizeof(PairParams)), o_cls = lay.take(kClassTableDoubles * sizeof(double));
+  const size_t o_d0 = lay.take((size_t)n0 * 48), o_b0 = lay.take((size_t)n0 * 24), o_v0 = lay.take(n0),
+               o_k0 = lay.take((size_t)n0 * sizeof(okvfe_keypoint));
+  const size_t o_d1 = lay.take((size_t)n1 * 48), o_b1 = lay.take((size_t)n1 * 24), o_v1 = lay.take(n1),
+               o_k1 = lay.take((size_t)n1 * sizeof(okvfe_keypoint));
+  const size_t o_out = lay.take((size_t)n0 * sizeof(okvfe_stereo_match));
+  ScratchCall call(ctx, ctx->stream);
+  if ((st = call.reserve(lay, true)) != OKVFE_OK) return st;
   okvfe_stereo_pair sp{};
   sp.image0 = 0; sp.image1 = 0; sp.T_WC0 = *T_WC0; sp.T_WC1 = *T_WC1; sp.f0 = f0; sp.f1 = f1;
   PairParams pp = to_pair_params(sp);
   if (multi) {
-    fill_class_table(reinterpret_cast<double*>(hb + o_cls), f0, f1, false);
-    pp.cls = reinterpret_cast<const double*>(base + o_cls);
-    std::memcpy(hb + o_k0, kp0, (size_t)n0 * sizeof(okvfe_keypoint));
-    std::memcpy(hb + o_k1, kp1, (size_t)n1 * sizeof(okvfe_keypoint));
+    fill_class_table(call.host<double>(o_cls), f0, f1, false);
+    pp.cls = call.dev<double>(o_cls);
+    call.put(o_k0, kp0, (size_t)n0 * sizeof(okvfe_keypoint));
+    call.put(o_k1, kp1, (size_t)n1 * sizeof(okvfe_keypoint));
   }
-  std::memcpy(hb + o_pair, &pp, sizeof(pp));
-  std::memcpy(hb + o_d0, desc0, (size_t)n0 * 48);
-  std::memcpy(hb + o_b0, backproj0, (size_t)n0 * 24);
-  std::memcpy(hb + o_v0, valid0, (size_t)n0);
-  if (n1 > 0) {
-    std::memcpy(hb + o_d1, desc1, (size_t)n1 * 48);
-    std::memcpy(hb + o_b1, backproj1, (size_t)n1 * 24);
-    std::memcpy(hb + o_v1, valid1, (size_t)n1);
-  }
+  call.put(o_pair, &pp, sizeof(pp));
+  call.put(o_d0, desc0, (size_t)n0 * 48);
+  call.put(o_b0, backproj0, (size_t)n0 * 24);
+  call.put(o_v0, valid0, (size_t)n0);
+  call.put(o_d1, desc1, (size_t)n1 * 48);
+  call.put(o_b1, backproj1, (size_t)n1 * 24);
+  call.put(o_v1, valid1, (size_t)n1);
   // One kernel moves every input (it reads the pinned block in place), the matcher writes its rows
   // straight into the pinned block, one synchronisation: a frame's matchStereo was seven pageable
   // host-to-device copies, a synchronisation, the kernel, a copy back and another synchronisation
   // (75 us for a 17 us kernel at B = 1)
-  okvfe_stereo_match* out_dev = reinterpret_cast<okvfe_stereo_match*>(base + o_out);
-  if (ctx->h_pinned_dev) {
-    launch_param_copy(base, ctx->h_pinned_dev, o_out, nullptr, 0, s);
-    out_dev = reinterpret_cast<okvfe_stereo_match*>(static_cast<uint8_t*>(ctx->h_pinned_dev) + o_out);
-  } else {
-    HIP_TRY(ctx, hipMemcpyAsync(base, hb, o_out, hipMemcpyHostToDevice, s));
-  }
-  launch_match_stereo_arrays(reinterpret_cast<PairParams*>(base + o_pair), base + o_d0,
-                             reinterpret_cast<double*>(base + o_b0), base + o_v0, nullptr, n0, base + o_d1,
-                             reinterpret_cast<double*>(base + o_b1), base + o_v1, nullptr, n1, n0,
-                             ctx->cfg.match_threshold, out_dev, s,
-                             multi ? reinterpret_cast<const okvfe_keypoint*>(base + o_k0) : nullptr,
-                             multi ? reinterpret_cast<const okvfe_keypoint*>(base + o_k1) : nullptr);
+  HIP_TRY(ctx, call.move_in(o_out));
+  launch_match_stereo_arrays(call.dev<PairParams>(o_pair), call.dev(o_d0), call.dev<double>(o_b0), call.dev(o_v0), nullptr,
+                             n0, call.dev(o_d1), call.dev<double>(o_b1), call.dev(o_v1), nullptr, n1, n0,
+                             ctx->cfg.match_threshold, call.result<okvfe_stereo_match>(o_out), ctx->stream,
+                             multi ? call.dev<const okvfe_keypoint>(o_k0) : nullptr,
+                             multi ? call.dev<const okvfe_keypoint>(o_k1) : nullptr);
   HIP_TRY(ctx, hipGetLastError());
-  if (!ctx->h_pinned_dev)
-    HIP_TRY(ctx, hipMemcpyAsync(hb + o_out, base + o_out, (size_t)n0 * sizeof(okvfe_stereo_match), hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipStreamSynchronize(s));
-  std::memcpy(matches, hb + o_out, (size_t)n0 * sizeof(okvfe_stereo_match));
+  HIP_TRY(ctx, call.fetch(matches, o_out, (size_t)n0 * sizeof(okvfe_stereo_match)));
   return OKVFE_OK;
 }
 
@@ -200,68 +184,50 @@ okvfe_status okvfe_match_motion_stereo_ext(okvfe_ctx* ctx, const okvfe_camera_ex
   }
   if (n0 == 0) return OKVFE_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
-  hipStream_t s = ctx->stream;
-  const size_t a = 256;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = off; off = align_up(off + std::max<size_t>(bytes, 1), a); return o; };
-  const size_t o_pair = take(sizeof(PairParams)), o_cam = take(sizeof(DeviceCamera)),
-               o_cls = take(kClassTableDoubles * sizeof(double));
-  const size_t o_d0 = take((size_t)n0 * 48), o_k0 = take((size_t)n0 * sizeof(okvfe_keypoint)), o_b0 = take((size_t)n0 * 24),
-               o_v0 = take(n0), o_s0 = take(n0);
-  const size_t o_d1 = take((size_t)n1 * 48), o_k1 = take((size_t)n1 * sizeof(okvfe_keypoint)), o_b1 = take((size_t)n1 * 24),
-               o_v1 = take(n1), o_m1 = take(n1);
-  const size_t o_out = take((size_t)n0 * sizeof(okvfe_motion_match));
-  okvfe_status st = ensure_scratch(ctx, off);
-  if (st == OKVFE_OK) st = ensure_pinned(ctx, off);
+  ScratchLayout lay;
+  const size_t o_pair = lay.take(sizeof(PairParams)), o_cam = lay.take(sizeof(DeviceCamera)),
+               o_cls = lay.take(kClassTableDoubles * sizeof(double));
+  const size_t o_d0 = lay.take((size_t)n0 * 48), o_k0 = lay.take((size_t)n0 * sizeof(okvfe_keypoint)),
+               o_b0 = lay.take((size_t)n0 * 24), o_v0 = lay.take(n0), o_s0 = lay.take(n0);
+  const size_t o_d1 = lay.take((size_t)n1 * 48), o_k1 = lay.take((size_t)n1 * sizeof(okvfe_keypoint)),
+               o_b1 = lay.take((size_t)n1 * 24), o_v1 = lay.take(n1), o_m1 = lay.take(n1);
+  const size_t o_out = lay.take((size_t)n0 * sizeof(okvfe_motion_match));
+  ScratchCall call(ctx, ctx->stream);  // the pinned variant (see okvfe_match_stereo)
+  const okvfe_status st = call.reserve(lay, true);
   if (st != OKVFE_OK) return st;
-  uint8_t* base = static_cast<uint8_t*>(ctx->scratch);
-  uint8_t* hb = ctx->h_pinned;  // the same layout in pinned host memory (see okvfe_match_stereo)
   okvfe_stereo_pair sp{};
   sp.T_WC0 = *T_WC0; sp.T_WC1 = *T_WC1;
   sp.f0 = sp.f1 = 0.5 * (camera->fu + camera->fv);  // sigma = size0 / f0 * 0.125 (Frontend.cpp:1834)
   PairParams pp = to_pair_params(sp);
   const DeviceCamera dc = to_device_camera(*camera_ext);
-  auto put = [&](size_t o, const void* src, size_t bytes) {
-    if (bytes) std::memcpy(hb + o, src, bytes);
-  };
   if (multi) {
-    fill_class_table(reinterpret_cast<double*>(hb + o_cls), sp.f0, sp.f1, true);
-    pp.cls = reinterpret_cast<const double*>(base + o_cls);
+    fill_class_table(call.host<double>(o_cls), sp.f0, sp.f1, true);
+    pp.cls = call.dev<double>(o_cls);
   }
-  put(o_pair, &pp, sizeof(pp));
-  put(o_cam, &dc, sizeof(dc));
-  put(o_d0, desc0, (size_t)n0 * 48);
-  put(o_k0, kp0, (size_t)n0 * sizeof(okvfe_keypoint));
-  put(o_b0, backproj0, (size_t)n0 * 24);
-  put(o_v0, valid0, n0);
-  if (skip0) put(o_s0, skip0, n0);
-  if (n1 > 0) {
-    put(o_d1, desc1, (size_t)n1 * 48);
-    put(o_k1, kp1, (size_t)n1 * sizeof(okvfe_keypoint));
-    put(o_b1, backproj1, (size_t)n1 * 24);
-    put(o_v1, valid1, n1);
-    if (matched1) put(o_m1, matched1, n1);
-  }
-  okvfe_motion_match* out_dev = reinterpret_cast<okvfe_motion_match*>(base + o_out);
-  if (ctx->h_pinned_dev) {
-    launch_param_copy(base, ctx->h_pinned_dev, o_out, nullptr, 0, s);
-    out_dev = reinterpret_cast<okvfe_motion_match*>(static_cast<uint8_t*>(ctx->h_pinned_dev) + o_out);
-  } else {
-    HIP_TRY(ctx, hipMemcpyAsync(base, hb, o_out, hipMemcpyHostToDevice, s));
-  }
-  launch_match_motion(reinterpret_cast<PairParams*>(base + o_pair), reinterpret_cast<DeviceCamera*>(base + o_cam),
-                      camera->width, camera->height, base + o_d0, reinterpret_cast<okvfe_keypoint*>(base + o_k0),
-                      reinterpret_cast<double*>(base + o_b0), base + o_v0, skip0 ? base + o_s0 : nullptr, n0,
-                      base + o_d1, reinterpret_cast<okvfe_keypoint*>(base + o_k1),
-                      reinterpret_cast<double*>(base + o_b1), base + o_v1, matched1 ? base + o_m1 : nullptr, n1,
-                      ctx->cfg.match_threshold, out_dev, s, dc.distortion == OKVFE_DIST_RADTAN8);
+  call.put(o_pair, &pp, sizeof(pp));
+  call.put(o_cam, &dc, sizeof(dc));
+  call.put(o_d0, desc0, (size_t)n0 * 48);
+  call.put(o_k0, kp0, (size_t)n0 * sizeof(okvfe_keypoint));
+  call.put(o_b0, backproj0, (size_t)n0 * 24);
+  call.put(o_v0, valid0, n0);
+  if (skip0) call.put(o_s0, skip0, n0);
+  call.put(o_d1, desc1, (size_t)n1 * 48);
+  call.put(o_k1, kp1, (size_t)n1 * sizeof(okvfe_keypoint));
+  call.put(o_b1, backproj1, (size_t)n1 * 24);
+  call.put(o_v1, valid1, n1);
+  if (matched1) call.put(o_m1, matched1, n1);
+  HIP_TRY(ctx, call.move_in(o_out));
+  launch_match_motion(call.dev<PairParams>(o_pair), call.dev<DeviceCamera>(o_cam), camera->width, camera->height,
+                      call.dev(o_d0), call.dev<okvfe_keypoint>(o_k0), call.dev<double>(o_b0), call.dev(o_v0),
+                      skip0 ? call.dev(o_s0) : nullptr, n0, call.dev(o_d1), call.dev<okvfe_keypoint>(o_k1),
+                      call.dev<double>(o_b1), call.dev(o_v1), matched1 ? call.dev(o_m1) : nullptr, n1,
+                      ctx->cfg.match_threshold, call.result<okvfe_motion_match>(o_out), ctx->stream,
+                      dc.distortion == OKVFE_DIST_RADTAN8);
   HIP_TRY(ctx, hipGetLastError());
-  if (!ctx->h_pinned_dev)
-    HIP_TRY(ctx, hipMemcpyAsync(hb + o_out, base + o_out, (size_t)n0 * sizeof(okvfe_motion_match), hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipStreamSynchronize(s));
-  std::memcpy(matches, hb + o_out, (size_t)n0 * sizeof(okvfe_motion_match));
+  HIP_TRY(ctx, call.fetch(matches, o_out, (size_t)n0 * sizeof(okvfe_motion_match)));
   return OKVFE_OK;
 }
+
 okvfe_status okvfe_hamming_candidates(okvfe_ctx* ctx, const uint8_t* A, int32_t nA, const uint8_t* B,
                                       int32_t nB, int32_t threshold, okvfe_candidate* out, int32_t cap,
                                       int32_t* n_out) {
@@ -272,23 +238,19 @@ okvfe_status okvfe_hamming_candidates(okvfe_ctx* ctx, const uint8_t* A, int32_t 
   if (nA == 0 || nB == 0) return OKVFE_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
   hipStream_t s = ctx->stream;
-  const size_t a = 256;
-  const size_t o_A = 0;
-  const size_t o_B = align_up(o_A + (size_t)nA * 48, a);
-  const size_t o_rows = align_up(o_B + (size_t)nB * 48, a);
-  const size_t o_out = align_up(o_rows + (size_t)nA * 4, a);
-  const size_t total = o_out + (size_t)std::max(cap, 1) * sizeof(okvfe_candidate);
-  okvfe_status st = ensure_scratch(ctx, total);
+  ScratchLayout lay;
+  const size_t o_A = lay.take((size_t)nA * 48), o_B = lay.take((size_t)nB * 48), o_rows = lay.take((size_t)nA * 4),
+               o_out = lay.take((size_t)cap * sizeof(okvfe_candidate));
+  ScratchCall call(ctx, s);
+  const okvfe_status st = call.reserve(lay);
   if (st != OKVFE_OK) return st;
-  uint8_t* base = static_cast<uint8_t*>(ctx->scratch);
-  HIP_TRY(ctx, hipMemcpyAsync(base + o_A, A, (size_t)nA * 48, hipMemcpyHostToDevice, s));
-  HIP_TRY(ctx, hipMemcpyAsync(base + o_B, B, (size_t)nB * 48, hipMemcpyHostToDevice, s));
-  HIP_TRY(ctx, hipStreamSynchronize(s));
-  int32_t* d_rows = reinterpret_cast<int32_t*>(base + o_rows);
-  launch_hamming_count(base + o_A, nA, base + o_B, nB, threshold, d_rows, s);
+  HIP_TRY(ctx, call.up(o_A, A, (size_t)nA * 48));
+  HIP_TRY(ctx, call.up(o_B, B, (size_t)nB * 48));
+  HIP_TRY(ctx, call.sync());
+  launch_hamming_count(call.dev(o_A), nA, call.dev(o_B), nB, threshold, call.dev<int32_t>(o_rows), s);
   std::vector<int32_t> rows(nA);
-  HIP_TRY(ctx, hipMemcpyAsync(rows.data(), d_rows, (size_t)nA * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipStreamSynchronize(s));
+  HIP_TRY(ctx, call.down(rows.data(), o_rows, (size_t)nA * 4));
+  HIP_TRY(ctx, call.sync());
   int64_t total_c = 0;
   for (int i = 0; i < nA; ++i) {
     const int32_t c = rows[i];
@@ -296,15 +258,13 @@ okvfe_status okvfe_hamming_candidates(okvfe_ctx* ctx, const uint8_t* A, int32_t 
     total_c += c;
   }
   *n_out = (int32_t)std::min<int64_t>(total_c, INT32_MAX);
-  HIP_TRY(ctx, hipMemcpyAsync(d_rows, rows.data(), (size_t)nA * 4, hipMemcpyHostToDevice, s));
-  HIP_TRY(ctx, hipStreamSynchronize(s));
-  launch_hamming_emit(base + o_A, nA, base + o_B, nB, threshold, d_rows,
-                      reinterpret_cast<okvfe_candidate*>(base + o_out), cap, s);
+  HIP_TRY(ctx, call.up(o_rows, rows.data(), (size_t)nA * 4));
+  HIP_TRY(ctx, call.sync());
+  launch_hamming_emit(call.dev(o_A), nA, call.dev(o_B), nB, threshold, call.dev<int32_t>(o_rows),
+                      call.dev<okvfe_candidate>(o_out), cap, s);
   HIP_TRY(ctx, hipGetLastError());
-  const int32_t ncopy = (int32_t)std::min<int64_t>(total_c, cap);
-  if (ncopy > 0)
-    HIP_TRY(ctx, hipMemcpyAsync(out, base + o_out, (size_t)ncopy * sizeof(okvfe_candidate), hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipStreamSynchronize(s));
+  HIP_TRY(ctx, call.down(out, o_out, (size_t)std::min<int64_t>(total_c, cap) * sizeof(okvfe_candidate)));
+  HIP_TRY(ctx, call.sync());
   if (total_c > cap) return fail(ctx, OKVFE_ERR_CAPACITY, "%lld candidates, caller capacity %d", (long long)total_c, cap);
   return OKVFE_OK;
 }
@@ -316,25 +276,21 @@ okvfe_status okvfe_hamming_argmin(okvfe_ctx* ctx, const uint8_t* A, int32_t nA, 
     return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_hamming_argmin: bad argument");
   if (nA == 0) return OKVFE_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
-  hipStream_t s = ctx->stream;
-  const size_t a = 256;
-  const size_t o_A = 0;
-  const size_t o_B = align_up(o_A + (size_t)nA * 48, a);
-  const size_t o_j = align_up(o_B + (size_t)std::max(nB, 1) * 48, a);
-  const size_t o_d = align_up(o_j + (size_t)nA * 4, a);
-  const size_t total = o_d + (size_t)nA * 4;
-  okvfe_status st = ensure_scratch(ctx, total);
+  ScratchLayout lay;
+  const size_t o_A = lay.take((size_t)nA * 48), o_B = lay.take((size_t)nB * 48), o_j = lay.take((size_t)nA * 4),
+               o_d = lay.take((size_t)nA * 4);
+  ScratchCall call(ctx, ctx->stream);
+  const okvfe_status st = call.reserve(lay);
   if (st != OKVFE_OK) return st;
-  uint8_t* base = static_cast<uint8_t*>(ctx->scratch);
-  HIP_TRY(ctx, hipMemcpyAsync(base + o_A, A, (size_t)nA * 48, hipMemcpyHostToDevice, s));
-  if (nB > 0) HIP_TRY(ctx, hipMemcpyAsync(base + o_B, B, (size_t)nB * 48, hipMemcpyHostToDevice, s));
-  HIP_TRY(ctx, hipStreamSynchronize(s));
-  launch_hamming_argmin(base + o_A, nA, base + o_B, nB, threshold, reinterpret_cast<int32_t*>(base + o_j),
-                        reinterpret_cast<uint32_t*>(base + o_d), s);
+  HIP_TRY(ctx, call.up(o_A, A, (size_t)nA * 48));
+  HIP_TRY(ctx, call.up(o_B, B, (size_t)nB * 48));
+  HIP_TRY(ctx, call.sync());
+  launch_hamming_argmin(call.dev(o_A), nA, call.dev(o_B), nB, threshold, call.dev<int32_t>(o_j), call.dev<uint32_t>(o_d),
+                        ctx->stream);
   HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipMemcpyAsync(best_j, base + o_j, (size_t)nA * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipMemcpyAsync(best_dist, base + o_d, (size_t)nA * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipStreamSynchronize(s));
+  HIP_TRY(ctx, call.down(best_j, o_j, (size_t)nA * 4));
+  HIP_TRY(ctx, call.down(best_dist, o_d, (size_t)nA * 4));
+  HIP_TRY(ctx, call.sync());
   return OKVFE_OK;
 }
 
@@ -397,9 +353,10 @@ okvfe_status okvfe_match_motion_stereo_blocks_device(okvfe_ctx* ctx, int32_t cam
   if (!block0_dev || !block1_dev || !T_WC0 || !T_WC1 || !matches_dev || cam < 0 ||
       cam >= (int)ctx->h_cams.size())
     return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_match_motion_stereo_blocks_device: bad argument");
-  if (!slot_camera(ctx, cam))
-    return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "camera slot %d has no intrinsics (okvfe_set_camera)", cam);
-  const DeviceCamera& dc = ctx->h_cams[cam];
+  const RigWho who{nullptr, nullptr, OKVFE_ERR_INVALID_ARGUMENT};
+  const DeviceCamera* slot = rig_slot(ctx, who, 0, cam);
+  if (!slot) return who.bad;
+  const DeviceCamera& dc = *slot;
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
   hipStream_t s = pick_stream(ctx, stream);
   const BlockLayout L = block_layout(ctx->kp_cap);
@@ -447,6 +404,7 @@ okvfe_status okvfe_match_motion_stereo_blocks_batch_device(
   std::vector<int> slot_of((size_t)n_pairs);                // ... and each pair's position among them
   std::vector<int32_t> user(claim ? (size_t)n_blocks1 : 0, -1);  // with claims: the pair that names a current block
   bool rt8 = false;
+  const RigWho who{fn, "pair", OKVFE_ERR_INVALID_ARGUMENT};
   for (int p = 0; p < n_pairs; ++p) {
     const int i0 = idx0 ? idx0[p] : p, i1 = idx1 ? idx1[p] : p, cam = cam_ids[p];
     if (i0 < 0 || i0 >= n_blocks0)
@@ -456,10 +414,9 @@ okvfe_status okvfe_match_motion_stereo_blocks_batch_device(
     if (cam < 0 || cam >= (int)ctx->h_cams.size())
       return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "%s: pair %d: camera slot %d outside [0, %d)", fn, p, cam,
                   (int)ctx->h_cams.size());
-    if (!slot_camera(ctx, cam))
-      return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "%s: pair %d: camera slot %d has no intrinsics (okvfe_set_camera)", fn,
-                  p, cam);
-    const DeviceCamera& dc = ctx->h_cams[cam];
+    const DeviceCamera* slot = rig_slot(ctx, who, p, cam);  // (not rig_slots: a pair's checks stay in their order)
+    if (!slot) return who.bad;
+    const DeviceCamera& dc = *slot;
     if (claim) {
       if (user[i1] >= 0)
         return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT,

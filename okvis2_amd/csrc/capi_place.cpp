@@ -10,6 +10,29 @@
 
 using namespace okvfe;
 
+namespace {
+// What the Hessian and the refinement share.  The rig: pose parameters and slot per camera, 64 bytes each; *rt8 asks for
+// the 8-coefficient form of the projection only when a slot this call uses holds that model.
+okvfe_status hessian_rig(okvfe_ctx* ctx, const char* who, int n_cams, const int32_t* cam_ids, const double* T_SC_params,
+                         std::vector<HessianCamParams>* cp, bool* rt8) {
+  return rig_slots(ctx, RigWho{who, "frame"}, n_cams, cam_ids, rt8, [&](int c, const DeviceCamera&) {
+    std::copy_n(T_SC_params + 7 * (size_t)c, 7, (*cp)[(size_t)c].pose);
+    (*cp)[(size_t)c].cam = cam_ids[c];
+  });
+}
+// ... and the terms' arguments, all but where the results go
+void hessian_args(const okvfe_ctx* ctx, const okvfe_place_set_device* set, const void* blocks_dev, int n_cams,
+                  const HessianCamParams* rig, const double* poses, const int32_t* match_landmark, const uint8_t* state,
+                  const uint8_t* verdict, PlaceHessianArgs* A) {
+  const BlockLayout L = block_layout(ctx->kp_cap);
+  A->hp = set->hp; A->n_landmarks = set->n_landmarks; A->blocks = static_cast<const uint8_t*>(blocks_dev);
+  A->o_count = (int)L.o_count; A->o_kps = (int)L.o_kps; A->block_bytes = L.total;
+  A->kp_cap = ctx->kp_cap; A->n_cams = n_cams; A->w = ctx->w; A->h = ctx->h;
+  A->cams = rig; A->dcams = ctx->d_cams; A->poses = poses;
+  A->match_landmark = match_landmark; A->state = state; A->verdict = verdict;
+}
+}  // namespace
+
 extern "C" {
 
 okvfe_status okvfe_place_landmark_set(int32_t n_cams, const int32_t* n_kps, const uint64_t* landmark_ids,
@@ -102,43 +125,19 @@ okvfe_status okvfe_place_hessian_blocks_device(okvfe_ctx* ctx, const okvfe_place
     return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_place_hessian_blocks_device: bad argument");
   if ((int64_t)n_cams * ctx->kp_cap >= (int64_t)1 << 30 || (int64_t)n_multiframes * n_cams >= (int64_t)1 << 30)
     return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_place_hessian_blocks_device: too many keypoints or blocks");
-  bool rt8 = false;  // the 8-coefficient form of the projection only when a slot this call uses holds that model
+  bool rt8 = false;
   std::vector<HessianCamParams> cp((size_t)n_cams);
-  for (int c = 0; c < n_cams; ++c) {
-    const DeviceCamera* dc = slot_camera(ctx, cam_ids[c]);
-    if (!dc)
-      return fail(ctx, OKVFE_ERR_NOT_READY,
-                  "okvfe_place_hessian_blocks_device: frame %d: camera slot %d has no intrinsics (okvfe_set_camera)", c,
-                  cam_ids[c]);
-    rt8 = rt8 || dc->distortion == OKVFE_DIST_RADTAN8;
-    cp[(size_t)c] = HessianCamParams{};
-    std::copy_n(T_SC_params + 7 * (size_t)c, 7, cp[(size_t)c].pose);
-    cp[(size_t)c].cam = cam_ids[c];
-  }
-  if (n_multiframes == 0) return OKVFE_OK;
+  const okvfe_status st = hessian_rig(ctx, "okvfe_place_hessian_blocks_device", n_cams, cam_ids, T_SC_params, &cp, &rt8);
+  if (st != OKVFE_OK || n_multiframes == 0) return st;
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
   hipStream_t s = pick_stream(ctx, stream);
-  const BlockLayout L = block_layout(ctx->kp_cap);
-  // the rig: 64 bytes per camera through the pinned parameter ring (one asynchronous copy, no host sync)
-  RingSlot rig(ctx, &ctx->pair_ring, s);
-  okvfe_status st = rig.upload(cp.data(), cp.size() * sizeof(HessianCamParams));
-  if (st != OKVFE_OK) return st;
-  PlaceHessianArgs A;
-  A.hp = set->hp; A.n_landmarks = set->n_landmarks; A.blocks = static_cast<const uint8_t*>(blocks_dev);
-  A.o_count = (int)L.o_count; A.o_kps = (int)L.o_kps; A.block_bytes = L.total;
-  A.kp_cap = ctx->kp_cap; A.n_cams = n_cams; A.w = ctx->w; A.h = ctx->h;
-  A.cams = rig.as<HessianCamParams>(); A.dcams = ctx->d_cams; A.poses = poses_dev;
-  A.match_landmark = match_landmark_dev; A.state = state_dev; A.verdict = verdict_dev;
-  A.H = result->H; A.n_terms = result->n_terms; A.n_singular = result->n_singular;
-  A.residual = result->residual; A.jacobian = result->jacobian_minimal;
-  {
-    StageTimer t(ctx, OKVFE_STAGE_MAP, s);
+  return ring_launch(ctx, s, cp, OKVFE_STAGE_MAP, [&](const HessianCamParams* rig) {
+    PlaceHessianArgs A;
+    hessian_args(ctx, set, blocks_dev, n_cams, rig, poses_dev, match_landmark_dev, state_dev, verdict_dev, &A);
+    A.H = result->H; A.n_terms = result->n_terms; A.n_singular = result->n_singular;
+    A.residual = result->residual; A.jacobian = result->jacobian_minimal;
     launch_place_hessian(A, n_multiframes, rt8, s);
-  }
-  HIP_TRY(ctx, hipGetLastError());
-  const okvfe_status rel = rig.release();
-  ctx->last_stream = s;
-  return rel;
+  });
 }
 
 // The refinement of T_Sold_Snew between the consensus and H (Frontend.cpp:399-527) as the defined algorithm of
@@ -159,45 +158,19 @@ okvfe_status okvfe_place_refine_blocks_device(okvfe_ctx* ctx, const okvfe_place_
     return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_place_refine_blocks_device: bad argument");
   if ((int64_t)n_cams * ctx->kp_cap >= (int64_t)1 << 30 || (int64_t)n_multiframes * n_cams >= (int64_t)1 << 30)
     return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_place_refine_blocks_device: too many keypoints or blocks");
-  bool rt8 = false;  // the 8-coefficient form of the projection only when a slot this call uses holds that model
+  bool rt8 = false;
   std::vector<HessianCamParams> cp((size_t)n_cams);
-  for (int c = 0; c < n_cams; ++c) {
-    const DeviceCamera* dc = slot_camera(ctx, cam_ids[c]);
-    if (!dc)
-      return fail(ctx, OKVFE_ERR_NOT_READY,
-                  "okvfe_place_refine_blocks_device: frame %d: camera slot %d has no intrinsics (okvfe_set_camera)", c,
-                  cam_ids[c]);
-    rt8 = rt8 || dc->distortion == OKVFE_DIST_RADTAN8;
-    cp[(size_t)c] = HessianCamParams{};
-    std::copy_n(T_SC_params + 7 * (size_t)c, 7, cp[(size_t)c].pose);
-    cp[(size_t)c].cam = cam_ids[c];
-  }
-  if (n_multiframes == 0) return OKVFE_OK;
+  okvfe_status st = hessian_rig(ctx, "okvfe_place_refine_blocks_device", n_cams, cam_ids, T_SC_params, &cp, &rt8);
+  if (st != OKVFE_OK || n_multiframes == 0) return st;
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
   hipStream_t s = pick_stream(ctx, stream);
-  const BlockLayout L = block_layout(ctx->kp_cap);
   // the stream's workspace: a record and an evaluation per multiframe, and the two counts of the Hessian call where the
   // caller does not ask for them
   const size_t n = (size_t)n_multiframes;
   const size_t o_evals = n * sizeof(PlaceRefineRecord), o_counts = o_evals + n * sizeof(PlaceRefineEval);
   uint8_t* ws = nullptr;
-  okvfe_status st = stream_workspace(ctx, &ctx->place_refine_ws, s, o_counts + 2 * n * sizeof(int32_t), &ws);
-  if (st != OKVFE_OK) return st;
-  // the rig: 64 bytes per camera through the pinned parameter ring, once for every launch of the call
-  RingSlot rig(ctx, &ctx->pair_ring, s);
-  st = rig.upload(cp.data(), cp.size() * sizeof(HessianCamParams));
-  if (st != OKVFE_OK) return st;
+  if ((st = stream_workspace(ctx, &ctx->place_refine_ws, s, o_counts + 2 * n * sizeof(int32_t), &ws)) != OKVFE_OK) return st;
   PlaceRefineArgs R{};
-  PlaceHessianArgs& A = R.term;
-  A.hp = set->hp; A.n_landmarks = set->n_landmarks; A.blocks = static_cast<const uint8_t*>(blocks_dev);
-  A.o_count = (int)L.o_count; A.o_kps = (int)L.o_kps; A.block_bytes = L.total;
-  A.kp_cap = ctx->kp_cap; A.n_cams = n_cams; A.w = ctx->w; A.h = ctx->h;
-  A.cams = rig.as<HessianCamParams>(); A.dcams = ctx->d_cams; A.poses = result->poses;
-  A.match_landmark = match_landmark_dev; A.state = state_dev; A.verdict = verdict_dev;
-  A.H = result->H;
-  A.n_terms = reinterpret_cast<int32_t*>(ws + o_counts);
-  A.n_singular = result->n_singular ? result->n_singular : A.n_terms + n;
-  A.residual = nullptr; A.jacobian = nullptr;
   R.records = reinterpret_cast<PlaceRefineRecord*>(ws);
   R.evals = reinterpret_cast<PlaceRefineEval*>(ws + o_evals);
   R.n_multiframes = n_multiframes; R.n_hyp = n_hyp; R.max_iterations = max_iterations;
@@ -205,8 +178,14 @@ okvfe_status okvfe_place_refine_blocks_device(okvfe_ctx* ctx, const okvfe_place_
   R.poses = result->poses; R.start_poses = result->start_poses; R.cost = result->cost;
   R.status = result->status; R.n_iterations = result->n_iterations; R.n_accepted = result->n_accepted;
   R.n_terms = result->n_terms;
-  {
-    StageTimer t(ctx, OKVFE_STAGE_MAP, s);
+  PlaceHessianArgs& A = R.term;
+  A.H = result->H;
+  A.n_terms = reinterpret_cast<int32_t*>(ws + o_counts);
+  A.n_singular = result->n_singular ? result->n_singular : A.n_terms + n;
+  A.residual = nullptr; A.jacobian = nullptr;
+  // the rig through the ring once for every launch of the call, released behind the last of them
+  return ring_launch(ctx, s, cp, OKVFE_STAGE_MAP, [&](const HessianCamParams* rig) {
+    hessian_args(ctx, set, blocks_dev, n_cams, rig, result->poses, match_landmark_dev, state_dev, verdict_dev, &A);
     launch_place_refine_start(R, s);
     launch_place_refine_eval(R, rt8, s);
     launch_place_refine_step(R, true, s);
@@ -216,11 +195,7 @@ okvfe_status okvfe_place_refine_blocks_device(okvfe_ctx* ctx, const okvfe_place_
       launch_place_refine_step(R, false, s);
     }
     if (result->H) launch_place_hessian(A, n_multiframes, rt8, s);
-  }
-  HIP_TRY(ctx, hipGetLastError());
-  const okvfe_status rel = rig.release();  // behind the last launch that reads the rig
-  ctx->last_stream = s;
-  return rel;
+  });
 }
 
 // Test hook, deliberately not in include/okvfe.h: the number of terms the Hessian kernel evaluates at a time, so that the

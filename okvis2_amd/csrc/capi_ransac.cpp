@@ -5,22 +5,24 @@
 using namespace okvfe;
 
 namespace {
-// the rig of a consensus call: one record per camera, its pose in the sensor frame and its slot
-okvfe_status rig_params(okvfe_ctx* ctx, const char* who, int n_cams, const int32_t* cam_ids, const okvfe_pose* T_SC,
-                        std::vector<RansacCamParams>* cp) {
+// What the four consensus and hypotheses calls share behind their argument checks, all of it before anything is queued:
+// the count guard (consensus: keypoint slots of a multiframe within an int32 with room; hypotheses: their list within
+// LDS) and the rig, one record per camera with its pose in the sensor frame and its slot.  ring_launch is the rest.
+okvfe_status rig_params(okvfe_ctx* ctx, const char* who, bool hypotheses, int n_cams, const int32_t* cam_ids,
+                        const okvfe_pose* T_SC, std::vector<RansacCamParams>* cp) {
+  if (hypotheses && !ransac_hypotheses_fits(n_cams, ctx->kp_cap))
+    return fail(ctx, OKVFE_ERR_UNSUPPORTED, "%s: the list of %d x %d keypoint slots does not fit in LDS", who, n_cams,
+                ctx->kp_cap);
+  if (!hypotheses && (int64_t)n_cams * ctx->kp_cap >= (int64_t)1 << 30)
+    return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "%s: too many keypoints per multiframe", who);
   cp->assign((size_t)n_cams, RansacCamParams{});
-  for (int c = 0; c < n_cams; ++c) {
-    const DeviceCamera* dc = slot_camera(ctx, cam_ids[c]);
-    if (!dc)
-      return fail(ctx, OKVFE_ERR_NOT_READY, "%s: frame %d: camera slot %d has no intrinsics (okvfe_set_camera)", who, c,
-                  cam_ids[c]);
+  return rig_slots(ctx, RigWho{who, "frame"}, n_cams, cam_ids, nullptr, [&](int c, const DeviceCamera& dc) {
     RansacCamParams& p = (*cp)[(size_t)c];
     std::memcpy(p.C, T_SC[c].C, sizeof(p.C));
     std::memcpy(p.r, T_SC[c].r, sizeof(p.r));
-    p.fu = dc->fu;
+    p.fu = dc.fu;
     p.cam = cam_ids[c];
-  }
-  return OKVFE_OK;
+  });
 }
 }  // namespace
 
@@ -37,28 +39,16 @@ okvfe_status okvfe_ransac3d2d_consensus_blocks_device(
       !hypotheses_dev || n_hyp < 1 || n_hyp > OKVFE_RANSAC_MAX_HYPOTHESES || !(threshold >= 0.0) || !result ||
       !result->n_correspondences || !result->best_hypothesis || !result->n_inliers || !result->accepted)
     return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_ransac3d2d_consensus_blocks_device: bad argument");
-  if ((int64_t)n_cams * ctx->kp_cap >= (int64_t)1 << 30)
-    return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_ransac3d2d_consensus_blocks_device: too many keypoints per multiframe");
   std::vector<RansacCamParams> cp;
-  okvfe_status st = rig_params(ctx, "okvfe_ransac3d2d_consensus_blocks_device", n_cams, cam_ids, T_SC, &cp);
-  if (st != OKVFE_OK) return st;
-  if (n_multiframes == 0) return OKVFE_OK;
+  const okvfe_status st = rig_params(ctx, "okvfe_ransac3d2d_consensus_blocks_device", false, n_cams, cam_ids, T_SC, &cp);
+  if (st != OKVFE_OK || n_multiframes == 0) return st;
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
   hipStream_t s = pick_stream(ctx, stream);
-  const BlockLayout L = block_layout(ctx->kp_cap);
-  // the rig: one record per camera through the pinned parameter ring (one asynchronous copy, no host sync)
-  RingSlot rig(ctx, &ctx->pair_ring, s);
-  if ((st = rig.upload(cp.data(), cp.size() * sizeof(RansacCamParams))) != OKVFE_OK) return st;
-  {
-    StageTimer t(ctx, OKVFE_STAGE_MAP, s);
-    launch_ransac_consensus(T->hp_W, T->obs_begin, T->n_landmarks, L, static_cast<const uint8_t*>(blocks_dev),
-                            n_multiframes, n_cams, ctx->kp_cap, rig.as<RansacCamParams>(), landmark_dev,
+  return ring_launch(ctx, s, cp, OKVFE_STAGE_MAP, [&](const RansacCamParams* rig) {
+    launch_ransac_consensus(T->hp_W, T->obs_begin, T->n_landmarks, block_layout(ctx->kp_cap),
+                            static_cast<const uint8_t*>(blocks_dev), n_multiframes, n_cams, ctx->kp_cap, rig, landmark_dev,
                             hypotheses_dev, hyp_valid_dev, n_hyp, threshold, remove_outliers ? 1 : 0, *result, s);
-  }
-  HIP_TRY(ctx, hipGetLastError());
-  const okvfe_status rel = rig.release();
-  ctx->last_stream = s;
-  return rel;
+  });
 }
 
 okvfe_status okvfe_remove_outliers_blocks_device(okvfe_ctx* ctx, const okvfe_landmark_table_device* T,
@@ -71,25 +61,18 @@ okvfe_status okvfe_remove_outliers_blocks_device(okvfe_ctx* ctx, const okvfe_lan
     return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_remove_outliers_blocks_device: bad argument");
   bool rt8 = false;  // the 8-coefficient form of the projection only when a slot this call uses holds that model
   std::vector<MapFrameParams> fp((size_t)n_frames);
-  for (int f = 0; f < n_frames; ++f) {
-    const DeviceCamera* dc = slot_camera(ctx, cam_ids[f]);
-    if (!dc)
-      return fail(ctx, OKVFE_ERR_NOT_READY,
-                  "okvfe_remove_outliers_blocks_device: frame %d: camera slot %d has no intrinsics (okvfe_set_camera)", f,
-                  cam_ids[f]);
-    rt8 = rt8 || dc->distortion == OKVFE_DIST_RADTAN8;
-    fp[(size_t)f] = MapFrameParams{};
-    fp[(size_t)f].T1 = T_WC[f];
-    fp[(size_t)f].cam = cam_ids[f];
-  }
-  if (n_frames == 0) return OKVFE_OK;
+  okvfe_status st = rig_slots(ctx, RigWho{"okvfe_remove_outliers_blocks_device", "frame"}, n_frames, cam_ids, &rt8,
+                              [&](int f, const DeviceCamera&) {
+                                fp[(size_t)f].T1 = T_WC[f];
+                                fp[(size_t)f].cam = cam_ids[f];
+                              });
+  if (st != OKVFE_OK || n_frames == 0) return st;
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
   hipStream_t s = pick_stream(ctx, stream);
   const BlockLayout L = block_layout(ctx->kp_cap);
   // pose and camera slot: one record per frame through the pinned parameter ring (one asynchronous copy, no host sync)
   RingSlot frames(ctx, &ctx->pair_ring, s);
-  okvfe_status st = frames.upload(fp.data(), fp.size() * sizeof(MapFrameParams));
-  if (st != OKVFE_OK) return st;
+  if ((st = frames.upload(fp.data(), fp.size() * sizeof(MapFrameParams))) != OKVFE_OK) return st;
   HIP_TRY(ctx, hipMemsetAsync(kept_dev, 0, (size_t)n_frames * sizeof(int32_t), s));
   {
     StageTimer t(ctx, OKVFE_STAGE_MAP, s);
@@ -97,10 +80,7 @@ okvfe_status okvfe_remove_outliers_blocks_device(okvfe_ctx* ctx, const okvfe_lan
                                   ctx->w, ctx->h, L, static_cast<const uint8_t*>(blocks_dev), ctx->kp_cap, max_error,
                                   landmark_dev, landmark_out_dev, kept_dev, s, rt8);
   }
-  HIP_TRY(ctx, hipGetLastError());
-  const okvfe_status rel = frames.release();
-  ctx->last_stream = s;
-  return rel;
+  return finish_call(ctx, &frames, s);
 }
 
 // The consensus of Frontend::verifyRecognisedPlace (Frontend.cpp:372-397): the kernel above under its kPlace policy, fed
@@ -116,27 +96,16 @@ okvfe_status okvfe_place_consensus_blocks_device(
       n_hyp < 1 || n_hyp > OKVFE_RANSAC_MAX_HYPOTHESES || !(threshold >= 0.0) || min_inliers < 0 || !result ||
       !result->n_correspondences || !result->best_hypothesis || !result->n_inliers || !result->accepted || !verdict_dev)
     return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_place_consensus_blocks_device: bad argument");
-  if ((int64_t)n_cams * ctx->kp_cap >= (int64_t)1 << 30)
-    return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_place_consensus_blocks_device: too many keypoints per multiframe");
   std::vector<RansacCamParams> cp;
-  okvfe_status st = rig_params(ctx, "okvfe_place_consensus_blocks_device", n_cams, cam_ids, T_SC, &cp);
-  if (st != OKVFE_OK) return st;
-  if (n_multiframes == 0) return OKVFE_OK;
+  const okvfe_status st = rig_params(ctx, "okvfe_place_consensus_blocks_device", false, n_cams, cam_ids, T_SC, &cp);
+  if (st != OKVFE_OK || n_multiframes == 0) return st;
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
   hipStream_t s = pick_stream(ctx, stream);
-  const BlockLayout L = block_layout(ctx->kp_cap);
-  RingSlot rig(ctx, &ctx->pair_ring, s);
-  if ((st = rig.upload(cp.data(), cp.size() * sizeof(RansacCamParams))) != OKVFE_OK) return st;
-  {
-    StageTimer t(ctx, OKVFE_STAGE_MAP, s);
-    launch_place_consensus(set->hp, set->n_landmarks, L, static_cast<const uint8_t*>(blocks_dev), n_multiframes, n_cams,
-                           ctx->kp_cap, rig.as<RansacCamParams>(), match_landmark_dev, gate_dev,
-                           hypotheses_dev, hyp_valid_dev, n_hyp, threshold, min_inliers, *result, verdict_dev, s);
-  }
-  HIP_TRY(ctx, hipGetLastError());
-  const okvfe_status rel = rig.release();
-  ctx->last_stream = s;
-  return rel;
+  return ring_launch(ctx, s, cp, OKVFE_STAGE_MAP, [&](const RansacCamParams* rig) {
+    launch_place_consensus(set->hp, set->n_landmarks, block_layout(ctx->kp_cap), static_cast<const uint8_t*>(blocks_dev),
+                           n_multiframes, n_cams, ctx->kp_cap, rig, match_landmark_dev, gate_dev, hypotheses_dev,
+                           hyp_valid_dev, n_hyp, threshold, min_inliers, *result, verdict_dev, s);
+  });
 }
 
 // The solver and the choice of ransac_hyp_dev.h for one sample on the host (k_ransac_hyp.hip): the B = 1 seam of the two
@@ -163,29 +132,16 @@ okvfe_status okvfe_ransac3d2d_hypotheses_blocks_device(
       n_multiframes < 0 || n_cams < 1 || n_cams > (int)ctx->h_cams.size() || !cam_ids || !T_SC || !landmark_dev ||
       n_hyp < 1 || n_hyp > OKVFE_RANSAC_MAX_HYPOTHESES || !result || !result->hypotheses || !result->hyp_valid)
     return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_ransac3d2d_hypotheses_blocks_device: bad argument");
-  if (!ransac_hypotheses_fits(n_cams, ctx->kp_cap))
-    return fail(ctx, OKVFE_ERR_UNSUPPORTED,
-                "okvfe_ransac3d2d_hypotheses_blocks_device: the list of %d x %d keypoint slots does not fit in LDS", n_cams,
-                ctx->kp_cap);
   std::vector<RansacCamParams> cp;
-  okvfe_status st = rig_params(ctx, "okvfe_ransac3d2d_hypotheses_blocks_device", n_cams, cam_ids, T_SC, &cp);
-  if (st != OKVFE_OK) return st;
-  if (n_multiframes == 0) return OKVFE_OK;
+  const okvfe_status st = rig_params(ctx, "okvfe_ransac3d2d_hypotheses_blocks_device", true, n_cams, cam_ids, T_SC, &cp);
+  if (st != OKVFE_OK || n_multiframes == 0) return st;
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
   hipStream_t s = pick_stream(ctx, stream);
-  const BlockLayout L = block_layout(ctx->kp_cap);
-  RingSlot rig(ctx, &ctx->pair_ring, s);
-  if ((st = rig.upload(cp.data(), cp.size() * sizeof(RansacCamParams))) != OKVFE_OK) return st;
-  {
-    StageTimer t(ctx, OKVFE_STAGE_MAP, s);
-    launch_ransac_hypotheses(T->hp_W, T->obs_begin, T->n_landmarks, L, static_cast<const uint8_t*>(blocks_dev),
-                             n_multiframes, n_cams, ctx->kp_cap, rig.as<RansacCamParams>(), landmark_dev, sample_keys_dev,
-                             seed, n_hyp, *result, s);
-  }
-  HIP_TRY(ctx, hipGetLastError());
-  const okvfe_status rel = rig.release();
-  ctx->last_stream = s;
-  return rel;
+  return ring_launch(ctx, s, cp, OKVFE_STAGE_MAP, [&](const RansacCamParams* rig) {
+    launch_ransac_hypotheses(T->hp_W, T->obs_begin, T->n_landmarks, block_layout(ctx->kp_cap),
+                             static_cast<const uint8_t*>(blocks_dev), n_multiframes, n_cams, ctx->kp_cap, rig, landmark_dev,
+                             sample_keys_dev, seed, n_hyp, *result, s);
+  });
 }
 
 // ... and of okvfe_place_consensus_blocks_device: the same kernel under its kPlace policy.
@@ -199,29 +155,16 @@ okvfe_status okvfe_place_hypotheses_blocks_device(
       n_cams < 1 || n_cams > (int)ctx->h_cams.size() || !cam_ids || !T_SC || !match_landmark_dev || n_hyp < 1 ||
       n_hyp > OKVFE_RANSAC_MAX_HYPOTHESES || !result || !result->hypotheses || !result->hyp_valid)
     return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_place_hypotheses_blocks_device: bad argument");
-  if (!ransac_hypotheses_fits(n_cams, ctx->kp_cap))
-    return fail(ctx, OKVFE_ERR_UNSUPPORTED,
-                "okvfe_place_hypotheses_blocks_device: the list of %d x %d keypoint slots does not fit in LDS", n_cams,
-                ctx->kp_cap);
   std::vector<RansacCamParams> cp;
-  okvfe_status st = rig_params(ctx, "okvfe_place_hypotheses_blocks_device", n_cams, cam_ids, T_SC, &cp);
-  if (st != OKVFE_OK) return st;
-  if (n_multiframes == 0) return OKVFE_OK;
+  const okvfe_status st = rig_params(ctx, "okvfe_place_hypotheses_blocks_device", true, n_cams, cam_ids, T_SC, &cp);
+  if (st != OKVFE_OK || n_multiframes == 0) return st;
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
   hipStream_t s = pick_stream(ctx, stream);
-  const BlockLayout L = block_layout(ctx->kp_cap);
-  RingSlot rig(ctx, &ctx->pair_ring, s);
-  if ((st = rig.upload(cp.data(), cp.size() * sizeof(RansacCamParams))) != OKVFE_OK) return st;
-  {
-    StageTimer t(ctx, OKVFE_STAGE_MAP, s);
-    launch_place_hypotheses(set->hp, set->n_landmarks, L, static_cast<const uint8_t*>(blocks_dev), n_multiframes, n_cams,
-                            ctx->kp_cap, rig.as<RansacCamParams>(), match_landmark_dev, gate_dev, sample_keys_dev, seed,
+  return ring_launch(ctx, s, cp, OKVFE_STAGE_MAP, [&](const RansacCamParams* rig) {
+    launch_place_hypotheses(set->hp, set->n_landmarks, block_layout(ctx->kp_cap), static_cast<const uint8_t*>(blocks_dev),
+                            n_multiframes, n_cams, ctx->kp_cap, rig, match_landmark_dev, gate_dev, sample_keys_dev, seed,
                             n_hyp, *result, s);
-  }
-  HIP_TRY(ctx, hipGetLastError());
-  const okvfe_status rel = rig.release();
-  ctx->last_stream = s;
-  return rel;
+  });
 }
 
 // Test hook, deliberately not in include/okvfe.h: the number of correspondences the consensus kernel scores at a time,

@@ -26,13 +26,10 @@ okvfe_status okvfe_ransac2d2d_consensus_blocks_device(
                 ctx->kp_cap, kRansac2dMaxKeypoints);
   // the parameter block: fu per camera, then {mf0, mf1} per pair
   std::vector<uint8_t> prm((size_t)n_cams * sizeof(double) + (size_t)n_pairs * 2 * sizeof(int32_t));
-  for (int c = 0; c < n_cams; ++c) {
-    const DeviceCamera* dc = slot_camera(ctx, cam_ids[c]);
-    if (!dc)
-      return fail(ctx, OKVFE_ERR_NOT_READY, "%s: frame %d: camera slot %d has no intrinsics (okvfe_set_camera)", fn, c,
-                  cam_ids[c]);
-    std::memcpy(prm.data() + (size_t)c * sizeof(double), &dc->fu, sizeof(double));
-  }
+  const okvfe_status st = rig_slots(ctx, RigWho{fn, "frame"}, n_cams, cam_ids, nullptr, [&](int c, const DeviceCamera& dc) {
+    std::memcpy(prm.data() + (size_t)c * sizeof(double), &dc.fu, sizeof(double));
+  });
+  if (st != OKVFE_OK) return st;
   int32_t* pr = reinterpret_cast<int32_t*>(prm.data() + (size_t)n_cams * sizeof(double));
   std::vector<int> user(result->landmark1_out ? (size_t)n_multiframes1 : 0, -1);
   for (int p = 0; p < n_pairs; ++p) {
@@ -53,28 +50,20 @@ okvfe_status okvfe_ransac2d2d_consensus_blocks_device(
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device));
   hipStream_t s = pick_stream(ctx, stream);
   const BlockLayout L = block_layout(ctx->kp_cap);
-  RingSlot slot(ctx, &ctx->pair_ring, s);  // one asynchronous copy, no host sync
-  okvfe_status st = slot.upload(prm.data(), prm.size());
-  if (st != OKVFE_OK) return st;
   Ransac2d2dArgs A;
   A.blocks0 = static_cast<const uint8_t*>(blocks0_dev);
   A.blocks1 = static_cast<const uint8_t*>(blocks1_dev);
   A.o_count = (int)L.o_count; A.o_kps = (int)L.o_kps; A.o_bp = (int)L.o_bp; A.o_bpv = (int)L.o_bpv;
   A.block_bytes = L.total; A.kp_cap = ctx->kp_cap; A.n_cams = n_cams;
-  A.fu = slot.as<double>();
-  A.pairs = reinterpret_cast<const int32_t*>(slot.as<uint8_t>() + (size_t)n_cams * sizeof(double));
   A.landmark0 = landmark0_dev; A.landmark1 = landmark1_dev; A.added = added_dev; A.n_landmarks = n_landmarks;
   A.rot_hyp = rot_hyp_dev; A.rot_valid = rot_valid_dev; A.rel_hyp = rel_hyp_dev; A.rel_valid = rel_valid_dev;
   A.n_hyp = n_hyp; A.threshold = threshold; A.remove_outliers = remove_outliers ? 1 : 0;
   A.out = *result;
-  {
-    StageTimer t(ctx, OKVFE_STAGE_MAP, s);
+  return ring_launch(ctx, s, prm, OKVFE_STAGE_MAP, [&](const uint8_t* prm_dev) {  // one asynchronous copy, no host sync
+    A.fu = reinterpret_cast<const double*>(prm_dev);
+    A.pairs = reinterpret_cast<const int32_t*>(prm_dev + (size_t)n_cams * sizeof(double));
     launch_ransac2d2d_consensus(A, n_pairs, s);
-  }
-  HIP_TRY(ctx, hipGetLastError());
-  const okvfe_status rel = slot.release();
-  ctx->last_stream = s;
-  return rel;
+  });
 }
 
 // Test hook, deliberately not in include/okvfe.h: the number of correspondences the 2d2d consensus kernel scores at a

@@ -30,18 +30,12 @@ okvfe_status okvfe_stereo_insert_blocks_device(
     A.pair_c1[p] = (int8_t)c1;
   }
   bool rt8 = false;
-  for (int c = 0; c < n_cams; ++c) {
-    const DeviceCamera* dc = slot_camera(ctx, cam_ids[c]);
-    if (!dc)
-      return fail(ctx, OKVFE_ERR_NOT_READY, "%s: camera %d: camera slot %d has no intrinsics (okvfe_set_camera)", kName, c,
-                  cam_ids[c]);
-    rt8 = rt8 || dc->distortion == OKVFE_DIST_RADTAN8;
-  }
+  okvfe_status st = rig_slots(ctx, RigWho{kName, "camera"}, n_cams, cam_ids, &rt8, [](int, const DeviceCamera&) {});
+  if (st != OKVFE_OK) return st;
   if ((int64_t)T->n_landmarks + (int64_t)n_pairs * K > (int64_t)INT32_MAX)
     return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "%s: %d table rows + %d x %d created ids do not fit an int32", kName,
                 T->n_landmarks, n_pairs, K);
-  okvfe_status st = check_block_strides(ctx, kName, block_stride_m, block_stride_c, n_multiframes, n_cams);
-  if (st != OKVFE_OK) return st;
+  if ((st = check_block_strides(ctx, kName, block_stride_m, block_stride_c, n_multiframes, n_cams)) != OKVFE_OK) return st;
   int ov_log2 = 0, kh_log2 = 0;
   const size_t lds = stereo_insert_lds_bytes(n_cams, K, &ov_log2, &kh_log2);
   if (lds > kStereoInsertMaxLds)
@@ -58,15 +52,10 @@ okvfe_status okvfe_stereo_insert_blocks_device(
   std::vector<uint8_t> block(slots_bytes + poses_bytes, 0);
   std::memcpy(block.data(), cam_ids, (size_t)n_cams * sizeof(int32_t));
   std::memcpy(block.data() + slots_bytes, T_WC, poses_bytes);
-  RingSlot params(ctx, &ctx->pair_ring, s);
-  st = params.upload(block.data(), block.size());
-  if (st != OKVFE_OK) return st;
   A.hp_W = T->hp_W;
   A.initialised = initialised_dev;
   A.blocks = static_cast<const uint8_t*>(blocks_dev);
   A.cameras = ctx->d_cams;
-  A.cam_slots = params.as<int32_t>();
-  A.poses = reinterpret_cast<const okvfe_pose*>(params.as<uint8_t>() + slots_bytes);
   A.matches = matches_dev;
   A.landmark = landmark_dev;
   A.as_keyframe = as_keyframe_dev;
@@ -88,14 +77,11 @@ okvfe_status okvfe_stereo_insert_blocks_device(
   A.stride_c = block_stride_c;
   A.ov_log2 = ov_log2;
   A.kh_log2 = kh_log2;
-  {
-    StageTimer t(ctx, OKVFE_STAGE_MATCH, s);
+  return ring_launch(ctx, s, block, OKVFE_STAGE_MATCH, [&](const uint8_t* params) {
+    A.cam_slots = reinterpret_cast<const int32_t*>(params);
+    A.poses = reinterpret_cast<const okvfe_pose*>(params + slots_bytes);
     launch_stereo_insert(A, lds, s, rt8);
-  }
-  HIP_TRY(ctx, hipGetLastError());
-  const okvfe_status rel = params.release();
-  ctx->last_stream = s;
-  return rel;
+  });
 }
 
 }  // extern "C"

@@ -1,7 +1,15 @@
 // okvfe_ctx.h -- the context behind the C ABI and the runtime helpers its entry points share
 // (capi_context.cpp: creation, cameras, pattern, profiling; capi_detect.cpp: detector / extractor
 // pipeline; capi_match.cpp: stereo / motion / Hamming matchers and gather blocks; capi_map.cpp: map
-// matchers and place recognition).  Internal to libokvfe.so.
+// matchers and the host seam of place recognition; capi_ransac.cpp: consensus, hypotheses and outlier removal
+// between the two matcher passes; capi_ransac2d2d.cpp: the consensus of runRansac2d2d; capi_stereo.cpp: matchStereo's
+// landmark bookkeeping; capi_place.cpp: verifyRecognisedPlace, its Hessian and refinement; capi_bow.cpp: vocabulary,
+// BoW vectors and the place database; capi_keyframe.cpp: coverage masks and the keyframe decision; capi_overlap.cpp:
+// overlapFraction / trackingQuality; capi_imu.cpp: IMU propagation).  Internal to libokvfe.so.
+//
+// A new entry point writes none of the plumbing itself: a call on the caller's host arrays lays them out with
+// ScratchLayout and moves them with ScratchCall; a call on device batches checks its camera slots with rig_slots and
+// ends in ring_launch or finish_call.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -14,6 +22,7 @@
 #include <vector>
 
 #include "okvfe_internal.h"
+#include "scratch_layout.h"
 
 using namespace okvfe;  // internal header of the runtime's own translation units
 
@@ -246,6 +255,60 @@ okvfe_status dev_alloc(okvfe_ctx* ctx, T** p, size_t count) {
 
 okvfe_status ensure_scratch(okvfe_ctx* ctx, size_t bytes);
 okvfe_status ensure_pinned(okvfe_ctx* ctx, size_t bytes);
+#pragma GCC visibility push(hidden)  // (the shared plumbing adds nothing to the library's dynamic symbols)
+// One call on the caller's host arrays: the regions of a ScratchLayout in ctx->scratch, the copies in and out on stream
+// s.  The pinned variant keeps the same layout in ctx->h_pinned: the inputs are staged there, ONE move brings [0, o_out)
+// to the device and the result is read from the pinned block (okvfe_match_stereo says why).
+class ScratchCall {
+ public:
+  ScratchCall(okvfe_ctx* ctx, hipStream_t s) : ctx_(ctx), s_(s) {}
+  okvfe_status reserve(const ScratchLayout& L, bool pinned = false) {
+    okvfe_status st = ensure_scratch(ctx_, L.total());
+    if (st == OKVFE_OK && pinned) st = ensure_pinned(ctx_, L.total());
+    base_ = static_cast<uint8_t*>(ctx_->scratch);
+    return st;
+  }
+  template <typename T = uint8_t>
+  T* dev(size_t o) const { return reinterpret_cast<T*>(base_ + o); }
+  hipError_t up(size_t o, const void* src, size_t bytes) const {  // an empty array is no copy
+    return bytes ? hipMemcpyAsync(base_ + o, src, bytes, hipMemcpyHostToDevice, s_) : hipSuccess;
+  }
+  hipError_t down(void* dst, size_t o, size_t bytes) const {
+    return bytes ? hipMemcpyAsync(dst, base_ + o, bytes, hipMemcpyDeviceToHost, s_) : hipSuccess;
+  }
+  hipError_t sync() const { return hipStreamSynchronize(s_); }
+  // ---- the pinned variant
+  template <typename T = uint8_t>
+  T* host(size_t o) const { return reinterpret_cast<T*>(ctx_->h_pinned + o); }
+  void put(size_t o, const void* src, size_t bytes) const {
+    if (bytes) std::memcpy(ctx_->h_pinned + o, src, bytes);
+  }
+  // every input at once: a kernel that reads the pinned block in place, or one copy where the block has no device address
+  hipError_t move_in(size_t o_out) const {
+    if (!ctx_->h_pinned_dev) return hipMemcpyAsync(base_, ctx_->h_pinned, o_out, hipMemcpyHostToDevice, s_);
+    launch_param_copy(base_, ctx_->h_pinned_dev, o_out, nullptr, 0, s_);
+    return hipSuccess;
+  }
+  // where the kernel writes its result: straight into the pinned block if the device sees it
+  template <typename T>
+  T* result(size_t o_out) const {
+    return ctx_->h_pinned_dev ? reinterpret_cast<T*>(static_cast<uint8_t*>(ctx_->h_pinned_dev) + o_out) : dev<T>(o_out);
+  }
+  // the call's one synchronisation, and the result from the pinned block
+  hipError_t fetch(void* dst, size_t o_out, size_t bytes) const {
+    hipError_t e = hipSuccess;
+    if (!ctx_->h_pinned_dev) e = hipMemcpyAsync(ctx_->h_pinned + o_out, base_ + o_out, bytes, hipMemcpyDeviceToHost, s_);
+    if (e == hipSuccess) e = hipStreamSynchronize(s_);
+    if (e == hipSuccess) std::memcpy(dst, ctx_->h_pinned + o_out, bytes);
+    return e;
+  }
+
+ private:
+  okvfe_ctx* ctx_;
+  hipStream_t s_;
+  uint8_t* base_ = nullptr;
+};
+#pragma GCC visibility pop
 okvfe_status ring_reserve(okvfe_ctx* ctx, okvfe_ctx::ParamRing* r, size_t slot_bytes);
 okvfe_status ring_upload(okvfe_ctx* ctx, okvfe_ctx::ParamRing* r, const void* src, size_t bytes, hipStream_t s,
                          void** d_out, int* slot_out, int32_t* zero_dev = nullptr, int n_zero = 0,
@@ -344,6 +407,52 @@ struct StageTimer {
     if (idx >= 0) (void)hipEventRecord(ctx->prof_events[idx].b, s);
   }
 };
+
+#pragma GCC visibility push(hidden)
+// Who asks for a camera slot: the entry point's name (or none), what it calls the things that name a slot ("frame",
+// "camera", "pair", or nothing) and the status of a slot without intrinsics.  They differ between the entry points for
+// no recorded reason; each keeps its own until someone decides.
+struct RigWho {
+  const char* fn;
+  const char* noun;
+  okvfe_status bad = OKVFE_ERR_NOT_READY;
+};
+// the intrinsics of slot `cam`, named by the call's `index`-th frame / camera / pair; null if it has none: the message is
+// set and the call returns who.bad
+const DeviceCamera* rig_slot(okvfe_ctx* ctx, const RigWho& who, int index, int cam);
+// The camera slots of a call, checked in order before anything is queued: fill(index, camera) builds the caller's record
+// of each, *rt8 (if asked for) says whether one of them holds the 8-coefficient model.
+template <typename Fill>
+okvfe_status rig_slots(okvfe_ctx* ctx, const RigWho& who, int n, const int32_t* cam_ids, bool* rt8, Fill&& fill) {
+  for (int c = 0; c < n; ++c) {
+    const DeviceCamera* dc = rig_slot(ctx, who, c, cam_ids[c]);
+    if (!dc) return who.bad;
+    if (rt8) *rt8 = *rt8 || dc->distortion == OKVFE_DIST_RADTAN8;
+    fill(c, *dc);
+  }
+  return OKVFE_OK;
+}
+// the end of a device-batch call whose launches read `slot`: the slot is released behind them
+inline okvfe_status finish_call(okvfe_ctx* ctx, RingSlot* slot, hipStream_t s) {
+  HIP_TRY(ctx, hipGetLastError());
+  const okvfe_status rel = slot->release();
+  ctx->last_stream = s;
+  return rel;
+}
+// ... and the whole tail of one that uploads once and launches: the records through the pinned parameter ring (one
+// asynchronous copy, no host synchronisation), launch(device records) under the stage's timer, finish_call
+template <typename Rec, typename Launch>
+okvfe_status ring_launch(okvfe_ctx* ctx, hipStream_t s, const std::vector<Rec>& recs, int stage, Launch&& launch) {
+  RingSlot slot(ctx, &ctx->pair_ring, s);
+  const okvfe_status st = slot.upload(recs.data(), recs.size() * sizeof(Rec));
+  if (st != OKVFE_OK) return st;
+  {
+    StageTimer t(ctx, stage, s);
+    launch(slot.as<Rec>());
+  }
+  return finish_call(ctx, &slot, s);
+}
+#pragma GCC visibility pop
 
 // okvfe_match_to_map_table_blocks_device: frames per slice when a frame needs `per_frame` bytes of workspace and a call
 // may hold `limit`: all of them if they fit, never fewer than one, never more than a launch's grid.y
