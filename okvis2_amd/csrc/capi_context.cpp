@@ -352,6 +352,15 @@ BlockLayout block_layout(int kp_cap) {
   L.total = align_up(L.o_bpv + (size_t)kp_cap, 256);
   return L;
 }
+
+// the host side of okvfe_set_fp64_reduction (okvfe_internal.h): the launchers of the kTree kernels read it
+static std::atomic<int> g_fp64_ltr[kMaxAttrDevices];  // per device ordinal: 1 = left to right (0: Eigen's order, the default)
+int current_device_slot() {
+  int dev = 0;
+  return hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < kMaxAttrDevices ? dev : 0;
+}
+bool fp64_left_to_right() { return g_fp64_ltr[current_device_slot()].load() != 0; }
+void set_fp64_left_to_right(bool ltr) { g_fp64_ltr[current_device_slot()].store(ltr ? 1 : 0); }
 }  // namespace okvfe
 
 extern "C" {
@@ -393,10 +402,9 @@ okvfe_status okvfe_set_fp64_reduction(okvfe_ctx* ctx, int32_t order) {
     return fail(ctx, OKVFE_ERR_INVALID_ARGUMENT, "okvfe_set_fp64_reduction: order %d", order);
   if (hipSetDevice(ctx->cfg.device) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
     return fail(ctx, OKVFE_ERR_DEVICE, "okvfe_set_fp64_reduction: device %d", ctx->cfg.device);
-  if (!okvfe::set_fp64_tree_match(order) || !okvfe::set_fp64_tree_map(order) || !okvfe::set_fp64_tree_ransac(order) ||
-      !okvfe::set_fp64_tree_ransac2d2d(order) || !okvfe::set_fp64_tree_place_hessian(order) ||
-      !okvfe::set_fp64_tree_place_refine(order) || !okvfe::set_fp64_tree_imu(order))
+  if (!okvfe::set_fp64_tree_match(order) || !okvfe::set_fp64_tree_map(order))
     return fail(ctx, OKVFE_ERR_DEVICE, "okvfe_set_fp64_reduction: writing the device flag failed");
+  okvfe::set_fp64_left_to_right(order == OKVFE_SUM3_LEFT_TO_RIGHT);  // (after the symbols: a failed write leaves it as it was)
   return OKVFE_OK;
 }
 

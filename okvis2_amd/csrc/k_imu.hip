@@ -17,12 +17,6 @@
 namespace okvfe {
 namespace {
 
-std::atomic<int> g_fp64_ltr_imu[kMaxAttrDevices];  // host, per device ordinal: 1 = left to right (0: Eigen's order, the default)
-int current_device_slot() {
-  int dev = 0;
-  return hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < kMaxAttrDevices ? dev : 0;
-}
-
 constexpr int kImuThreads = 64;  // one wave per work-group in every form
 
 __device__ __forceinline__ ImuParams load_params(const double* rig) {
@@ -103,7 +97,7 @@ __global__ __launch_bounds__(kImuThreads) void imu_cov_kernel(ImuArgs A) {
 
 void launch_imu_propagation(const ImuArgs& args, hipStream_t stream) {
   if (args.n_multiframes <= 0) return;
-  const bool ltr = g_fp64_ltr_imu[current_device_slot()].load() != 0;
+  const bool ltr = fp64_left_to_right();
   const unsigned lane_blocks = (unsigned)((args.n_multiframes + kImuThreads - 1) / kImuThreads);
   if (args.out.covariance) {
     auto* kernel = ltr ? imu_cov_kernel<false> : imu_cov_kernel<true>;
@@ -115,11 +109,6 @@ void launch_imu_propagation(const ImuArgs& args, hipStream_t stream) {
     auto* kernel = ltr ? imu_lane_kernel<false, false> : imu_lane_kernel<true, false>;
     hipLaunchKernelGGL(kernel, dim3(lane_blocks), dim3(kImuThreads), 0, stream, args);
   }
-}
-
-bool set_fp64_tree_imu(int tree) {
-  g_fp64_ltr_imu[current_device_slot()].store(tree ? 0 : 1);  // (the caller has set and drained the device)
-  return true;
 }
 
 }  // namespace okvfe

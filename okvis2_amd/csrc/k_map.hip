@@ -18,24 +18,22 @@
 //                              multiframe, on this file's projection chain.
 // FP64, 3-term sums in the order of okvfe_set_fp64_reduction, no FMA; acos / cos through atan_fixed.h resp. host-computed constants.
 #include "camera_dev.h"
+#include "fp64_ops.h"
 #include "okvfe_internal.h"
 
 namespace okvfe {
 namespace {
 
-// order of the 3-term sums: as in k_match.hip (okvfe_set_fp64_reduction), this translation unit's copy of the flag
+// order of the 3-term sums: as in k_match.hip (okvfe_set_fp64_reduction), this translation unit's device symbol
 __device__ int g_fp64_tree_map = 1;
-__device__ __forceinline__ double sum3m(double p0, double p1, double p2) {
-  const bool tree = g_fp64_tree_map != 0;
-  const double u = tree ? p1 : p0, v = tree ? p2 : p1, w = tree ? p0 : p2;
-  const double s = u + v;
-  return tree ? w + s : s + w;
+__device__ __forceinline__ double sum3(double p0, double p1, double p2) {
+  return fp64::sum3_select(g_fp64_tree_map != 0, p0, p1, p2);
 }
 __device__ __forceinline__ double dot3m(const double a[3], const double b[3]) {
   const double p0 = a[0] * b[0];
   const double p1 = a[1] * b[1];
   const double p2 = a[2] * b[2];
-  return sum3m(p0, p1, p2);
+  return sum3(p0, p1, p2);
 }
 __device__ __forceinline__ void normalize3m(const double v[3], double out[3]) {
   const double n = sqrt(dot3m(v, v));
@@ -49,8 +47,8 @@ __device__ __forceinline__ void normalize3m(const double v[3], double out[3]) {
 __device__ __forceinline__ void pose_inverse_times(const okvfe_pose& T1, const double hp[4], double hp_C[4]) {
   double cr[3], hh[3];
   for (int i = 0; i < 3; ++i) {
-    cr[i] = sum3m(T1.C[i] * T1.r[0], T1.C[3 + i] * T1.r[1], T1.C[6 + i] * T1.r[2]);
-    hh[i] = sum3m(T1.C[i] * hp[0], T1.C[3 + i] * hp[1], T1.C[6 + i] * hp[2]);
+    cr[i] = sum3(T1.C[i] * T1.r[0], T1.C[3 + i] * T1.r[1], T1.C[6 + i] * T1.r[2]);
+    hh[i] = sum3(T1.C[i] * hp[0], T1.C[3 + i] * hp[1], T1.C[6 + i] * hp[2]);
   }
   for (int i = 0; i < 3; ++i) hp_C[i] = hh[i] + (-cr[i]) * hp[3];
   hp_C[3] = hp[3];

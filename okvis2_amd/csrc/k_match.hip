@@ -29,18 +29,17 @@
 
 #include "okvfe_internal.h"
 #include "bow_dev.h"
+#include "fp64_ops.h"
 
 namespace okvfe {
 namespace {
 
 // Order of every 3-term FP64 sum (okvfe_set_fp64_reduction; oracle/orc_match.c states the reasoning):
 // 1 = Eigen's unrolled non-vectorised redux x0 + (x1 + x2) (default), 0 = left to right.
+// This translation unit's device symbol (the library is built without relocatable device code); k_map.hip has the other.
 __device__ int g_fp64_tree = 1;
 __device__ __forceinline__ double sum3(double p0, double p1, double p2) {
-  const bool tree = g_fp64_tree != 0;  // scalar load, uniform branch-free select
-  const double u = tree ? p1 : p0, v = tree ? p2 : p1, w = tree ? p0 : p2;
-  const double s = u + v;
-  return tree ? w + s : s + w;  // (addition commutes bit-exactly: one add either way)
+  return fp64::sum3_select(g_fp64_tree != 0, p0, p1, p2);
 }
 __device__ __forceinline__ double dot3(const double a[3], const double b[3]) {
   const double p0 = a[0] * b[0];

@@ -13,17 +13,11 @@
 // operand spreads as it does in Eigen.
 // PARITY UNPINNED: Eigen's Quaternion::normalize() and toRotationMatrix() (Eigen is not in the tree), restated from the
 // published source (Eigen/src/Geometry/Quaternion.h, Eigen/src/Core/Dot.h).
-// The term itself (sum3h, sum4h, quaternion_rotation, inverse_transform, hessian_term) is place_term_dev.h.
+// The term itself (quaternion_rotation, inverse_transform, hessian_term) is place_term_dev.h, its sums fp64_ops.h.
 #include "place_term_dev.h"
 
 namespace okvfe {
 namespace {
-
-std::atomic<int> g_fp64_ltr_hessian[kMaxAttrDevices];  // host, per device ordinal: 1 = left to right (0: Eigen's order, the default)
-int current_device_slot() {
-  int dev = 0;
-  return hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < kMaxAttrDevices ? dev : 0;
-}
 
 constexpr int kHessThreads = 256;
 constexpr int kHessChunk = kHessThreads;   // terms evaluated at a time: one per lane
@@ -140,17 +134,12 @@ __global__ __launch_bounds__(kHessThreads) void place_hessian_kernel(PlaceHessia
 
 void launch_place_hessian(const PlaceHessianArgs& args, int n_multiframes, bool rt8, hipStream_t stream) {
   if (n_multiframes <= 0) return;
-  const bool ltr = g_fp64_ltr_hessian[current_device_slot()].load() != 0;
+  const bool ltr = fp64_left_to_right();
   auto* kernel = rt8 ? (ltr ? place_hessian_kernel<false, true> : place_hessian_kernel<true, true>)
                      : (ltr ? place_hessian_kernel<false, false> : place_hessian_kernel<true, false>);
   hipLaunchKernelGGL(kernel, dim3(n_multiframes), dim3(kHessThreads), 0, stream, args);
 }
 
 int place_hessian_chunk_terms() { return kHessChunk; }
-
-bool set_fp64_tree_place_hessian(int tree) {
-  g_fp64_ltr_hessian[current_device_slot()].store(tree ? 0 : 1);  // (the caller has set and drained the device)
-  return true;
-}
 
 }  // namespace okvfe

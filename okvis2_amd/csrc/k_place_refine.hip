@@ -22,12 +22,6 @@
 namespace okvfe {
 namespace {
 
-std::atomic<int> g_fp64_ltr_refine[kMaxAttrDevices];  // host, per device ordinal: 1 = left to right (0: Eigen's order, the default)
-int current_device_slot() {
-  int dev = 0;
-  return hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < kMaxAttrDevices ? dev : 0;
-}
-
 constexpr int kLaneThreads = 64;           // the per-multiframe kernels: one wave per work-group
 constexpr int kEvalThreads = 256;
 constexpr int kEvalChunk = kEvalThreads;   // terms evaluated at a time: one per lane
@@ -226,7 +220,6 @@ __global__ __launch_bounds__(kLaneThreads) void place_refine_step_kernel(PlaceRe
   }
 }
 
-bool ltr() { return g_fp64_ltr_refine[current_device_slot()].load() != 0; }
 dim3 lane_grid(int n) { return dim3((unsigned)((n + kLaneThreads - 1) / kLaneThreads)); }
 
 }  // namespace
@@ -238,21 +231,16 @@ void launch_place_refine_start(const PlaceRefineArgs& args, hipStream_t stream) 
 
 void launch_place_refine_eval(const PlaceRefineArgs& args, bool rt8, hipStream_t stream) {
   if (args.n_multiframes <= 0) return;
-  const bool l = ltr();
-  auto* kernel = rt8 ? (l ? place_refine_eval_kernel<false, true> : place_refine_eval_kernel<true, true>)
-                     : (l ? place_refine_eval_kernel<false, false> : place_refine_eval_kernel<true, false>);
+  const bool ltr = fp64_left_to_right();
+  auto* kernel = rt8 ? (ltr ? place_refine_eval_kernel<false, true> : place_refine_eval_kernel<true, true>)
+                     : (ltr ? place_refine_eval_kernel<false, false> : place_refine_eval_kernel<true, false>);
   hipLaunchKernelGGL(kernel, dim3(args.n_multiframes), dim3(kEvalThreads), 0, stream, args);
 }
 
 void launch_place_refine_step(const PlaceRefineArgs& args, bool first, hipStream_t stream) {
   if (args.n_multiframes <= 0) return;
-  auto* kernel = ltr() ? place_refine_step_kernel<false> : place_refine_step_kernel<true>;
+  auto* kernel = fp64_left_to_right() ? place_refine_step_kernel<false> : place_refine_step_kernel<true>;
   hipLaunchKernelGGL(kernel, lane_grid(args.n_multiframes), dim3(kLaneThreads), 0, stream, args, first ? 1 : 0);
-}
-
-bool set_fp64_tree_place_refine(int tree) {
-  g_fp64_ltr_refine[current_device_slot()].store(tree ? 0 : 1);  // (the caller has set and drained the device)
-  return true;
 }
 
 }  // namespace okvfe

@@ -11,33 +11,15 @@
 //                             keeps one record (and its camera's extrinsics) in registers and walks the inverted
 //                             hypotheses, which sit in LDS; a wave's inliers of a hypothesis are a ballot + popcount.
 //                             A final sweep over the keypoints with the winner writes state / distance / landmark_out.
-// FP64, 3- and 4-term sums in the order of okvfe_set_fp64_reduction (a template argument: the host launches the kernel
-// compiled for the order in force), no FMA.
-// The sums, the inverse of a hypothesis and the distance also compile for the host: the choice among the solutions of a
+// FP64, 3- and 4-term sums (fp64_ops.h) in the order of okvfe_set_fp64_reduction (a template argument: the host launches
+// the kernel compiled for the order in force, fp64_left_to_right(); no selects in the scoring loop), no FMA.
+// The inverse of a hypothesis and the distance also compile for the host: the choice among the solutions of a
 // P3P sample (k_ransac_hyp.hip, included at the end of this file so that it uses these copies) runs there as well.
+#include "fp64_ops.h"
 #include "okvfe_internal.h"
 
 namespace okvfe {
 namespace {
-
-// order of the sums: as in k_map.hip / k_match.hip (okvfe_set_fp64_reduction), this translation unit's copy of the flag;
-// the host reads its own copy and launches the kernel compiled for that order (no selects in the scoring loop)
-std::atomic<int> g_fp64_ltr_ransac[kMaxAttrDevices];  // host, per device ordinal: 1 = left to right (0: Eigen's order, the default)
-int current_device_slot() {
-  int dev = 0;
-  return hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < kMaxAttrDevices ? dev : 0;
-}
-template <bool kTree>
-__host__ __device__ __forceinline__ double sum3m(double p0, double p1, double p2) {
-  if constexpr (kTree) return p0 + (p1 + p2);
-  return (p0 + p1) + p2;
-}
-// four terms: Eigen's redux_novec_unroller splits at Length / 2, (x0 + x1) + (x2 + x3); left to right ((x0 + x1) + x2) + x3
-template <bool kTree>
-__host__ __device__ __forceinline__ double sum4m(double p0, double p1, double p2, double p3) {
-  if constexpr (kTree) return (p0 + p1) + (p2 + p3);
-  return ((p0 + p1) + p2) + p3;
-}
 
 constexpr int kRansacThreads = 256;
 constexpr int kRansacChunk = kRansacThreads;    // records scored at a time: one per lane
@@ -107,7 +89,7 @@ __device__ __forceinline__ bool make_correspondence(const RansacArgs& A, const u
   const double fu = A.cams[c].fu;
   const double sqrt2 = __longlong_as_double(0x3FF6A09E667F3BCDLL);
   R.sigma = ((sqrt2 * s) * s) / (fu * fu);                       // :135
-  const double z = sum3m<kTree>(v[0] * v[0], v[1] * v[1], v[2] * v[2]);  // :137, Eigen's normalize()
+  const double z = fp64::sum3<kTree>(v[0] * v[0], v[1] * v[1], v[2] * v[2]);  // :137, Eigen's normalize()
   if (z > 0) {
     const double n = sqrt(z);
     v[0] = v[0] / n; v[1] = v[1] / n; v[2] = v[2] / n;
@@ -124,7 +106,7 @@ __host__ __device__ __forceinline__ void invert_hypothesis(const double* H /* 3 
   for (int i = 0; i < 3; ++i)
     for (int j = 0; j < 3; ++j) inv[3 * i + j] = H[4 * j + i];
   for (int i = 0; i < 3; ++i)
-    inv[9 + i] = sum3m<kTree>((-inv[3 * i]) * H[3], (-inv[3 * i + 1]) * H[7], (-inv[3 * i + 2]) * H[11]);
+    inv[9 + i] = fp64::sum3<kTree>((-inv[3 * i]) * H[3], (-inv[3 * i + 1]) * H[7], (-inv[3 * i + 2]) * H[11]);
 }
 
 // FrameAbsolutePoseSacProblem.hpp:151-165.  The ONE copy of the distance: the scoring loop and the final sweep call it.
@@ -133,13 +115,13 @@ __host__ __device__ __forceinline__ double ransac_distance(const double* inv, co
                                                            const double r_SC[3], const double b[3], double sigma) {
   double d[3], rep[3], e[3];
   for (int i = 0; i < 3; ++i) {
-    const double body = sum4m<kTree>(inv[3 * i] * p[0], inv[3 * i + 1] * p[1], inv[3 * i + 2] * p[2], inv[9 + i] * 1.0);
+    const double body = fp64::sum4<kTree>(inv[3 * i] * p[0], inv[3 * i + 1] * p[1], inv[3 * i + 2] * p[2], inv[9 + i] * 1.0);
     d[i] = body - r_SC[i];
   }
-  for (int i = 0; i < 3; ++i) rep[i] = sum3m<kTree>(C_SC[i] * d[0], C_SC[3 + i] * d[1], C_SC[6 + i] * d[2]);
-  const double n = sqrt(sum3m<kTree>(rep[0] * rep[0], rep[1] * rep[1], rep[2] * rep[2]));
+  for (int i = 0; i < 3; ++i) rep[i] = fp64::sum3<kTree>(C_SC[i] * d[0], C_SC[3 + i] * d[1], C_SC[6 + i] * d[2]);
+  const double n = sqrt(fp64::sum3<kTree>(rep[0] * rep[0], rep[1] * rep[1], rep[2] * rep[2]));
   for (int i = 0; i < 3; ++i) e[i] = rep[i] / n - b[i];
-  return sum3m<kTree>(e[0] * e[0], e[1] * e[1], e[2] * e[2]) / sigma;
+  return fp64::sum3<kTree>(e[0] * e[0], e[1] * e[1], e[2] * e[2]) / sigma;
 }
 
 template <bool kTree, bool kPlace>
@@ -296,7 +278,7 @@ void launch_ransac_consensus(const double* hp_W, const int32_t* obs_begin, int n
   if (n_multiframes <= 0) return;
   const RansacArgs A = ransac_args(hp_W, obs_begin, n_landmarks, L, blocks, n_cams, kp_cap, cams, landmark, hypotheses,
                                    hyp_valid, n_hyp, threshold, remove_outliers, out);
-  const bool ltr = g_fp64_ltr_ransac[current_device_slot()].load() != 0;
+  const bool ltr = fp64_left_to_right();
   auto* kernel = ltr ? ransac_consensus_kernel<false, false> : ransac_consensus_kernel<true, false>;
   hipLaunchKernelGGL(kernel, dim3(n_multiframes), dim3(kRansacThreads), 0, stream, A);
 }
@@ -310,18 +292,13 @@ void launch_place_consensus(const double* hp, int n_landmarks, const BlockLayout
   RansacArgs A = ransac_args(hp, nullptr, n_landmarks, L, blocks, n_cams, kp_cap, cams, match_landmark, hypotheses,
                              hyp_valid, n_hyp, threshold, 1, out);
   A.gate = gate; A.verdict = verdict; A.min_inliers = min_inliers;
-  const bool ltr = g_fp64_ltr_ransac[current_device_slot()].load() != 0;
+  const bool ltr = fp64_left_to_right();
   auto* kernel = ltr ? ransac_consensus_kernel<false, true> : ransac_consensus_kernel<true, true>;
   hipLaunchKernelGGL(kernel, dim3(n_multiframes), dim3(kRansacThreads), 0, stream, A);
 }
 
 int ransac_chunk_records() { return kRansacChunk; }
 int ransac_ring_records() { return kRansacRing; }
-
-bool set_fp64_tree_ransac(int tree) {
-  g_fp64_ltr_ransac[current_device_slot()].store(tree ? 0 : 1);  // (the caller has set and drained the device)
-  return true;
-}
 
 }  // namespace okvfe
 

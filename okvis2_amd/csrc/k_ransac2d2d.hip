@@ -15,32 +15,17 @@
 //                                 decision; a final sweep over the older keypoints with the taken winner writes
 //                                 match1 / state / distance and marks the current keypoints to remove.
 // opengv::triangulation::triangulate2 and Eigen's 2 x 2 inverse are restated from their published sources (the header
-// marks the call PARITY UNPINNED for them).  FP64, 3- and 4-term sums in the order of okvfe_set_fp64_reduction (a
-// template argument: the host launches the kernel compiled for the order in force), no FMA.
+// marks the call PARITY UNPINNED for them).  FP64, 3- and 4-term sums (fp64_ops.h) in the order of
+// okvfe_set_fp64_reduction (a template argument: the host launches the kernel compiled for the order in force), no FMA.
+#include "fp64_ops.h"
 #include "okvfe_internal.h"
 
 namespace okvfe {
 namespace {
 
-// order of the sums: this translation unit's copy of the flag (as k_ransac.hip keeps its own)
-std::atomic<int> g_fp64_ltr_ransac2d2d[kMaxAttrDevices];  // host, per device ordinal: 1 = left to right (0: Eigen's order)
-int current_device_slot() {
-  int dev = 0;
-  return hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < kMaxAttrDevices ? dev : 0;
-}
 template <bool kTree>
-__device__ __forceinline__ double sum3r(double p0, double p1, double p2) {
-  if constexpr (kTree) return p0 + (p1 + p2);
-  return (p0 + p1) + p2;
-}
-template <bool kTree>
-__device__ __forceinline__ double sum4r(double p0, double p1, double p2, double p3) {
-  if constexpr (kTree) return (p0 + p1) + (p2 + p3);
-  return ((p0 + p1) + p2) + p3;
-}
-template <bool kTree>
-__device__ __forceinline__ double dot3r(const double a[3], const double b[3]) {
-  return sum3r<kTree>(a[0] * b[0], a[1] * b[1], a[2] * b[2]);
+__device__ __forceinline__ double dot3(const double a[3], const double b[3]) {
+  return fp64::sum3<kTree>(a[0] * b[0], a[1] * b[1], a[2] * b[2]);
 }
 
 constexpr int kRansac2Threads = 256;
@@ -61,7 +46,7 @@ static_assert(sizeof(Corr2) == 64, "64-byte LDS records");
 // Eigen's normalize(): z = squaredNorm, divided by sqrt(z) iff z > 0
 template <bool kTree>
 __device__ __forceinline__ void normalize3(double v[3]) {
-  const double z = sum3r<kTree>(v[0] * v[0], v[1] * v[1], v[2] * v[2]);
+  const double z = fp64::sum3<kTree>(v[0] * v[0], v[1] * v[1], v[2] * v[2]);
   if (z > 0) {
     const double n = sqrt(z);
     v[0] = v[0] / n; v[1] = v[1] / n; v[2] = v[2] / n;
@@ -97,7 +82,7 @@ __device__ __forceinline__ void make_correspondence2(const Ransac2d2dArgs& A, co
 // FrameRotationOnlySacProblem.hpp:140-143 and FrameRelativePoseSacProblem.hpp:157-160
 template <bool kTree>
 __device__ __forceinline__ double score_of_errors(const double e1[3], const double e2[3], double s1, double s2) {
-  const double q1 = dot3r<kTree>(e1, e1), q2 = dot3r<kTree>(e2, e2);
+  const double q1 = dot3<kTree>(e1, e1), q2 = dot3<kTree>(e2, e2);
   return (q1 * 0.5) / s1 + (q2 * 0.5) / s2;
 }
 
@@ -106,8 +91,8 @@ template <bool kTree>
 __device__ __forceinline__ double rotation_only_distance(const double* M /* 3 x 3 row-major */, const Corr2& R) {
   double e1[3], e2[3];
   for (int i = 0; i < 3; ++i) {
-    const double f2u = sum3r<kTree>(M[3 * i] * R.b2[0], M[3 * i + 1] * R.b2[1], M[3 * i + 2] * R.b2[2]);  // :131
-    const double f1u = sum3r<kTree>(M[i] * R.b1[0], M[3 + i] * R.b1[1], M[6 + i] * R.b1[2]);              // :134
+    const double f2u = fp64::sum3<kTree>(M[3 * i] * R.b2[0], M[3 * i + 1] * R.b2[1], M[3 * i + 2] * R.b2[2]);  // :131
+    const double f1u = fp64::sum3<kTree>(M[i] * R.b1[0], M[3 + i] * R.b1[1], M[6 + i] * R.b1[2]);              // :134
     e1[i] = f2u - R.b1[i];                                                                                // :136
     e2[i] = f1u - R.b2[i];                                                                                // :137
   }
@@ -117,7 +102,7 @@ __device__ __forceinline__ double rotation_only_distance(const double* M /* 3 x 
 // FrameRelativePoseSacProblem.hpp:137: ti = (-R^T) t
 template <bool kTree>
 __device__ __forceinline__ void inverse_translation(const double* H /* 3 x 4 row-major */, double* ti) {
-  for (int i = 0; i < 3; ++i) ti[i] = sum3r<kTree>((-H[i]) * H[3], (-H[4 + i]) * H[7], (-H[8 + i]) * H[11]);
+  for (int i = 0; i < 3; ++i) ti[i] = fp64::sum3<kTree>((-H[i]) * H[3], (-H[4 + i]) * H[7], (-H[8 + i]) * H[11]);
 }
 
 // FrameRelativePoseSacProblem.hpp:130-160 with opengv's triangulate2 (and Eigen's 2 x 2 inverse) as published.  The ONE
@@ -127,18 +112,18 @@ __device__ __forceinline__ double relative_pose_distance(const double* H /* [R |
                                                          const Corr2& R) {
   const double t[3] = {H[3], H[7], H[11]};
   double f2u[3];
-  for (int i = 0; i < 3; ++i) f2u[i] = sum3r<kTree>(H[4 * i] * R.b2[0], H[4 * i + 1] * R.b2[1], H[4 * i + 2] * R.b2[2]);
-  const double c0 = dot3r<kTree>(t, R.b1), c1 = dot3r<kTree>(t, f2u);
-  const double A00 = dot3r<kTree>(R.b1, R.b1), A10 = dot3r<kTree>(R.b1, f2u);
-  const double A01 = -A10, A11 = -dot3r<kTree>(f2u, f2u);
+  for (int i = 0; i < 3; ++i) f2u[i] = fp64::sum3<kTree>(H[4 * i] * R.b2[0], H[4 * i + 1] * R.b2[1], H[4 * i + 2] * R.b2[2]);
+  const double c0 = dot3<kTree>(t, R.b1), c1 = dot3<kTree>(t, f2u);
+  const double A00 = dot3<kTree>(R.b1, R.b1), A10 = dot3<kTree>(R.b1, f2u);
+  const double A01 = -A10, A11 = -dot3<kTree>(f2u, f2u);
   const double det = A00 * A11 - A10 * A01;
   const double invdet = 1.0 / det;  // parallel bearings: det == 0, the lambdas and the distance become NaN
   const double I00 = A11 * invdet, I10 = (-A10) * invdet, I01 = (-A01) * invdet, I11 = A00 * invdet;
   const double l0 = I00 * c0 + I01 * c1, l1 = I10 * c0 + I11 * c1;
   double p[3], rep2[3], e1[3], e2[3];
   for (int i = 0; i < 3; ++i) p[i] = (l0 * R.b1[i] + (t[i] + l1 * f2u[i])) / 2.0;
-  for (int i = 0; i < 3; ++i) rep2[i] = sum4r<kTree>(H[i] * p[0], H[4 + i] * p[1], H[8 + i] * p[2], ti[i] * 1.0);  // :146
-  const double n1 = sqrt(dot3r<kTree>(p, p)), n2 = sqrt(dot3r<kTree>(rep2, rep2));                                 // :147-148
+  for (int i = 0; i < 3; ++i) rep2[i] = fp64::sum4<kTree>(H[i] * p[0], H[4 + i] * p[1], H[8 + i] * p[2], ti[i] * 1.0);  // :146
+  const double n1 = sqrt(dot3<kTree>(p, p)), n2 = sqrt(dot3<kTree>(rep2, rep2));                                 // :147-148
   for (int i = 0; i < 3; ++i) {
     e1[i] = p[i] / n1 - R.b1[i];     // :153
     e2[i] = rep2[i] / n2 - R.b2[i];  // :154
@@ -362,17 +347,12 @@ __global__ __launch_bounds__(kRansac2Threads) void ransac2d2d_consensus_kernel(R
 
 void launch_ransac2d2d_consensus(const Ransac2d2dArgs& args, int n_pairs, hipStream_t stream) {
   if (n_pairs <= 0) return;
-  const bool ltr = g_fp64_ltr_ransac2d2d[current_device_slot()].load() != 0;
+  const bool ltr = fp64_left_to_right();
   auto* kernel = ltr ? ransac2d2d_consensus_kernel<false> : ransac2d2d_consensus_kernel<true>;
   hipLaunchKernelGGL(kernel, dim3(n_pairs), dim3(kRansac2Threads), 0, stream, args);
 }
 
 int ransac2d2d_chunk_records() { return kRansac2Chunk; }
 int ransac2d2d_ring_records() { return kRansac2Ring; }
-
-bool set_fp64_tree_ransac2d2d(int tree) {
-  g_fp64_ltr_ransac2d2d[current_device_slot()].store(tree ? 0 : 1);  // (the caller has set and drained the device)
-  return true;
-}
 
 }  // namespace okvfe

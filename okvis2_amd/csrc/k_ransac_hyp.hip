@@ -11,7 +11,7 @@
 //              correspondences from the list, runs the solver and stores 12 doubles and the byte.
 // Trip counts (doublings, bisection steps) depend on the data: the lanes of a wave diverge, bounded by
 // kHypMaxDoublings + kHypMaxBisections.  FP64, no FMA; the sums of the consensus' functions in the order of
-// okvfe_set_fp64_reduction (a template argument, the flag of k_ransac.hip).
+// okvfe_set_fp64_reduction (a template argument).
 #include "ransac_hyp_dev.h"
 
 namespace okvfe {
@@ -182,7 +182,8 @@ void launch_ransac_hypotheses(const double* hp_W, const int32_t* obs_begin, int 
   if (n_multiframes <= 0) return;
   const HypArgs G = hyp_args(hp_W, obs_begin, n_landmarks, L, blocks, n_cams, kp_cap, cams, landmark, nullptr, keys, seed,
                              n_hyp, out);
-  auto* kernel = g_fp64_ltr_ransac[current_device_slot()].load() != 0 ? ransac_hypotheses_kernel<false, false> : ransac_hypotheses_kernel<true, false>;
+  const bool ltr = fp64_left_to_right();
+  auto* kernel = ltr ? ransac_hypotheses_kernel<false, false> : ransac_hypotheses_kernel<true, false>;
   hipLaunchKernelGGL(kernel, dim3(n_multiframes), dim3(kHypThreads), ransac_hypotheses_lds_bytes(n_cams, kp_cap), stream, G);
 }
 
@@ -193,7 +194,8 @@ void launch_place_hypotheses(const double* hp, int n_landmarks, const BlockLayou
   if (n_multiframes <= 0) return;
   const HypArgs G = hyp_args(hp, nullptr, n_landmarks, L, blocks, n_cams, kp_cap, cams, match_landmark, gate, keys, seed,
                              n_hyp, out);
-  auto* kernel = g_fp64_ltr_ransac[current_device_slot()].load() != 0 ? ransac_hypotheses_kernel<false, true> : ransac_hypotheses_kernel<true, true>;
+  const bool ltr = fp64_left_to_right();
+  auto* kernel = ltr ? ransac_hypotheses_kernel<false, true> : ransac_hypotheses_kernel<true, true>;
   hipLaunchKernelGGL(kernel, dim3(n_multiframes), dim3(kHypThreads), ransac_hypotheses_lds_bytes(n_cams, kp_cap), stream, G);
 }
 

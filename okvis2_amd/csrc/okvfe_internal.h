@@ -287,11 +287,15 @@ __device__ __forceinline__ void xcd_tile(int tiles, int n_images, int* image, in
 // ---- kernel launchers (defined in the .hip files) ----------------------------------------------
 namespace okvfe {
 
-// 3-term FP64 sum order of the matcher / landmark kernels (one device flag per translation unit)
+// The order of the 3- and 4-term FP64 sums (fp64_ops.h, okvfe_set_fp64_reduction).  k_match.hip and k_map.hip read a
+// device symbol each (no relocatable device code: one symbol cannot serve both); false: the symbol write failed.
 bool set_fp64_tree_match(int tree);
 bool set_fp64_tree_map(int tree);
-bool set_fp64_tree_ransac(int tree);
-bool set_fp64_tree_ransac2d2d(int tree);
+// Every other kernel takes the order as a template argument, and its launcher picks the instantiation from ONE host flag
+// per device ordinal (capi_context.cpp): 0 = Eigen's order (the default), 1 = left to right.
+int current_device_slot();   // the current device's ordinal; 0 where it is unknown or beyond kMaxAttrDevices
+bool fp64_left_to_right();   // the flag of the current device
+void set_fp64_left_to_right(bool ltr);  // (the caller has set and drained the device)
 void launch_bow_query_l1(const int32_t* db_begin, const int32_t* db_ids, const double* db_values, int n_entries,
                          const int32_t* q_ids, const double* q_values, int n_q, double* scores,
                          hipStream_t stream);
@@ -660,7 +664,6 @@ struct PlaceHessianArgs {
 };
 void launch_place_hessian(const PlaceHessianArgs& args, int n_multiframes, bool rt8, hipStream_t stream);
 int place_hessian_chunk_terms();  // terms the kernel evaluates at a time
-bool set_fp64_tree_place_hessian(int tree);
 // the refinement of verifyRecognisedPlace's pose (Frontend.cpp:399-527) for a batch of multiframes (k_place_refine.hip; the
 // solver is place_refine_dev.h, the term place_term_dev.h).  term: the Hessian call's arguments (poses, H and the rows are
 // not read: an evaluation takes its pose from the multiframe's record); records and evals lie in the call's workspace.
@@ -678,7 +681,6 @@ struct PlaceRefineArgs {
 void launch_place_refine_start(const PlaceRefineArgs& args, hipStream_t stream);
 void launch_place_refine_eval(const PlaceRefineArgs& args, bool rt8, hipStream_t stream);
 void launch_place_refine_step(const PlaceRefineArgs& args, bool first, hipStream_t stream);
-bool set_fp64_tree_place_refine(int tree);
 // ImuError::propagation for a batch of multiframes (k_imu.hip; the arithmetic is imu_dev.h).  rig lies in the parameter
 // block of the call: the seven doubles of okvfe_imu_params, one unused, then seven per camera of T_SC; every other pointer
 // is the caller's.  The form follows out: covariance != null -> a wave per multiframe, else a lane per multiframe with
@@ -693,7 +695,6 @@ struct ImuArgs {
   ImuResultPtrs out;
 };
 void launch_imu_propagation(const ImuArgs& args, hipStream_t stream);
-bool set_fp64_tree_imu(int tree);
 // scale space (k_pyramid.hip)
 void launch_halfsample(const uint8_t* src, int w, int h, int n_images, uint8_t* dst, hipStream_t stream);
 void launch_twothird(const uint8_t* src, int w, int h, int n_images, uint8_t* dst, hipStream_t stream);

@@ -2,34 +2,24 @@
 // (okvis_ceres/include/okvis/ceres/implementation/ReprojectionError.hpp:99-183 with jacobians[0] only): the residual and
 // J0_minimal at a pose T_Sold_Snew.  Shared, text unchanged, by place_hessian_kernel (k_place_hessian.hip) and
 // place_refine_eval_kernel (k_place_refine.hip).  Device only.
-// FP64, 3- and 4-term sums in the order of okvfe_set_fp64_reduction (a template argument), no FMA.  The matrix products
-// are full: the zeros of T_CS, J, Jh and the square-root information are multiplied and added, so that a non-finite
-// operand spreads as it does in Eigen.
+// FP64, 3- and 4-term sums (fp64_ops.h) in the order of okvfe_set_fp64_reduction (a template argument), no FMA.  The
+// matrix products are full: the zeros of T_CS, J, Jh and the square-root information are multiplied and added, so that a
+// non-finite operand spreads as it does in Eigen.
 // PARITY UNPINNED: Eigen's Quaternion::normalize() and toRotationMatrix() (Eigen is not in the tree), restated from the
 // published source (Eigen/src/Geometry/Quaternion.h, Eigen/src/Core/Dot.h).
 #pragma once
 #include "camera_dev.h"
+#include "fp64_ops.h"
 #include "okvfe_internal.h"
 
 namespace okvfe {
-
-template <bool kTree>
-__device__ __forceinline__ double sum3h(double p0, double p1, double p2) {
-  if constexpr (kTree) return p0 + (p1 + p2);
-  return (p0 + p1) + p2;
-}
-template <bool kTree>
-__device__ __forceinline__ double sum4h(double p0, double p1, double p2, double p3) {
-  if constexpr (kTree) return (p0 + p1) + (p2 + p3);
-  return ((p0 + p1) + p2) + p3;
-}
 
 // q.normalize() and q.toRotationMatrix() of a PoseParameterBlock's (qx, qy, qz, qw) (ReprojectionError.hpp:101-103,
 // :110-112, :115, :120): Eigen divides by sqrt(z) iff z = squaredNorm() > 0, so a zero or NaN quaternion stays as it is
 template <bool kTree>
 __device__ inline void quaternion_rotation(const double* q, double R[9]) {
   double x = q[0], y = q[1], z = q[2], w = q[3];
-  const double n2 = sum4h<kTree>(x * x, y * y, z * z, w * w);
+  const double n2 = fp64::sum4<kTree>(x * x, y * y, z * z, w * w);
   if (n2 > 0) {
     const double n = sqrt(n2);
     x = x / n; y = y / n; z = z / n; w = w / n;
@@ -51,7 +41,7 @@ __device__ inline void inverse_transform(const double* pose /* t[3], qx qy qz qw
   quaternion_rotation<kTree>(pose + 3, C);
   for (int i = 0; i < 3; ++i) {
     for (int j = 0; j < 3; ++j) T[4 * i + j] = C[3 * j + i];
-    T[4 * i + 3] = sum3h<kTree>((-C[i]) * pose[0], (-C[3 + i]) * pose[1], (-C[6 + i]) * pose[2]);
+    T[4 * i + 3] = fp64::sum3<kTree>((-C[i]) * pose[0], (-C[3 + i]) * pose[1], (-C[6 + i]) * pose[2]);
   }
   T[12] = 0.0; T[13] = 0.0; T[14] = 0.0; T[15] = 1.0;
 }
@@ -66,11 +56,11 @@ __device__ __forceinline__ bool hessian_term(const DeviceCamera& cam, int w, int
   double hp_S[4], hp_C[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i)
-    hp_S[i] = sum4h<kTree>(T_SW[4 * i] * hp_W[0], T_SW[4 * i + 1] * hp_W[1], T_SW[4 * i + 2] * hp_W[2],
+    hp_S[i] = fp64::sum4<kTree>(T_SW[4 * i] * hp_W[0], T_SW[4 * i + 1] * hp_W[1], T_SW[4 * i + 2] * hp_W[2],
                            T_SW[4 * i + 3] * hp_W[3]);                                      // :125
 #pragma unroll
   for (int i = 0; i < 4; ++i)
-    hp_C[i] = sum4h<kTree>(T_CS[4 * i] * hp_S[0], T_CS[4 * i + 1] * hp_S[1], T_CS[4 * i + 2] * hp_S[2],
+    hp_C[i] = fp64::sum4<kTree>(T_CS[4 * i] * hp_S[0], T_CS[4 * i + 1] * hp_S[1], T_CS[4 * i + 2] * hp_S[2],
                            T_CS[4 * i + 3] * hp_S[3]);                                      // :126
   // projectHomogeneous (PinholeCamera.hpp:506-526): the head negated when w < 0, its Jacobian not negated back
   double head[3] = {hp_C[0], hp_C[1], hp_C[2]};
@@ -104,7 +94,7 @@ __device__ __forceinline__ bool hessian_term(const DeviceCamera& cam, int w, int
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
       Jp[i][j] = T_SW[4 * i + j] * hp_W[3];
-      Jp[i][3 + j] = sum3h<kTree>((-T_SW[4 * i]) * X[0][j], (-T_SW[4 * i + 1]) * X[1][j], (-T_SW[4 * i + 2]) * X[2][j]);
+      Jp[i][3 + j] = fp64::sum3<kTree>((-T_SW[4 * i]) * X[0][j], (-T_SW[4 * i + 1]) * X[1][j], (-T_SW[4 * i + 2]) * X[2][j]);
     }
 #pragma unroll
   for (int j = 0; j < 6; ++j) Jp[3][j] = 0.0;
@@ -114,12 +104,12 @@ __device__ __forceinline__ bool hessian_term(const DeviceCamera& cam, int w, int
   for (int i = 0; i < 2; ++i)
 #pragma unroll
     for (int j = 0; j < 4; ++j)
-      A[i][j] = sum4h<kTree>(Jw[i][0] * T_CS[j], Jw[i][1] * T_CS[4 + j], Jw[i][2] * T_CS[8 + j], Jw[i][3] * T_CS[12 + j]);
+      A[i][j] = fp64::sum4<kTree>(Jw[i][0] * T_CS[j], Jw[i][1] * T_CS[4 + j], Jw[i][2] * T_CS[8 + j], Jw[i][3] * T_CS[12 + j]);
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
     for (int j = 0; j < 6; ++j)
-      J[6 * i + j] = sum4h<kTree>(A[i][0] * Jp[0][j], A[i][1] * Jp[1][j], A[i][2] * Jp[2][j], A[i][3] * Jp[3][j]);
+      J[6 * i + j] = fp64::sum4<kTree>(A[i][0] * Jp[0][j], A[i][1] * Jp[1][j], A[i][2] * Jp[2][j], A[i][3] * Jp[3][j]);
   if (singular || bad_size) {
     r[0] = nan; r[1] = nan;
 #pragma unroll

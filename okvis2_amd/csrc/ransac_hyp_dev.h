@@ -34,13 +34,7 @@
 #pragma once
 #include <stdint.h>
 
-#if defined(__HIPCC__)
-#define OKVFE_RH_HD __host__ __device__ inline __attribute__((always_inline))
-#define OKVFE_RH_NOUNROLL _Pragma("unroll 1")
-#else
-#define OKVFE_RH_HD inline
-#define OKVFE_RH_NOUNROLL
-#endif
+#include "fp64_ops.h"
 
 namespace okvfe {
 namespace {
@@ -48,15 +42,8 @@ namespace {
 constexpr int kHypMaxDoublings = 64;    // hi = 2^64 at the most
 constexpr int kHypMaxBisections = 128;
 
-OKVFE_RH_HD bool hyp_finite(double v) {
-  unsigned long long bits;
-  __builtin_memcpy(&bits, &v, 8);
-  return (bits & 0x7FF0000000000000ull) != 0x7FF0000000000000ull;
-}
-OKVFE_RH_HD double hyp_sqrt(double v) { return __builtin_sqrt(v); }
-
 // ---- the sampler ----------------------------------------------------------------------------------------------------
-OKVFE_RH_HD uint64_t hyp_hash(uint64_t seed, uint64_t key, int h, int j) {
+OKVFE_FP64_HD uint64_t hyp_hash(uint64_t seed, uint64_t key, int h, int j) {
   uint64_t z = seed + (key * 512ull + (uint64_t)h * 8ull + (uint64_t)j + 1ull) * 0x9E3779B97F4A7C15ull;
   z ^= z >> 30;
   z *= 0xBF58476D1CE4E5B9ull;
@@ -65,7 +52,7 @@ OKVFE_RH_HD uint64_t hyp_hash(uint64_t seed, uint64_t key, int h, int j) {
   z ^= z >> 31;
   return z;
 }
-OKVFE_RH_HD int hyp_draw(uint64_t seed, uint64_t key, int h, int j, int range) {
+OKVFE_FP64_HD int hyp_draw(uint64_t seed, uint64_t key, int h, int j, int range) {
   return (int)(((hyp_hash(seed, key, h, j) >> 32) * (uint64_t)range) >> 32);
 }
 
@@ -73,7 +60,7 @@ OKVFE_RH_HD int hyp_draw(uint64_t seed, uint64_t key, int h, int j, int range) {
 // range_of(i, &b, &e): the range of the camera that owns position i.  -> positions drawn: 0 (n == 0), 1 (the camera
 // has fewer than four correspondences) or 4; the positions not drawn are -1.
 template <class RangeOf>
-OKVFE_RH_HD int hyp_sample(uint64_t seed, uint64_t key, int h, int n, const RangeOf& range_of, int pos[4]) {
+OKVFE_FP64_HD int hyp_sample(uint64_t seed, uint64_t key, int h, int n, const RangeOf& range_of, int pos[4]) {
   pos[0] = -1; pos[1] = -1; pos[2] = -1; pos[3] = -1;
   if (n <= 0) return 0;
   const int i0 = hyp_draw(seed, key, h, 0, n);
@@ -107,18 +94,18 @@ OKVFE_RH_HD int hyp_sample(uint64_t seed, uint64_t key, int h, int n, const Rang
 }
 
 // ---- the solver -----------------------------------------------------------------------------------------------------
-OKVFE_RH_HD double hyp_dot(const double* a, const double* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
-OKVFE_RH_HD void hyp_cross(const double* a, const double* b, double* c) {
+OKVFE_FP64_HD double hyp_dot(const double* a, const double* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
+OKVFE_FP64_HD void hyp_cross(const double* a, const double* b, double* c) {
   c[0] = a[1] * b[2] - a[2] * b[1];
   c[1] = a[2] * b[0] - a[0] * b[2];
   c[2] = a[0] * b[1] - a[1] * b[0];
 }
-OKVFE_RH_HD void hyp_unit(double* a) {
-  const double n = hyp_sqrt(hyp_dot(a, a));
+OKVFE_FP64_HD void hyp_unit(double* a) {
+  const double n = fp64::sqrt(hyp_dot(a, a));
   a[0] = a[0] / n; a[1] = a[1] / n; a[2] = a[2] / n;
 }
 // e1 = (X2 - X1) / |..|, e3 = e1 x (X3 - X1) normalised, e2 = e3 x e1: E[0..2] = e1, E[3..5] = e2, E[6..8] = e3
-OKVFE_RH_HD void hyp_triad(const double* X1, const double* X2, const double* X3, double* E) {
+OKVFE_FP64_HD void hyp_triad(const double* X1, const double* X2, const double* X3, double* E) {
   double d[3];
   for (int i = 0; i < 3; ++i) {
     E[i] = X2[i] - X1[i];
@@ -146,12 +133,12 @@ struct P3pState {
 
 // one root of the quartic, already polished: the test, the pose, the distance of sample 3, the choice
 template <class Dist>
-OKVFE_RH_HD void p3p_consider(const P3pProblem& Q, double v, P3pState& S, const Dist& dist) {
+OKVFE_FP64_HD void p3p_consider(const P3pProblem& Q, double v, P3pState& S, const Dist& dist) {
   const double u = ((((Q.k - 1.0) * v) * v - ((2.0 * Q.k) * Q.cb) * v) + 1.0 + Q.k) / (2.0 * (Q.cg - v * Q.ca));
   const double s1sq = Q.b2 / ((1.0 + v * v) - (2.0 * v) * Q.cb);
   if (!(v > 0.0 && u > 0.0 && s1sq > 0.0)) return;
   S.n_solutions += 1;
-  const double s1 = hyp_sqrt(s1sq), s2 = u * s1, s3 = v * s1;
+  const double s1 = fp64::sqrt(s1sq), s2 = u * s1, s3 = v * s1;
   double X[3][3], Ec[9], R[9], t[3], H[12];
   for (int i = 0; i < 3; ++i) {
     X[0][i] = s1 * Q.f[0][i];
@@ -179,7 +166,7 @@ OKVFE_RH_HD void p3p_consider(const P3pProblem& Q, double v, P3pState& S, const 
 
 // a root y of the depressed quartic: back to v, three Newton steps on the original quartic, then p3p_consider
 template <class Dist>
-OKVFE_RH_HD void p3p_root(const P3pProblem& Q, double y, double shift, P3pState& S, const Dist& dist) {
+OKVFE_FP64_HD void p3p_root(const P3pProblem& Q, double y, double shift, P3pState& S, const Dist& dist) {
   double v = y - shift;
   for (int it = 0; it < 3; ++it) {
     const double f = (((Q.A[4] * v + Q.A[3]) * v + Q.A[2]) * v + Q.A[1]) * v + Q.A[0];
@@ -195,7 +182,7 @@ OKVFE_RH_HD void p3p_root(const P3pProblem& Q, double y, double shift, P3pState&
 // consensus kernel's own invert_hypothesis + ransac_distance (k_ransac.hip); this header holds no copy of it.
 // -> H (12 doubles, zeros when invalid), *n_solutions; returns the validity.
 template <class Dist>
-OKVFE_RH_HD bool p3p_hypothesis(const double* P /* 4 x 3 */, const double* f /* 4 x 3 */, double sigma3, const double* C,
+OKVFE_FP64_HD bool p3p_hypothesis(const double* P /* 4 x 3 */, const double* f /* 4 x 3 */, double sigma3, const double* C,
                                 const double* r, double* H, int* n_solutions, const Dist& dist) {
   P3pProblem Q;
   for (int i = 0; i < 3; ++i) {
@@ -246,7 +233,7 @@ OKVFE_RH_HD bool p3p_hypothesis(const double* P /* 4 x 3 */, const double* f /* 
   }
   Q.A[0] = (1.0 + k) * (1.0 + k) - ((4.0 * ra) * cg) * cg;
   bool ok = Q.A[4] != 0.0;
-  for (int i = 0; i < 5; ++i) ok = ok && hyp_finite(Q.A[i]);
+  for (int i = 0; i < 5; ++i) ok = ok && fp64::finite(Q.A[i]);
   if (!ok) return false;
   hyp_triad(Q.P[0], Q.P[1], Q.P[2], Q.Ew);
 
@@ -261,14 +248,14 @@ OKVFE_RH_HD bool p3p_hypothesis(const double* P /* 4 x 3 */, const double* f /* 
   if (q == 0.0) {
     const double disc = p * p - 4.0 * rr;
     if (disc >= 0.0) {
-      const double sd = hyp_sqrt(disc);
+      const double sd = fp64::sqrt(disc);
       const double w1 = ((-p) + sd) / 2.0, w2 = ((-p) - sd) / 2.0;
       if (w1 >= 0.0) {
-        y0 = hyp_sqrt(w1);
+        y0 = fp64::sqrt(w1);
         y1 = -y0;
       }
       if (w2 >= 0.0) {
-        y2 = hyp_sqrt(w2);
+        y2 = fp64::sqrt(w2);
         y3 = -y2;
       }
     }
@@ -289,26 +276,26 @@ OKVFE_RH_HD bool p3p_hypothesis(const double* P /* 4 x 3 */, const double* f /* 
         if ((((8.0 * mid + g1) * mid + g2) * mid - g3) > 0.0) hi = mid; else lo = mid;
       }
       const double m = hi;
-      const double s = hyp_sqrt(2.0 * m), t0 = p / 2.0 + m, u0 = q / (2.0 * s);
+      const double s = fp64::sqrt(2.0 * m), t0 = p / 2.0 + m, u0 = q / (2.0 * s);
       const double disc1 = s * s - 4.0 * (t0 + u0), disc2 = s * s - 4.0 * (t0 - u0);
       if (disc1 >= 0.0) {
-        const double sd = hyp_sqrt(disc1);
+        const double sd = fp64::sqrt(disc1);
         y0 = (s + sd) / 2.0;
         y1 = (s - sd) / 2.0;
       }
       if (disc2 >= 0.0) {
-        const double sd = hyp_sqrt(disc2);
+        const double sd = fp64::sqrt(disc2);
         y2 = ((-s) + sd) / 2.0;
         y3 = ((-s) - sd) / 2.0;
       }
     }
   }
-  OKVFE_RH_NOUNROLL
+  OKVFE_FP64_NOUNROLL
   for (int i = 0; i < 4; ++i)  // (one copy of the pose chain in the code; selects, not an indexed array in memory)
     p3p_root(Q, i == 0 ? y0 : i == 1 ? y1 : i == 2 ? y2 : y3, shift, S, dist);
   *n_solutions = S.n_solutions;
   bool valid = S.found != 0;
-  for (int i = 0; i < 12; ++i) valid = valid && hyp_finite(S.H[i]);
+  for (int i = 0; i < 12; ++i) valid = valid && fp64::finite(S.H[i]);
   if (valid)
     for (int i = 0; i < 12; ++i) H[i] = S.H[i];
   return valid;

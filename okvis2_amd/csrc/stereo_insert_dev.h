@@ -1,6 +1,6 @@
 // stereo_insert_dev.h -- the kernel of okvfe_stereo_insert_blocks_device.  Included by k_map.hip inside its anonymous
 // namespace, so that it compiles that file's ONE copy of the projection chain (pose_inverse_times, the camera's
-// project) under that file's copy of the okvfe_set_fp64_reduction flag.  Not a header for anything else.
+// project) under that file's device symbol of the okvfe_set_fp64_reduction order.  Not a header for anything else.
 // ---- okvfe_stereo_insert_blocks_device: matchStereo's landmark bookkeeping (Frontend.cpp:2076-2141) ----
 // One work-group per multiframe walks the camera pairs in list order; the rig's landmark ids live in LDS.  Dynamic LDS,
 // int32 each (K = kp_cap):

@@ -66,7 +66,8 @@ def test_one_copy_of_the_distance_and_of_the_pose_inverse():
     assert src.count("double ransac_distance(") == 1
     assert src.count("= ransac_distance<kTree>(") == 2  # the scoring loop and the final sweep
     assert src.count("rep[i] / n - b[i]") == 1 and src.count("bool make_correspondence(") == 1
-    assert src.count("double sum4m(") == 1
+    ops = open(os.path.join(ROOT, "okvis2_amd", "csrc", "fp64_ops.h")).read()
+    assert ops.count("double sum4(") == 1 and "double sum4" not in src
     kmap = open(os.path.join(ROOT, "okvis2_amd", "csrc", "k_map.hip")).read()
     assert kmap.count("void pose_inverse_times(") == 1
     assert kmap.count("hh[i] + (-cr[i]) * hp[3]") == 1
