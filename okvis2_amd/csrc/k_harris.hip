@@ -646,7 +646,11 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) OKVFE_K1_WAVES void harris_ker
     for (int i = 0; i < 4; ++i) {
       const unsigned AB = (unsigned)(Vp[0][i] + V[0][i]);  // A | B << 16
       const int Cc = Vp[1][i] + V[1][i];
-      const int tq = (int)((((AB >> 1) & 0x7FFFu) + (AB >> 17)) >> 1);  // ((A>>1)+(B>>1))>>1
+      // ((A >> 1) + (B >> 1)) >> 1 == ((A & ~1) + (B & ~1)) >> 2, and the sum of the two halves is one v_sad_u16 against
+      // zero.  The mask is needed: for A and B both odd with (A + B) % 4 == 0, (A + B) >> 2 is one too large.
+      unsigned s = AB & 0xFFFEFFFEu;
+      asm("v_sad_u16 %0, %0, 0, 0" : "+v"(s));
+      const int tq = (int)(s >> 2);
       int ab;  // A * B straight from the packed halves (SDWA word selects): no unpacking
       asm("v_mul_u32_u24_sdwa %0, %1, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_0 "
           "src1_sel:WORD_1"

@@ -76,6 +76,63 @@
 #define MINU32(x) asm volatile("v_min_u32 %0, %0, %1" : "+v"(x) : "v"(b));
 #define MINIMUM3F32(x) asm volatile("v_minimum3_f32 %0, %0, %1, %1" : "+v"(x) : "v"(b));
 #define MINU16(x) asm volatile("v_min_u16 %0, %0, %1" : "+v"(x) : "v"(b));
+// score arithmetic of K1 (LAB_NOTES.md "K1: score on SAD and dot2"): v_sad_u16, the 16-bit dot product in its VOP2 form
+// (accumulates into its destination) and in its VOP3P form with the inline constant 0 as accumulator, and the score of
+// four pixels from AB = A | B << 16 and C, as the nine instructions per pixel of the kernel before and as the seven
+// after.  The chains work on four accumulators at a time, as score_row does on a lane's four pixels: in CHAIN7 the four
+// dots and then the four subtractions, so that three instructions stand between a dot and the reader of its result
+// (the wait states a v_dot result needs before another vector instruction may read it).  A chain counts as 9 (7) x 4
+// instructions: the printed figure is cycles per instruction, times 9 (7) = cycles per pixel.
+#define SADU16(x) asm volatile("v_sad_u16 %0, %0, %1, %0" : "+v"(x) : "v"(b));
+#define DOT2C(x) asm volatile("v_dot2c_i32_i16 %0, %0, %1" : "+v"(x) : "v"(b));
+#define DOT2Z(x) asm volatile("v_dot2_i32_i16 %0, %0, %1, 0" : "+v"(x) : "v"(b));
+#define MULAB " dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_0 src1_sel:WORD_1\n\t"
+#define TQ9(x, t, u) "v_lshrrev_b32 " t ", 1, " x "\n\tv_and_b32 " t ", 0x7fff, " t "\n\tv_lshrrev_b32 " u ", 17, " x "\n\t" \
+                     "v_add_u32 " t ", " t ", " u "\n\tv_lshrrev_b32 " t ", 1, " t "\n\t"
+#define SC9(x, t, u) TQ9(x, t, u) "v_mul_u32_u24_sdwa " u ", " x ", " x MULAB "v_mul_i32_i24 " x ", %12, %12\n\t" \
+                     "v_mad_i32_i24 " x ", " t ", " t ", " x "\n\tv_sub_u32 " x ", " u ", " x "\n\t"
+#define OP7(x, t, u) "v_and_b32 " t ", 0xfffefffe, " x "\n\tv_sad_u16 " t ", " t ", 0, 0\n\tv_lshrrev_b32 " t ", 2, " t "\n\t" \
+                     "v_mul_u32_u24_sdwa " u ", " x ", " x MULAB "v_or_b32 " t ", %12, " t "\n\t"
+#define CHAIN_OPS(w, x, y, z) \
+  : "+v"(w), "+v"(x), "+v"(y), "+v"(z), "=&v"(t0), "=&v"(t1), "=&v"(t2), "=&v"(t3), "=&v"(u0), "=&v"(u1), "=&v"(u2), "=&v"(u3) : "v"(b)
+#define CHAIN9(w, x, y, z) { int t0, t1, t2, t3, u0, u1, u2, u3; \
+  asm volatile(SC9("%0", "%4", "%8") SC9("%1", "%5", "%9") SC9("%2", "%6", "%10") SC9("%3", "%7", "%11") CHAIN_OPS(w, x, y, z)); }
+#define CHAIN7(w, x, y, z) { int t0, t1, t2, t3, u0, u1, u2, u3; \
+  asm volatile(OP7("%0", "%4", "%8") OP7("%1", "%5", "%9") OP7("%2", "%6", "%10") OP7("%3", "%7", "%11") \
+               "v_dot2_i32_i16 %4, %4, %4, 0\n\tv_dot2_i32_i16 %5, %5, %5, 0\n\t" \
+               "v_dot2_i32_i16 %6, %6, %6, 0\n\tv_dot2_i32_i16 %7, %7, %7, 0\n\t" \
+               "v_sub_u32 %0, %8, %4\n\tv_sub_u32 %1, %9, %5\n\tv_sub_u32 %2, %10, %6\n\tv_sub_u32 %3, %11, %7" \
+               CHAIN_OPS(w, x, y, z)); }
+KERNEL(k_sadu16, DECL_I, OP8(SADU16))
+KERNEL(k_dot2c, DECL_I, OP8(DOT2C))
+KERNEL(k_dot2z, DECL_I, OP8(DOT2Z))
+KERNEL(k_score9, DECL_I, CHAIN9(a0, a1, a2, a3) CHAIN9(a4, a5, a6, a7))
+KERNEL(k_score7, DECL_I, CHAIN7(a0, a1, a2, a3) CHAIN7(a4, a5, a6, a7))
+// the same operations with K1's matrix instruction between them (one v_mfma_i32_4x4x4i8 per vector instruction, four
+// accumulators in turn): what a dot product costs while MFMAs are in flight, against a 24-bit multiply and an add
+typedef int v4i_t __attribute__((ext_vector_type(4)));
+#define KERNELM(name, body)                                                 \
+  __global__ void name(int* out, int seed) {                                \
+    DECL_I;                                                                 \
+    v4i_t m0 = {seed, 1, 2, 3}, m1 = m0, m2 = m0, m3 = m0;                  \
+    int ma = threadIdx.x * 0x01010101, mb = seed * 0x01020304;              \
+    asm volatile("" : "+v"(ma), "+v"(mb));                                  \
+    for (int it = 0; it < ITERS; ++it) {                                    \
+      _Pragma("unroll") for (int r = 0; r < REP / 8; ++r) { body }          \
+    }                                                                       \
+    const v4i_t m = m0 + m1 + m2 + m3;                                      \
+    out[blockIdx.x * blockDim.x + threadIdx.x] = a0 + a1 + a2 + a3 + a4 + a5 + a6 + a7 + m[0] + m[1] + m[2] + m[3]; \
+  }
+#define MF(acc) asm volatile("v_mfma_i32_4x4x4_16b_i8 %0, %1, %2, %0" : "+v"(acc) : "v"(ma), "v"(mb));
+#define NOP1(x)
+#define MIX8(OP) OP(a0) MF(m0) OP(a1) MF(m1) OP(a2) MF(m2) OP(a3) MF(m3) OP(a4) MF(m0) OP(a5) MF(m1) OP(a6) MF(m2) OP(a7) MF(m3)
+KERNELM(k_mfma, MIX8(NOP1))
+KERNELM(k_mfma_add, MIX8(ADD))
+KERNELM(k_mfma_mul24, MIX8(MUL24))
+KERNELM(k_mfma_mad24, MIX8(MAD24))
+KERNELM(k_mfma_sadu16, MIX8(SADU16))
+KERNELM(k_mfma_dot2z, MIX8(DOT2Z))
+KERNELM(k_mfma_dot2c, MIX8(DOT2C))
 KERNEL(k_pkmin3h, DECL_H, OP8(PKMIN3H))
 KERNEL(k_pkminh, DECL_H, OP8(PKMINH))
 KERNEL(k_pkmini16, DECL_H, OP8(PKMINI16))
@@ -140,7 +197,8 @@ int main() {
   hipEvent_t a, b;
   hipEventCreate(&a);
   hipEventCreate(&b);
-#define RUN(k)                                                                              \
+#define RUN(k) RUNN(k, 1)
+#define RUNN(k, N)                                                                          \
   {                                                                                         \
     k<<<blocks, threads>>>(d, 1);                                                           \
     hipDeviceSynchronize();                                                                 \
@@ -150,7 +208,7 @@ int main() {
     hipEventSynchronize(b);                                                                 \
     float ms;                                                                               \
     hipEventElapsedTime(&ms, a, b);                                                         \
-    const double instr = (double)blocks * (threads / 64) * ITERS * REP;                     \
+    const double instr = (double)blocks * (threads / 64) * ITERS * REP * (N);                   \
     const double per_simd = instr / (p.multiProcessorCount * 4);                            \
     printf("%-10s %.3f ms  -> %.2f ns per wave-instr per SIMD (= %.2f cycles @2.4GHz)\n", #k, ms, \
            ms * 1e6 / per_simd, ms * 1e6 / per_simd * 2.4);                                 \
@@ -166,5 +224,9 @@ int main() {
   printf("-- round 4: minima / maxima (AGAST kernel)\n");
   RUN(k_pkmin3h) RUN(k_pkminh) RUN(k_pkmini16) RUN(k_pkmaxu16) RUN(k_min3i16) RUN(k_min3f16) RUN(k_min3u32)
   RUN(k_minu32) RUN(k_minimum3f32) RUN(k_minu16)
+  printf("-- K1 score arithmetic (k_score9 / k_score7: per instruction of the 9- / 7-instruction chain per pixel)\n");
+  RUN(k_sadu16) RUN(k_dot2c) RUN(k_dot2z) RUNN(k_score9, 9) RUNN(k_score7, 7)
+  printf("-- one v_mfma_i32_4x4x4i8 per vector instruction (figures per PAIR; k_mfma: the MFMA alone)\n");
+  RUN(k_mfma) RUN(k_mfma_add) RUN(k_mfma_mul24) RUN(k_mfma_mad24) RUN(k_mfma_sadu16) RUN(k_mfma_dot2z) RUN(k_mfma_dot2c)
   return 0;
 }
