@@ -1055,9 +1055,10 @@ okvfe_status okvfe_remove_outliers_blocks_device(
  * multiframe and both pairs named), and its rows must not be the OLDER rows of another pair of the same call: the
  * reference visits the older frames one after another, so J older frames are J calls on one stream.
  *
- * NOT restated: the sampler; opengv's twopt_rotationOnly and the Stewenius five-point solver, which work on two and
- * five correspondences and stay with the caller; opengv's adaptive stop (this call scores every hypothesis it is
- * given); estimator.removeObservation beyond the id row; the LOG lines of :2378-2384; firstFrame and rotationOnly_tmp
+ * The hypotheses: okvfe_ransac2d2d_hypotheses_blocks_device (further below) writes both lists and their validity bytes
+ * on the device, with a defined sampler and defined two-point and five-point solvers (opengv's rand() sampler,
+ * twopt_rotationOnly and Stewenius solver are not restated bit for bit).  NOT restated: opengv's adaptive stop (this call
+ * scores every hypothesis it is given); estimator.removeObservation beyond the id row; the LOG lines of :2378-2384; firstFrame and rotationOnly_tmp
  * (:1971-1974) and :644, host lines over the result bytes.  PARITY UNPINNED: opengv's winner
  * rule, as for okvfe_ransac3d2d_consensus_blocks_device.  PARITY UNPINNED: opengv::triangulation::triangulate2 and
  * Eigen's 2 x 2 inverse are not in the reference tree; they are restated above from their published sources.
@@ -1357,6 +1358,94 @@ okvfe_status okvfe_place_hypotheses_blocks_device(
     const int32_t* cam_ids /* HOST, n_cams */, const okvfe_pose* T_SC /* HOST, n_cams */,
     const int32_t* match_landmark_dev, const uint8_t* gate_dev /* or NULL */, const uint64_t* sample_keys_dev /* or NULL */,
     uint64_t seed, int32_t n_hyp, const okvfe_ransac_hypotheses_device* result, void* stream);
+
+/* ---- the hypotheses of runRansac2d2d: sampler, two-point rotation, five-point relative pose ------
+ * What fills rot_hyp_dev / rot_valid_dev / rel_hyp_dev / rel_valid_dev of okvfe_ransac2d2d_consensus_blocks_device
+ * without a host step in between.  A DEFINED ALGORITHM, PARITY UNPINNED: opengv (not in the reference tree) samples with
+ * rand() and solves with twopt_rotationOnly and Stewenius' five-point, so sample-for-sample parity is impossible by
+ * construction; what is stated here is restated in tests/ransac2d2d_hyp_ref.py one IEEE operation per line, and host,
+ * device and restatement agree byte for byte.  The caller's own solvers remain an option: the consensus call takes any
+ * hypotheses.
+ *
+ * Correspondences: exactly those of the consensus call, per (pair, camera): FrameRelativeAdapter's list in
+ * older-keypoint order, built by the same device functions; n of them.  n < 10: the reference skips the camera
+ * (:2300) and the consensus scores nothing: every hypothesis of both problems is invalid, nothing is drawn or solved.
+ * Sampler: the draw of the absolute-pose hypotheses above, unchanged, r(j, range) of (seed, key, h, j), under the key
+ *   key = (pair_key 128 + c 2 + problem) mod 2^64, pair_key = sample_keys_dev[p] (or p where that pointer is NULL),
+ *   c the camera's index in the call (< 64), problem 0 = rotation only, 1 = relative pose,
+ * so a pair's samples do not depend on its place in the batch.  The rotation-only problem takes draws j = 0, 1, the
+ * relative-pose problem j = 0 .. 7: t = r(j, n - j), then, over the already chosen positions x in ascending order,
+ * t += 1 where x <= t (no rejection loop).
+ * Rotation only (opengv's twopt_rotationOnly restated from its published source): M = T1 T2^T with the orthonormal
+ * triads e1 = f_0, e3 = f_0 x f_1 normalised, e2 = e3 x e1, T1 over the two b1, T2 over the two b2, so that b1 ~ M b2,
+ * M[i][j] = (e1[i] e1'[j] + e2[i] e2'[j]) + e3[i] e3'[j].  Invalid: a cross product of squared norm 0, a non-finite M.
+ * Relative pose (opengv's STEWENIUS sample size, 5 + 3: samples 0 .. 4 solve, samples 5 .. 7 disambiguate).
+ * DEVIATION from Stewenius' Groebner-basis / eigenvalue form: Nister's formulation, the same ten cubic constraints solved
+ * through a univariate polynomial; no eigen-solver and no SVD.  Every sum of the solver runs left to right, whatever
+ * okvfe_set_fp64_reduction says.
+ *   Null space: Q (5 x 9), row i = b1_i (x) b2_i (b1^T E b2 = 0, E row-major).  Gauss-Jordan with FULL pivoting: step s
+ *     takes the largest |a| over rows s .. 4 and the columns not yet used (the first in row-major order on ties; 0 or
+ *     non-finite: invalid), swaps its row into s, takes (entry of the column / pivot) times that row from every other
+ *     row (a row equal to it becomes exactly zero: a pair listed twice fails the next pivot), then divides the row by it.
+ *     The free columns f_0 < f_1 < f_2 < f_3 give X, Y, Z, W: 1 at f_k, -a[s][f_k] at the pivot column of row s.
+ *     E = x X + y Y + z Z + W.
+ *   Constraints: det E = e0 (e4 e8 - e5 e7) - e1 (e3 e8 - e5 e6) + e2 (e3 e7 - e4 e6), then the nine entries of
+ *     L E, L = E E^T - 1/2 tr(E E^T) I, row-major: (L_i0 e_0j + L_i1 e_1j) + L_i2 e_2j, (E E^T)_ij = (e_i0 e_j0 +
+ *     e_i1 e_j1) + e_i2 e_j2, tr = (d00 + d11) + d22, all coefficient-wise on polynomials.  Columns: x^3, y^3, x^2y, xy^2,
+ *     x^2z, x^2, y^2z, y^2, xyz, xy | xz^2, xz, x, yz^2, yz, y, z^3, z^2, z, 1.  An entry of E is a 4-vector over
+ *     (x, y, z, 1), a product of two entries a 10-vector over (x^2, xy, xz, x, y^2, yz, y, z^2, z, 1); a product starts
+ *     from zeros and adds a_i b_j to its monomial in the order i outer, j inner.
+ *   Elimination: Gauss-Jordan on the first ten columns with partial pivoting (the largest |a| of column c over rows
+ *     c .. 9, the first on ties; 0 or non-finite: invalid), in the same three steps, over all twenty columns.
+ *   The polynomial: rows (x^2z) - z (x^2), (y^2z) - z (y^2), (xyz) - z (xy) give B(z), 3 x 3, columns of degree 3, 3, 4;
+ *     det B = B00 (B11 B22 - B12 B21) - B01 (B10 B22 - B12 B20) + B02 (B10 B21 - B11 B20), degree 10.
+ *   Real roots: a_10 zero or non-finite: invalid.  bound = 1 + max |a_i / a_10|.  For d = 9 .. 0 the d-th derivative's
+ *     roots are sought in the intervals that the (d+1)-th derivative's roots and -bound, +bound cut; an interval whose
+ *     end values have strictly opposite signs is bisected (mid = (lo + hi) / 2; a midpoint whose value is > 0 exactly
+ *     when the upper end's is becomes the upper end) until the midpoint equals an end, at most 128 steps; the root is
+ *     the upper end.  Ascending, at most 10 (rel_n_roots).  A root of even multiplicity is NOT found, nor one whose
+ *     interval has an end value of exactly 0.  No Newton polish.
+ *   Per root: (x, y, 1) ~ the cross product of the pair of B(z) rows with the largest |third component|, pairs (0,1),
+ *     (0,2), (1,2), the first on ties; E = ((x X + y Y) + z Z) + W.
+ *   Decomposition (Horn's closed form, no SVD): T = 1/2 tr(E E^T) I - E E^T = b b^T; b = the row of T with the largest
+ *     diagonal entry (the first on ties; not > 0: the root has no candidate) over the square root of that entry;
+ *     R-/+ = (cof(E) -/+ [b]x E) / (b.b), row i of cof(E) = row i+1 x row i+2; candidates in the order (R-, +b^),
+ *     (R-, -b^), (R+, +b^), (R+, -b^), b^ = b / |b|: [R | t] with |t| = 1, p_older = R p_current + t.
+ *   Choice: over every candidate of every root, roots ascending then candidate order, the sum (d5 + d6) + d7 of the
+ *     consensus call's relative-pose distance (the same function, which does follow okvfe_set_fp64_reduction; it
+ *     triangulates, so cheirality needs no test of its own); the smallest wins, the first on ties, a NaN or infinite
+ *     sum never.
+ *   Invalid (valid byte 0, the 12 doubles zero): n < 10, a failed pivot, no real root, no finite sum, a non-finite output.
+ *
+ * okvfe_twopt_rotation_hypothesis / okvfe_fivept_hypothesis: ONE sample on the host, no context (what a caller at B = 1,
+ * or one with its own sampler, uses).  b1 / b2: 2 x 3 resp. 8 x 3 unit bearings of the older / current frame; sigma1 /
+ * sigma2: the sigmas of rows 5 .. 7; order: OKVFE_SUM3_EIGEN_TREE or OKVFE_SUM3_LEFT_TO_RIGHT; valid: one byte; n_roots: optional. */
+okvfe_status okvfe_twopt_rotation_hypothesis(const double* b1, const double* b2, double* M, uint8_t* valid);
+okvfe_status okvfe_fivept_hypothesis(const double* b1, const double* b2, const double* sigma1, const double* sigma2,
+                                     int32_t order, double* hypothesis, uint8_t* valid, int32_t* n_roots);
+/* The device call: layouts, argument rules, limits (K <= 4095) and errors of okvfe_ransac2d2d_consensus_blocks_device,
+ * before anything is launched; n_cams <= 64; sample_keys_dev: n_pairs uint64 or NULL; n_hyp in
+ * 1 .. OKVFE_RANSAC_MAX_HYPOTHESES.  One work-group per (pair, camera), 114 KiB of LDS (one per CU).  Nothing synchronises the host; no
+ * workspace; 8 bytes per pair and 8 per camera go through the pinned parameter ring; n_pairs == 0 is OK and launches
+ * nothing. */
+typedef struct okvfe_ransac2d2d_hypotheses_device {
+  double* rot_hyp;             /* n_pairs x n_cams x n_hyp x 9: IS the consensus call's rot_hyp_dev */
+  uint8_t* rot_valid;          /* n_pairs x n_cams x n_hyp: IS rot_valid_dev */
+  double* rel_hyp;             /* n_pairs x n_cams x n_hyp x 12: IS rel_hyp_dev */
+  uint8_t* rel_valid;          /* IS rel_valid_dev */
+  /* optional, NULL allowed */
+  int32_t* n_correspondences;  /* n_pairs x n_cams */
+  int32_t* rot_samples;        /* n_pairs x n_cams x n_hyp x 2: the drawn list positions as OLDER keypoint index, -1: not drawn */
+  int32_t* rel_samples;        /* n_pairs x n_cams x n_hyp x 8: the same encoding */
+  int32_t* rel_n_roots;        /* n_pairs x n_cams x n_hyp */
+} okvfe_ransac2d2d_hypotheses_device;
+okvfe_status okvfe_ransac2d2d_hypotheses_blocks_device(
+    okvfe_ctx* ctx, const void* blocks0_dev, int32_t n_multiframes0, const void* blocks1_dev, int32_t n_multiframes1,
+    int32_t n_pairs, const int32_t* mf0 /* HOST, n_pairs */, const int32_t* mf1 /* HOST, n_pairs */, int32_t n_cams,
+    const int32_t* cam_ids /* HOST, n_cams */, const int32_t* landmark0_dev, const int32_t* landmark1_dev,
+    const uint8_t* added_dev /* n_landmarks bytes or NULL */, int32_t n_landmarks,
+    const uint64_t* sample_keys_dev /* n_pairs or NULL */, uint64_t seed, int32_t n_hyp,
+    const okvfe_ransac2d2d_hypotheses_device* result, void* stream);
 
 typedef struct okvfe_place_hessian_device {
   double* H;                /* device, n_multiframes x 36, row-major 6 x 6 */

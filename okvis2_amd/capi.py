@@ -130,6 +130,7 @@ EXPORTS = [
     "okvfe_tracking_quality",
     "okvfe_imu_propagation", "okvfe_imu_propagation_blocks_device",
     "okvfe_p3p_hypothesis", "okvfe_ransac3d2d_hypotheses_blocks_device", "okvfe_place_hypotheses_blocks_device",
+    "okvfe_twopt_rotation_hypothesis", "okvfe_fivept_hypothesis", "okvfe_ransac2d2d_hypotheses_blocks_device",
 ]
 # exported for the tests and deliberately not declared in include/okvfe.h (EXPORTS is exactly what the header declares)
 TEST_HOOKS = [
@@ -193,6 +194,12 @@ class Ransac2d2dResultDevice(C.Structure):
         "n_correspondences", "rot_best", "rot_inliers", "rel_best", "rel_inliers", "branch", "removed",
         "total_inliers", "rotation_only", "success",
         "rot_hyp_inliers", "rel_hyp_inliers", "match1", "state", "distance", "landmark1_out")]
+
+
+class Ransac2d2dHypothesesDevice(C.Structure):
+    """okvfe_ransac2d2d_hypotheses_device: device pointers; the last four are optional (None)."""
+    _fields_ = [(n, C.c_void_p) for n in (
+        "rot_hyp", "rot_valid", "rel_hyp", "rel_valid", "n_correspondences", "rot_samples", "rel_samples", "rel_n_roots")]
 
 
 class PlaceSetDevice(C.Structure):
@@ -323,6 +330,14 @@ def lib():
         L.okvfe_ransac2d2d_consensus_blocks_device.argtypes = [
             V, V, C.c_int32, V, C.c_int32, C.c_int32, V, V, C.c_int32, V, V, V, V, C.c_int32, V, V, V, V, C.c_int32,
             C.c_double, C.c_int32, V, V]
+        L.okvfe_ransac2d2d_hypotheses_blocks_device.restype = C.c_int32
+        L.okvfe_ransac2d2d_hypotheses_blocks_device.argtypes = [
+            V, V, C.c_int32, V, C.c_int32, C.c_int32, V, V, C.c_int32, V, V, V, V, C.c_int32, V, C.c_uint64, C.c_int32,
+            V, V]
+        L.okvfe_twopt_rotation_hypothesis.restype = C.c_int32
+        L.okvfe_twopt_rotation_hypothesis.argtypes = [V, V, V, V]
+        L.okvfe_fivept_hypothesis.restype = C.c_int32
+        L.okvfe_fivept_hypothesis.argtypes = [V, V, V, V, C.c_int32, V, V, V]
         L.okvfe_stereo_insert_blocks_device.restype = C.c_int32
         L.okvfe_stereo_insert_blocks_device.argtypes = [
             V, V, V, V, C.c_int32, C.c_int32, C.c_int32, C.c_int32, V, C.c_int32, V, V, V, V, V, V, V]
@@ -564,6 +579,40 @@ def p3p_hypothesis(points, bearings, sigma, T_SC, eigen_tree=True):
     if st != OK:
         raise OkvfeError(st, "okvfe_p3p_hypothesis")
     return H, int(valid.value), int(n_sol.value)
+
+
+def twopt_rotation_hypothesis(b1, b2):
+    """okvfe_twopt_rotation_hypothesis (host arithmetic, no context): b1 / b2 [2, 3] unit bearings of the older / current
+    frame.  -> (M [9] row-major with b1 ~ M b2, valid)"""
+    a = np.ascontiguousarray(b1, dtype=np.float64).reshape(-1)
+    b = np.ascontiguousarray(b2, dtype=np.float64).reshape(-1)
+    if len(a) != 6 or len(b) != 6:
+        raise ValueError("two bearings per frame")
+    M = np.zeros(9)
+    valid = C.c_uint8(0)
+    st = lib().okvfe_twopt_rotation_hypothesis(_p(a), _p(b), _p(M), C.byref(valid))
+    if st != OK:
+        raise OkvfeError(st, "okvfe_twopt_rotation_hypothesis")
+    return M, int(valid.value)
+
+
+def fivept_hypothesis(b1, b2, sigma1, sigma2, eigen_tree=True):
+    """okvfe_fivept_hypothesis (host arithmetic, no context): b1 / b2 [8, 3] unit bearings of the older / current frame
+    (rows 0 .. 4 are solved, rows 5 .. 7 choose among the candidates), sigma1 / sigma2 [3] of rows 5 .. 7.
+    -> (hypothesis [12] = row-major [R | t], valid, n_roots)"""
+    a = np.ascontiguousarray(b1, dtype=np.float64).reshape(-1)
+    b = np.ascontiguousarray(b2, dtype=np.float64).reshape(-1)
+    s1 = np.ascontiguousarray(sigma1, dtype=np.float64).reshape(-1)
+    s2 = np.ascontiguousarray(sigma2, dtype=np.float64).reshape(-1)
+    if len(a) != 24 or len(b) != 24 or len(s1) != 3 or len(s2) != 3:
+        raise ValueError("eight bearings per frame and three sigmas per frame")
+    H = np.zeros(12)
+    valid, n_roots = C.c_uint8(0), C.c_int32(0)
+    st = lib().okvfe_fivept_hypothesis(_p(a), _p(b), _p(s1), _p(s2), 1 if eigen_tree else 0, _p(H), C.byref(valid),
+                                       C.byref(n_roots))
+    if st != OK:
+        raise OkvfeError(st, "okvfe_fivept_hypothesis")
+    return H, int(valid.value), int(n_roots.value)
 
 
 def keyframe_decision(current, others=None, overlap_threshold=KEYFRAME_OVERLAP_THRESHOLD):
@@ -1320,6 +1369,35 @@ class Frontend:
             _p(cams) if len(cams) else _p(one), _p(landmark0_ptr), _p(landmark1_ptr), _p(added_ptr), int(n_landmarks),
             _p(rot_hyp_ptr), _p(rot_valid_ptr), _p(rel_hyp_ptr), _p(rel_valid_ptr), int(n_hyp), C.c_double(threshold),
             int(bool(remove_outliers)), C.byref(result) if result is not None else None, _s(stream)))
+
+    @staticmethod
+    def make_ransac2d2d_hypotheses_device(rot_hyp_ptr, rot_valid_ptr, rel_hyp_ptr, rel_valid_ptr,
+                                          n_correspondences_ptr=None, rot_samples_ptr=None, rel_samples_ptr=None,
+                                          rel_n_roots_ptr=None) -> Ransac2d2dHypothesesDevice:
+        return Ransac2d2dHypothesesDevice(*[int(p) if p else None for p in (
+            rot_hyp_ptr, rot_valid_ptr, rel_hyp_ptr, rel_valid_ptr, n_correspondences_ptr, rot_samples_ptr,
+            rel_samples_ptr, rel_n_roots_ptr)])
+
+    def ransac2d2d_hypotheses_blocks_device(self, blocks0_ptr, n_multiframes0, blocks1_ptr, n_multiframes1, mf0, mf1,
+                                            cam_ids, landmark0_ptr, landmark1_ptr, added_ptr, n_landmarks,
+                                            sample_keys_ptr, seed, n_hyp, result: Ransac2d2dHypothesesDevice,
+                                            stream=None):
+        """n_hyp hypotheses of both problems per (pair, camera) for ransac2d2d_consensus_blocks_device (the defined
+        sampler, two-point and five-point solvers of include/okvfe.h).  The block, pair and id arguments are that
+        call's; sample_keys_ptr: device n_pairs uint64 or None (the pair's index); result.rot_hyp / rot_valid /
+        rel_hyp / rel_valid are that call's rot_hyp_ptr / rot_valid_ptr / rel_hyp_ptr / rel_valid_ptr."""
+        a0 = np.ascontiguousarray(mf0, dtype=np.int32).reshape(-1)
+        a1 = np.ascontiguousarray(mf1, dtype=np.int32).reshape(-1)
+        if len(a0) != len(a1):
+            raise ValueError("mf0 and mf1: one per pair")
+        cams = np.ascontiguousarray(cam_ids, dtype=np.int32)
+        one = np.zeros(1, np.int32)
+        self._check(lib().okvfe_ransac2d2d_hypotheses_blocks_device(
+            self._h, _p(blocks0_ptr), int(n_multiframes0), _p(blocks1_ptr), int(n_multiframes1), len(a0),
+            _p(a0) if len(a0) else _p(one), _p(a1) if len(a1) else _p(one), len(cams),
+            _p(cams) if len(cams) else _p(one), _p(landmark0_ptr), _p(landmark1_ptr), _p(added_ptr), int(n_landmarks),
+            _p(sample_keys_ptr), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), int(n_hyp),
+            C.byref(result) if result is not None else None, _s(stream)))
 
     # -- matchStereo's landmark bookkeeping, chained over the pairs of a rig ---------------------
     @staticmethod

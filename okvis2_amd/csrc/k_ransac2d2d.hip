@@ -3,7 +3,8 @@
 // (FrameRelativeAdapter.cpp:137-194), every correspondence against every hypothesis of FrameRotationOnlySacProblem
 // (FrameRotationOnlySacProblem.hpp:126-144) and of FrameRelativePoseSacProblem (FrameRelativePoseSacProblem.hpp:130-160),
 // the two winners, the choice between them (:2341-2358), the success flags shared by the cameras of a pair (:2289-2290,
-// :2361) and the outlier removal (:2365-2375).  The sampler and the two minimal solvers stay with the caller.
+// :2361) and the outlier removal (:2365-2375).  The sampler and the two minimal solvers are k_ransac2d2d_hyp.hip, included at
+// the end of this file.
 //   ransac2d2d_consensus_kernel   one work-group per pair, the cameras one after another.  Per camera: the first k per
 //                                 landmark id of the CURRENT block goes into an LDS open-addressing table (a slot keeps
 //                                 the minimum k of its id: std::map::insert does not overwrite); the OLDER block's
@@ -24,7 +25,7 @@ namespace okvfe {
 namespace {
 
 template <bool kTree>
-__device__ __forceinline__ double dot3(const double a[3], const double b[3]) {
+__host__ __device__ __forceinline__ double dot3(const double a[3], const double b[3]) {
   return fp64::sum3<kTree>(a[0] * b[0], a[1] * b[1], a[2] * b[2]);
 }
 
@@ -81,14 +82,14 @@ __device__ __forceinline__ void make_correspondence2(const Ransac2d2dArgs& A, co
 
 // FrameRotationOnlySacProblem.hpp:140-143 and FrameRelativePoseSacProblem.hpp:157-160
 template <bool kTree>
-__device__ __forceinline__ double score_of_errors(const double e1[3], const double e2[3], double s1, double s2) {
+__host__ __device__ __forceinline__ double score_of_errors(const double e1[3], const double e2[3], double s1, double s2) {
   const double q1 = dot3<kTree>(e1, e1), q2 = dot3<kTree>(e2, e2);
   return (q1 * 0.5) / s1 + (q2 * 0.5) / s2;
 }
 
 // FrameRotationOnlySacProblem.hpp:126-144.  The ONE copy: the scoring loop and the final sweep call it.
 template <bool kTree>
-__device__ __forceinline__ double rotation_only_distance(const double* M /* 3 x 3 row-major */, const Corr2& R) {
+__host__ __device__ __forceinline__ double rotation_only_distance(const double* M /* 3 x 3 row-major */, const Corr2& R) {
   double e1[3], e2[3];
   for (int i = 0; i < 3; ++i) {
     const double f2u = fp64::sum3<kTree>(M[3 * i] * R.b2[0], M[3 * i + 1] * R.b2[1], M[3 * i + 2] * R.b2[2]);  // :131
@@ -101,14 +102,14 @@ __device__ __forceinline__ double rotation_only_distance(const double* M /* 3 x 
 
 // FrameRelativePoseSacProblem.hpp:137: ti = (-R^T) t
 template <bool kTree>
-__device__ __forceinline__ void inverse_translation(const double* H /* 3 x 4 row-major */, double* ti) {
+__host__ __device__ __forceinline__ void inverse_translation(const double* H /* 3 x 4 row-major */, double* ti) {
   for (int i = 0; i < 3; ++i) ti[i] = fp64::sum3<kTree>((-H[i]) * H[3], (-H[4 + i]) * H[7], (-H[8 + i]) * H[11]);
 }
 
 // FrameRelativePoseSacProblem.hpp:130-160 with opengv's triangulate2 (and Eigen's 2 x 2 inverse) as published.  The ONE
 // copy: the scoring loop and the final sweep call it.
 template <bool kTree>
-__device__ __forceinline__ double relative_pose_distance(const double* H /* [R | t] row-major */, const double* ti,
+__host__ __device__ __forceinline__ double relative_pose_distance(const double* H /* [R | t] row-major */, const double* ti,
                                                          const Corr2& R) {
   const double t[3] = {H[3], H[7], H[11]};
   double f2u[3];
@@ -137,6 +138,22 @@ __device__ __forceinline__ int id_lookup(const int* tab, const int32_t* lm1, int
     const int k = tab[s];
     if (k < 0) return -1;
     if (lm1[k] == id) return k;
+  }
+}
+
+// FrameRelativeAdapter.cpp:139-152 for the current keypoint k: idMap keeps the FIRST current keypoint of every added
+// landmark id.  The ONE copy: the consensus kernel and the hypotheses kernel build their tables with it.
+__device__ __forceinline__ void id_insert(const Ransac2d2dArgs& A, int* tab, const int32_t* lm1, int k) {
+  const int id = lm1[k];
+  if (id < 0) return;                                                  // :143
+  if (A.added && (id >= A.n_landmarks || A.added[id] == 0)) return;    // :147
+  for (uint32_t s = ransac2d2d_id_slot(id);; s = (s + 1) & (uint32_t)(kRansac2Slots - 1)) {
+    const int old = atomicCAS(&tab[s], -1, k);
+    if (old < 0) break;
+    if (lm1[old] == id) {  // the slot is this id's (it only ever holds keypoints of one id): :151 keeps the first
+      atomicMin(&tab[s], k);
+      break;
+    }
   }
 }
 
@@ -207,19 +224,7 @@ __global__ __launch_bounds__(kRansac2Threads) void ransac2d2d_consensus_kernel(R
     __syncthreads();
 
     // FrameRelativeAdapter.cpp:139-152: idMap, the FIRST current keypoint of every added landmark id
-    for (int k = tid; k < count1; k += kRansac2Threads) {
-      const int id = lm1[k];
-      if (id < 0) continue;                                                  // :143
-      if (A.added && (id >= A.n_landmarks || A.added[id] == 0)) continue;    // :147
-      for (uint32_t s = ransac2d2d_id_slot(id);; s = (s + 1) & (uint32_t)(kRansac2Slots - 1)) {
-        const int old = atomicCAS(&s_tab[s], -1, k);
-        if (old < 0) break;
-        if (lm1[old] == id) {  // the slot is this id's (it only ever holds keypoints of one id): :151 keeps the first
-          atomicMin(&s_tab[s], k);
-          break;
-        }
-      }
-    }
+    for (int k = tid; k < count1; k += kRansac2Threads) id_insert(A, s_tab, lm1, k);
     __syncthreads();
 
     // :154-165: the matches in older-keypoint order, a tile of keypoints at a time
@@ -356,3 +361,5 @@ int ransac2d2d_chunk_records() { return kRansac2Chunk; }
 int ransac2d2d_ring_records() { return kRansac2Ring; }
 
 }  // namespace okvfe
+
+#include "k_ransac2d2d_hyp.hip"

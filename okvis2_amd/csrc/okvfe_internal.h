@@ -625,6 +625,14 @@ struct Ransac2d2dArgs {
 void launch_ransac2d2d_consensus(const Ransac2d2dArgs& args, int n_pairs, hipStream_t stream);
 int ransac2d2d_chunk_records();
 int ransac2d2d_ring_records();
+// the hypotheses of both problems of runRansac2d2d (k_ransac2d2d_hyp.hip, a part of k_ransac2d2d.hip's translation unit):
+// sampler, rotation from two triads, five-point, the choice by samples 5 .. 7.  args: the consensus call's (its
+// hypothesis lists, threshold and result are not read)
+bool twopt_rotation_host(const double* b1, const double* b2, double* M);
+bool fivept_hypothesis_host(bool tree, const double* b1, const double* b2, const double* sigma1, const double* sigma2,
+                            double* hypothesis, int* n_roots);
+void launch_ransac2d2d_hypotheses(const Ransac2d2dArgs& args, const uint64_t* keys, uint64_t seed,
+                                  const okvfe_ransac2d2d_hypotheses_device& out, int n_pairs, hipStream_t stream);
 // verifyRecognisedPlace after the descriptor matching (Frontend.cpp:347-397): the claims (k_place.hip) and the consensus
 // over LoopclosureNoncentralAbsoluteAdapter's correspondences (k_ransac.hip, the kPlace policy of the kernel above)
 constexpr int kPlaceClaimsMaxKeypoints = 12288;  // one int per keypoint in LDS

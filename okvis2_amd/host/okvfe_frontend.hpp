@@ -992,6 +992,30 @@ class HipFrontend {
     c.check(okvfe_ransac3d2d_hypotheses_blocks_device(c.get(), &table.get(), blocksDev, nMultiframes, 1, &cam, &T_SC,
                                                       landmarkDev, sampleKeysDev, seed, nHyp, &result, stream));
   }
+  // The hypotheses of both problems of runRansac2d2d, made on the device for the pairs (older frame mf0[p] of blocks0Dev,
+  // current frame mf1[p] of blocks1Dev) of camera `cameraIndex`: the defined sampler, two-point rotation and five-point
+  // relative pose of okvfe_ransac2d2d_hypotheses_blocks_device (include/okvfe.h: not opengv's).  sampleKeysDev: device
+  // nPairs uint64 or null (the pair's index); result.rot_hyp / rot_valid / rel_hyp / rel_valid are what
+  // okvfe_ransac2d2d_consensus_blocks_device takes as rot_hyp_dev / rot_valid_dev / rel_hyp_dev / rel_valid_dev.  ONE
+  // camera per context, as in ransac2d2dBlocks.  Nothing synchronises the host.
+  void ransac2d2dHypothesesBlocks(size_t cameraIndex, const void* blocks0Dev, int nFrames0, const void* blocks1Dev,
+                                  int nFrames1, const std::vector<int32_t>& mf0, const std::vector<int32_t>& mf1,
+                                  const int32_t* landmark0Dev, const int32_t* landmark1Dev, const uint8_t* addedDev,
+                                  int nLandmarks, const uint64_t* sampleKeysDev, uint64_t seed, int nHyp,
+                                  const okvfe_ransac2d2d_hypotheses_device& result, void* stream = nullptr) {
+    if (cameraIndex >= cameras_.size())
+      throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "Camera index exceeds number of cameras.");
+    if (mf0.size() != mf1.size()) throw Exception(OKVFE_ERR_INVALID_ARGUMENT, "ransac2d2dHypothesesBlocks: mf0 / mf1 sizes");
+    std::lock_guard<std::mutex> lock(mutexes_[cameraIndex]);
+    if (!extractors_[cameraIndex].isCameraAware()) extractors_[cameraIndex].setCamera(cameras_[cameraIndex]);
+    Context& c = *contexts_[cameraIndex];
+    const int32_t cam = 0;  // slot 0 of the camera's own context
+    const int32_t none = 0;
+    c.check(okvfe_ransac2d2d_hypotheses_blocks_device(
+        c.get(), blocks0Dev, nFrames0, blocks1Dev, nFrames1, (int32_t)mf0.size(), mf0.empty() ? &none : mf0.data(),
+        mf1.empty() ? &none : mf1.data(), 1, &cam, landmark0Dev, landmark1Dev, addedDev, nLandmarks, sampleKeysDev, seed,
+        nHyp, &result, stream));
+  }
   // Before initialisation (Frontend.cpp:1961-1969): the consensus step of runRansac2d2d for the pairs (older frame
   // mf0[p] of blocks0Dev, current frame mf1[p] of blocks1Dev) of camera `cameraIndex` (ONE camera per context, so a
   // multiframe is one gather block here; a rig whose cameras share a context calls
